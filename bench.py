@@ -3,13 +3,18 @@
 the BASELINE.json workload: DTU-scan1-like 3 views of 400x400, 160^3 grid, 186 samples/ray, N_rand = 1024 rays per
 GPU (weak scaling: global batch = 1024 * n_gpus), fp32, synthetic inputs resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With N > 1 and no RANK in the environment the script starts its own N ranks (one `python -m torch.distributed.run`
 child, before anything touches the GPU), relays rank 0's JSON line and exits with the child's return code; the driver's
 own `torch.distributed.run` launch (RANK set) runs the ranks directly.
 
-Prints ONE JSON line on rank 0 (driver contract).  Objects besides the contract's scalar fields:
+A plain run sets up, warms up, times the K steps and prints the headline record: the contract's scalar fields (metric,
+value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data), `arithmetic` and
+`config`.  --dump-outputs DIR writes what the last timed step left to a caller (write_outputs()) as DIR/<name>.npy.
+
+Prints ONE JSON line on rank 0 (driver contract).  With --full the record also holds these objects (each leg can still be
+dropped with its --no-* switch):
   roofline          the longest kernel of the timed step, priced live with HIP events inside the timed region: the fused
                     TV + Adam grid pass (HBM), the warp MLP's data-gradient kernel or its weight-gradient kernel (MFMA; a
                     split-precision kernel is priced against the fp16 pipe with the 3 x FLOPs it issues)
@@ -87,6 +92,67 @@ def pmc_traffic(grid, voxels, sparse):
         except Exception:
             pass
     return None
+
+
+def _randomness_of_step(a):
+    from poseprobe_amd import synthetic as syn
+    n_total, n_rand, seed = a
+    return syn.step_randomness(n_total, n_rand, seed)
+
+
+def all_step_randomness(n_total, n_rand, seeds, workers=8):
+    """[(ray idx, jitter)] of every seed.  One permutation of n_total pixels costs ~7 ms of host time, more than a step on
+    the GPU, so long runs draw them in forked worker processes: call this before anything initialises the GPU.  Every step
+    has its own seeded generator, so the values do not depend on the number of workers."""
+    jobs = [(n_total, n_rand, s) for s in seeds]
+    workers = min(workers, os.cpu_count() or 1, len(jobs) // 32)
+    if workers < 2:
+        return [_randomness_of_step(a) for a in jobs]
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    with ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context('fork')) as ex:
+        return list(ex.map(_randomness_of_step, jobs, chunksize=16))
+
+
+def training_state(eng):
+    """Copy of everything a train step reads and advances: colour grid, Adam moments, packed MLP / alpha-beta block, poses,
+    step counter and learning rates (gradients and touched-voxel maps are zero / clean between steps)."""
+    tensors = [eng.k0_cl, eng.k0_m, eng.k0_v, eng.flat.data, eng.flat.m, eng.flat.v, eng.se3, eng.se3_m, eng.se3_v]
+    return [t.clone() for t in tensors], (eng.n_step, dict(eng.lr), eng.lr_pose)
+
+
+def restore_training_state(eng, state):
+    tensors, (n_step, lr, lr_pose) = state
+    for dst, src in zip([eng.k0_cl, eng.k0_m, eng.k0_v, eng.flat.data, eng.flat.m, eng.flat.v, eng.se3, eng.se3_m, eng.se3_v],
+                        tensors):
+        dst.copy_(src)
+    eng.n_step, eng.lr, eng.lr_pose = n_step, dict(lr), lr_pose
+
+
+DUMP_K0_SAMPLES = 1 << 21     # colour-grid entries drawn for --dump-outputs (<= 8 MB): a fixed, seeded sample of the grid
+
+
+def write_outputs(eng, out_dir):
+    """What one train step hands its caller, as float32 .npy files: the trained state after the step (colour grid: a
+    fixed seeded sample of up to DUMP_K0_SAMPLES entries of the [C,X,Y,Z] reference layout; the alpha / beta pair, both MLPs'
+    packed parameters, the pose corrections) and the step's rendered colours and loss terms.  -> {name: shape}.
+    The last timed step starts from the seeded initial state (main()), so two runs with the same arguments write the same
+    arrays up to rounding."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    k0 = eng.k0_reference_layout()[0]                                # [C,X,Y,Z] view of the current grid
+    pick = np.unique(np.random.default_rng(0).integers(0, k0.numel(), DUMP_K0_SAMPLES))
+    at = [torch.from_numpy(i).to(k0.device) for i in np.unravel_index(pick, tuple(k0.shape))]
+    arrays = {'rgb_marched': eng.ws.rgb_marched, 'losses': eng.ws.loss_out, 'se3': eng.se3,
+              'sdf_ab': eng.flat.view('sdf_ab'), 'rgbnet': eng.flat.view('rgbnet'), 'warp': eng.flat.view('warp'),
+              'k0_sample': k0[tuple(at)]}
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def init_engine_params(eng, cfg, seed):
@@ -575,6 +641,38 @@ def inference_leg(dev, G, H, W, reps=3):
             f'{nvs_fun.CHUNK}-ray chunks (rgb, disparity, opacity, normals), images assembled on the device'}
 
 
+def headline_record(args, eng, cfg, dt, world, split_bits, dctx):
+    """The result line of a plain run: the driver contract's fields, `arithmetic` and `config` (--full adds its objects)."""
+    import torch
+    G, H, W, V, N = args.grid, args.hw, args.hw, args.views, args.n_rand
+    if world > 1:
+        par = (f'ray-sharded dp{world}, k0 gradient exchanged per sample (all-gather of {dctx.rows} rows x 64 B per rank), replicated grid optimiser'
+               if dctx.mode == 'samples' else f'ray-sharded dp{world}, dense reduce-scatter + ZeRO-1 grid optimiser')
+    else:
+        par = 'single GPU'
+    out = {
+        'metric': 'rays_per_sec_train_step', 'value': N * world * args.steps / dt, 'unit': 'rays/s',
+        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': 'f32 (3xf16-split products)' if split_bits else 'f32', 'data': 'synthetic',
+        'arithmetic': ('fp32 operands, accumulation and results everywhere; ' +
+                       ('the 128 x 128 products of the two MLPs are evaluated as three fp16 MFMA products per fp32 product '
+                        '(operands split into 11 + 11 significant bits with a power-of-two scale, fp32 accumulation): measured error '
+                        'against fp64 equal to the fp32 MFMA instructions\' (3.4e-8 rms on the warp outputs for both, 4.5-6.8e-7 vs '
+                        '5.2-7.5e-7 relative on the weight gradients; tools/dbg/mlp_split_err.py, wgrad_err.py); `fp32_instructions` '
+                        '(--full) is the same step with those products on v_mfma_f32_32x32x2_f32' if split_bits else
+                        'all MLP products on v_mfma_f32_32x32x2_f32')),
+        'config': {'workload': f'DTU-scan1-like {V}-view {H}x{W}, object-branch train step (ray select, render, '
+                               f'losses, backward, TV+Adam), {G}^3 grid, {cfg.n_samples} samples/ray, '
+                               f'N_rand={N}/GPU; per-step ray permutation + jitter pre-generated on the host and resident '
+                               f'in HBM (the reference draws randperm inside the step)', 'grid': G, 'n_rand_per_gpu': N,
+                   'samples_in_bbox_last_step': int(eng.ws.count.item()), 'parallelism': par},
+    }
+    if os.environ.get('PP_BENCH_SHARED_GPU') == '1':
+        out['rehearsal'] = f'{world} ranks sharing {torch.cuda.device_count()} GPU(s), gloo transport: code-path check, NOT a measurement'
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -584,15 +682,22 @@ def main():
     ap.add_argument('--n-rand', type=int, default=1024)
     ap.add_argument('--hw', type=int, default=400)
     ap.add_argument('--views', type=int, default=3)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32, rank 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything besides the headline figure: per-kernel and roofline figures, the fp32-instruction, '
+                         'drop-in, dual-branch and inference legs, the CPU baseline and the PSNR-parity record')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-budget', type=float, default=20.0)
-    ap.add_argument('--no-dual', action='store_true', help='skip the dual-branch (object + scene) leg')
-    ap.add_argument('--no-inference', action='store_true', help='skip the whole-view inference leg')
-    ap.add_argument('--no-fp32', action='store_true', help='skip the fp32-instruction engine leg (second engine, mlp_split = 0)')
-    ap.add_argument('--no-dropin', action='store_true', help='skip the drop-in train step leg (Voxurf.forward -> object_losses -> backward -> utils.Adam.step)')
-    ap.add_argument('--no-psnr', action='store_true', help='skip the PSNR-parity leg (oracle vs HIP training run)')
+    ap.add_argument('--no-dual', action='store_true', help='with --full: skip the dual-branch (object + scene) leg')
+    ap.add_argument('--no-inference', action='store_true', help='with --full: skip the whole-view inference leg')
+    ap.add_argument('--no-fp32', action='store_true', help='with --full: skip the fp32-instruction engine leg (second engine, mlp_split = 0)')
+    ap.add_argument('--no-dropin', action='store_true', help='with --full: skip the drop-in train step leg (Voxurf.forward -> object_losses -> backward -> utils.Adam.step)')
+    ap.add_argument('--no-psnr', action='store_true', help='with --full: skip the PSNR-parity leg (oracle vs HIP training run)')
     ap.add_argument('--psnr-steps', type=int, default=40, help='long-horizon length of the PSNR-parity leg (>= 25; 96^3 workload, the oracle costs ~0.5-1 s per step and runs twice: itself and its twin)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves - before this process has touched the GPU
@@ -616,6 +721,14 @@ def main():
         sys.stderr.write(f'bench.py: --gpus {args.gpus} but WORLD_SIZE={world} (launch with torch.distributed.run '
                          f'--nproc-per-node {args.gpus}, or without RANK in the environment to let bench.py start the ranks)\n')
         sys.exit(2)
+
+    # every step's randomness (a prefix of a fresh permutation of all V*H*W pixels + per-ray jitter, as the reference draws
+    # per step at recon_scene.py:476,:598) is generated up front on the host - here, before anything initialises the GPU, as
+    # the generator may fork - and is resident on the device when the timed region starts; rank r takes its own ray shard
+    G, H, W, V, N = args.grid, args.hw, args.hw, args.views, args.n_rand
+    total = args.steps + args.warmup
+    extra = min(10, args.steps) if args.full else 0       # untimed post-pass that prices each MLP kernel separately (kernel table)
+    randomness = all_step_randomness(V * H * W, N * world, range(2000, 2000 + total + extra))
     # PP_BENCH_SHARED_GPU=1: REHEARSAL of the N > 1 code path on a box with fewer GPUs - the ranks share the visible cards and the
     # collectives travel over gloo (RCCL refuses two ranks on one device); the record says so and is not a measurement
     rehearsal = os.environ.get('PP_BENCH_SHARED_GPU') == '1'
@@ -636,7 +749,6 @@ def main():
         from poseprobe_amd.dist import DistContext
         dctx = DistContext()
 
-    G, H, W, V, N = args.grid, args.hw, args.hw, args.views, args.n_rand
     rs = syn.range_shape()
     cfg = SceneConfig(syn.XYZ_MIN, syn.XYZ_MAX, G ** 3, out_range=float(rs.max()))
     views = syn.make_views(V, H, W)
@@ -645,27 +757,19 @@ def main():
     init_engine_params(eng, cfg, seed=3)
     eng.zero_grads()
 
-    # every step's randomness (a prefix of a fresh permutation of all V*H*W pixels + per-ray jitter, as the reference draws
-    # per step at recon_scene.py:476,:598) is generated up front on the host and is resident on the device when the timed
-    # region starts; rank r takes its own ray shard
-    total = args.steps + args.warmup
-    extra = min(10, args.steps)          # untimed post-pass that prices each MLP kernel separately (kernel table)
-    idx_all, jit_all = [], []
-    for s in range(total + extra):
-        idx, jit = syn.step_randomness(V * H * W, N * world, seed=2000 + s)
-        idx_all.append(idx[rank::world])
-        jit_all.append(jit[rank::world])
-    idx_all = torch.tensor(np.stack(idx_all), dtype=torch.int32, device=dev)
-    jit_all = torch.tensor(np.stack(jit_all), dtype=torch.float32, device=dev)
+    idx_all = torch.tensor(np.stack([idx[rank::world] for idx, _ in randomness]), dtype=torch.int32, device=dev)
+    jit_all = torch.tensor(np.stack([jit[rank::world] for _, jit in randomness]), dtype=torch.float32, device=dev)
+    del randomness
 
     def barrier():
         if use_dist:
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    # HIP events on the launch stream (torch's current stream == the library's launch stream) around the two candidates for
-    # the longest kernel of the step, INSIDE the timed region: the fused grid pass and the warp MLP's data-gradient kernel
-    from poseprobe_amd import ops
+    # --full: HIP events on the launch stream (torch's current stream == the library's launch stream) around the two
+    # candidates for the longest kernel of the step, INSIDE the timed region: the fused grid pass and the warp MLP's
+    # data-gradient kernel.  A plain run times the step without them.
+    from poseprobe_amd import _lib, ops
     events = {}
 
     def timed(name, fn):
@@ -691,30 +795,54 @@ def main():
     originals = {n: getattr(ops, n) for n in ('grid_tv_adam_step', 'grid_tv_adam_step_sparse', 'warp_bwd_data', 'warp_bwd',
                                               'rgbnet_bwd', 'warp_fwd', 'rgbnet_fwd', 'warp_bwd_weights', 'rgbnet_bwd_data',
                                               'rgbnet_bwd_weights')}
-    ops.grid_tv_adam_step = timed('k_grid_tv_adam', ops.grid_tv_adam_step)                   # dense pass (ZeRO-1 slabs)
-    ops.grid_tv_adam_step_sparse = timed('k_grid_tv_adam', ops.grid_tv_adam_step_sparse)     # same kernel, touched-voxel map
-    ops.warp_bwd_data = timed('k_warp_fused_bwd', ops.warp_bwd_data)
-    ops.warp_bwd_weights = timed('k_wgrad_chain<128> (warp)', ops.warp_bwd_weights)
-    ops.warp_bwd = staged_warp_bwd
+    if args.full:
+        ops.grid_tv_adam_step = timed('k_grid_tv_adam', ops.grid_tv_adam_step)                   # dense pass (ZeRO-1 slabs)
+        ops.grid_tv_adam_step_sparse = timed('k_grid_tv_adam', ops.grid_tv_adam_step_sparse)     # same kernel, touched-voxel map
+        ops.warp_bwd_data = timed('k_warp_fused_bwd', ops.warp_bwd_data)
+        ops.warp_bwd_weights = timed('k_wgrad_chain<128> (warp)', ops.warp_bwd_weights)
+        ops.warp_bwd = staged_warp_bwd
 
+    # Training this model is chaotic: the float atomics of the gradient reductions leave rounding-level differences between
+    # runs, and Adam's sign-like steps grow them until runs of more than a few steps are unrelated.  So the LAST timed step
+    # starts from the seeded initial state again (restored outside the clock): what it computes - the step's outputs and the
+    # state after it - is the same from run to run up to rounding, for any --steps / --warmup.  The other steps train on.
+    initial_state = training_state(eng)
     gs = 10
     for s in range(args.warmup):
         eng.train_step(idx_all[s], jit_all[s], gs + s)
     barrier()
     events.clear()
     t0 = time.perf_counter()
-    for s in range(args.warmup, total):
+    for s in range(args.warmup, total - 1):
         eng.train_step(idx_all[s], jit_all[s], gs + s)
     barrier()
     dt = time.perf_counter() - t0
+    restore_training_state(eng, initial_state)
+    del initial_state
+    barrier()
+    t0 = time.perf_counter()
+    eng.train_step(idx_all[total - 1], jit_all[total - 1], gs + total - 1)
+    barrier()
+    dt += time.perf_counter() - t0
     if use_dist:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        write_outputs(eng, args.dump_outputs)          # before anything below runs more steps on this engine
+    split_bits = _lib.get_option('mlp_split') if _lib.get_option('mlp_fused') else 0
+    out = headline_record(args, eng, cfg, dt, world, split_bits, dctx)
+    if not args.full:
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(out) + '\n').encode())
+        if use_dist:
+            torch.distributed.destroy_process_group()
+        return
+
     M = int(eng.ws.count.item())
     mean_ms = lambda name: float(np.mean([a.elapsed_time(b) for a, b in events[name]])) if events.get(name) else float('nan')
     grid_ms, warp_bwd_ms, wgrad_ms = mean_ms('k_grid_tv_adam'), mean_ms('k_warp_fused_bwd'), mean_ms('k_wgrad_chain<128> (warp)')
-    exchange_rows = None if dctx is None else dctx.rows
 
     # post-pass (untimed): every MLP kernel on its own event pair -> kernel table and the MLP-chain roofline
     events.clear()
@@ -738,7 +866,6 @@ def main():
     # both arithmetic paths of the MLP kernels are on the record (same engine, the same pre-generated rays reused)
     # A SECOND engine with its own pp_context (mlp_split = 0) beside the default one: options are per context, nothing
     # process-wide is flipped.
-    from poseprobe_amd import _lib
     split_default = _lib.get_option('mlp_split')
     fp32_path = None
     if split_default and _lib.get_option('mlp_fused') and not use_dist and not args.no_fp32:
@@ -765,7 +892,6 @@ def main():
              'k_wgrad_chain<64> (rgbnet)': 2 * (64 * 128 + 2 * 128 * 128)}          # MFMA-shaped FLOP per sample
     # which kernels run their 128 x 128 products as three fp16 MFMA products per fp32 product (option mlp_split, pp_mlp_split.hip):
     # those are priced against the fp16 pipe with the FLOPs they actually issue (3 x), the others against the fp32 instructions
-    split_bits = _lib.get_option('mlp_split') if _lib.get_option('mlp_fused') else 0
     split_of = {'k_warp_fused_fwd': split_bits & 1, 'k_warp_fused_bwd': split_bits & 2, 'k_rgb_fused_fwd': split_bits & 4,
                 'k_rgb_fused_bwd': split_bits & 8, 'k_wgrad_chain<128> (warp)': split_bits & 16, 'k_wgrad_chain<64> (rgbnet)': split_bits & 16}
 
@@ -847,29 +973,8 @@ def main():
         dual = dual_branch_leg(eng, idx_all, jit_all, gs, N, V, H, W, dt / args.steps * 1e3, dev)
 
     if rank == 0:
-        if world > 1:
-            par = (f'ray-sharded dp{world}, k0 gradient exchanged per sample (all-gather of {exchange_rows} rows x 64 B per rank), replicated grid optimiser'
-                   if dctx.mode == 'samples' else f'ray-sharded dp{world}, dense reduce-scatter + ZeRO-1 grid optimiser')
-        else:
-            par = 'single GPU'
-        out = {
-            'metric': 'rays_per_sec_train_step', 'value': N * world * args.steps / dt, 'unit': 'rays/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'f32 (3xf16-split products)' if split_bits else 'f32', 'data': 'synthetic',
-            'arithmetic': ('fp32 operands, accumulation and results everywhere; ' +
-                           ('the 128 x 128 products of the two MLPs are evaluated as three fp16 MFMA products per fp32 product '
-                            '(operands split into 11 + 11 significant bits with a power-of-two scale, fp32 accumulation): measured error '
-                            'against fp64 equal to the fp32 MFMA instructions\' (3.4e-8 rms on the warp outputs for both, 4.5-6.8e-7 vs '
-                            '5.2-7.5e-7 relative on the weight gradients; tools/dbg/mlp_split_err.py, wgrad_err.py); `fp32_instructions` '
-                            'is the same step with those products on v_mfma_f32_32x32x2_f32' if split_bits else
-                            'all MLP products on v_mfma_f32_32x32x2_f32')),
+        out.update({
             'fp32_instructions': fp32_path,
-            'config': {'workload': f'DTU-scan1-like {V}-view {H}x{W}, object-branch train step (ray select, render, '
-                                   f'losses, backward, TV+Adam), {G}^3 grid, {cfg.n_samples} samples/ray, '
-                                   f'N_rand={N}/GPU; per-step ray permutation + jitter pre-generated on the host and resident '
-                                   f'in HBM (the reference draws randperm inside the step)', 'grid': G, 'n_rand_per_gpu': N,
-                       'samples_in_bbox_last_step': M, 'parallelism': par},
             'roofline': dominant, 'roofline_step': roofline_step, 'dropin_train_step': dropin, 'roofline_grid': roofline_grid,
             'roofline_mlp': {'bound': 'mfma', 'kernel': 'warp + rgbnet MLP chains (6 layer-fused kernels: fwd / bwd-data / weight-gradient); ALGORITHMIC '
                                                         'fp32 FLOP/s of the six kernels together over the fp32 MFMA peak - the kernels listed with an fp16 pipe '
@@ -877,9 +982,7 @@ def main():
                              'achieved': mlp_tflops, 'peak': FP32_MFMA_PEAK_TF, 'unit': 'TFLOP/s', 'frac': mlp_tflops / FP32_MFMA_PEAK_TF,
                              'traffic': None, 'ms_per_step': mlp_ms, 'flop_per_sample': flop_per_sample, 'kernels': kernels,
                              'measured': f'untimed post-pass of {extra} steps, one HIP event pair per kernel'},
-        }
-        if rehearsal:
-            out['rehearsal'] = f'{world} ranks sharing {torch.cuda.device_count()} GPU(s), gloo transport: code-path check, NOT a measurement'
+        })
         out['dual_branch'] = dual
         if dual is not None:
             out['dual_branch_rays_per_s'] = dual['coarse_phase']['rays_per_s']

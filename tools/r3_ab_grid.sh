@@ -1,6 +1,6 @@
 set -e
 mkdir -p gpurun_out
-F="--gpus 1 --steps 60 --warmup 5 --no-psnr --no-cpu-baseline --no-dual --no-dropin --no-inference --no-fp32"
+F="--gpus 1 --steps 60 --warmup 5 --full --no-psnr --no-cpu-baseline --no-dual --no-dropin --no-inference --no-fp32"
 for skew in 0 12288 4096 16384 53248 0 12288; do
   PP_GRID_SKEW=$skew python bench.py $F 2>/dev/null | python -c "
 import json,sys

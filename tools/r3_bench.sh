@@ -1,12 +1,13 @@
 set -e
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
 start=$(date +%s)
-timeout -k 10 1000 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r3_bench.json 2> gpurun_out/r3_bench.err
+timeout -k 10 1000 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/r3_bench.json 2> $OUT/r3_bench.err
 end=$(date +%s)
 echo "bench wall: $((end-start)) s"
-python - <<'PY'
-import json
-d=json.loads(open('gpurun_out/r3_bench.json').read().strip().splitlines()[-1])
+OUT=$OUT python - <<'PY'
+import json, os
+d=json.loads(open(os.path.join(os.environ['OUT'], 'r3_bench.json')).read().strip().splitlines()[-1])
 print({k:d[k] for k in ('value','ms_per_step','dtype')})
 print('roofline', {k:d['roofline'][k] for k in ('kernel','frac','ms_per_launch')})
 print('roofline_step', {k:(v if not isinstance(v,dict) else {kk:v[kk] for kk in ('bytes','frac')}) for k,v in d['roofline_step'].items()})
