@@ -224,15 +224,15 @@ int pp_color_feat_bwd(const pp_scene* sc, const float* k0_cl, const float* pts, 
  * coexist in one process and on concurrent threads (a context itself must not be modified while a call uses it).
  * Names (meaning and ranges: csrc/pp_common.h, csrc/pp_error.hip):
  *   arithmetic   mlp_split (bit mask: object-branch MLP kernels as 3 fp16 products per fp32 product; 0 = fp32 MFMA instructions),
- *                nerf_split, nerf_split_tn (scene branch likewise), mlp_fused, wgrad_split, nerf_bitmask, nerf_planes, nerf_chain, nerf_tn256, nerf_tn_tr
- *   scheduling   side_stream, mlp_wgs, wgrad_side_wgs, grid_chunks, nerf_gemm_wgs, nerf_tn_ch, nerf_tn_split_wgs, nerf_tn_wgs, nerf_bn, nerf_chain_nw, nerf_chain_head
+ *                nerf_split (scene branch likewise), mlp_fused, nerf_chain
+ *   scheduling   side_stream, mlp_wgs, wgrad_side_wgs, grid_chunks, nerf_chain_nw, nerf_chain_head
  * pp_nerf_fwd and pp_nerf_bwd of one pass (and the two stages of a two-stage backward) must see the same option values.
  * Unknown names / out-of-range values are refused; pp_context_get_option(NULL, ...) reads the defaults. */
 int pp_context_create(void** ctx);
 int pp_context_destroy(void* ctx);
 int pp_context_set_option(void* ctx, const char* name, int32_t value);
 int pp_context_get_option(const void* ctx, const char* name, int32_t* value);
-/* Option side_stream = 1 (2: rgbnet only): the weight-gradient kernel of pp_rgbnet_bwd / pp_mlp_bwd / pp_warp_bwd is launched
+/* Option side_stream = 1: the weight-gradient kernel of pp_rgbnet_bwd / pp_mlp_bwd / pp_warp_bwd is launched
  * on the context's auxiliary stream and NOT joined before the call returns, so that the caller's next (small) kernels run
  * beside it (fork / join are event edges: the sequence stays hipGraph-capturable).  Call pp_context_join before `scratch` is
  * reused, before params_grad is read, and at most 4 forks apart: it makes `stream` wait for every deferred launch issued so
@@ -441,8 +441,8 @@ int pp_march_dvgo_fwd(const float* alpha, const float* rgb, const float* step_w,
  * weights of the 10 point bands then the 4 view bands (ones without a schedule).  count: device int32 holding R * S.
  * Workspaces in floats from pp_nerf_workspace(R * S, R, &acts, &scratch).
  * Arithmetic: fp32 operands and accumulation; the forward / data-gradient / weight-gradient matrix products are evaluated as
- * three fp16 products per fp32 product (error against fp64 equal to the fp32 matrix instructions'); options
- * nerf_split = 0 / nerf_split_tn = 0 (of the context handed to the call) select the fp32 matrix instructions instead. */
+ * three fp16 products per fp32 product (error against fp64 equal to the fp32 matrix instructions'); option
+ * nerf_split = 0 (of the context handed to the call) selects the fp32 matrix instructions instead. */
 int pp_nerf_layout(int64_t* offsets);
 int pp_nerf_workspace(int64_t n_samples, int64_t n_rays, int64_t* acts_floats, int64_t* scratch_floats);
 int pp_nerf_fwd(const float* params, const float* center, const float* ray, const float* depth, const float* bands,

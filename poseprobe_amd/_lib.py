@@ -90,9 +90,8 @@ def header_abi_version(path=HEADER):
 # (include/poseprobe_hip.h).  The Python host keeps ONE default context per process for callers that do not bring their own;
 # PP_<NAME>=<int> in the host's environment seeds it once.  set_option / get_option below act on that host-side default
 # context (A/B scripts, tests); engines built with `options=...` own a private context and are unaffected by it.
-OPTION_NAMES = ('mlp_fused', 'wgrad_split', 'grid_chunks', 'nerf_split', 'nerf_split_tn', 'nerf_bitmask', 'nerf_gemm_wgs',
-                'nerf_tn_ch', 'nerf_tn_split_wgs', 'nerf_tn_wgs', 'nerf_bn', 'nerf_planes', 'mlp_split', 'nerf_tn256', 'mlp_wgs',
-                'wgrad_side_wgs', 'side_stream', 'nerf_chain', 'nerf_chain_nw', 'nerf_chain_head', 'nerf_tn_tr')
+OPTION_NAMES = ('mlp_fused', 'grid_chunks', 'nerf_split', 'mlp_split', 'mlp_wgs', 'wgrad_side_wgs', 'side_stream', 'nerf_chain',
+                'nerf_chain_nw', 'nerf_chain_head')
 
 
 class Context:
@@ -134,8 +133,6 @@ def default_context():
             v = os.environ.get('PP_' + name.upper())
             if v not in (None, ''):
                 c.set(name, int(v))
-        if os.environ.get('PP_SIDE_STREAM') in ('1', '2'):
-            c.set('side_stream', int(os.environ['PP_SIDE_STREAM']))
         _default_ctx = c
     return _default_ctx
 

@@ -16,29 +16,18 @@ void pp_set_error(const char* fmt, ...);
 // The library holds NO process-wide mutable state and never reads the environment.
 enum PPOption {
   PP_OPT_MLP_FUSED = 0,        // 1: layer-fused object-branch MLP kernels, 0: layer-by-layer GEMMs (A/B runs)
-  PP_OPT_WGRAD_SPLIT,          // 1: split-precision weight-gradient kernels in the object branch (measured slower)
   PP_OPT_GRID_CHUNKS,          // x-chunks of the fused TV + Adam pass (0 = heuristic)
-  PP_OPT_NERF_SPLIT,           // scene branch: NT products as three fp16 products (1) or on the fp32 instructions (0)
-  PP_OPT_NERF_SPLIT_TN,        // scene branch: weight-gradient products likewise
-  PP_OPT_NERF_BITMASK,         // scene branch: one-bit ReLU masks
-  PP_OPT_NERF_GEMM_WGS,        // scene branch: persistent work-groups per column block
-  PP_OPT_NERF_TN_CH,           // scene branch: rows per LDS chunk of the fp32 weight-gradient GEMM (32 | 64)
-  PP_OPT_NERF_TN_SPLIT_WGS,    // scene branch: row splits of the split-precision weight-gradient kernel
-  PP_OPT_NERF_TN_WGS,          // scene branch: row splits of the fp32 weight-gradient kernel
-  PP_OPT_NERF_BN,              // scene branch: 256 selects the 128 x 256 tile of the fp32 NT GEMM
-  PP_OPT_NERF_PLANES,          // scene branch: 1 = activations travel as pre-split fp16 hi / lo planes (pp_gemm_planes.h)
+  PP_OPT_NERF_SPLIT,           // scene branch: every matrix product as three fp16 products (1) or on the fp32 instructions (0)
   PP_OPT_MLP_SPLIT,            // bit mask: layer-fused object-branch MLP kernels with three fp16 products per fp32 product (pp_mlp_split.hip); 1 warp fwd, 2 warp bwd, 4 rgb fwd, 8 rgb bwd, 16 weight-gradient chains
-  PP_OPT_NERF_TN256,           // scene branch: 1 = 256 x 256 weight gradients by the one-work-group-per-row-range kernel (pp_gemm_tn256.h; measured equal: 127 vs 123 us)
   PP_OPT_MLP_WGS,              // work-groups of the persistent object-branch MLP kernels (0 = one per CU); fewer leave CUs to a concurrent HBM-bound kernel
   PP_OPT_WGRAD_SIDE_WGS,       // work-groups of a weight-gradient chain kernel launched on a pp_context's auxiliary stream (0 = as on the main stream):
                                // fewer leave whole CUs to the small kernels that run beside it
   PP_OPT_SIDE_STREAM,          // 1: the weight-gradient kernels of both object-branch MLP chains are forked onto the context's auxiliary stream
-                               // (joined by pp_context_join), 2: rgbnet's only, 0 (default): strictly sequential on the caller's stream
+                               // (joined by pp_context_join), 0 (default): strictly sequential on the caller's stream
   PP_OPT_NERF_CHAIN,           // scene branch: bit 1 = the eight feature layers + density head of the forward pass as one kernel with the tile resident in LDS
                                // (pp_nerf_trunk.h), 3 = the data-gradient chain of the backward pass too (0 = one GEMM per layer)
   PP_OPT_NERF_CHAIN_NW,        // scene branch: wavefronts per work-group of the fused chains (8: one 128-sample tile per CU, 4: two 64-sample tiles per CU)
   PP_OPT_NERF_CHAIN_HEAD,      // scene branch: 1 = the colour head's hidden layer as a ninth stage of the fused forward chain
-  PP_OPT_NERF_TN_TR,           // scene branch: 1 = weight-gradient kernel with row-major LDS images and transposed fragment reads (k_gemm_tn_tr)
   PP_OPT_COUNT
 };
 

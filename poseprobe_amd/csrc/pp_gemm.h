@@ -67,9 +67,9 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TNW], int r0, in
 
 // C[r][n] = epi( sum_k A[r][k] * B(n,k) ),  NT: B(n,k) = W[n*ldw + k]   NN: B(n,k) = W[k*ldw + n]
 // Register budget: the 128-column tile is left to the compiler (it takes 190-280 registers, 1-2 wavefronts per SIMD; capping
-// it at 168 for three work-groups per CU measured 10 % slower); the 256-column tile is capped at 256.
+// it at 168 for three work-groups per CU measured 10 % slower).
 template <int MODE, int EPI, int COLS, int BM, int BN = 128, bool BITS = false>
-__global__ __launch_bounds__(256, ((BN == 256 || (EPI == EPI_MASK && BM == 128)) ? 2 : 1)) void k_gemm128(const float* __restrict__ A, int lda, const float* __restrict__ W_,
+__global__ __launch_bounds__(256, ((EPI == EPI_MASK && BM == 128) ? 2 : 1)) void k_gemm128(const float* __restrict__ A, int lda, const float* __restrict__ W_,
                                                  int ldw, int K, int Nout_, const float* __restrict__ bias_,
                                                  const float* __restrict__ Xmask_, int ldm, float* __restrict__ C_,
                                                  int ldc, const int32_t* __restrict__ count, int rmul, int rcap,
@@ -171,14 +171,6 @@ __global__ __launch_bounds__(256, ((BN == 256 || (EPI == EPI_MASK && BM == 128))
     else
       gemm_epilogue<EPI, COLS, false, TM, TNW, BITS>(acc, r0, R, Nout, wr, wc, l31, lh, bias, Xmask, ldm, C, ldc, bits16, cb);
   }
-}
-
-// dst[c][r] = src[r][c]  (weights are tiny: 128x128 / 128x64); lets the backward-data GEMM run in the same NT form
-static __global__ __launch_bounds__(256) void k_transpose(const float* __restrict__ src, float* __restrict__ dst, int rows, int cols) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows * cols) return;
-  int c = i / rows, r = i - c * rows;           // consecutive threads write consecutive dst elements
-  dst[i] = src[r * cols + c];
 }
 
 // Wbar[n][k] += sum_r Y[r][n] * X[r][k]   (n < 128, k < Kx) ;  bbar[n] += sum_{r % COLS == 0} Y[r][n]

@@ -23,6 +23,14 @@
 
 #include "pp_gemm.h"
 
+// dst[c][r] = src[r][c]  (weights are tiny: 128x128 / 128x64); lets the backward-data GEMM run in the same NT form
+static __global__ __launch_bounds__(256) void k_transpose(const float* __restrict__ src, float* __restrict__ dst, int rows, int cols) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * cols) return;
+  int c = i / rows, r = i - c * rows;           // consecutive threads write consecutive dst elements
+  dst[i] = src[r * cols + c];
+}
+
 // ------------------------------------------------------------------------------------------------ small layers
 // warp layer 0 (3 -> 128) in 4-row form.  block = 2 samples x 128 features.
 __global__ __launch_bounds__(256) void k_warp_l0_fwd(const float* __restrict__ W0, const float* __restrict__ b0,
@@ -252,9 +260,9 @@ static const int TN_WGS = 448;
 // nothing downstream needs it before the optimiser, so with a context it is launched on the auxiliary stream and NOT
 // joined here: the caller's next kernels (small, latency-bound ones: colour-feature / geometry backward, ray and pose
 // backward) run beside it, and pp_context_join() is called before the scratch buffer or the gradients are touched again.
-static hipStream_t deferred_fork(void* ctx, hipStream_t main, int min_mode = 1) {
+static hipStream_t deferred_fork(void* ctx, hipStream_t main) {
   PPContext* c = static_cast<PPContext*>(ctx);
-  if (!c || c->opt[PP_OPT_SIDE_STREAM] < min_mode || c->pending >= 4 || !pp_context_aux(c)) return main;
+  if (!c || c->opt[PP_OPT_SIDE_STREAM] == 0 || c->pending >= 4 || !pp_context_aux(c)) return main;
   hipEventRecord(c->dfork[c->pending], main);
   hipStreamWaitEvent(c->aux, c->dfork[c->pending], 0);
   return c->aux;
@@ -362,7 +370,7 @@ extern "C" int pp_mlp_bwd(const float* params, const float* feat, int32_t in_ld,
     else pp_launch_rgb_fused_bwd(params, acts, out, out_grad, count, capacity, scratch, params_grad, feat_grad, logit_add_grad,
                                  logit_add_ld, st);
     const size_t FLS = (size_t)capacity * 128;
-    hipStream_t ws = deferred_fork(ctx, st, 1);
+    hipStream_t ws = deferred_fork(ctx, st);
     pp_launch_wgrad_chain(scratch, acts + FLS, params_grad + RGF_W2, scratch + FLS, acts, params_grad + RGF_W1,
                           scratch + 2 * FLS, feat, params_grad + RGF_W0, 64, count, 1, capacity, ws,
                           sb ? params_grad + RGF_B2 : nullptr, sb ? params_grad + RGF_B1 : nullptr, sb ? params_grad + RGF_B0 : nullptr,
@@ -465,7 +473,7 @@ extern "C" int pp_warp_bwd(const float* params, const float* pts, const float* a
     // one fused data-gradient kernel (+ thin layers), then the three weight-gradient GEMMs on the Ybar it left behind
     if (pp_opt(PP_OPT_MLP_SPLIT) & 2) pp_launch_warp_fused_bwd_s(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st);
     else pp_launch_warp_fused_bwd(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st);
-    hipStream_t ws = deferred_fork(ctx, st, 1);                // option side_stream = 2 keeps the warp chain sequential
+    hipStream_t ws = deferred_fork(ctx, st);
     const bool sb = (pp_opt(PP_OPT_MLP_SPLIT) & 2) != 0;   // the split-precision data-gradient kernel leaves b1..b3 to this one
     pp_launch_wgrad_chain(scratch, acts + 2 * LS, params_grad + WP_W3, scratch + LS, acts + LS, params_grad + WP_W2,
                           scratch + 2 * LS, acts, params_grad + WP_W1, 128, count, 4, rcap, ws,

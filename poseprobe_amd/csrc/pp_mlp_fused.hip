@@ -14,7 +14,6 @@
 #include "pp_common.h"
 #include "pp_mlp_fused.h"
 #include "pp_wgrad_asm.inc"
-#include "pp_gemm_split.h"
 #include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -763,26 +762,11 @@ __global__ __launch_bounds__(256) void k_wgrad_chain(WgradLayer LA, WgradLayer L
   if (LC.bbar) atomicAdd(&LC.bbar[tid & 127], bC);
 }
 
-// option "wgrad_split" = 1 replaces the fp32-instruction chain kernel above by three launches of the self-scaling split-precision
-// kernel.  Parity suite green, but SLOWER on MI355X (1.405 vs 1.356 ms per step): the chain kernel reads each operand once,
-// keeps 192 accumulators resident and is hand-scheduled; three load-bound launches with an extra barrier per chunk are not
-// a match for it.  Off by default; kept as the starting point for a fused split-precision chain.
-static bool wgrad_split_enabled() { return pp_opt(PP_OPT_WGRAD_SPLIT) == 1; }
-
 int pp_launch_wgrad_chain(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                           const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
                           hipStream_t st, float* bA, float* bB, float* bC, int wgs) {
   if (pp_opt(PP_OPT_MLP_SPLIT) & 16)            // split-precision chain kernel (pp_mlp_split.hip): bias sums included when asked for
     return pp_launch_wgrad_chain_s(YA, XA, WA, YB, XB, WB, YC, XC, WC, kxc, count, rmul, rcap, st, bA, bB, bC, wgs);
-  if (wgrad_split_enabled() && !bA) {
-    // three launches of the self-scaling split-precision kernel (pp_gemm_split.h): three fp16 products per fp32 product,
-    // error against fp64 equal to the fp32 matrix instructions'; load-bound instead of matrix-pipe bound
-    const int splits = rcap >= 131072 ? 256 : 128;
-    hipLaunchKernelGGL(k_gemm_tn_split_auto, dim3(splits), dim3(256), 0, st, YA, XA, 128, 128, WA, 128, count, rmul, rcap);
-    hipLaunchKernelGGL(k_gemm_tn_split_auto, dim3(splits), dim3(256), 0, st, YB, XB, 128, 128, WB, 128, count, rmul, rcap);
-    hipLaunchKernelGGL(k_gemm_tn_split_auto, dim3(splits), dim3(256), 0, st, YC, XC, kxc, kxc, WC, kxc, count, rmul, rcap);
-    return 0;
-  }
   WgradLayer LA{YA, XA, WA, bA}, LB{YB, XB, WB, bB}, LC{YC, XC, WC, bC};
   const int npairs = pp_div_up(rcap, 2 * TILE_ROWS);
   const int cap_wgs = wgs > 0 ? (wgs < 16 ? 16 : wgs) : PP_FUSED_WGS;

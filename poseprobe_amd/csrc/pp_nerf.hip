@@ -1,7 +1,7 @@
 // Scene branch (lib/bg_nerf): the 8 x 256 NeRF MLP with BARF positional encoding and exp-cumsum compositing, forward and
 // backward.  fp32 in memory, fp32 accumulation, fp32-accurate matrix products: every product runs as three fp16 products on
 // v_mfma_f32_32x32x16_f16 (pp_gemm_split.h; error against fp64 equal to the fp32 matrix instructions'); option
-// "nerf_split" = 0 selects the fp32 instructions (pp_gemm.h) for all of them, "nerf_split_tn" = 0 for the weight gradients only.
+// "nerf_split" = 0 selects the fp32 instructions (pp_gemm.h) for all of them.
 //
 //   reference: lib/bg_nerf/source/models/frequency_nerf.py
 //     :42-69    FrequencyEmbedder          (sin / cos of 2^l * pi * x, layout [coordinate][sin|cos][band])
@@ -18,12 +18,11 @@
 // With the three-product scheme the matrix time drops to a third and the GEMMs become load-bound.  The thin
 // ends of the network (encoding, density head, 128 -> 3 colour head, compositing, encoding backward) are bandwidth-bound
 // streaming kernels.
-#define PP_NERF_TU 1
 #include "pp_common.h"
 #include "pp_gemm.h"
 #include "pp_gemm_split.h"
 #include "pp_gemm_planes.h"
-#include "pp_gemm_tn256.h"
+#include "pp_gemm_tn_tr.h"
 
 #define NERF_L3D 10
 #define NERF_LV 4
@@ -657,40 +656,21 @@ __global__ __launch_bounds__(256) void k_nerf_encode_bwd(const float* __restrict
 
 // ------------------------------------------------------------------------------------------------ host side
 static const int NERF_BM = 128;
-// Tuning options (pp_set_option; defaults = the measured best on MI355X):
-//   nerf_gemm_wgs      persistent work-groups per column block (256 = 512 > 384 > 128)
-//   nerf_tn_ch         rows per LDS chunk of the fp32 weight-gradient GEMM (32 | 64)
-//   nerf_tn_split_wgs  row splits of the split-precision weight-gradient kernel
-//   nerf_tn_wgs        row splits of a weight-gradient block: 128 x 4 blocks = 2 work-groups per CU, one round
-//   nerf_bn = 256      128 x 256 tiles for the fp32 NT GEMM (activation tile read once, half the barriers per MFMA).  Measured
-//                      SLOWER (3072 x 128 samples: 15.8 vs 13.8 ms per step): 128 accumulators + operand staging do not fit 256
-//                      registers without spills inside the K loop.  Kept for A/B runs.
-//   nerf_split         NT GEMMs (forward and data gradients) as three fp16 products with fp32 accumulation (pp_gemm_split.h:
-//                      error against fp64 equal to the fp32 matrix instructions', a third of their matrix-pipe time); 0 puts
-//                      them on the fp32 matrix instructions (A/B runs, bisecting)
-//   nerf_split_tn      the same for the weight-gradient products
-//   nerf_bitmask       one-bit ReLU masks (pp_gemm.h gemm_epilogue): the forward epilogue packs a lane's 16 rows of a column into
-//                      a 16-bit word, the data-gradient epilogue reads that word instead of 16 floats of the forward activation
-//                      (neutral for the exact-fp32 path, -11..-17 % with the split-precision path)
-#define NERF_GEMM_WGS pp_opt(PP_OPT_NERF_GEMM_WGS)
-static const int NERF_GEMM_WGS_WIDE = 512;   // 128 x 256 tiles: 2 resident per CU (55 KB LDS, ~220 registers)
-#define NERF_TN_CH pp_opt(PP_OPT_NERF_TN_CH)
-#define NERF_TN_SPLIT_WGS pp_opt(PP_OPT_NERF_TN_SPLIT_WGS)
-#define NERF_TN_WGS pp_opt(PP_OPT_NERF_TN_WGS)
-static int nerf_wide_tiles() { return pp_opt(PP_OPT_NERF_BN) == 256; }
+static constexpr int NERF_GEMM_WGS = 256;   // persistent work-groups per column block of the NT GEMMs (measured 256 = 512 > 384 > 128)
+static constexpr int NERF_TN_WGS = 128;     // row splits of a weight-gradient block: 128 x 4 blocks = 2 work-groups per CU, one round
+// Options (pp_context_set_option; defaults = the measured best on MI355X):
+//   nerf_split         every matrix product (forward, data and weight gradients) as three fp16 products with fp32 accumulation
+//                      (pp_gemm_split.h: error against fp64 equal to the fp32 matrix instructions', a third of their matrix-pipe
+//                      time); the 256-wide layers on pp_gemm_planes.h (weights pre-split into LDS images once per pass, 128 x 256
+//                      tile on eight wavefronts).  0 puts all of them on the fp32 matrix instructions (A/B runs, bisecting)
 #define NERF_SPLIT (pp_opt(PP_OPT_NERF_SPLIT) == 1)
-#define NERF_SPLIT_TN (pp_opt(PP_OPT_NERF_SPLIT_TN) == 1)
-#define NERF_TN256 (pp_opt(PP_OPT_NERF_TN256) == 1)
-#define NERF_BITMASK (pp_opt(PP_OPT_NERF_BITMASK) == 1)
-//   nerf_planes        256-wide layers on the second-generation kernel (pp_gemm_planes.h: weights pre-split into LDS images once
-//                      per pass, 128 x 256 tile on eight wavefronts); needs nerf_split and nerf_bitmask; 0 = first generation
-#define NERF_PLANES (pp_opt(PP_OPT_NERF_PLANES) == 1 && NERF_SPLIT && NERF_BITMASK)
 //   nerf_chain         forward pass: the eight feature layers and the density head as ONE kernel that keeps a 128-sample tile in LDS
-//                      across the layers (pp_nerf_trunk.h); needs nerf_planes; 0 = one GEMM per layer
+//                      across the layers (pp_nerf_trunk.h); needs nerf_split (every use below is behind the operand maxima `mx`);
+//                      0 = one GEMM per layer
 //                      bit 2 (value 3): the data-gradient chain of the backward pass likewise; the ReLU masks then travel in the
 //                      fused kernels' own layout, so both passes of a step must see the same value
-#define NERF_CHAIN ((pp_opt(PP_OPT_NERF_CHAIN) & 1) && NERF_PLANES)
-#define NERF_CHAIN_BWD (pp_opt(PP_OPT_NERF_CHAIN) == 3 && NERF_PLANES)
+#define NERF_CHAIN (pp_opt(PP_OPT_NERF_CHAIN) & 1)
+#define NERF_CHAIN_BWD (pp_opt(PP_OPT_NERF_CHAIN) == 3)
 //   nerf_chain_nw      wavefronts per work-group of the fused chains: 8 = one work-group on a 128-sample tile per CU, 4 = two work-groups on
 //                      64-sample tiles per CU (one's epilogue beside the other's matrix instructions; twice the weight traffic from L2)
 #define NERF_CHAIN_NW pp_opt(PP_OPT_NERF_CHAIN_NW)
@@ -704,8 +684,7 @@ static void nerf_gemm(hipStream_t st, const float* A, int lda, const float* W, i
                       uint16_t* bits = nullptr, const _Float16* wimg = nullptr) {
   const int tiles = pp_div_up(rows, NERF_BM);
   dim3 b(256);
-  if (!NERF_BITMASK) bits = nullptr;
-  if (wimg && bits && EPI != EPI_PLAIN && Nout == 256 && (K & 31) == 0 && a_max && w_max && NERF_PLANES) {
+  if (wimg && bits && EPI != EPI_PLAIN && Nout == 256 && (K & 31) == 0 && a_max && w_max && NERF_SPLIT) {
     const int cus = pp_num_cus();
     constexpr int E = (EPI == EPI_PLAIN) ? EPI_MASK : EPI;
     hipLaunchKernelGGL((k_gemm256p<E>), dim3(tiles < cus ? tiles : cus), dim3(512), 0, st, A, lda, wimg, K, bias, C, ldc, count, rows,
@@ -722,12 +701,6 @@ static void nerf_gemm(hipStream_t st, const float* A, int lda, const float* W, i
       hipLaunchKernelGGL((k_gemm128s<EPI, 128>), g, b, 0, st, A, lda, W, ldw, K, Nout, bias, mask, ldm, C, ldc, count, rows, a_max,
                          w_max, c_max, bits);
     }
-    return;
-  }
-  if (Nout == 256 && nerf_wide_tiles()) {    // 128 x 256 tile: the activation tile is read once, half the barriers per MFMA
-    dim3 g(tiles < NERF_GEMM_WGS_WIDE ? tiles : NERF_GEMM_WGS_WIDE, 1);
-    hipLaunchKernelGGL((k_gemm128<MODE_NT, EPI, 1, NERF_BM, 256>), g, b, 0, st, A, lda, W, ldw, K, Nout, bias, mask, ldm, C,
-                       ldc, count, 1, rows);
     return;
   }
   if (Nout <= 64) {                          // encoding / view-direction gradients: 64-column tile instead of a half-empty one
@@ -747,29 +720,14 @@ static void nerf_gemm(hipStream_t st, const float* A, int lda, const float* W, i
 
 static void nerf_gemm_tn(hipStream_t st, const float* Y, int ldy, int N, const float* X, int ldx, int Kx, float* Wbar,
                          float* bbar, const int32_t* count, int rows, const float* y_max = nullptr, const float* x_max = nullptr) {
-  if (NERF_SPLIT && NERF_SPLIT_TN && NERF_TN256 && y_max && x_max && N == 256 && Kx >= 256) {
-    // all 256 x 256 outputs of a row range in one work-group (pp_gemm_tn256.h); the 64 skip columns of layer 4 go the old way
-    const int tiles = pp_div_up(rows, TN256_ROWS);
-    const int grid = tiles < pp_num_cus() ? tiles : pp_num_cus();
-    hipLaunchKernelGGL(k_gemm_tn256, dim3(grid), dim3(512), 0, st, Y, ldy, X, ldx, Wbar, ldx, bbar, count, rows, y_max, x_max);
-    if (Kx > 256) nerf_gemm_tn(st, Y, ldy, N, X + 256, ldx, Kx - 256, Wbar + 256, nullptr, count, rows, y_max, x_max);
-    return;
-  }
   const int blocks = (N / 128) * pp_div_up(Kx, 128);
-  dim3 b(256);
-  if (NERF_SPLIT && NERF_SPLIT_TN && y_max && x_max) {     // two work-groups per CU (option nerf_tn_split_wgs = 128) since the operand conversion
-                                                           // is three instructions per pair: 2.90 vs 2.99 ms per scene step (round 1, with the
-                                                           // compiler's conversion: one per CU was best, 3.69 vs 3.85 ms)
-    dim3 gs(NERF_TN_SPLIT_WGS * 4 / blocks, blocks);
-    if (pp_opt(PP_OPT_NERF_TN_TR) == 1) hipLaunchKernelGGL(k_gemm_tn_tr, gs, b, 0, st, Y, ldy, X, ldx, Kx, Wbar, ldx, bbar, count, rows, y_max, x_max);
-    else hipLaunchKernelGGL(k_gemm_tn_split, gs, b, 0, st, Y, ldy, X, ldx, Kx, Wbar, ldx, bbar, count, rows, y_max, x_max);
-    return;
-  }
-  dim3 g(NERF_TN_WGS * 4 / blocks, blocks);               // ~ 4 x NERF_TN_WGS work-groups whatever the block count (2, 3, 4 or 6)
-  if (NERF_TN_CH == 64)
-    hipLaunchKernelGGL((k_gemm_tn<1, 64>), g, b, 0, st, Y, ldy, X, ldx, Kx, Wbar, ldx, bbar, count, 1, rows);
+  dim3 g(NERF_TN_WGS * 4 / blocks, blocks), b(256);       // ~ 4 x NERF_TN_WGS work-groups whatever the block count (2, 3, 4 or 6)
+  if (NERF_SPLIT && y_max && x_max)     // two work-groups per CU since the operand conversion is three instructions per pair: 2.90
+                                        // vs 2.99 ms per scene step (round 1, with the compiler's conversion: one per CU was best,
+                                        // 3.69 vs 3.85 ms)
+    hipLaunchKernelGGL(k_gemm_tn_tr, g, b, 0, st, Y, ldy, X, ldx, Kx, Wbar, ldx, bbar, count, rows, y_max, x_max);
   else
-    hipLaunchKernelGGL((k_gemm_tn<1>), g, b, 0, st, Y, ldy, X, ldx, Kx, Wbar, ldx, bbar, count, 1, rows);
+    hipLaunchKernelGGL((k_gemm_tn<1, 64>), g, b, 0, st, Y, ldy, X, ldx, Kx, Wbar, ldx, bbar, count, 1, rows);
 }
 
 extern "C" int pp_nerf_fwd(const float* params, const float* center, const float* ray, const float* depth,
@@ -797,7 +755,7 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
       P.src[8] = params + L.r0; P.ld[8] = 288; P.mx_w[8] = MX_R0;        // the colour head's hidden layer rides as a ninth stage
       P.nsteps = NERF_CHAIN_HEAD ? TR_STEPS + 10 : TR_STEPS; P.nw = NERF_CHAIN_NW == 4 ? 4 : 8;
       hipLaunchKernelGGL(k_pack_trunk<false>, dim3(P.nsteps * 4), dim3(256), 0, st, P, mx, reinterpret_cast<unsigned char*>(A.wimg[0]));
-    } else if (NERF_PLANES) {
+    } else {
       PlanePackJobs P;
       P.n = 8;
       for (int l = 0; l < 8; ++l) {
@@ -896,7 +854,6 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
   // split-precision path: operand maxima of the gradient tensors are recorded by their producers (slots MX_DH .. MX_DHSUM)
   float* mx = NERF_SPLIT ? A.mx : nullptr;
   if (mx) hipMemsetAsync(mx + MX_DH, 0, (MX_DHSUM - MX_DH + 1) * sizeof(float), st);
-  const bool planes = mx && NERF_PLANES;
   const bool chain = mx && NERF_CHAIN_BWD;
   float* DY[7];                                    // d(pre-activation of layer l), l = 0 .. 6, for the fused chain
   for (int l = 0; l < 7; ++l) DY[l] = part + NERF_PART_FLOATS + (size_t)l * M * 256;
@@ -907,7 +864,7 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
     for (int s_ = 1; s_ < 8; ++s_) { J.src[s_] = params + L.w[8 - s_]; J.ld[s_] = NERF_IN_LD[8 - s_]; J.mx_w[s_] = MX_W0 + 8 - s_; }
     J.nsteps = TR_STEPS; J.nw = 0;
     hipLaunchKernelGGL(k_pack_trunk<true>, dim3(TR_STEPS * 4), dim3(256), 0, st, J, mx, reinterpret_cast<unsigned char*>(r0t_img));
-  } else if (planes) {
+  } else if (mx) {
     PlanePackJobs P;
     P.n = 8;
     P.src[0] = R0T; P.dst[0] = r0t_img; P.ld[0] = 128; P.K[0] = 128; P.mx_slot[0] = MX_R0;
@@ -969,7 +926,7 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
   } else {
     // last feature layer: columns 0..255 through the colour head, column 256 from the density
     nerf_gemm<EPI_MASK>(st, dH, 128, R0T, 128, 128, 256, nullptr, A.a[7], 288, P, 288, count, M, slot(MX_DH), slot(MX_R0),
-                        slot(MX_P), A.bits[7], planes ? r0t_img : nullptr);
+                        slot(MX_P), A.bits[7], r0t_img);
     {
       const int wgs = min(pp_div_up(M, NERF_DSTRIP), NERF_PART_WGS);
       hipLaunchKernelGGL(k_nerf_density_bwd, dim3(wgs), dim3(512), 0, st, A.a[6], A.raw, g_density_samples, M, P, part);
@@ -978,7 +935,7 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
     }
     nerf_gemm_tn(st, P, 288, 256, A.a[6], 256, 256, params_grad + L.w[7], params_grad + L.b[7], count, M, slot(MX_P), slot(MX_A0 + 6));
     nerf_gemm<EPI_MASK>(st, P, 288, WT[7], 288, 288, 256, nullptr, A.a[6], 256, Q, 256, count, M, slot(MX_P), slot(MX_W0 + 7),
-                        slot(MX_DY6), A.bits[6], planes ? wt7_img : nullptr);
+                        slot(MX_DY6), A.bits[6], wt7_img);
     float* cur = Q;
     float* nxt = P;
     for (int l = 6; l >= 1; --l) {                   // cur = d(pre-activation of layer l), [M][256]
@@ -987,7 +944,7 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
       nerf_gemm_tn(st, cur, 256, 256, x, ldx, NERF_IN_LD[l], params_grad + L.w[l], params_grad + L.b[l], count, M,
                    slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1));
       nerf_gemm<EPI_MASK>(st, cur, 256, WT[l], 256, 256, 256, nullptr, x, ldx, nxt, 256, count, M, slot(MX_DY6 + 6 - l),
-                          slot(MX_W0 + l), slot(MX_DY6 + 7 - l), A.bits[l - 1], planes ? wt_img[l] : nullptr);
+                          slot(MX_W0 + l), slot(MX_DY6 + 7 - l), A.bits[l - 1], wt_img[l]);
       if (l == 4)                                    // skip columns: gradient of the encoding, no activation in between
         nerf_gemm<EPI_PLAIN>(st, cur, 256, WT[4] + 256 * 256, 256, 256, 64, nullptr, nullptr, 0, dEncS, 64, count, M,
                              slot(MX_DY6 + 2), slot(MX_W0 + 4), nullptr);

@@ -209,7 +209,7 @@ class RenderCore:
 
     def __init__(self, cfg: SceneConfig, ctx=None):
         """ctx: the pp_context (ops.Context) every option-dependent kernel of this core is called with; None = the host's
-        default context.  Its option `side_stream` (1 / 2) runs the weight-gradient kernel of each MLP chain on the context's
+        default context.  Its option `side_stream` = 1 runs the weight-gradient kernel of each MLP chain on the context's
         auxiliary stream beside the small, latency-bound kernels that follow the chain's data-gradient kernel and joins it before
         the next register-hungry MLP kernel.  Measured on MI355X (kernel trace): the overlap happens, but the small kernels only
         get the leftover wave slots (15 -> 45 us each) and the fork / join edges cost ~10 us per chain, so the step is 1 % SLOWER:

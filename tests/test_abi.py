@@ -61,6 +61,10 @@ def test_options_live_in_caller_owned_contexts():
     with pytest.raises(_lib.PoseProbeError):
         a.set('no_such_option', 1)
     with pytest.raises(_lib.PoseProbeError):
+        a.set('nerf_tn256', 1)              # retired option
+    with pytest.raises(_lib.PoseProbeError):
+        a.set('side_stream', 2)
+    with pytest.raises(_lib.PoseProbeError):
         a.set('mlp_split', 64)
     assert set(a.options()) == set(_lib.OPTION_NAMES)
 

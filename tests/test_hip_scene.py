@@ -674,7 +674,7 @@ def test_scene_kernels_stay_inside_their_buffers(nerf_split):
 
     opt = bg_nerf.default_options(sample_intvs=128)
     torch.manual_seed(3)
-    net = bg_nerf.NeRF(opt, device=dev, options={'nerf_split': nerf_split, 'nerf_split_tn': nerf_split})
+    net = bg_nerf.NeRF(opt, device=dev, options={'nerf_split': nerf_split})
     net.progress.data.fill_(0.7)
     g = torch.Generator().manual_seed(21)
     for R, S in ((1023, 128), (1, 2), (37, 50)):

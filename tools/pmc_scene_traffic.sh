@@ -24,7 +24,7 @@ for c in ('FETCH_SIZE', 'WRITE_SIZE'):
 M = 1023 * 128
 # algorithmic bytes per sample: forward chain = 256 B encoded points in, 8 x 1 KB activations + 8 x 32 B masks + 8 B density out; backward chain =
 # 512 B d(hidden) + 8 x 32 B masks + 4 B d raw in, 1152 B d(layer 7) (288-float rows, 256 written) + 7 x 1 KB out; a weight gradient = 2 KB in
-alg = {'k_nerf_trunk<false': 256 + 8 * 1024 + 8 * 32 + 8, 'k_nerf_trunk<true': 512 + 8 * 32 + 4 + 8 * 1024, 'k_gemm_tn_split': 2048}
+alg = {'k_nerf_trunk<false': 256 + 8 * 1024 + 8 * 32 + 8, 'k_nerf_trunk<true': 512 + 8 * 32 + 4 + 8 * 1024, 'k_gemm_tn_tr': 2048}
 res = {}
 for k, v in sorted(out.items(), key=lambda kv: -(2 * kv[1].get('FETCH_SIZE_KB', 0) + kv[1].get('WRITE_SIZE_KB', 0)) * kv[1].get('launches', 1))[:12]:
     a = [alg[x] for x in alg if k.startswith(x)]
