@@ -1,20 +1,18 @@
 // Split-precision weight gradient of the scene branch (pp_nerf.hip is its only user):  Wbar[n][k] += sum_r Y[r][n] X[r][k]
 // (one 128 x 128 block per blockIdx.y, row splits along blockIdx.x, as k_gemm_tn), three fp16 products per fp32 product with
 // the scales of pp_gemm_split.h.  The reduction runs over ROWS, so an MFMA operand fragment is 8 consecutive rows of one column.
-// Row-major LDS images and hardware-transposed fragment reads (gfx950 ds_read_b64_tr_b16).  The first generation transposed on
+// Row-major LDS images and hardware-transposed fragment reads (pp_split_image.h).  The first generation transposed on
 // the way INTO LDS: 16-byte stores of eight rows of one column, 4-way bank conflicts by construction - on the LDS store path
 // (13 cycles per conflict-free ds_write_b128 already, MI355X_MICROARCH.md LDS table) that was ~32 cycles per wave-instruction,
 // 64 of them per chunk and work-group: more LDS time than the chunk's matrix instructions (PMC: matrix pipe busy 25 %).  Here a
-// thread stores what it loaded - four consecutive columns of a row, hi and lo, as 8-byte conflict-free stores into [64 rows][128
-// halfs] images with 256-byte rows whose 16-byte chunks are XOR-swizzled (cdna_hip_programming.md T10, image (b)) - and a
-// fragment (eight consecutive rows of one column per lane) is two transposed reads of 4 rows x 16 columns per 16-lane group.
+// thread stores what it loaded - four consecutive columns of a row, hi and lo, as 8-byte conflict-free stores - and a
+// fragment is two transposed reads.
 #pragma once
-#include "pp_gemm_split.h"
+#include "pp_split_image.h"
 
 #ifndef TN_DBG
 #define TN_DBG 0      // experiments only (k_gemm_tn_tr), bit mask: 1 no row fetches in the loop, 2 fragments read once per chunk
 #endif
-__device__ __forceinline__ int tn_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
 
 #ifdef TN_TIMERS      // phase timers (experiments): wave 0 of every work-group sums s_memtime deltas per phase
 #define TN_TIMERS_ON 1
@@ -77,19 +75,7 @@ static __global__ __launch_bounds__(256, 2) void k_gemm_tn_tr(const float* __res
       else rx[i] = *reinterpret_cast<const float4*>(X + (size_t)gr * ldx + (c4 < kx4 ? c4 : 0) * 4);
     }
   };
-  // transposed fragment: lane (group g = lane / 16, q = (lane & 15) / 4, p = lane & 3) addresses row q, columns 4 p .. 4 p + 3 of its
-  // group's 4 x 16 block and receives column (lane & 15) of the block's four rows; two blocks = the eight rows of the lane's half
-  typedef __fp16 tn_h4 __attribute__((vector_size(8)));
-  const int fg = lane >> 4, fq = (lane & 15) >> 2, fp = lane & 3;
-  auto frag = [&](const unsigned char* plane, int cb, int ks) -> pp_half8 {        // cb: first of the tile's 32 columns, ks: first of its 16 rows
-    const int ch = ((cb + 16 * (fg & 1)) >> 3) + (fp >> 1);
-    const int row = ks + 8 * (fg >> 1) + fq;
-    const tn_h4 a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) tn_h4*)(plane + tn_off(row, ch) + 8 * (fp & 1)));
-    const tn_h4 b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) tn_h4*)(plane + tn_off(row + 4, ch) + 8 * (fp & 1)));
-    typedef __fp16 tn_h8 __attribute__((vector_size(16)));
-    const tn_h8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(pp_half8, v);
-  };
+  auto frag = [&](const unsigned char* plane, int cb, int ks) { return tn_frag(plane, cb, ks, lane); };
 #ifdef TN_TIMERS_ON
   unsigned long long tsum[8] = {0}, tprev = __builtin_readcyclecounter();
 #define TN_TICK(i) do { const unsigned long long t__ = __builtin_readcyclecounter(); tsum[i] += t__ - tprev; tprev = t__; } while (0)
@@ -102,17 +88,11 @@ static __global__ __launch_bounds__(256, 2) void k_gemm_tn_tr(const float* __res
     TN_TICK(0);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const int o = tn_off(rblk * 8 + i, c4 >> 1) + 8 * (c4 & 1);
       const float ky = (r0 + rblk * 8 + i < re) ? 1.f : 0.f, kx = (c4 < kx4) ? ky : 0.f;
       ry[i].x *= ky; ry[i].y *= ky; ry[i].z *= ky; ry[i].w *= ky;
       rx[i].x *= kx; rx[i].y *= kx; rx[i].z *= kx; rx[i].w *= kx;
-      pp_half4 h, l;
-      pp_split4(ry[i], sY, h, l);
-      *reinterpret_cast<pp_half4*>(Yh + o) = h;
-      *reinterpret_cast<pp_half4*>(Yl + o) = l;
-      pp_split4(rx[i], sX, h, l);
-      *reinterpret_cast<pp_half4*>(Xh + o) = h;
-      *reinterpret_cast<pp_half4*>(Xl + o) = l;
+      tn_store4(Yh, Yl, rblk * 8 + i, c4, ry[i], sY);
+      tn_store4(Xh, Xl, rblk * 8 + i, c4, rx[i], sX);
     }
     if (bbar) {
 #pragma unroll

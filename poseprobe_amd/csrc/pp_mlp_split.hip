@@ -35,6 +35,7 @@
 #include "pp_common.h"
 #include "pp_mlp_fused.h"
 #include "pp_gemm_split.h"
+#include "pp_split_image.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -1352,95 +1353,105 @@ int pp_launch_rgb_fused_bwd_s(const float* params, const float* acts, const floa
 }
 
 // ================================================================================================ weight gradients
-// Wbar_l[n][k] += sum_r Ybar_l[r][n] * X_l[r][k] for three layers in ONE launch, as k_wgrad_chain (pp_mlp_fused.hip: a step = one
-// 64-row tile of one layer, both operand tiles by LDS-direct loads into a double buffer, the accumulators resident over the
-// work-group's whole row range) - with the product on the fp16 MFMAs, three per fp32 product.
-// The reduction runs over ROWS, so an operand fragment is 8 consecutive rows of one column: a lane gathers them from the row-major
-// fp32 tile (conflict-free: consecutive lanes read consecutive columns; two rows per ds_read2st64_b32), scales, splits, and feeds
-// them to the MFMAs - 20 vector instructions per fragment, issued between the MFMAs of the previous 16-row group.
-// Scale: one power of two per operand for a wavefront's whole row range (its accumulators see every tile), kept as a RUNNING
-// exponent: the magnitudes of every 16-row group's fragments are checked against what the running scale can hold before they are
-// converted (v_max3 + one ballot); a group that exceeds it lowers the exponent (with a factor 4 of headroom) and the accumulators
-// are rescaled by the exact power of two - a handful of times per launch.  Rows far below the running maximum are converted with
-// its absolute floor (2^-40 of it), which is what a sum needs.
+// Wbar_l[n][k] += sum_r Ybar_l[r][n] * X_l[r][k] for three layers in ONE launch, as k_wgrad_chain (pp_mlp_fused.hip) - with the
+// product on the fp16 MFMAs, three per fp32 product (lo.hi + hi.lo + hi.hi).  One work-group works on ONE layer: the layers share
+// nothing, and 64 resident accumulators per lane leave room for two work-groups per CU.  A step is a 64-row tile of both operands:
+// every thread loads 8 rows x 4 columns of Y (and of X) as float4, scales and splits them ONCE for the whole work-group into the
+// swizzled hi / lo images of pp_split_image.h, and the four wavefronts (2 x 2 over the 128 x KX block) read their MFMA fragments
+// with transposed LDS reads.  The next tile's rows are fetched into registers between the matrix instructions.
+// Scale: one power of two per operand for the work-group's whole row range (its accumulators see every tile), kept as a RUNNING
+// exponent that only lowers: every tile's magnitudes are checked against what the running scale can hold while the tile is
+// converted; a wavefront that sees a larger one publishes its maximum beside the image, under the barrier that publishes the
+// image.  If any did, all lower the exponent alike (with a factor 4 of headroom), rescale the accumulators by the exact power of
+// two and convert the tile again behind one more barrier - a handful of times per launch.  Rows far below the running maximum are
+// converted with its absolute floor (2^-40 of it), which is what a sum needs.
 namespace {
 
-// piece i of 8 of the LDS-direct loads of one tile pair (Y: two 512-byte rows; X: two rows, or four 256-byte rows on the first
-// four pieces when KX == 64)
-template <int KX>
-__device__ __forceinline__ void wgs_issue_piece(const WgradOperands& L, int r0, int R, float* Ybuf, float* Xbuf, int wid, int lane, int i) {
-  const int l31 = lane & 31, lh = lane >> 5;
-  {
-    const int rl = 16 * wid + 2 * i;
-    const int row = min(r0 + rl + lh, R - 1);
-    __builtin_amdgcn_global_load_lds(PP_GLOBAL_PTR(L.Y + (size_t)row * 128 + l31 * 4), PP_LDS_PTR(Ybuf + rl * 128), 16, 0, 0);
+// rows [r0, rend) of one step: a whole 64-row tile, or the last, partial piece of the row range (pieces are multiples of 16 rows
+// except where the range ends)
+struct WgsUnit { int r0, rend; };
+
+// The tiles of a layer go round-robin to its work-groups from the END of the row range (what the data-gradient kernel wrote last
+// is what the Infinity Cache still holds).  The rows of the last, incomplete round are shared out evenly in 16-row steps, so that
+// no work-group does a whole tile more than another.
+__device__ __forceinline__ WgsUnit wgs_unit(int k, int full, int wg, int nwg, int ntiles, int R, int rem_rows, int q) {
+  if (k < full) {
+    const int t = ntiles - 1 - wg - k * nwg;
+    return {t * TILE_ROWS, R};
   }
-  if (KX == 128) {
-    const int rl = 16 * wid + 2 * i;
-    const int row = min(r0 + rl + lh, R - 1);
-    __builtin_amdgcn_global_load_lds(PP_GLOBAL_PTR(L.X + (size_t)row * 128 + l31 * 4), PP_LDS_PTR(Xbuf + rl * 128), 16, 0, 0);
-  } else if (i < 4) {
-    const int l15 = lane & 15, lq = lane >> 4;
-    const int rl = 16 * wid + 4 * i;
-    const int row = min(r0 + rl + lq, R - 1);
-    __builtin_amdgcn_global_load_lds(PP_GLOBAL_PTR(L.X + (size_t)row * 64 + l15 * 4), PP_LDS_PTR(Xbuf + rl * 64), 16, 0, 0);
-  }
-}
-template <int KX>
-__device__ __forceinline__ void wgs_issue(const WgradOperands& L, int r0, int R, float* Ybuf, float* Xbuf, int wid, int lane) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) wgs_issue_piece<KX>(L, r0, R, Ybuf, Xbuf, wid, lane, i);
+  const int hi = rem_rows - wg * q;
+  return {max(hi - q, 0), hi};
 }
 
-// eight consecutive rows of one column, scaled and split (v: the raw values, kept for the bias sums)
-__device__ __forceinline__ void frag_split(const float (&v)[8], float s, pp_half8& h, pp_half8& l) {
-  unsigned hh[4], ll[4];
+template <int KX, int CSTEP>
+__device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int ntiles, int wg, int nwg, unsigned char* __restrict__ img,
+                                          float2* __restrict__ flags) {
+  constexpr int NB = KX / 64;            // 32-column X blocks per wavefront
+  constexpr int XR = KX / 16;            // X rows per thread: 8 (KX = 128) or 4 (KX = 64)
+  constexpr int XC = KX / 4;             // threads per X row
+  const int full = ntiles / nwg;
+  const int rem_rows = min((ntiles - full * nwg) * TILE_ROWS, R);
+  const int q = ((rem_rows + nwg - 1) / nwg + 15) & ~15;
+  const int nunits = full + (rem_rows - wg * q > 0 ? 1 : 0);
+  if (nunits == 0) return;
+  unsigned char* const Yh = img;
+  unsigned char* const Yl = img + TILE_ROWS * 256;
+  unsigned char* const Xh = img + 2 * TILE_ROWS * 256;
+  unsigned char* const Xl = img + 3 * TILE_ROWS * 256;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wr = wid >> 1, wc = wid & 1, l31 = lane & 31, lh = lane >> 5;
+  const int c4 = tid & 31, rblk = tid >> 5;                   // Y: columns 4 c4 .. 4 c4 + 3 of rows 8 rblk .. 8 rblk + 7
+  const int xc4 = c4 % XC, xrow = 8 * rblk + (c4 / XC) * XR;  // X: columns 4 xc4 .. 4 xc4 + 3 of rows xrow .. xrow + XR - 1
+  const bool bias = L.bbar != nullptr;
+  f32x16 acc[2][NB];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float x0 = v[2 * k] * s, x1 = v[2 * k + 1] * s;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hh[k]) : "v"(x0), "v"(x1));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(ll[k]) : "v"(hh[k]), "v"(x0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(ll[k]) : "v"(hh[k]), "v"(x1));
-  }
-  typedef unsigned u4 __attribute__((ext_vector_type(4)));
-  const u4 hv = {hh[0], hh[1], hh[2], hh[3]}, lv = {ll[0], ll[1], ll[2], ll[3]};
-  h = __builtin_bit_cast(pp_half8, hv);
-  l = __builtin_bit_cast(pp_half8, lv);
-}
-
-// state of one wavefront: running scale exponents of its Y / X fragments (a wavefront's accumulators only ever see its own
-// fragments, so the scales are per wavefront and need no work-group-wide maximum), bias partial sums
-struct WgsLayer {
-  int eY, eX;
-  float bsum[2];
-};
-
-// largest magnitude of the fragments against what the running scale can hold; true if any lane exceeds it
-template <int NF>
-__device__ __forceinline__ bool frag_exceeds(const float (&v)[NF][8], float lim, float& m) {
-  m = 0.f;
+  for (int t = 0; t < 2; ++t)
 #pragma unroll
-  for (int f = 0; f < NF; ++f)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(v[f][2 * k]), "v"(v[f][2 * k + 1]));
-  return __builtin_amdgcn_ballot_w64(m > lim) != 0ull;
-}
+    for (int u = 0; u < NB; ++u) zero16(acc[t][u]);
+  float bsum[4] = {0.f, 0.f, 0.f, 0.f};
+  int eY = 60, eX = 60;
+  float sY = pow2(eY), sX = pow2(eX), limY = pow2(15 - eY), limX = pow2(15 - eX);
 
-// 64 rows x (64 x 32 NB) outputs of one wavefront: acc[t][u] += Y[:, 64 wr + 32 t + .]^T X[:, 32 NB wc + 32 u + .]; issue(i), i = 0..7,
-// is called between the MFMA groups of the first two 16-row groups (the next tile's loads ride there).
-// Group -1 only converts.  Cold path: a fragment that exceeds the running scale lowers the exponent, with a factor 4 of headroom,
-// and rescales the accumulators by the exact power of two.  (A rolled loop over the groups would hold one copy of it instead of
-// ten, but measures 2.2 x slower: the copies of the fragments between iterations and the uniform branches defeat the scheduling.)
-template <int KX, int CSTEP, class Issue>
-__device__ __forceinline__ void wgs_compute(const float* __restrict__ Ybuf, const float* __restrict__ Xbuf, f32x16 (&acc)[2][KX / 64],
-                                            WgsLayer& st, bool bias, int wr, int wc, int l31, int lh, Issue issue) {
-  constexpr int NB = KX / 64;
-  float sY = pow2(st.eY), sX = pow2(st.eX), limY = pow2(15 - st.eY), limX = pow2(15 - st.eX);
-  const float* yp = Ybuf + (8 * lh) * 128 + 64 * wr + l31;
-  const float* xp = Xbuf + (8 * lh) * KX + 32 * NB * wc + l31;
-  float ry[2][8], rx[NB][8];
-  pp_half8 ah[2] = {}, al[2] = {}, bh[NB] = {}, bl[NB] = {};
-  auto rescale = [&](int d) {
+  // rows i0 .. i1 - 1 of this thread's eight of the step at r0 (clamped addresses; rows past the step are zeroed by mask())
+  float4 ry[8], rx[XR];
+  auto load_rows = [&](int r0, int i0, int i1) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (i < i0 || i >= i1) continue;
+      ry[i] = *reinterpret_cast<const float4*>(L.Y + (size_t)min(r0 + 8 * rblk + i, R - 1) * 128 + c4 * 4);
+      if (i < XR) rx[i] = *reinterpret_cast<const float4*>(L.X + (size_t)min(r0 + xrow + i, R - 1) * KX + xc4 * 4);
+    }
+  };
+  auto mask = [&](const WgsUnit& u) {
+    if (u.r0 + TILE_ROWS > u.rend) {                          // (uniform) partial step
+      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) if (u.r0 + 8 * rblk + i >= u.rend) ry[i] = z;
+#pragma unroll
+      for (int i = 0; i < XR; ++i) if (u.r0 + xrow + i >= u.rend) rx[i] = z;
+    }
+  };
+  // does any lane hold a magnitude the running scales cannot take?  Lane 0 publishes the wavefront's maxima (0: none) in `set`
+  auto check = [&](float2* set) {
+    float my = 0.f, mx = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) my = fmaxf(my, amax4(ry[i]));
+#pragma unroll
+    for (int i = 0; i < XR; ++i) mx = fmaxf(mx, amax4(rx[i]));
+    float py = 0.f, px = 0.f;
+    if (__builtin_amdgcn_ballot_w64(my > limY) != 0ull) py = wave_max(my);      // cold
+    if (__builtin_amdgcn_ballot_w64(mx > limX) != 0ull) px = wave_max(mx);      // cold
+    if (lane == 0) set[wid] = make_float2(py, px);
+  };
+  // after the barrier that published `set`: every wavefront lowers the exponents alike; returns which operands changed (1 Y, 2 X)
+  auto adopt = [&](const float2* set) -> int {
+    const float4 a = *reinterpret_cast<const float4*>(set), b = *reinterpret_cast<const float4*>(set + 2);
+    const float my = fmaxf(fmaxf(a.x, a.z), fmaxf(b.x, b.z)), mx = fmaxf(fmaxf(a.y, a.w), fmaxf(b.y, b.w));
+    if (!(my > 0.f) && !(mx > 0.f)) return 0;
+    int d = 0, changed = 0;
+    if (my > 0.f) { const int e = scale_exp(my) - 2; d += e - eY; eY = e; changed |= 1; }
+    if (mx > 0.f) { const int e = scale_exp(mx) - 2; d += e - eX; eX = e; changed |= 2; }
+    sY = pow2(eY); sX = pow2(eX); limY = pow2(15 - eY); limX = pow2(15 - eX);
     const float f = pow2(d);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -1448,134 +1459,87 @@ __device__ __forceinline__ void wgs_compute(const float* __restrict__ Ybuf, cons
       for (int u = 0; u < NB; ++u)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[t][u][i] *= f;
+    return changed;
   };
+  auto convert = [&](bool y, bool x) {
+    if (y) {
 #pragma unroll
-  for (int ks = -1; ks < 4; ++ks) {
-    pp_half8 ch[2] = {ah[0], ah[1]}, cl[2] = {al[0], al[1]}, dh[NB], dl[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) { dh[u] = bh[u]; dl[u] = bl[u]; }
-    __builtin_amdgcn_sched_barrier(0);
-    if (ks < 3) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ry[t][j] = yp[(16 * (ks + 1) + j) * 128 + 32 * t];
-#pragma unroll
-      for (int u = 0; u < NB; ++u)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) rx[u][j] = xp[(16 * (ks + 1) + j) * KX + 32 * u];
+      for (int i = 0; i < 8; ++i) tn_store4(Yh, Yl, 8 * rblk + i, c4, ry[i], sY);
     }
-    __builtin_amdgcn_sched_barrier(0);
-    if (ks >= 0) {
+    if (x) {
 #pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        acc[0][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl[0], dh[u], acc[0][u], 0, 0, 0);
-        acc[0][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[0], dl[u], acc[0][u], 0, 0, 0);
-        acc[0][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[0], dh[u], acc[0][u], 0, 0, 0);
+      for (int i = 0; i < XR; ++i) tn_store4(Xh, Xl, xrow + i, xc4, rx[i], sX);
+    }
+  };
+  auto frag = [&](const unsigned char* plane, int cb, int ks) { return tn_frag(plane, cb, ks, lane); };
+
+  // prologue: the first step's maxima set the starting exponents (flag set 1; the steps use set 0)
+  WgsUnit cur = wgs_unit(0, full, wg, nwg, ntiles, R, rem_rows, q);
+  load_rows(cur.r0, 0, 8);
+  PP_WAIT_VMEM();
+  mask(cur);
+  check(flags + 4);
+  __syncthreads();
+  adopt(flags + 4);
+  for (int k = 0; k < nunits; ++k) {
+    const bool has_next = k + 1 < nunits;
+    const WgsUnit nxt = has_next ? wgs_unit(k + 1, full, wg, nwg, ntiles, R, rem_rows, q) : cur;
+    if (k > 0) {
+      PP_WAIT_VMEM();
+      mask(cur);
+    }
+    check(flags);
+    convert(true, true);
+    if (bias) {               // column sums of Y over the rows that count (every row / the primal rows of the 4-row form)
+#pragma unroll
+      for (int i = 0; i < 8; i += CSTEP) { bsum[0] += ry[i].x; bsum[1] += ry[i].y; bsum[2] += ry[i].z; bsum[3] += ry[i].w; }
+    }
+    __syncthreads();
+    {
+      const int changed = adopt(flags);                        // cold: convert the step again with the lowered scales
+      if (changed) {                                           // (the flags are not written again before the barrier below)
+        convert(changed & 1, changed & 2);
+        __syncthreads();
       }
     }
-    __builtin_amdgcn_sched_barrier(0);
-    if (ks >= 0 && ks < 2) { issue(4 * ks); issue(4 * ks + 1); issue(4 * ks + 2); issue(4 * ks + 3); }
-    __builtin_amdgcn_sched_barrier(0);
-    if (ks >= 0) {
+    // 16-row groups of this step: fragments of the next group are on their way while the matrix instructions of this one issue,
+    // a quarter of the next step's rows is fetched behind the first six matrix instructions (pp_gemm_tn_tr.h explains both).
+    // Rescales happen only between steps: never between the two MFMA groups of one 16-row group.
+    const int ng = (min(cur.rend - cur.r0, TILE_ROWS) + 15) >> 4;
+    pp_half8 fa[2][4], fb[2][2 * NB];                        // [parity][tile 0 hi, tile 0 lo, tile 1 hi, tile 1 lo]
+    auto fetch = [&](int par, int ks) {
 #pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        acc[1][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl[1], dh[u], acc[1][u], 0, 0, 0);
-        acc[1][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[1], dl[u], acc[1][u], 0, 0, 0);
-        acc[1][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[1], dh[u], acc[1][u], 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // the next group's fragments, converted while the MFMAs above run.  The scale checks come AFTER both MFMA groups of this
-    // 16-row group: a rescale between them would add the second group's products, still at the old scale, to rescaled sums.
-    if (ks < 3) {
-      float m;
-      if (frag_exceeds<2>(ry, limY, m)) {                        // cold
-        const int e = scale_exp(wave_max(m)) - 2;
-        rescale(e - st.eY);
-        st.eY = e; sY = pow2(e); limY = pow2(15 - e);
-      }
-      if (frag_exceeds<NB>(rx, limX, m)) {                       // cold
-        const int e = scale_exp(wave_max(m)) - 2;
-        rescale(e - st.eX);
-        st.eX = e; sX = pow2(e); limX = pow2(15 - e);
-      }
+      for (int t = 0; t < 2; ++t) { fa[par][2 * t] = frag(Yh, wr * 64 + t * 32, ks); fa[par][2 * t + 1] = frag(Yl, wr * 64 + t * 32, ks); }
+#pragma unroll
+      for (int u = 0; u < NB; ++u) { fb[par][2 * u] = frag(Xh, 32 * NB * wc + u * 32, ks); fb[par][2 * u + 1] = frag(Xl, 32 * NB * wc + u * 32, ks); }
+    };
+    fetch(0, 0);
+#pragma unroll
+    for (int s4 = 0; s4 < TILE_ROWS / 16; ++s4) {
+      const int par = s4 & 1;
+      if (s4 + 1 < ng) fetch(par ^ 1, (s4 + 1) * 16);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        if (bias) {               // column sums of Y over the rows that count (every row / the primal rows of the 4-row form)
+        if (s4 < ng) {
 #pragma unroll
-          for (int j = 0; j < 8; j += CSTEP) st.bsum[t] += ry[t][j];
+          for (int u = 0; u < NB; ++u) {
+            acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[par][2 * t + 1], fb[par][2 * u], acc[t][u], 0, 0, 0);
+            acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[par][2 * t], fb[par][2 * u + 1], acc[t][u], 0, 0, 0);
+            acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[par][2 * t], fb[par][2 * u], acc[t][u], 0, 0, 0);
+          }
         }
-        frag_split(ry[t], sY, ah[t], al[t]);
+        if (t == 0 && has_next) {
+          __builtin_amdgcn_sched_barrier(0);
+          load_rows(nxt.r0, 2 * s4, 2 * s4 + 2);
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
-#pragma unroll
-      for (int u = 0; u < NB; ++u) frag_split(rx[u], sX, bh[u], bl[u]);
     }
-    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();                                           // the images are free
+    cur = nxt;
   }
-}
-
-}  // namespace
-
-// One work-group works on ONE layer (blockIdx.y) - the three layers share nothing, and 64 resident accumulators instead of 192
-// leave the registers the conversion needs; the persistent work-groups of a layer walk its tiles from the end of the row range
-// (what the data-gradient kernel wrote last is what the Infinity Cache still holds).
-template <int KX, int CSTEP>
-__device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int ntiles, int wg, int nwg, float* __restrict__ Yb0,
-                                          float* __restrict__ Xb0, float* __restrict__ Yb1, float* __restrict__ Xb1) {
-  constexpr int NB = KX / 64;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wr = wid >> 1, wc = wid & 1, l31 = lane & 31, lh = lane >> 5;
-  f32x16 acc[2][NB];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int u = 0; u < NB; ++u) zero16(acc[t][u]);
-  WgsLayer st = {60, 60, {0.f, 0.f}};
-  const bool bias = L.bbar != nullptr && wc == 0;
-  // after the loads of a tile have landed: zero the Y rows past R (last tile only)
-  auto prepare = [&](int r0, float* Ybuf) {
-    if (r0 + TILE_ROWS > R) {
-      for (int i = tid; i < TILE_ROWS * 128; i += 256)
-        if (r0 + (i >> 7) >= R) Ybuf[i] = 0.f;
-      __syncthreads();
-    }
-  };
-  const int first = ntiles - 1 - wg;
-  wgs_issue<KX>(L, first * TILE_ROWS, R, Yb0, Xb0, wid, lane);
-  // two tiles per iteration keep the buffer assignment static
-#ifdef MS_TIMERS
-  unsigned long long tsum[16] = {0}, tprev = __builtin_readcyclecounter();
-#endif
-  for (int t0 = first; t0 >= 0; t0 -= 2 * nwg) {
-    const int t1 = t0 - nwg, t2 = t1 - nwg;
-    TICK(4);
-    PP_WAIT_VMEM(); __syncthreads();
-    TICK(0);
-    prepare(t0 * TILE_ROWS, Yb0);
-    TICK(1);
-    TICK(2);
-    wgs_compute<KX, CSTEP>(Yb0, Xb0, acc, st, bias, wr, wc, l31, lh, [&](int i) {
-      if (t1 >= 0) wgs_issue_piece<KX>(L, t1 * TILE_ROWS, R, Yb1, Xb1, wid, lane, i);
-    });
-    TICK(3);
-    if (t1 < 0) break;
-    PP_WAIT_VMEM(); __syncthreads();
-    TICK(0);
-    prepare(t1 * TILE_ROWS, Yb1);
-    TICK(1);
-    TICK(2);
-    wgs_compute<KX, CSTEP>(Yb1, Xb1, acc, st, bias, wr, wc, l31, lh, [&](int i) {
-      if (t2 >= 0) wgs_issue_piece<KX>(L, t2 * TILE_ROWS, R, Yb0, Xb0, wid, lane, i);
-    });
-    TICK(3);
-  }
-#ifdef MS_TIMERS
-  if (tid == 0)
-    for (int i = 0; i < 16; ++i) atomicAdd(&g_ms_t[i], tsum[i]);
-#endif
   // flush: one atomic per entry, scaled back
-  const float f = pow2(-(st.eY + st.eX));
+  const float f = pow2(-(eY + eX));
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -1587,33 +1551,46 @@ __device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int nti
         atomicAdd(&L.Wbar[(size_t)n * KX + k], acc[t][u][reg] * f);
       }
     }
-  if (bias) {
+  if (bias) {                              // 8 row blocks x 128 columns of partial sums -> one atomic per column
+    float* red = reinterpret_cast<float*>(img);               // the images are dead (the last step ended with a barrier)
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const float v = st.bsum[t] + __shfl_xor(st.bsum[t], 32, 64);
-      if (lh == 0) atomicAdd(&L.bbar[64 * wr + 32 * t + l31], v);
+    for (int j = 0; j < 4; ++j) red[rblk * 128 + c4 * 4 + j] = bsum[j];
+    __syncthreads();
+    if (tid < 128) {
+      float sum = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) sum += red[i * 128 + tid];
+      atomicAdd(&L.bbar[tid], sum);
     }
   }
 }
 
+}  // namespace
+
 template <int KXC, int CSTEP>
-__global__ __launch_bounds__(256) void k_wgrad_chain_s(WgradOperands LA, WgradOperands LB, WgradOperands LC,
-                                                       const int32_t* __restrict__ count, int rmul, int rcap, int nwg_ab, int nwg_c) {
-  __shared__ __attribute__((aligned(16))) float Yb0[TILE_ROWS * 128];
-  __shared__ __attribute__((aligned(16))) float Xb0[TILE_ROWS * 128];
-  __shared__ __attribute__((aligned(16))) float Yb1[TILE_ROWS * 128];
-  __shared__ __attribute__((aligned(16))) float Xb1[TILE_ROWS * 128];
+__global__ __launch_bounds__(256, 2) void k_wgrad_chain_s(WgradOperands LA, WgradOperands LB, WgradOperands LC,
+                                                          const int32_t* __restrict__ count, int rmul, int rcap, int nwg_ab, int nwg_c) {
+  __shared__ __attribute__((aligned(1024))) unsigned char img[4 * TILE_ROWS * 256];      // Yh | Yl | Xh | Xl
+  __shared__ __attribute__((aligned(16))) float2 flags[8];                                // [2 sets][4 wavefronts]
   const int R = min(count[0] * rmul, rcap);
   const int ntiles = (R + TILE_ROWS - 1) / TILE_ROWS;
-  // work-groups 0 .. nwg_ab - 1: layer A, the next nwg_ab: layer B, the last nwg_c: layer C (fewer when its operand is narrower)
+  // Every work-group ends in one atomic per entry of its 128 x KX block (64 KB at 1.3 TB/s chip-wide), so the second work-group per
+  // CU pays only where each gets many tiles (warp net at 55 k samples: 20 tiles each, 159 us against 166 us with one per CU;
+  // rgbnet: 1.7 tiles each, 56 us against 47 us).  With fewer than 8 tiles per work-group only the first half of the grid works:
+  // the work-groups dispatched first, one per CU.
+  if (ntiles < 8 * nwg_ab) {
+    nwg_ab = max(nwg_ab / 2, 1);
+    nwg_c = max(nwg_c / 2, 1);
+  }
+  // work-groups 0 .. nwg_ab - 1: layer A, the next nwg_ab: layer B, the next nwg_c: layer C (fewer when its operand is narrower)
   const int bx = blockIdx.x;
+  if (bx >= 2 * nwg_ab + nwg_c) return;
   const int layer = bx < nwg_ab ? 0 : (bx < 2 * nwg_ab ? 1 : 2);
   const int wg = bx - layer * nwg_ab, nwg = layer < 2 ? nwg_ab : nwg_c;
-  if (wg >= ntiles) return;
   // one copy of the layer code per operand width (three calls would triple the instruction footprint)
   const WgradOperands L = layer == 0 ? LA : (layer == 1 ? LB : LC);
-  if (KXC == 128 || layer < 2) wgs_layer<128, CSTEP>(L, R, ntiles, wg, nwg, Yb0, Xb0, Yb1, Xb1);
-  else wgs_layer<KXC, CSTEP>(L, R, ntiles, wg, nwg, Yb0, Xb0, Yb1, Xb1);
+  if (KXC == 128 || layer < 2) wgs_layer<128, CSTEP>(L, R, ntiles, wg, nwg, img, flags);
+  else wgs_layer<KXC, CSTEP>(L, R, ntiles, wg, nwg, img, flags);
 }
 
 int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
@@ -1621,11 +1598,11 @@ int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const f
                             hipStream_t st, float* bA, float* bB, float* bC, int wgs_) {
   WgradOperands LA{YA, XA, WA, bA}, LB{YB, XB, WB, bB}, LC{YC, XC, WC, bC};
   const int ntiles = pp_div_up(rcap, TILE_ROWS);
-  // persistent work-groups, at most one per CU over the three layers, shared out in proportion to the layers' work (wgs_ > 0: the
-  // caller's number - a launch on an auxiliary stream that leaves CUs to the kernels running beside it)
-  const int wgs = wgs_ > 0 ? (wgs_ < 16 ? 16 : wgs_) : PP_FUSED_WGS;
-  // (a 64-wide layer costs 3/4 of a 128-wide one: three instead of four operand fragments to convert per 16-row group - the
-  // conversion, not the MFMA count, is what the time follows)
+  // persistent work-groups, two per CU over the three layers, shared out in proportion to the layers' work (wgs_ > 0: the caller's
+  // number of CUs - a launch on an auxiliary stream that leaves CUs to the kernels running beside it); the kernel idles half of
+  // them when the row count is small
+  const int wgs = 2 * (wgs_ > 0 ? (wgs_ < 16 ? 16 : wgs_) : PP_FUSED_WGS);
+  // (a 64-wide layer costs about 3/4 of a 128-wide one: 3/4 of the bytes and of the values to convert, half the MFMAs)
   int nab = kxc == 128 ? wgs / 3 : (wgs * 4) / 11, nc = kxc == 128 ? wgs / 3 : wgs - 2 * ((wgs * 4) / 11);
   if (nab > ntiles) nab = ntiles;
   if (nc > ntiles) nc = ntiles;
