@@ -473,6 +473,26 @@ int pp_nerf_band_weights(const float* progress, float start, float width, int32_
 int pp_nerf_huber_loss(const float* pred, const float* label, int32_t n, float delta, float weight, float* loss, float* g_pred,
                        void* stream);
 
+/* SPARF correspondence loss on rendered depths (lib/bg_nerf/source/training/core/corres_loss.py:93-222, the re-projection of
+ * batched_geometry_utils.py:199-228 and the Huber term of base_losses.py:197-224), forward and backward in one launch.
+ * depth0 / depth1 = the coarse / fine pass's rendered depths of the matched rows, [self n_pairs | other n_pairs] each (depth1 =
+ * NULL: one pass); pix_self, pix_other [n_pairs,2], conf [n_pairs]; K_self, K_other [3,3]; w2c_self, w2c_other [3,4] - all
+ * read from device memory.  Both directions of every pass, each normalised by its count of valid rows + 1e-6 (the detached
+ * pixel / depth re-projection filters), summed, / 2 (one pass) or / 4, times `weight`, into loss[0].  g_depth0 / g_depth1
+ * [2 n_pairs] = d loss / d depth (overwritten); g_w2c [2,3,4] = d loss / d (w2c_self, w2c_other) through T_self2other and
+ * its inverse (overwritten).  Deterministic (one work-group, fixed summation order); no valid row gives 0 everywhere. */
+int pp_nerf_corres_loss(const float* depth0, const float* depth1, int32_t n_pairs, const float* pix_self, const float* pix_other,
+                        const float* conf, const float* K_self, const float* K_other, const float* w2c_self,
+                        const float* w2c_other, int32_t pixel_check, float pixel_thresh, int32_t depth_check, float depth_thresh,
+                        float weight, float* loss, float* g_depth0, float* g_depth1, float* g_w2c, void* stream);
+/* Pose gradient of the matched rows: rows [0, n_pairs) of g_center / g_ray / dir_cam [2 n_pairs, 3] are view view_self's,
+ * rows [n_pairs, 2 n_pairs) view view_other's.  g_c2w[v] += [sum g_ray (x) dir_cam | sum g_center] + g_w2c (may be NULL)
+ * [2,3,4] moved onto c2w through w2c = [R^T | -R^T t] with w2c [n_views,3,4].  g_c2w [n_views,3,4] is ACCUMULATED into, so
+ * it composes with the photometric rows' gradient before pp_pose_bwd.  Deterministic (one work-group). */
+int pp_nerf_pair_pose_bwd(const float* g_center, const float* g_ray, const float* dir_cam, int32_t n_pairs, const float* w2c,
+                          const float* g_w2c, int32_t n_views, int32_t view_self, int32_t view_other, float* g_c2w,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

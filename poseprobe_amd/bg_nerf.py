@@ -49,6 +49,24 @@ def default_options(barf_c2f=(0.4, 0.7), sample_intvs=128, white_bg=False):
                    camera=Options(ndc=False), huber_loss_for_photometric=True)
 
 
+def sparf_dtu_options(barf_c2f=(0.4, 0.7), sample_intvs=128, white_bg=False, max_iter=60000):
+    """default_options plus the loss settings of the reference's DTU configuration (joint_pose_nerf_training/dtu/sparf.py:40-74)
+    and the correspondence loss's own defaults (corres_loss.py:37-46): photometric + correspondence (+ depth consistency,
+    which contributes nothing to the gradient in the reference - see trainer.loss_terms), weights 10^0 / 10^-2 / 10^-3, the
+    correspondence weight halved every 5000 iterations from iteration 0 on, hierarchical sampling from 0.3 * max_iter on."""
+    opt = default_options(barf_c2f=barf_c2f, sample_intvs=sample_intvs, white_bg=white_bg)
+    opt.nerf.fine_sampling = True
+    opt.nerf.ratio_start_fine_sampling_at_x = 0.3
+    opt.update(max_iter=max_iter, loss_type='photometric_and_corres_and_depth_cons',
+               loss_weight=Options(equalize_losses=False, parametrization='exp', render=0, corres=-2., depth_cons=-3),
+               start_iter=Options(photometric=0, corres=0, depth_cons=0),
+               gradually_decrease_corres_weight=True, ratio_start_decrease_corres_weight=0., iter_start_decrease_corres_weight=0,
+               corres_weight_reduct_at_x_iter=5000, diff_loss_type='huber', renderrepro_do_pixel_reprojection_check=False,
+               renderrepro_do_depth_reprojection_check=False, renderrepro_pixel_reprojection_thresh=10.,
+               renderrepro_depth_reprojection_thresh=0.1)
+    return opt
+
+
 def sample_depth(opt, batch_size, num_rays, n_samples, depth_range, mode=None, device='cuda', generator=None):
     """Stratified depth samples [B, num_rays, n_samples, 1] (renderer.py:665-700)."""
     depth_min, depth_max = depth_range
@@ -63,7 +81,8 @@ def sample_depth(opt, batch_size, num_rays, n_samples, depth_range, mode=None, d
 
 def sample_depth_from_pdf(weights, n_samples_coarse, n_samples_fine, depth_range, det, generator=None, grid=None):
     """Inverse-transform sampling from the coarse weights (renderer.py:702-738); weights [B, R, N] -> [B, R, Nf, 1].
-    `grid` [Nf + 1] replays a recorded draw of the (shared across rays) uniform grid."""
+    `grid` [Nf + 1] replays a recorded draw of the (shared across rays) uniform grid; a grid [R, Nf + 1] gives every ray its
+    own (rays of separate render calls that share one pass)."""
     depth_min, depth_max = depth_range
     dev = weights.device
     pdf = weights / (weights.sum(dim=-1, keepdim=True) + 1e-6)
@@ -74,7 +93,10 @@ def sample_depth_from_pdf(weights, n_samples_coarse, n_samples_fine, depth_range
         grid = torch.linspace(0, 1, n_samples_fine + 1, device=dev)
     else:
         grid = torch.rand(n_samples_fine + 1, generator=generator).to(dev)
-    unif = (0.5 * (grid[:-1] + grid[1:])).repeat(*cdf.shape[:-1], 1)
+    if grid.dim() == 2:
+        unif = (0.5 * (grid[:, :-1] + grid[:, 1:])).expand(*cdf.shape[:-1], n_samples_fine).contiguous()
+    else:
+        unif = (0.5 * (grid[:-1] + grid[1:])).repeat(*cdf.shape[:-1], 1)
     idx = torch.searchsorted(cdf, unif, right=True)
     bins = torch.linspace(depth_min, depth_max, n_samples_coarse + 1, device=dev).repeat(*cdf.shape[:-1], 1)
     lo, hi = (idx - 1).clamp(min=0), idx.clamp(max=n_samples_coarse)
@@ -451,6 +473,26 @@ def photometric_loss(rgb, image, huber=True):
     return torch.nn.functional.mse_loss(rgb, image)
 
 
+class CorresRows:
+    """The matched-pixel rows of one view pair for SceneEngine's union pass (corres_loss.py:140-222): pix_self, pix_other [M,2]
+    (matcher pixel coordinates: rays through K^-1 [x, y, 1], no half-pixel offset), conf [M], the intrinsics K_self, K_other
+    [3,3] and the CURRENT w2c_self, w2c_other [3,4] as device tensors (the kernel reads them; the host reads no pose), the loss
+    weight (10^loss_weight.corres / gamma), the filters of `opt` (renderrepro_*, defaults of corres_loss.py:37-46), the
+    photometric term's weight 10^loss_weight.render and, optionally, the replayed uniform grid of the tail's fine samples."""
+
+    def __init__(self, pix_self, pix_other, conf, K_self, K_other, w2c_self, w2c_other, weight, opt=None, fine_grid=None,
+                 photo_weight=1.0):
+        if str(getattr(opt, 'diff_loss_type', 'huber')).lower() != 'huber':
+            raise NotImplementedError('correspondence loss: only diff_loss_type = huber (the reference default) has a kernel')
+        self.pix_self, self.pix_other, self.conf = pix_self.contiguous(), pix_other.contiguous(), conf.reshape(-1).contiguous()
+        self.K_self, self.K_other, self.w2c_self, self.w2c_other = K_self, K_other, w2c_self, w2c_other
+        self.weight, self.fine_grid, self.photo_weight = float(weight), fine_grid, float(photo_weight)
+        self.pixel_check = bool(getattr(opt, 'renderrepro_do_pixel_reprojection_check', False))
+        self.depth_check = bool(getattr(opt, 'renderrepro_do_depth_reprojection_check', False))
+        self.pixel_thresh = float(getattr(opt, 'renderrepro_pixel_reprojection_thresh', 10.))
+        self.depth_thresh = float(getattr(opt, 'renderrepro_depth_reprojection_thresh', 0.1))
+
+
 class _NetState:
     """Gradient block and Adam moments of one packed network."""
 
@@ -480,8 +522,8 @@ class SceneEngine:
         self.seg_lr = torch.tensor([lr], dtype=torch.float32, device=net.flat.device)
 
     @staticmethod
-    def _pass(state, center, ray, depth, image):
-        """One network: forward, compositing, 2 * huber(delta = 0.5, mean), backward.  -> loss, g_center, g_ray, weights."""
+    def _fwd(state, center, ray, depth):
+        """One network's forward and compositing into the per-shape step buffers -> (workspace, buffers)."""
         net = state.net
         R, S = depth.shape
         ws = net._workspace(R, S)
@@ -498,22 +540,46 @@ class SceneEngine:
         ops.nerf_fwd(net.flat, center, ray, depth, net.band_weights(), ws.count, R, S, ws.acts, b['rgb_s'], b['dens'], net.ctx)
         ops.nerf_composite_fwd(b['rgb_s'], b['dens'], depth, ray, R, S, white, b['rgb'], b['d'], b['op'], b['w'], b['cum'],
                                b['rv'], b['dv'])
-        # 2 * huber(delta = 0.5, mean) and its gradient on the [R,3] colours in one launch; the loss lands in a ring slot (the
-        # returned 0-dim tensor is rewritten 256 passes later: read it - .item() / copy - before that)
+        return ws, b
+
+    @staticmethod
+    def _photometric(b, rgb, image, g_rgb, weight=2.0):
+        """2 * huber(delta = 0.5, mean) and its gradient on the [R,3] colours in one launch; the loss lands in a ring slot (the
+        returned 0-dim tensor is rewritten 256 passes later: read it - .item() / copy - before that)"""
         b['loss_i'] = (b['loss_i'] + 1) % 256
         loss = b['loss'][b['loss_i']]
-        ops.nerf_huber_loss(b['rgb'], image.contiguous(), 0.5, 2.0, loss, b['g_rgb'])
-        ops.nerf_composite_bwd(b['rgb_s'], b['dens'], depth, ray, b['w'], R, S, white, b['g_rgb'], b['zero_r'],
+        ops.nerf_huber_loss(rgb, image.contiguous(), 0.5, weight, loss, g_rgb)
+        return loss
+
+    @staticmethod
+    def _bwd(state, ws, b, ray, depth, g_rgb, g_depth):
+        """Compositing and network backward of a pass run by _fwd -> (g_center, g_ray)."""
+        net = state.net
+        R, S = depth.shape
+        white = bool(net.opt.nerf.setbg_opaque or net.opt.mask_img)
+        ops.nerf_composite_bwd(b['rgb_s'], b['dens'], depth, ray, b['w'], R, S, white, g_rgb, g_depth,
                                b['zero_r'], None, b['g_rgb_s'], b['g_dens'], b['g_ray_c'])
         ops.nerf_bwd(net.flat, ray, depth, ws.count, R, S, ws.acts, b['rgb_s'], b['g_rgb_s'], b['g_dens'], ws.scratch,
                      state.grad, b['g_center'], b['g_ray'], net.ctx)
         state.has_grad = True
-        return loss, b['g_center'], b['g_ray'] + b['g_ray_c'], b['w']
+        return b['g_center'], b['g_ray'] + b['g_ray_c']
 
-    def forward_backward(self, center, ray, depth, image, fine=False, depth_range=None, fine_grid=None):
+    @classmethod
+    def _pass(cls, state, center, ray, depth, image):
+        """One network: forward, compositing, 2 * huber(delta = 0.5, mean), backward.  -> loss, g_center, g_ray, weights."""
+        ws, b = cls._fwd(state, center, ray, depth)
+        loss = cls._photometric(b, b['rgb'], image, b['g_rgb'])
+        g_center, g_ray = cls._bwd(state, ws, b, ray, depth, b['g_rgb'], b['zero_r'])
+        return loss, g_center, g_ray, b['w']
+
+    def forward_backward(self, center, ray, depth, image, fine=False, depth_range=None, fine_grid=None, corres=None):
         """center, ray [R,3]; depth [R,S]; image [R,3] -> (loss, g_center, g_ray); parameter gradients are accumulated into the
         networks' gradient blocks, which optimizer_step() consumes and re-zeroes.  fine=True adds the second pass
-        (`depth_range` required; `fine_grid` [Nf + 1] replays the sampler's uniform draw)."""
+        (`depth_range` required; `fine_grid` [Nf + 1] replays the sampler's uniform draw).
+        corres (CorresRows): the union pass - center / ray / depth hold R = R_photo + 2M rows, image the R_photo photometric
+        rows, and the last 2M rows are the matched pixels of one view pair [self M | other M]; see _forward_backward_corres."""
+        if corres is not None:
+            return self._forward_backward_corres(center, ray, depth, image, fine, depth_range, fine_grid, corres)
         loss, g_center, g_ray, w = self._pass(self.states[0], center, ray, depth, image)
         if fine:
             if self.net_fine is None or depth_range is None:
@@ -526,6 +592,59 @@ class SceneEngine:
             loss_f, gc_f, gr_f, _ = self._pass(self.states[1], center, ray, depth_f, image)
             loss, g_center, g_ray = loss + loss_f, g_center + gc_f, g_ray + gr_f
         return loss, g_center, g_ray
+
+    def _forward_backward_corres(self, center, ray, depth, image, fine, depth_range, fine_grid, corres):
+        """Photometric rows and matched-pixel rows in the same launches (the reference renders them in two calls, renderer.py
+        :420-423 and corres_loss.py:178-183): forward of every pass first, then the losses - huber on the photometric prefix,
+        pp_nerf_corres_loss on the tail, which needs the rendered depths of all passes - then the backward of every pass with
+        g_rgb zero on the tail and g_depth zero on the prefix.  The tail's fine samples come from its own coarse weights and
+        its own uniform grid (corres.fine_grid), as in a separate render call.  Also sets last_terms (photometric,
+        correspondence loss) and last_g_w2c [2,3,4] (the correspondence loss's direct pose gradient, overwritten next call)."""
+        Rp, R, M = image.shape[0], depth.shape[0], corres.pix_self.shape[0]
+        if R != Rp + 2 * M:
+            raise ValueError(f'SceneEngine: union pass of {R} rows, expected {Rp} photometric + 2 x {M} matched rows')
+        if fine and (self.net_fine is None or depth_range is None):
+            raise ValueError('SceneEngine: fine=True needs net_fine and depth_range')
+        dev = depth.device
+        f = dict(dtype=torch.float32, device=dev)
+        passes = [(self.states[0], depth) + self._fwd(self.states[0], center, ray, depth)]
+        if fine:
+            opt = self.net.opt
+            S, Nf = depth.shape[1], opt.nerf.sample_intvs_fine
+            det = not opt.nerf.sample_stratified
+            grid = None
+            if not det:
+                gp = fine_grid if fine_grid is not None else torch.rand(Nf + 1)
+                gc = corres.fine_grid if corres.fine_grid is not None else torch.rand(Nf + 1)
+                grid = torch.cat([gp.to(dev).expand(Rp, Nf + 1), gc.to(dev).expand(2 * M, Nf + 1)])
+            fine_t = sample_depth_from_pdf(passes[0][3]['w'][None], S, Nf, depth_range, det=det, grid=grid)
+            depth_f = torch.cat([depth, fine_t[0, :, :, 0]], dim=1).sort(dim=1).values.contiguous()
+            passes.append((self.states[1], depth_f) + self._fwd(self.states[1], center, ray, depth_f))
+        grads, loss_photo = [], None
+        for st, dep, ws, b in passes:
+            cb = getattr(ws, 'corres_bufs', None)
+            if cb is None or cb['Rp'] != Rp:          # g_rgb stays zero on the tail, g_depth on the prefix
+                cb = ws.corres_bufs = dict(Rp=Rp, g_rgb=torch.zeros(R, 3, **f), g_d=torch.zeros(R, **f))
+            l = self._photometric(b, b['rgb'][:Rp], image, cb['g_rgb'][:Rp], 2.0 * corres.photo_weight)
+            loss_photo = l if loss_photo is None else loss_photo + l
+            grads.append(cb)
+        if getattr(self, '_corres', None) is None:
+            self._corres = dict(loss=torch.zeros(256, **f), i=-1, g_w2c=torch.zeros(2, 3, 4, **f))
+        c = self._corres
+        c['i'] = (c['i'] + 1) % 256
+        loss_corr = c['loss'][c['i']]
+        fine_b = passes[1][3] if fine else None
+        ops.nerf_corres_loss(passes[0][3]['d'][Rp:], fine_b['d'][Rp:] if fine else None, corres.pix_self, corres.pix_other,
+                             corres.conf, corres.K_self, corres.K_other, corres.w2c_self, corres.w2c_other, corres.pixel_check,
+                             corres.pixel_thresh, corres.depth_check, corres.depth_thresh, corres.weight, loss_corr,
+                             grads[0]['g_d'][Rp:], grads[1]['g_d'][Rp:] if fine else None, c['g_w2c'])
+        g_center = g_ray = None
+        for (st, dep, ws, b), cb in zip(passes, grads):
+            gc, gr = self._bwd(st, ws, b, ray, dep, cb['g_rgb'], cb['g_d'])
+            g_center, g_ray = (gc, gr) if g_center is None else (g_center + gc, g_ray + gr)
+        self.last_terms = dict(photometric=loss_photo, corres=loss_corr)
+        self.last_g_w2c = c['g_w2c']
+        return loss_photo + loss_corr, g_center, g_ray
 
     def optimizer_step(self, grad_scale=1.0):
         """torch.optim.Adam semantics (lib/utils.py:294-299); also re-zeroes the gradient blocks for the next step.  Like

@@ -21,6 +21,8 @@ class DualBranchEngine:
         e = obj_engine
         self._se3_tmp = torch.zeros_like(e.se3_grad)
         self.last_scene_loss = None
+        self.last_scene_terms = None
+        self._K = None
 
     def scene_rays(self, pixels, n_views=None):
         """pixels [N, 2] (x, y; the same for every view, as the reference's sampler draws them) -> center, ray [V, N, 3] and
@@ -36,13 +38,41 @@ class DualBranchEngine:
         center = c2w[:, None, :, 3].expand_as(ray)
         return center, ray, dir_cam
 
+    def intrinsics(self):
+        """[V,3,3] intrinsic matrices of the object engine's views, rebuilt only when its intrinsics change."""
+        e = self.obj
+        key = (e.intr.data_ptr(), e.intr._version)
+        if self._K is None or self._K[0] != key:
+            K = torch.zeros(e.V, 3, 3, device=e.intr.device)
+            K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = e.intr[:, 0], e.intr[:, 1], e.intr[:, 2], e.intr[:, 3], 1.
+            self._K = (key, K)
+        return self._K[1]
+
+    def pair_rays(self, i, j, pix_self, pix_other):
+        """Rays of the matched pixels of views (i, j) (bg_nerf.get_center_and_ray_at_pixels: K^-1 [x, y, 1], no half-pixel
+        offset) on the current c2w -> center, ray, dir_cam [2, M, 3] (self rows, then other rows)."""
+        e = self.obj
+        pix = torch.stack([pix_self, pix_other])
+        fx, fy, cx, cy = (torch.stack([e.intr[i], e.intr[j]])[:, k][:, None] for k in range(4))
+        x, y = pix[..., 0], pix[..., 1]
+        dir_cam = torch.stack([(x - cx) / fx, (y - cy) / fy, torch.ones_like(x)], dim=-1)
+        c2w = torch.stack([e.c2w[i], e.c2w[j]])
+        ray = dir_cam @ c2w[:, :, :3].transpose(-1, -2)
+        return c2w[:, None, :, 3].expand_as(ray), ray, dir_cam
+
     def forward_backward(self, ray_idx, jitter, global_step, pixels, image, depth_rand=None, fine=False, fine_grid=None,
-                         n_views=None):
+                         n_views=None, corres=None, corres_rand=None, corres_fine_grid=None):
         """ray_idx / jitter: the object branch's batch (engine.TrainEngine.train_step); pixels [N, 2] + image [V, N, 3]: the
         scene branch's batch; depth_rand [V, N, S, 1] / fine_grid [Nf + 1] optionally replay the samplers' draws.  On return every gradient
         buffer (object engine's k0 / MLPs / se3 - the pose gradient of BOTH branches - and the scene engine's block) is
-        filled; the object engine's gradients must be zero on entry (its optimiser kernels leave them so)."""
+        filled; the object engine's gradients must be zero on entry (its optimiser kernels leave them so).
+        corres: dict(i, j, pix_self [M,2], pix_other [M,2], conf [M], weight, opt=None, photo_weight=1.0) adds SPARF's
+        correspondence term of the view pair (i, j) (corres_loss.py:140-222, weight = 10^-2 / gamma in the reference's DTU
+        setting): its rows render in the same scene launches as the photometric rays, L_bg = photometric + weight * corres
+        (last_scene_terms holds both parts); corres_rand [2, M, S, 1] / corres_fine_grid [Nf + 1] replay its draws."""
         e, sc = self.obj, self.scene
+        if corres is not None and e.dist is not None:
+            raise NotImplementedError('DualBranchEngine: the correspondence term is not sharded across ranks')
         out = e.render_and_grads(ray_idx, jitter, global_step)            # also refreshes e.c2w / e.jac for this step
         opt = sc.net.opt
         V, N, S = (e.V if n_views is None else n_views), pixels.shape[0], opt.nerf.sample_intvs
@@ -52,26 +82,58 @@ class DualBranchEngine:
         else:
             jit = depth_rand + torch.arange(S, device=pixels.device)[None, None, :, None].float()
             depth = jit / S * (self.depth_range[1] - self.depth_range[0]) + self.depth_range[0]
-        loss_bg, g_center, g_ray = sc.forward_backward(center.reshape(V * N, 3).contiguous(), ray.reshape(V * N, 3).contiguous(),
-                                                       depth.reshape(V * N, S).contiguous(), image.reshape(V * N, 3),
-                                                       fine=fine, depth_range=self.depth_range, fine_grid=fine_grid)
+        if corres is None:
+            loss_bg, g_center, g_ray = sc.forward_backward(center.reshape(V * N, 3).contiguous(),
+                                                           ray.reshape(V * N, 3).contiguous(), depth.reshape(V * N, S).contiguous(),
+                                                           image.reshape(V * N, 3), fine=fine, depth_range=self.depth_range,
+                                                           fine_grid=fine_grid)
+        else:
+            i, j = int(corres['i']), int(corres['j'])
+            if not (0 <= i < V and 0 <= j < V and i != j):
+                raise ValueError(f'DualBranchEngine: correspondence pair ({i}, {j}) is not a pair of the {V} views in play')
+            M = corres['pix_self'].shape[0]
+            c_center, c_ray, c_dir = self.pair_rays(i, j, corres['pix_self'], corres['pix_other'])
+            if corres_rand is None:
+                c_depth = bg_nerf.sample_depth(opt, 2, M, S, self.depth_range, mode='train', device=pixels.device)
+            else:
+                jit = corres_rand + torch.arange(S, device=pixels.device)[None, None, :, None].float()
+                c_depth = jit / S * (self.depth_range[1] - self.depth_range[0]) + self.depth_range[0]
+            K = self.intrinsics()
+            rows = bg_nerf.CorresRows(corres['pix_self'], corres['pix_other'], corres['conf'], K[i], K[j], e.w2c[i], e.w2c[j],
+                                      corres['weight'], opt=corres.get('opt', opt), fine_grid=corres_fine_grid,
+                                      photo_weight=corres.get('photo_weight', 1.0))
+            loss_bg, g_center, g_ray = sc.forward_backward(
+                torch.cat([center.reshape(V * N, 3), c_center.reshape(2 * M, 3)]),
+                torch.cat([ray.reshape(V * N, 3), c_ray.reshape(2 * M, 3)]),
+                torch.cat([depth.reshape(V * N, S), c_depth.reshape(2 * M, S)]), image.reshape(V * N, 3), fine=fine,
+                depth_range=self.depth_range, fine_grid=fine_grid, corres=rows)
         # fold the ray gradients into d L_bg / d c2w and through the object engine's pose Jacobian
-        g_ray, g_center = g_ray.view(V, N, 3), g_center.view(V, N, 3)
-        g_c2w = torch.cat([torch.einsum('vni,vnj->vij', g_ray, dir_cam), g_center.sum(1)[..., None]], dim=-1)
+        g_ray_p, g_center_p = g_ray[:V * N].view(V, N, 3), g_center[:V * N].view(V, N, 3)
+        g_c2w = torch.cat([torch.einsum('vni,vnj->vij', g_ray_p, dir_cam), g_center_p.sum(1)[..., None]], dim=-1)
         if V < e.V:                                     # views that are not in play yet receive no scene gradient
             g_c2w = torch.cat([g_c2w, torch.zeros(e.V - V, 3, 4, device=g_c2w.device)], dim=0)
         g_c2w = g_c2w.contiguous()
+        if corres is not None:
+            # the matched rows' ray gradients and the loss's direct gradient on both w2c, accumulated into views i and j
+            ops.nerf_pair_pose_bwd(g_center[V * N:], g_ray[V * N:], c_dir.reshape(2 * M, 3), e.w2c, sc.last_g_w2c, i, j, g_c2w)
+            self.last_scene_terms = sc.last_terms
+        else:
+            self.last_scene_terms = None
         ops.pose_bwd(e.jac, g_c2w, self._se3_tmp)
         e.se3_grad += self._se3_tmp
         self.last_scene_loss = loss_bg
         return out, loss_bg
 
     def train_step(self, ray_idx, jitter, global_step, pixels, image, depth_rand=None, optimize_pose=True, fine=False,
-                   fine_grid=None, n_views=None, before_step=None):
+                   fine_grid=None, n_views=None, before_step=None, corres=None):
         """fine=True: the scene branch also runs its fine network (after ratio_start_fine_sampling_at_x of the schedule).
         before_step: callable run after both branches' backward and before the optimiser step (the trainer mixes its extra
-        pose-only loss terms into se3_grad there)."""
-        out = self.forward_backward(ray_idx, jitter, global_step, pixels, image, depth_rand, fine, fine_grid, n_views)
+        pose-only loss terms into se3_grad there).  corres: see forward_backward."""
+        if corres is None:
+            out = self.forward_backward(ray_idx, jitter, global_step, pixels, image, depth_rand, fine, fine_grid, n_views)
+        else:
+            out = self.forward_backward(ray_idx, jitter, global_step, pixels, image, depth_rand, fine, fine_grid, n_views,
+                                        corres=corres)
         if before_step is not None:
             before_step()
         e = self.obj

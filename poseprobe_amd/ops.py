@@ -409,3 +409,29 @@ def nerf_huber_loss(pred, label, delta, weight, loss, g_pred):
     """loss[0] = weight * huber(pred, label, delta, mean); g_pred = its gradient (base_losses.py:155-156)."""
     _lib.call('pp_nerf_huber_loss', _f(pred), _f(label), int(pred.numel()), ctypes.c_float(delta), ctypes.c_float(weight), _f(loss),
               _f(g_pred), _stream())
+
+
+def nerf_corres_loss(depth0, depth1, pix_self, pix_other, conf, K_self, K_other, w2c_self, w2c_other, pixel_check, pixel_thresh,
+                     depth_check, depth_thresh, weight, loss, g_depth0, g_depth1, g_w2c):
+    """depth0 / depth1 (None: one pass) [2M] = [self M | other M]; the rest as pp_nerf_corres_loss (include/poseprobe_hip.h)."""
+    M = pix_self.shape[0]
+    for t, n, what in ((depth0, 2 * M, 'depth0'), (g_depth0, 2 * M, 'g_depth0'), (pix_other, 2 * M, 'pix_other'),
+                       (pix_self, 2 * M, 'pix_self'), (conf, M, 'conf'), (K_self, 9, 'K_self'), (K_other, 9, 'K_other'),
+                       (w2c_self, 12, 'w2c_self'), (w2c_other, 12, 'w2c_other'), (g_w2c, 24, 'g_w2c'), (loss, 1, 'loss')):
+        if t.numel() < n:
+            raise RuntimeError(f'{what} holds {t.numel()} floats, needs {n}')
+    if (depth1 is None) != (g_depth1 is None) or (depth1 is not None and min(depth1.numel(), g_depth1.numel()) < 2 * M):
+        raise RuntimeError('depth1 / g_depth1: both None or both [2M]')
+    _lib.call('pp_nerf_corres_loss', _f(depth0), _f(depth1), int(M), _f(pix_self), _f(pix_other), _f(conf), _f(K_self),
+              _f(K_other), _f(w2c_self), _f(w2c_other), int(bool(pixel_check)), ctypes.c_float(pixel_thresh),
+              int(bool(depth_check)), ctypes.c_float(depth_thresh), ctypes.c_float(weight), _f(loss), _f(g_depth0), _f(g_depth1),
+              _f(g_w2c), _stream())
+
+
+def nerf_pair_pose_bwd(g_center, g_ray, dir_cam, w2c, g_w2c, view_self, view_other, g_c2w):
+    """g_center / g_ray / dir_cam [2M,3] (self rows, then other rows); w2c / g_c2w [V,3,4]; g_w2c [2,3,4] or None."""
+    M2, V = g_center.shape[0], w2c.shape[0]
+    if M2 % 2 or g_ray.shape[0] != M2 or dir_cam.shape[0] != M2 or g_c2w.shape[0] != V or (g_w2c is not None and g_w2c.numel() < 24):
+        raise RuntimeError('nerf_pair_pose_bwd: inconsistent shapes')
+    _lib.call('pp_nerf_pair_pose_bwd', _f(g_center), _f(g_ray), _f(dir_cam), int(M2 // 2), _f(w2c), _f(g_w2c), int(V),
+              int(view_self), int(view_other), _f(g_c2w), _stream())

@@ -9,9 +9,12 @@ Schedules (all pure functions of the step, unit-tested on the CPU):
                           default_config.py:176-180),
   * coarse-to-fine window `progress = iteration_nerf / max_iter` written into both NeRFs (renderer.py:399-402),
   * fine network          from `ratio_start_fine_sampling_at_x * max_iter` on (renderer.py:580-584),
-  * pose refinement       while `step < ratio_end_joint_nerf_pose_refinement * max_iter` (sparf.py:33, recon_scene.py:770).
+  * pose refinement       while `step < ratio_end_joint_nerf_pose_refinement * max_iter` (sparf.py:33, recon_scene.py:770),
+  * scene objective       `opt.loss_type` (loss_factory.py:25-42): the photometric term, plus SPARF's correspondence term
+                          weighted 10^loss_weight.corres / gamma from `start_iter.corres` on (corres_loss.py:78-90, :151).
 """
 import os
+import random
 
 import numpy as np
 import torch
@@ -50,6 +53,87 @@ def active_views(global_step, n_views, incremental_step, incremental=True, start
 def object_phase(global_step, n_iters_object, start_object=0):
     """The object branch is optimised while start_object <= step <= cfg_train.N_iters (lib/recon_scene.py:584)."""
     return start_object <= global_step <= n_iters_object
+
+
+SCENE_TERMS = ('photometric', 'corres', 'depth_cons')
+
+
+def loss_terms(loss_type):
+    """`opt.loss_type` -> the set of scene-branch terms (loss_factory.py:25-42 builds one module per '_and_'-joined name).
+    None / absent = 'photometric', the objective before loss_type was read.  'depth_cons' is accepted and adds NOTHING:
+    the reference's DepthConsistencyLoss.compute_loss (depth_cons_loss.py:128-230) computes its loss into a local variable
+    and returns the empty loss_dict it created on entry, so no depth_cons key ever reaches the weighted sum
+    (base_losses.py:37-55) - its renders cost time there and change no parameter update."""
+    if loss_type is None or loss_type == '':
+        return frozenset(['photometric'])
+    names = str(loss_type).split('_and_')
+    unknown = [n for n in names if n not in SCENE_TERMS]
+    if unknown:
+        raise NotImplementedError(f'scene loss term(s) {unknown} of loss_type {loss_type!r} are not implemented '
+                                  f'(supported: {" / ".join(SCENE_TERMS)})')
+    if 'photometric' not in names:
+        raise NotImplementedError(f'loss_type {loss_type!r}: the scene branch always trains the photometric term')
+    return frozenset(names)
+
+
+def loss_weight(opt, key):
+    """Weight of term `key` (base_losses.py:111-130): 10^w under the 'exp' parametrization, w otherwise; None = term off."""
+    lw = getattr(opt, 'loss_weight', None)
+    if lw is None:
+        return 1.0 if key == 'photometric' else None
+    if lw.get('equalize_losses', False):
+        raise NotImplementedError('loss_weight.equalize_losses is not implemented')
+    w = lw.get('render' if key == 'photometric' else key)
+    if w is None:
+        return None
+    return 10 ** float(w) if lw.get('parametrization', 'exp') == 'exp' else float(w)
+
+
+def corres_gamma(iteration, opt, max_iter):
+    """Divisor of the correspondence weight (corres_loss.py:78-90): 2^((iteration - start) // corres_weight_reduct_at_x_iter)
+    from start = ratio_start_decrease_corres_weight * max_iter (or iter_start_decrease_corres_weight) on, 1 before."""
+    if not getattr(opt, 'gradually_decrease_corres_weight', False):
+        return 1.0
+    ratio = getattr(opt, 'ratio_start_decrease_corres_weight', None)
+    start = ratio * max_iter if ratio is not None else getattr(opt, 'iter_start_decrease_corres_weight', 0)
+    if iteration < start:
+        return 1.0
+    return float(2 ** ((iteration - start) // getattr(opt, 'corres_weight_reduct_at_x_iter', 10000)))
+
+
+def corres_started(iteration, opt):
+    """The term is skipped while iteration < start_iter.corres (corres_loss.py:151)."""
+    st = getattr(opt, 'start_iter', None)
+    return iteration >= (st.get('corres', 0) if st is not None else 0)
+
+
+def pair_partner(i):
+    """Partner of view i in the scene matches: i - 1, and 1 for view 0 (setup_matcher_results with num_camera = 1,
+    recon_scene.py:225-245)."""
+    return 1 if i == 0 else i - 1
+
+
+def pair_table(scene_matches):
+    """scene_matches[i] = (pix_self [P,2], pix_other [P,2], conf [P]) or with an explicit partner as a 4th entry (None = the
+    default rule) -> [(i, j, pix_self, pix_other, conf)], keeping the rows with conf > 0 (corres_loss.py:160-162: the mask is
+    applied here, once, so that no step has a data-dependent shape)."""
+    table = []
+    for i, entry in enumerate(scene_matches):
+        if entry is None:
+            table.append(None)
+            continue
+        ps, po, conf = entry[:3]
+        j = pair_partner(i) if len(entry) < 4 or entry[3] is None else int(entry[3])
+        conf = torch.as_tensor(conf).reshape(-1)
+        keep = conf > 0
+        table.append((i, j, torch.as_tensor(ps)[keep], torch.as_tensor(po)[keep], conf[keep]))
+    return table
+
+
+def corres_sample_size(n_matches, rand_rays):
+    """Matched rows rendered per step: all of them up to rand_rays // 2, a random subset of that many beyond
+    (corres_loss.py:171-176)."""
+    return min(int(n_matches), int(rand_rays) // 2)
 
 
 class ReprojectionTerm:
@@ -101,14 +185,31 @@ class ReprojectionTerm:
 
 class DualBranchTrainer:
     def __init__(self, obj_engine, opt, max_iter=60000, lr=1e-3, lr_end=1e-4, ratio_start_fine=0.3, ratio_end_pose=0.3,
-                 depth_range=(0.5, 3.0), seed=0, incremental_step=0, pose_initialiser=None, pose_terms=()):
+                 depth_range=(0.5, 3.0), seed=0, incremental_step=0, pose_initialiser=None, pose_terms=(), scene_matches=None):
         """incremental_step > 0: the incremental view schedule (`active_views`); a view that joins gets its initial pose from
         `pose_initialiser(view, w2c_of_previous_view [3,4]) -> w2c [3,4]` - the reference's PnP hand-off (cv2.solvePnPRansac on
         matcher output, lib/recon_scene.py:202-214, :276-310) plugs in here; the default is its `use_identical` variant (the
         previous view's current pose).  pose_terms: extra pose-only loss terms mixed into the object loss as the reference
         mixes its reprojection / near-surface terms (:616-637): callables `f(se3 [V,6] requiring grad, w2c_init, n_active)
-        -> (weight, scalar loss)`, differentiated by torch autograd through camera.current_pose_c2w."""
+        -> (weight, scalar loss)`, differentiated by torch autograd through camera.current_pose_c2w.
+        scene_matches: per view i, (pix_self [P,2], pix_other [P,2], conf [P][, partner]) - the reference's coord1_scene[i],
+        coord0_scene[i], mconf_scene[i] (recon_scene.py:247-257), paired with view pair_partner(i) unless a partner is given;
+        read when opt.loss_type contains 'corres'."""
         self.opt, self.max_iter = opt, max_iter
+        self.terms = loss_terms(getattr(opt, 'loss_type', None))
+        self.photo_weight = loss_weight(opt, 'photometric') if 'loss_type' in opt else 1.0
+        if self.photo_weight != 1.0:
+            raise NotImplementedError('loss_weight.render other than 10^0 is not implemented')
+        self.corres_weight = None
+        if 'corres' in self.terms:
+            self.corres_weight = loss_weight(opt, 'corres')
+            if scene_matches is None:
+                raise ValueError(f'loss_type {opt.loss_type!r} needs scene_matches')
+        self.pairs = None if scene_matches is None or self.corres_weight is None else [
+            None if p is None else (p[0], p[1], *(t.float().to(obj_engine.dev) for t in p[2:]))
+            for p in pair_table(scene_matches)]
+        self.pair_rng = random.Random(seed)
+        self.last_scene_terms = None
         self.incremental_step, self.pose_initialiser, self.pose_terms = incremental_step, pose_initialiser, tuple(pose_terms)
         self.n_active = None
         self.lr, self.lr_end = lr, lr_end
@@ -156,6 +257,26 @@ class DualBranchTrainer:
             self.n_active += 1
         return self.n_active
 
+    def _corres_batch(self, global_step, k):
+        """The correspondence rows of this step, or None: one view drawn uniformly among the k active ones with its partner
+        (recon_scene.py:642-644; `iteration` of the loss is the joint loop's global_step, :643), its matches subsampled on the
+        device to rand_rays // 2 (corres_loss.py:171-176), weight 10^loss_weight.corres / gamma."""
+        if self.pairs is None or not corres_started(global_step, self.opt):
+            return None
+        v = self.pair_rng.randrange(k)
+        entry = self.pairs[v] if v < len(self.pairs) else None
+        if entry is None:
+            return None
+        i, j, ps, po, conf = entry
+        if j >= k or ps.shape[0] == 0:                      # an explicit partner that is not in play yet / no match left
+            return None
+        n = corres_sample_size(ps.shape[0], self.opt.nerf.rand_rays)
+        if n < ps.shape[0]:
+            sel = torch.randperm(ps.shape[0], device=self.dev, generator=self.gen)[:n]
+            ps, po, conf = ps[sel], po[sel], conf[sel]
+        return dict(i=i, j=j, pix_self=ps, pix_other=po, conf=conf, opt=self.opt,
+                    weight=self.corres_weight / corres_gamma(global_step, self.opt, self.max_iter))
+
     def _mix_pose_terms(self, k):
         """loss += w_i * L_i(poses) for the extra pose-only terms: their se3 gradient joins the object branch's (which the
         engine scales by loss_scale = 0.1, lib/recon_scene.py:648)."""
@@ -182,9 +303,12 @@ class DualBranchTrainer:
         fine = fine_phase(global_step, self.max_iter, self.ratio_start_fine, self.nerf_fine is not None)
         ray_idx, jitter, pixels, image = self.sample_batch(k)
         self.last_pose_terms = {}
+        corres = self._corres_batch(global_step, k)
         out = self.joint.train_step(ray_idx, jitter, global_step, pixels, image, fine=fine,
                                     optimize_pose=pose_phase(global_step, self.max_iter, self.ratio_end_pose), n_views=k,
-                                    before_step=(lambda: self.last_pose_terms.update(self._mix_pose_terms(k))) if self.pose_terms else None)
+                                    before_step=(lambda: self.last_pose_terms.update(self._mix_pose_terms(k))) if self.pose_terms else None,
+                                    corres=corres)
+        self.last_scene_terms = self.joint.last_scene_terms
         self.joint.scene.set_lr(scene_lr(self.iteration, self.lr, self.lr_end, self.max_iter))
         p = c2f_progress(self.iteration, self.max_iter)                # takes effect from the next iteration (renderer.py:399)
         self.nerf.progress.data.fill_(p)
