@@ -225,7 +225,7 @@ int pp_color_feat_bwd(const pp_scene* sc, const float* k0_cl, const float* pts, 
  * Names (meaning and ranges: csrc/pp_common.h, csrc/pp_error.hip):
  *   arithmetic   mlp_split (bit mask: object-branch MLP kernels as 3 fp16 products per fp32 product; 0 = fp32 MFMA instructions),
  *                nerf_split (scene branch likewise), mlp_fused, nerf_chain
- *   scheduling   side_stream, mlp_wgs, wgrad_side_wgs, grid_chunks, nerf_chain_nw, nerf_chain_head
+ *   scheduling   side_stream, mlp_wgs, wgrad_side_wgs, grid_chunks, nerf_chain_nw, nerf_chain_head, mlp_pack (see pp_mlp_pack)
  * pp_nerf_fwd and pp_nerf_bwd of one pass (and the two stages of a two-stage backward) must see the same option values.
  * Unknown names / out-of-range values are refused; pp_context_get_option(NULL, ...) reads the defaults. */
 int pp_context_create(void** ctx);
@@ -287,6 +287,22 @@ int pp_rgbnet_bwd_data(const float* params, const float* acts, const float* rgb,
                        int32_t* stage2_host, void* ctx, void* stream);
 int pp_rgbnet_bwd_weights(const float* feat, const float* acts, const float* scratch, const int32_t* count,
                           int32_t capacity, float* params_grad, int32_t stage2, void* ctx, void* stream);
+
+/* Weight pack of the two object-branch MLPs (option mlp_pack, default 1).  The split-precision data-path kernels behind
+ * pp_warp_fwd / pp_warp_bwd(_data) / pp_rgbnet_fwd / pp_rgbnet_bwd(_data) / pp_mlp_fwd / pp_mlp_bwd start by turning the
+ * hidden layers' weights into fp16 hi | lo register images and by reducing their maxima and L1 norms - in every work-group of
+ * every launch.  pp_mlp_pack does that work once (one small kernel on `stream`) into `pack` (pp_mlp_pack_workspace floats,
+ * 16-byte aligned, caller-owned) and records `pack` and the two params pointers in `ctx` (required; either params pointer may be
+ * NULL: that net is not packed).  A later call with THAT context and exactly THAT params pointer reads the pack (bit-identical
+ * results); a call with ctx = NULL, with option mlp_pack = 0 or with any other params pointer derives everything itself, as
+ * before.  The library cannot see writes to the parameters: whoever changes them (an optimiser step, a checkpoint load, a copy
+ * into the buffer) must call pp_mlp_pack again, or pp_mlp_pack_invalidate, BEFORE the next MLP call with that context - on the
+ * same stream as the write, so that the pack kernel reads the new values.  `pack` must stay alive, and unwritten by others,
+ * until the record is replaced or invalidated and the kernels that read it are done.  With option mlp_pack = 0 (or no
+ * split-precision kernel selected) pp_mlp_pack launches nothing and records nothing. */
+int pp_mlp_pack_workspace(int64_t* pack_floats);
+int pp_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, void* ctx, void* stream);
+int pp_mlp_pack_invalidate(void* ctx);
 
 /* ---------------------------------------------------------------- losses: lib/losses.py:6-74 (object_losses),
  * forward values + gradients w.r.t. the render outputs in one pass.  loss_scale multiplies every gradient

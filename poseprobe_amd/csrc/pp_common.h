@@ -28,6 +28,8 @@ enum PPOption {
                                // (pp_nerf_trunk.h), 3 = the data-gradient chain of the backward pass too (0 = one GEMM per layer)
   PP_OPT_NERF_CHAIN_NW,        // scene branch: wavefronts per work-group of the fused chains (8: one 128-sample tile per CU, 4: two 64-sample tiles per CU)
   PP_OPT_NERF_CHAIN_HEAD,      // scene branch: 1 = the colour head's hidden layer as a ninth stage of the fused forward chain
+  PP_OPT_MLP_PACK,             // 1: the split-precision object-branch MLP kernels read a weight pack recorded in the context by pp_mlp_pack
+                               // for the params pointer they are given, 0: they always derive it in their prologues
   PP_OPT_COUNT
 };
 
@@ -39,6 +41,10 @@ struct PPContext {
   hipEvent_t fork[16], join[16];
   int pending;                      // deferred side launches of the fused paths not yet joined (pp_context_join)
   hipEvent_t dfork[4], djoin[4];
+  // weight pack of the object-branch MLPs (pp_mlp_pack): the buffer and the two parameter blocks it was computed from
+  // ([0] warp net, [1] rgbnet); pack == nullptr: none
+  const float* pack;
+  const float* pack_params[2];
 };
 bool pp_context_aux(PPContext* c);   // creates the auxiliary stream + events on first use; false when HIP refuses
 

@@ -19,6 +19,7 @@
 // cross-lane traffic.
 #include "pp_common.h"
 #include "pp_mlp_fused.h"
+#include "pp_mlp_pack.h"
 #include <stdlib.h>
 
 #include "pp_gemm.h"
@@ -308,6 +309,46 @@ struct SideLane {
 // option "mlp_fused" = 0 selects the layer-by-layer kernels (A/B measurements, generic shapes always use them)
 static bool mlp_fused_enabled() { return pp_opt(PP_OPT_MLP_FUSED) == 1; }
 
+// the weight pack a split-precision kernel may read instead of its prologue: only the one recorded in THIS call's context for
+// exactly these params (net 0: warp net, 1: rgbnet); no context, option mlp_pack = 0 or another pointer: none
+static const float* mlp_pack_for(const void* ctx, const float* params, int net) {
+  if (!ctx) return nullptr;
+  const PPContext* c = static_cast<const PPContext*>(ctx);
+  if (c->opt[PP_OPT_MLP_PACK] != 1 || !c->pack || c->pack_params[net] != params) return nullptr;
+  return c->pack;
+}
+
+extern "C" int pp_mlp_pack_workspace(int64_t* pack_floats) {
+  PP_REQUIRE(pack_floats, "null pointer");
+  *pack_floats = PK_FLOATS;
+  return PP_OK;
+}
+
+extern "C" int pp_mlp_pack_invalidate(void* ctx) {
+  PP_REQUIRE(ctx, "null context");
+  PPContext* c = static_cast<PPContext*>(ctx);
+  c->pack = nullptr;
+  c->pack_params[0] = c->pack_params[1] = nullptr;
+  return PP_OK;
+}
+
+extern "C" int pp_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, void* ctx, void* stream) {
+  PPOptScope scope(ctx);
+  PP_REQUIRE(ctx, "null context (the pack is recorded in a context: create one)");
+  PP_REQUIRE(pack && (warp_params || rgbnet_params), "null pointer");
+  PP_REQUIRE((reinterpret_cast<uintptr_t>(pack) & 15) == 0, "pack must be 16-byte aligned");
+  pp_mlp_pack_invalidate(ctx);
+  // nothing would read it: option off, or none of the four split-precision data-path kernels selected
+  if (pp_opt(PP_OPT_MLP_PACK) != 1 || !mlp_fused_enabled() || (pp_opt(PP_OPT_MLP_SPLIT) & 15) == 0) return PP_OK;
+  pp_launch_mlp_pack(warp_params, rgbnet_params, pack, pp_stream(stream));
+  PP_CHECK_LAUNCH();
+  PPContext* c = static_cast<PPContext*>(ctx);
+  c->pack = pack;
+  c->pack_params[0] = warp_params;
+  c->pack_params[1] = rgbnet_params;
+  return PP_OK;
+}
+
 static const int GEMM_MAX_WG = 256 * 5;     // 5 resident work-groups per CU at BM=64 (25 KB LDS, 90 regs)
 static const int GEMM_MAX_WG_SHARED = 256 * 3;   // when a weight-gradient GEMM runs beside it (register file: 2 x 96 + 2 x 144)
 static inline int gemm_grid(int rows, int bm, bool shared = false) {
@@ -334,7 +375,7 @@ extern "C" int pp_mlp_fwd(const float* params, const float* feat, int32_t in_ld,
              "acts may be NULL only for the rgbnet shape with the split-precision forward kernel (option mlp_split bit 4)");
   hipStream_t st = pp_stream(stream);
   if (in_ld == 64 && n_gemm == 3 && mlp_fused_enabled()) {       // the Voxurf rgbnet shape: layer-fused kernel
-    if (pp_opt(PP_OPT_MLP_SPLIT) & 4) pp_launch_rgb_fused_fwd_s(params, feat, count, capacity, logit_add, logit_add_ld, acts, out, st);
+    if (pp_opt(PP_OPT_MLP_SPLIT) & 4) pp_launch_rgb_fused_fwd_s(params, feat, count, capacity, logit_add, logit_add_ld, acts, out, st, mlp_pack_for(ctx, params, 1));
     else pp_launch_rgb_fused_fwd(params, feat, count, capacity, logit_add, logit_add_ld, acts, out, st);
     PP_CHECK_LAUNCH();
     return PP_OK;
@@ -366,7 +407,7 @@ extern "C" int pp_mlp_bwd(const float* params, const float* feat, int32_t in_ld,
   if (in_ld == 64 && n_gemm == 3 && feat_grad && mlp_fused_enabled()) {
     const bool sb = (pp_opt(PP_OPT_MLP_SPLIT) & 8) != 0;   // split-precision data-gradient kernel: b0..b2 come from the weight-gradient kernel
     if (sb) pp_launch_rgb_fused_bwd_s(params, acts, out, out_grad, count, capacity, scratch, params_grad, feat_grad, logit_add_grad,
-                                      logit_add_ld, st);
+                                      logit_add_ld, st, mlp_pack_for(ctx, params, 1));
     else pp_launch_rgb_fused_bwd(params, acts, out, out_grad, count, capacity, scratch, params_grad, feat_grad, logit_add_grad,
                                  logit_add_ld, st);
     const size_t FLS = (size_t)capacity * 128;
@@ -438,7 +479,7 @@ extern "C" int pp_warp_fwd(const float* params, const float* pts, const int32_t*
              "acts may be NULL (forward only) only with the split-precision forward kernel (option mlp_split bit 1)");
   hipStream_t st = pp_stream(stream);
   if (mlp_fused_enabled()) {
-    if (pp_opt(PP_OPT_MLP_SPLIT) & 1) pp_launch_warp_fused_fwd_s(params, pts, count, capacity, out_range, acts, out, st);
+    if (pp_opt(PP_OPT_MLP_SPLIT) & 1) pp_launch_warp_fused_fwd_s(params, pts, count, capacity, out_range, acts, out, st, mlp_pack_for(ctx, params, 0));
     else pp_launch_warp_fused_fwd(params, pts, count, capacity, out_range, acts, out, st);
     PP_CHECK_LAUNCH();
     return PP_OK;
@@ -471,7 +512,7 @@ extern "C" int pp_warp_bwd(const float* params, const float* pts, const float* a
   const size_t LS = (size_t)rcap * 128;
   if (mlp_fused_enabled()) {
     // one fused data-gradient kernel (+ thin layers), then the three weight-gradient GEMMs on the Ybar it left behind
-    if (pp_opt(PP_OPT_MLP_SPLIT) & 2) pp_launch_warp_fused_bwd_s(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st);
+    if (pp_opt(PP_OPT_MLP_SPLIT) & 2) pp_launch_warp_fused_bwd_s(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st, mlp_pack_for(ctx, params, 0));
     else pp_launch_warp_fused_bwd(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st);
     hipStream_t ws = deferred_fork(ctx, st);
     const bool sb = (pp_opt(PP_OPT_MLP_SPLIT) & 2) != 0;   // the split-precision data-gradient kernel leaves b1..b3 to this one
@@ -531,7 +572,7 @@ extern "C" int pp_warp_bwd_data(const float* params, const float* pts, const flo
   *stage2_host = (pp_opt(PP_OPT_MLP_SPLIT) & 2) ? 1 : 0;       // 1: the hidden layers' bias gradients are stage 2's to produce
   if (pp_opt(PP_OPT_MLP_SPLIT) & 2)
     pp_launch_warp_fused_bwd_s(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad,
-                               pp_stream(stream));
+                               pp_stream(stream), mlp_pack_for(ctx, params, 0));
   else
     pp_launch_warp_fused_bwd(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad,
                              pp_stream(stream));
@@ -565,7 +606,7 @@ extern "C" int pp_rgbnet_bwd_data(const float* params, const float* acts, const 
   *stage2_host = (pp_opt(PP_OPT_MLP_SPLIT) & 8) ? 1 : 0;
   if (pp_opt(PP_OPT_MLP_SPLIT) & 8)
     pp_launch_rgb_fused_bwd_s(params, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, nullptr, 0,
-                              pp_stream(stream));
+                              pp_stream(stream), mlp_pack_for(ctx, params, 1));
   else
     pp_launch_rgb_fused_bwd(params, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, nullptr, 0,
                             pp_stream(stream));

@@ -35,12 +35,14 @@ struct WgradOperands {
 int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                             const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
                             hipStream_t st, float* bA, float* bB, float* bC, int wgs = 0);
-// split-precision variants (pp_mlp_split.hip, option "mlp_split"): same contracts
+// split-precision variants (pp_mlp_split.hip, option "mlp_split"): same contracts.  pack: the weight pack written by
+// pp_launch_mlp_pack FOR THESE params (pp_mlp_pack.h), or nullptr = the kernel derives the same quantities in its prologue
 int pp_launch_warp_fused_fwd_s(const float* params, const float* pts, const int32_t* count, int capacity, float out_range,
-                               float* acts, float* out, hipStream_t st);
+                               float* acts, float* out, hipStream_t st, const float* pack);
 int pp_launch_warp_fused_bwd_s(const float* params, const float* pts, const float* acts, const float* out_grad,
                                const int32_t* count, int capacity, float out_range, float* ybar, float* params_grad,
-                               float* pts_grad, hipStream_t st);
+                               float* pts_grad, hipStream_t st, const float* pack);
+int pp_launch_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, hipStream_t st);
 // weight gradients of three layers (Y_l^T X_l accumulated into W_l) in one persistent kernel; kxc = width of X of layer C;
 // bA / bB / bC: also accumulate the bias gradients = column sums of Y over the primal rows (kxc == 128: the warp net's 4-row
 // form, every fourth row) or over all rows (kxc == 64: rgbnet)
@@ -61,10 +63,10 @@ int pp_launch_wgrad_chain(const float* YA, const float* XA, float* WA, const flo
 int pp_launch_rgb_fused_fwd(const float* params, const float* feat, const int32_t* count, int capacity,
                             const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st);
 int pp_launch_rgb_fused_fwd_s(const float* params, const float* feat, const int32_t* count, int capacity,
-                              const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st);
+                              const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st, const float* pack);
 int pp_launch_rgb_fused_bwd_s(const float* params, const float* acts, const float* rgb, const float* rgb_grad,
                               const int32_t* count, int capacity, float* ybar, float* params_grad, float* feat_grad,
-                              float* logit_grad, int lg_ld, hipStream_t st);
+                              float* logit_grad, int lg_ld, hipStream_t st, const float* pack);
 int pp_launch_rgb_fused_bwd(const float* params, const float* acts, const float* rgb, const float* rgb_grad,
                             const int32_t* count, int capacity, float* ybar, float* params_grad, float* feat_grad,
                             float* logit_grad, int lg_ld, hipStream_t st);

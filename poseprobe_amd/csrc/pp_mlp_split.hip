@@ -36,6 +36,7 @@
 #include "pp_mlp_fused.h"
 #include "pp_gemm_split.h"
 #include "pp_split_image.h"
+#include "pp_mlp_pack.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -131,6 +132,23 @@ __device__ __forceinline__ int load_w_rows_split(SplitW& w, float& l1, const flo
   for (int ks = 0; ks < 8; ++ks) split8(v[2 * ks], v[2 * ks + 1], s, w.h[ks], w.l[ks]);
   return e;
 }
+
+// a layer's registers of this lane from / to its image in the weight pack (pp_mlp_pack.h): KS operand groups, 16 bytes each way
+template <int KS>
+__device__ __forceinline__ void load_w_packed(SplitW& w, const float* __restrict__ img, int tid) {
+  const pp_half8* __restrict__ p = reinterpret_cast<const pp_half8*>(img) + tid;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) { w.h[ks] = p[(2 * ks) * 256]; w.l[ks] = p[(2 * ks + 1) * 256]; }
+#pragma unroll
+  for (int ks = KS; ks < 8; ++ks) { w.h[ks] = w.h[0]; w.l[ks] = w.l[0]; }
+}
+template <int KS>
+__device__ __forceinline__ void store_w_packed(float* __restrict__ img, const SplitW& w, int tid) {
+  pp_half8* __restrict__ p = reinterpret_cast<pp_half8*>(img) + tid;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) { p[(2 * ks) * 256] = w.h[ks]; p[(2 * ks + 1) * 256] = w.l[ks]; }
+}
+__device__ __forceinline__ int pk_int(const float* __restrict__ pack, int slot) { return __float_as_int(pack[PK_SCAL + slot]); }
 
 struct NoHook { __device__ __forceinline__ void operator()(int) const {} };
 // acc[reg] += sum_k W[feature(reg)][k] X[row l31][k]  for 32 rows of a split tile (`rows` = hi plane of the first of them, lo
@@ -281,9 +299,12 @@ __device__ __forceinline__ float slot_get(const unsigned* slot) { return __uint_
 
 // ------------------------------------------------------------------------------------------------ warp net, forward
 // Same contract as k_warp_fused_fwd: pts[M][3] -> out[M][4][4], hidden activations X0..X3 ([4M][128] fp32 each) for backward.
+// PACK: the prologue reads the hidden layers' registers and every scalar from the weight pack instead of deriving them
+template <bool PACK>
 __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restrict__ params, const float* __restrict__ pts,
                                                           const int32_t* __restrict__ count, int capacity, float out_range,
-                                                          float* __restrict__ acts, float* __restrict__ out) {
+                                                          float* __restrict__ acts, float* __restrict__ out,
+                                                          const float* __restrict__ pack) {
   __shared__ __attribute__((aligned(16))) _Float16 At[2][2 * PLANE];      // tile 1 doubles as the fp32 [64][LDA] view
   __shared__ __attribute__((aligned(16))) float W4s[4 * LDA];
   __shared__ __attribute__((aligned(16))) float Red[4 * 64 * 4];
@@ -305,22 +326,37 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
 
   SplitW w1, w2, w3;
   int phase = 0;                        // call counter of block_max
-  float l1_1, l1_2, l1_3;
-  const int ew1 = load_w_rows_split(w1, l1_1, params + WPF_W1, col, lh, red4, tid, phase);
-  const int ew2 = load_w_rows_split(w2, l1_2, params + WPF_W2, col, lh, red4, tid, phase);
-  const int ew3 = load_w_rows_split(w3, l1_3, params + WPF_W3, col, lh, red4, tid, phase);
+  float l1_1, l1_2, l1_3, b1mx, b2mx, w0l1, w0mx, b0mx;
+  int ew1, ew2, ew3, ew0;
+  if (PACK) {
+    load_w_packed<8>(w1, pack + PK_WARP, tid);
+    load_w_packed<8>(w2, pack + PK_WARP + PK_IMG, tid);
+    load_w_packed<8>(w3, pack + PK_WARP + 2 * PK_IMG, tid);
+    ew1 = pk_int(pack, PKW_EW1); ew2 = pk_int(pack, PKW_EW2); ew3 = pk_int(pack, PKW_EW3); ew0 = pk_int(pack, PKW_EW0);
+    l1_1 = pack[PKW_L1_1]; l1_2 = pack[PKW_L1_2]; l1_3 = pack[PKW_L1_3];
+    b1mx = pack[PKW_B1MX]; b2mx = pack[PKW_B2MX]; w0l1 = pack[PKW_W0L1]; w0mx = pack[PKW_W0MX]; b0mx = pack[PKW_B0MX];
+  } else {
+    ew1 = load_w_rows_split(w1, l1_1, params + WPF_W1, col, lh, red4, tid, phase);
+    ew2 = load_w_rows_split(w2, l1_2, params + WPF_W2, col, lh, red4, tid, phase);
+    ew3 = load_w_rows_split(w3, l1_3, params + WPF_W3, col, lh, red4, tid, phase);
+  }
   // biases of the hidden layers in LDS: row l = the layer's biases, row 3 = zeros (tangent lanes, and the input layer whose
   // bias rides in the product); a lane reads its four runs of four from `brow(l)`
   if (tid < 128) { Bs[0][tid] = params[WPF_B1 + tid]; Bs[1][tid] = params[WPF_B2 + tid]; Bs[2][tid] = params[WPF_B3 + tid]; Bs[3][tid] = 0.f; }
   auto brow = [&](int l) -> const float* { return &Bs[primal ? l : 3][fb]; };
-  const float b1mx = block_max(fabsf(params[WPF_B1 + col]), red4, tid, phase), b2mx = block_max(fabsf(params[WPF_B2 + col]), red4, tid, phase);
+  if (!PACK) {
+    b1mx = block_max(fabsf(params[WPF_B1 + col]), red4, tid, phase);
+    b2mx = block_max(fabsf(params[WPF_B2 + col]), red4, tid, phase);
+  }
   // input layer as a K = 16 product: A = [w0x w0y w0z b0 0 ...] (lanes lh = 0), B = [px py pz 1 0 ...] / unit tangents
   const float w0x = params[WPF_W0 + col * 3], w0y = params[WPF_W0 + col * 3 + 1], w0z = params[WPF_W0 + col * 3 + 2];
   const float b0 = params[WPF_B0 + col];
-  const float w0l1 = block_max((fabsf(w0x) + fabsf(w0y)) + fabsf(w0z), red4, tid, phase) * 1.0001f;
-  const float w0mx = block_max(fmaxf(fmaxf(fabsf(w0x), fabsf(w0y)), fabsf(w0z)), red4, tid, phase);
-  const float b0mx = block_max(fabsf(b0), red4, tid, phase);
-  const int ew0 = scale_exp(fmaxf(w0mx, b0mx));
+  if (!PACK) {
+    w0l1 = block_max((fabsf(w0x) + fabsf(w0y)) + fabsf(w0z), red4, tid, phase) * 1.0001f;
+    w0mx = block_max(fmaxf(fmaxf(fabsf(w0x), fabsf(w0y)), fabsf(w0z)), red4, tid, phase);
+    b0mx = block_max(fabsf(b0), red4, tid, phase);
+    ew0 = scale_exp(fmaxf(w0mx, b0mx));
+  }
   pp_half8 a0h, a0l;
   {
     const float z = 0.f;
@@ -488,10 +524,11 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
 }
 
 int pp_launch_warp_fused_fwd_s(const float* params, const float* pts, const int32_t* count, int capacity, float out_range,
-                               float* acts, float* out, hipStream_t st) {
+                               float* acts, float* out, hipStream_t st, const float* pack) {
   const int ntiles = pp_div_up(capacity, 16);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
-  hipLaunchKernelGGL(k_warp_fused_fwd_s, dim3(grid), dim3(256), 0, st, params, pts, count, capacity, out_range, acts, out);
+  if (pack) hipLaunchKernelGGL(k_warp_fused_fwd_s<true>, dim3(grid), dim3(256), 0, st, params, pts, count, capacity, out_range, acts, out, pack);
+  else hipLaunchKernelGGL(k_warp_fused_fwd_s<false>, dim3(grid), dim3(256), 0, st, params, pts, count, capacity, out_range, acts, out, pack);
   return 0;
 }
 
@@ -611,11 +648,12 @@ struct HalfEpilogueB {
 
 }  // namespace
 
+template <bool PACK>
 __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restrict__ params, const float* __restrict__ pts,
                                                           const float* __restrict__ acts, const float* __restrict__ out_grad,
                                                           const int32_t* __restrict__ count, int capacity, float out_range,
                                                           float* __restrict__ ybar, float* __restrict__ params_grad,
-                                                          float* __restrict__ pts_grad) {
+                                                          float* __restrict__ pts_grad, const float* __restrict__ pack) {
   __shared__ __attribute__((aligned(16))) _Float16 At[2][2 * PLANE];      // tile 1 doubles as the fp32 [64][LDA] view (Ybar0)
   __shared__ __attribute__((aligned(16))) float XS[TILE_ROWS * 128];      // X3 rows of the NEXT tile (unpadded, lane-contiguous)
   __shared__ __attribute__((aligned(16))) float GT[2][16 * 128];          // primal rows of the gating activation of a layer
@@ -643,9 +681,19 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
   SplitW w3, w2, w1;
   int phase = 0;                        // call counter of block_max
   float l1_3, l1_2, l1_1;
-  const int ew3 = load_w_cols_split(w3, l1_3, params + WPF_W3, col, lh, red4, tid, phase);
-  const int ew2 = load_w_cols_split(w2, l1_2, params + WPF_W2, col, lh, red4, tid, phase);
-  const int ew1 = load_w_cols_split(w1, l1_1, params + WPF_W1, col, lh, red4, tid, phase);
+  int ew3, ew2, ew1;
+  if (PACK) {
+    load_w_packed<8>(w3, pack + PK_WARP + 3 * PK_IMG, tid);
+    load_w_packed<8>(w2, pack + PK_WARP + 4 * PK_IMG, tid);
+    load_w_packed<8>(w1, pack + PK_WARP + 5 * PK_IMG, tid);
+    ew3 = pk_int(pack, PKW_EW3C); ew2 = pk_int(pack, PKW_EW2C); ew1 = pk_int(pack, PKW_EW1C);
+    l1_3 = pack[PKW_L1_3C]; l1_2 = pack[PKW_L1_2C]; l1_1 = pack[PKW_L1_1C];
+  } else {
+    ew3 = load_w_cols_split(w3, l1_3, params + WPF_W3, col, lh, red4, tid, phase);
+    ew2 = load_w_cols_split(w2, l1_2, params + WPF_W2, col, lh, red4, tid, phase);
+    ew1 = load_w_cols_split(w1, l1_1, params + WPF_W1, col, lh, red4, tid, phase);
+  }
+  // (the output layer's quantities carry out_range, a per-call argument: they stay here)
   // output layer backward as a K = 16 product: A = [w4_0 w4_1 w4_2 w4_3 0 ...] * out_range of feature `col` (lanes lh = 0),
   // B = the row's four out_grad entries
   const float w4a = params[WPF_W4 + col] * out_range, w4b = params[WPF_W4 + 128 + col] * out_range,
@@ -893,11 +941,13 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
 
 int pp_launch_warp_fused_bwd_s(const float* params, const float* pts, const float* acts, const float* out_grad,
                                const int32_t* count, int capacity, float out_range, float* ybar, float* params_grad,
-                               float* pts_grad, hipStream_t st) {
+                               float* pts_grad, hipStream_t st, const float* pack) {
   const int ntiles = pp_div_up(capacity, 16);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
-  hipLaunchKernelGGL(k_warp_fused_bwd_s, dim3(grid), dim3(256), 0, st, params, pts, acts, out_grad, count, capacity, out_range,
-                     ybar, params_grad, pts_grad);
+  if (pack) hipLaunchKernelGGL(k_warp_fused_bwd_s<true>, dim3(grid), dim3(256), 0, st, params, pts, acts, out_grad, count, capacity, out_range,
+                               ybar, params_grad, pts_grad, pack);
+  else hipLaunchKernelGGL(k_warp_fused_bwd_s<false>, dim3(grid), dim3(256), 0, st, params, pts, acts, out_grad, count, capacity, out_range,
+                          ybar, params_grad, pts_grad, pack);
   return 0;
 }
 
@@ -934,6 +984,25 @@ __device__ __forceinline__ int load_w0_rows_split(SplitW& w, float& l1, const fl
   return e;
 }
 
+// transposed weights of input feature f of the 64-wide input layer (A operand of the feature-gradient product): k = hidden
+// feature 16 ks + 8 lh + jj, value W0[k][f].  Returns the exponent of the layer's scale.
+__device__ __forceinline__ int load_w0_cols_split(SplitW& w, const float* __restrict__ W, int f, int lh, float* red, int tid, int& phase) {
+  float4 v[16];
+  float mx = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) {
+    const float* p = W + (size_t)(16 * ks + 8 * lh) * 64 + f;
+    v[2 * ks] = make_float4(p[0], p[64], p[128], p[192]);
+    v[2 * ks + 1] = make_float4(p[256], p[320], p[384], p[448]);
+    mx = fmaxf(mx, fmaxf(amax4(v[2 * ks]), amax4(v[2 * ks + 1])));
+  }
+  const int e = scale_exp(block_max(mx, red, tid, phase));
+  const float s = pow2(e);
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) split8(v[2 * ks], v[2 * ks + 1], s, w.h[ks], w.l[ks]);
+  return e;
+}
+
 // LDS-direct load of a [64][64] fp32 tile into an unpadded buffer whose 16-byte slots are XOR-swizzled (pp_mlp_fused.hip)
 __device__ __forceinline__ void stage_feat_tile_s(const float* __restrict__ feat, int r0, int R, float* Fs, int wid, int lane) {
 #pragma unroll
@@ -947,10 +1016,12 @@ __device__ __forceinline__ void stage_feat_tile_s(const float* __restrict__ feat
 
 }  // namespace
 
+template <bool PACK>
 __global__ __launch_bounds__(256) void k_rgb_fused_fwd_s(const float* __restrict__ params, const float* __restrict__ feat,
                                                          const int32_t* __restrict__ count, int capacity,
                                                          const float* __restrict__ logit_add, int add_ld,
-                                                         float* __restrict__ acts, float* __restrict__ rgb) {
+                                                         float* __restrict__ acts, float* __restrict__ rgb,
+                                                         const float* __restrict__ pack) {
   __shared__ __attribute__((aligned(16))) _Float16 At[2][2 * PLANE];      // tile 0 doubles as the fp32 [64][LDA] view (H2)
   __shared__ __attribute__((aligned(16))) float Fs[2][TILE_ROWS * 64];    // fp32 feature tiles (current / next), swizzled slots
   __shared__ __attribute__((aligned(16))) _Float16 Fh[2 * FPL];           // split image of the current feature tile
@@ -971,12 +1042,23 @@ __global__ __launch_bounds__(256) void k_rgb_fused_fwd_s(const float* __restrict
 
   SplitW w0, w1, w2;
   int phase = 0;                        // call counter of block_max
-  float l1_0, l1_1, l1_2;
-  const int ew0 = load_w0_rows_split(w0, l1_0, params + RGF_W0, col, lh, red4, tid, phase);
-  const int ew1 = load_w_rows_split(w1, l1_1, params + RGF_W1, col, lh, red4, tid, phase);
-  const int ew2 = load_w_rows_split(w2, l1_2, params + RGF_W2, col, lh, red4, tid, phase);
+  float l1_0, l1_1, l1_2, b0mx, b1mx;
+  int ew0, ew1, ew2;
+  if (PACK) {
+    load_w_packed<4>(w0, pack + PK_RGB, tid);
+    load_w_packed<8>(w1, pack + PK_RGB_W1, tid);
+    load_w_packed<8>(w2, pack + PK_RGB_W1 + PK_IMG, tid);
+    ew0 = pk_int(pack, PKR_EW0); ew1 = pk_int(pack, PKR_EW1); ew2 = pk_int(pack, PKR_EW2);
+    l1_0 = pack[PKR_L1_0]; l1_1 = pack[PKR_L1_1]; l1_2 = pack[PKR_L1_2];
+    b0mx = pack[PKR_B0MX]; b1mx = pack[PKR_B1MX];
+  } else {
+    ew0 = load_w0_rows_split(w0, l1_0, params + RGF_W0, col, lh, red4, tid, phase);
+    ew1 = load_w_rows_split(w1, l1_1, params + RGF_W1, col, lh, red4, tid, phase);
+    ew2 = load_w_rows_split(w2, l1_2, params + RGF_W2, col, lh, red4, tid, phase);
+    b0mx = block_max(fabsf(params[RGF_B0 + col]), red4, tid, phase);
+    b1mx = block_max(fabsf(params[RGF_B1 + col]), red4, tid, phase);
+  }
   if (tid < 128) { Bs[0][tid] = params[RGF_B0 + tid]; Bs[1][tid] = params[RGF_B1 + tid]; Bs[2][tid] = params[RGF_B2 + tid]; }
-  const float b0mx = block_max(fabsf(params[RGF_B0 + col]), red4, tid, phase), b1mx = block_max(fabsf(params[RGF_B1 + col]), red4, tid, phase);
   for (int i = tid; i < 512; i += 256) {
     const int r = i >> 7, j = i & 127;
     W3s[r * LDA + j] = (r < 3) ? params[RGF_W3 + r * 128 + j] : 0.f;
@@ -1097,10 +1179,11 @@ __global__ __launch_bounds__(256) void k_rgb_fused_fwd_s(const float* __restrict
 }
 
 int pp_launch_rgb_fused_fwd_s(const float* params, const float* feat, const int32_t* count, int capacity,
-                              const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st) {
+                              const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st, const float* pack) {
   const int ntiles = pp_div_up(capacity, TILE_ROWS);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
-  hipLaunchKernelGGL(k_rgb_fused_fwd_s, dim3(grid), dim3(256), 0, st, params, feat, count, capacity, logit_add, add_ld, acts, rgb);
+  if (pack) hipLaunchKernelGGL(k_rgb_fused_fwd_s<true>, dim3(grid), dim3(256), 0, st, params, feat, count, capacity, logit_add, add_ld, acts, rgb, pack);
+  else hipLaunchKernelGGL(k_rgb_fused_fwd_s<false>, dim3(grid), dim3(256), 0, st, params, feat, count, capacity, logit_add, add_ld, acts, rgb, pack);
   return 0;
 }
 
@@ -1111,11 +1194,13 @@ int pp_launch_rgb_fused_fwd_s(const float* params, const float* feat, const int3
 // Gates are per element (the layer input's own activation); the tile of gating activations arrives by LDS-direct loads into ONE
 // buffer (H1, then H0 - a second 32 KB buffer does not fit beside the two images and the next tile's H2), so the two halves of
 // Ybar0 are written out without MFMAs beside them.
+template <bool PACK>
 __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict__ params, const float* __restrict__ acts,
                                                          const float* __restrict__ rgb, const float* __restrict__ rgb_grad,
                                                          const int32_t* __restrict__ count, int capacity,
                                                          float* __restrict__ ybar, float* __restrict__ params_grad,
-                                                         float* __restrict__ feat_grad, float* __restrict__ logit_grad, int lg_ld) {
+                                                         float* __restrict__ feat_grad, float* __restrict__ logit_grad, int lg_ld,
+                                                         const float* __restrict__ pack) {
   __shared__ __attribute__((aligned(16))) _Float16 At[2][2 * PLANE];
   __shared__ __attribute__((aligned(16))) float XS[TILE_ROWS * 128];      // H2 of the NEXT tile
   __shared__ __attribute__((aligned(16))) float GT[TILE_ROWS * 128];      // gates of the current layer (H1, then H0)
@@ -1138,31 +1223,26 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
   SplitW w2, w1, w0;
   int phase = 0;                        // call counter of block_max
   float l1_2, l1_1;
-  const int ew2 = load_w_cols_split(w2, l1_2, params + RGF_W2, col, lh, red4, tid, phase);
-  const int ew1 = load_w_cols_split(w1, l1_1, params + RGF_W1, col, lh, red4, tid, phase);
   // last product: feat_grad[64 rows][64] = Ybar0 . W0, wavefront = (row half wid >> 1, feature block wid & 1); A operand =
   // transposed W0 (k = hidden feature, value W0[k][f]) of input feature f = 32 (wid & 1) + l31
   const int rb = wid >> 1, fcol = (wid & 1) * 32 + l31;
-  int ew0;
-  {
-    float4 v[16];
-    float mx = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      const float* p = params + RGF_W0 + (size_t)(16 * ks + 8 * lh) * 64 + fcol;
-      v[2 * ks] = make_float4(p[0], p[64], p[128], p[192]);
-      v[2 * ks + 1] = make_float4(p[256], p[320], p[384], p[448]);
-      mx = fmaxf(mx, fmaxf(amax4(v[2 * ks]), amax4(v[2 * ks + 1])));
-    }
-    ew0 = scale_exp(block_max(mx, red4, tid, phase));
-    const float s = pow2(ew0);
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) split8(v[2 * ks], v[2 * ks + 1], s, w0.h[ks], w0.l[ks]);
-  }
   // output layer backward as a K = 16 product: A = [w3_0 w3_1 w3_2 0 ...] of feature `col` (lanes lh = 0), B = d loss / d logits
   const float w3a = params[RGF_W3 + col], w3b = params[RGF_W3 + 128 + col], w3c = params[RGF_W3 + 256 + col];
-  const float w3l1 = block_max((fabsf(w3a) + fabsf(w3b)) + fabsf(w3c), red4, tid, phase) * 1.0001f;
-  const int ew3 = scale_exp(block_max(fmaxf(fmaxf(fabsf(w3a), fabsf(w3b)), fabsf(w3c)), red4, tid, phase));
+  int ew2, ew1, ew0, ew3;
+  float w3l1;
+  if (PACK) {
+    load_w_packed<8>(w2, pack + PK_RGB_W1 + 2 * PK_IMG, tid);
+    load_w_packed<8>(w1, pack + PK_RGB_W1 + 3 * PK_IMG, tid);
+    load_w_packed<8>(w0, pack + PK_RGB_W1 + 4 * PK_IMG, tid);
+    ew2 = pk_int(pack, PKR_EW2C); ew1 = pk_int(pack, PKR_EW1C); ew0 = pk_int(pack, PKR_EW0T); ew3 = pk_int(pack, PKR_EW3);
+    l1_2 = pack[PKR_L1_2C]; l1_1 = pack[PKR_L1_1C]; w3l1 = pack[PKR_W3L1];
+  } else {
+    ew2 = load_w_cols_split(w2, l1_2, params + RGF_W2, col, lh, red4, tid, phase);
+    ew1 = load_w_cols_split(w1, l1_1, params + RGF_W1, col, lh, red4, tid, phase);
+    ew0 = load_w0_cols_split(w0, params + RGF_W0, fcol, lh, red4, tid, phase);
+    w3l1 = block_max((fabsf(w3a) + fabsf(w3b)) + fabsf(w3c), red4, tid, phase) * 1.0001f;
+    ew3 = scale_exp(block_max(fmaxf(fmaxf(fabsf(w3a), fabsf(w3b)), fabsf(w3c)), red4, tid, phase));
+  }
   pp_half8 a3h, a3l;
   {
     const float z = 0.f;
@@ -1344,11 +1424,85 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
 
 int pp_launch_rgb_fused_bwd_s(const float* params, const float* acts, const float* rgb, const float* rgb_grad,
                               const int32_t* count, int capacity, float* ybar, float* params_grad, float* feat_grad,
-                              float* logit_grad, int lg_ld, hipStream_t st) {
+                              float* logit_grad, int lg_ld, hipStream_t st, const float* pack) {
   const int ntiles = pp_div_up(capacity, TILE_ROWS);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
-  hipLaunchKernelGGL(k_rgb_fused_bwd_s, dim3(grid), dim3(256), 0, st, params, acts, rgb, rgb_grad, count, capacity, ybar,
-                     params_grad, feat_grad, logit_grad, lg_ld);
+  if (pack) hipLaunchKernelGGL(k_rgb_fused_bwd_s<true>, dim3(grid), dim3(256), 0, st, params, acts, rgb, rgb_grad, count, capacity, ybar,
+                               params_grad, feat_grad, logit_grad, lg_ld, pack);
+  else hipLaunchKernelGGL(k_rgb_fused_bwd_s<false>, dim3(grid), dim3(256), 0, st, params, acts, rgb, rgb_grad, count, capacity, ybar,
+                          params_grad, feat_grad, logit_grad, lg_ld, pack);
+  return 0;
+}
+
+// ================================================================================================ weight pack
+// One work-group per image (PK_TASKS, pp_mlp_pack.h): it runs the SAME prologue code as the kernels above - same loads, same
+// summation order, same reductions - and stores what that code leaves in registers, so a kernel that reads the pack starts from
+// bit-identical weights, exponents and norms.  `warp` / `rgb` == nullptr: that net's part of the pack is left alone.
+__global__ __launch_bounds__(256) void k_mlp_pack(const float* __restrict__ warp, const float* __restrict__ rgb, float* __restrict__ pack) {
+  __shared__ __attribute__((aligned(16))) float red4[32];
+  const int task = blockIdx.x;
+  const float* __restrict__ params = task < PK_TASKS_WARP ? warp : rgb;
+  if (params == nullptr) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int col = wid * 32 + l31;
+  int phase = 0;
+  SplitW w;
+  float l1 = 0.f;
+  float* __restrict__ S = pack + PK_SCAL;
+  auto put = [&](int se, int e, int sl, float v) {
+    if (tid == 0) { S[se] = __int_as_float(e); if (sl >= 0) S[sl] = v; }
+  };
+  if (task < 3) {                                           // warp net, forward: W1 W2 W3 by rows
+    const int off = task == 0 ? WPF_W1 : (task == 1 ? WPF_W2 : WPF_W3);
+    const int e = load_w_rows_split(w, l1, params + off, col, lh, red4, tid, phase);
+    store_w_packed<8>(pack + PK_WARP + task * PK_IMG, w, tid);
+    put(PKW_EW1 + 2 * task, e, PKW_L1_1 + 2 * task, l1);
+  } else if (task < 6) {                                    // warp net, data gradient: W3 W2 W1 by columns
+    const int t = task - 3;
+    const int off = t == 0 ? WPF_W3 : (t == 1 ? WPF_W2 : WPF_W1);
+    const int e = load_w_cols_split(w, l1, params + off, col, lh, red4, tid, phase);
+    store_w_packed<8>(pack + PK_WARP + task * PK_IMG, w, tid);
+    put(PKW_EW3C + 2 * t, e, PKW_L1_3C + 2 * t, l1);
+  } else if (task == 6) {                                   // warp net: bias maxima, input layer
+    const float b1mx = block_max(fabsf(params[WPF_B1 + col]), red4, tid, phase), b2mx = block_max(fabsf(params[WPF_B2 + col]), red4, tid, phase);
+    const float w0x = params[WPF_W0 + col * 3], w0y = params[WPF_W0 + col * 3 + 1], w0z = params[WPF_W0 + col * 3 + 2];
+    const float b0 = params[WPF_B0 + col];
+    const float w0l1 = block_max((fabsf(w0x) + fabsf(w0y)) + fabsf(w0z), red4, tid, phase) * 1.0001f;
+    const float w0mx = block_max(fmaxf(fmaxf(fabsf(w0x), fabsf(w0y)), fabsf(w0z)), red4, tid, phase);
+    const float b0mx = block_max(fabsf(b0), red4, tid, phase);
+    if (tid == 0) { S[PKW_B1MX] = b1mx; S[PKW_B2MX] = b2mx; S[PKW_W0L1] = w0l1; S[PKW_W0MX] = w0mx; S[PKW_B0MX] = b0mx; }
+    put(PKW_EW0, scale_exp(fmaxf(w0mx, b0mx)), -1, 0.f);
+  } else if (task == 7) {                                   // rgbnet, forward: W0 (64 wide), W1, W2 by rows
+    const int e = load_w0_rows_split(w, l1, params + RGF_W0, col, lh, red4, tid, phase);
+    store_w_packed<4>(pack + PK_RGB, w, tid);
+    put(PKR_EW0, e, PKR_L1_0, l1);
+  } else if (task < 10) {
+    const int t = task - 8;
+    const int e = load_w_rows_split(w, l1, params + (t == 0 ? RGF_W1 : RGF_W2), col, lh, red4, tid, phase);
+    store_w_packed<8>(pack + PK_RGB_W1 + t * PK_IMG, w, tid);
+    put(PKR_EW1 + 2 * t, e, PKR_L1_1 + 2 * t, l1);
+  } else if (task < 12) {                                   // rgbnet, data gradient: W2 W1 by columns
+    const int t = task - 10;
+    const int e = load_w_cols_split(w, l1, params + (t == 0 ? RGF_W2 : RGF_W1), col, lh, red4, tid, phase);
+    store_w_packed<8>(pack + PK_RGB_W1 + (2 + t) * PK_IMG, w, tid);
+    put(PKR_EW2C + 2 * t, e, PKR_L1_2C + 2 * t, l1);
+  } else if (task == 12) {                                  // rgbnet: W0^T of the feature-gradient product
+    const int e = load_w0_cols_split(w, params + RGF_W0, (wid & 1) * 32 + l31, lh, red4, tid, phase);
+    store_w_packed<8>(pack + PK_RGB_W1 + 4 * PK_IMG, w, tid);
+    put(PKR_EW0T, e, -1, 0.f);
+  } else {                                                  // rgbnet: bias maxima, output layer
+    const float b0mx = block_max(fabsf(params[RGF_B0 + col]), red4, tid, phase), b1mx = block_max(fabsf(params[RGF_B1 + col]), red4, tid, phase);
+    const float w3a = params[RGF_W3 + col], w3b = params[RGF_W3 + 128 + col], w3c = params[RGF_W3 + 256 + col];
+    const float w3l1 = block_max((fabsf(w3a) + fabsf(w3b)) + fabsf(w3c), red4, tid, phase) * 1.0001f;
+    const int ew3 = scale_exp(block_max(fmaxf(fmaxf(fabsf(w3a), fabsf(w3b)), fabsf(w3c)), red4, tid, phase));
+    if (tid == 0) { S[PKR_B0MX] = b0mx; S[PKR_B1MX] = b1mx; }
+    put(PKR_EW3, ew3, PKR_W3L1, w3l1);
+  }
+}
+
+int pp_launch_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, hipStream_t st) {
+  hipLaunchKernelGGL(k_mlp_pack, dim3(PK_TASKS), dim3(256), 0, st, warp_params, rgbnet_params, pack);
   return 0;
 }
 

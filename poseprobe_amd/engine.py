@@ -308,6 +308,8 @@ class TrainEngine:
         self.touch_par = 0
         self._k0_marked = False
         self.flat = FlatParams(self.dev)
+        # weight pack of the two MLPs (ops.mlp_pack): written at the start of every render_and_grads, valid until its end
+        self.mlp_pack = torch.empty(ops.mlp_pack_workspace(), **f)
         self.se3 = torch.zeros(n_views, 6, **f)
         self.se3_grad, self.se3_m, self.se3_v = (torch.zeros(n_views, 6, **f) for _ in range(3))
         self.w2c_init = torch.zeros(n_views, 3, 4, **f)
@@ -405,6 +407,10 @@ class TrainEngine:
         s_val = cfg.s_val(global_step)
         inv_s = float(np.float32(1.0) / np.float32(s_val))
         P = self.flat
+        # The MLP weights are packed HERE, on the step's stream, and the record is dropped when the step's kernels are enqueued:
+        # every writer of flat.data (the optimiser, load_reference_params, a checkpoint load, an in-place copy from outside)
+        # runs between two calls of this function, so no kernel can read a pack older than its parameters.
+        ops.mlp_pack(P.view('warp'), P.view('rgbnet'), self.mlp_pack, self.ctx)
         self.core.forward(ws, self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w,
                           before_k0_use=None if self.dist is None else (lambda: self.dist.wait_parameters(self)))
         ws.zero_block.zero_()
@@ -440,6 +446,7 @@ class TrainEngine:
                               None, self.c2w_grad)
         ops.pose_bwd(self.jac, self.c2w_grad, self.se3_grad)
         ops.context_join(ctx)           # the warp net's weight gradients (side stream) before anything reads flat.grad
+        ops.mlp_pack_invalidate(ctx)
         return s_val, w_dyn
 
     def _upload_step_scalars(self, progress):

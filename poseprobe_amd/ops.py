@@ -210,6 +210,23 @@ Context = _lib.Context
 _h = _lib.handle
 
 
+def mlp_pack_workspace():
+    """Floats of the weight-pack buffer of pp_mlp_pack."""
+    n = ctypes.c_int64()
+    _lib.call('pp_mlp_pack_workspace', ctypes.byref(n))
+    return n.value
+
+
+def mlp_pack(warp_params, rgbnet_params, pack, ctx=None):
+    """Pack both nets' weights for the split-precision MLP kernels and record the pack in `ctx` for exactly these two parameter
+    tensors; must be repeated (or mlp_pack_invalidate called) whenever their values change."""
+    _lib.call('pp_mlp_pack', _f(warp_params), _f(rgbnet_params), _f(pack), _h(ctx), _stream())
+
+
+def mlp_pack_invalidate(ctx=None):
+    _lib.call('pp_mlp_pack_invalidate', _h(ctx))
+
+
 def rgbnet_fwd(params, feat, count, capacity, acts, rgb, ctx=None):
     _lib.call('pp_rgbnet_fwd', _f(params), _f(feat), _i(count), capacity, _f(acts), _f(rgb), _h(ctx), _stream())
 

@@ -679,8 +679,14 @@ class Voxurf(torch.nn.Module):
         mlp = self._mlp_tensors()
         flat.load_reference(self.sdf_alpha, self.sdf_beta, [(mlp[2 * k], mlp[2 * k + 1]) for k in range(4)],
                             [(mlp[8 + 2 * k], mlp[8 + 2 * k + 1]) for k in range(5)])
-        core.forward(ws, channels_last_view(self.k0.grid), self.sdf.grid[0, 0].contiguous(), flat.view('sdf_ab'),
-                     flat.view('rgbnet'), flat.view('warp'), inv_s, pe_w)
+        # the weights are packed once per call (ops.mlp_pack) and the record is dropped before returning
+        pack = torch.empty(ops.mlp_pack_workspace(), **f)
+        ops.mlp_pack(flat.view('warp'), flat.view('rgbnet'), pack, core.ctx)
+        try:
+            core.forward(ws, channels_last_view(self.k0.grid), self.sdf.grid[0, 0].contiguous(), flat.view('sdf_ab'),
+                         flat.view('rgbnet'), flat.view('warp'), inv_s, pe_w)
+        finally:
+            ops.mlp_pack_invalidate(core.ctx)
         gradient = ws.gradient[:M]
         normal = gradient / (gradient.norm(2, -1, keepdim=True) + 1e-6)
         weights = ws.weights[:M]
@@ -720,7 +726,8 @@ class Voxurf(torch.nn.Module):
             ws.n_steps = torch.empty(N, **i)
             ws.nrm = torch.empty(cap, 3, **f)
             ws.normal_marched = torch.empty(N, 3, **f)
-            self._ray_cache = cache = dict(key=key, ws=ws, flat=FlatParams(dev, moments=False))
+            self._ray_cache = cache = dict(key=key, ws=ws, flat=FlatParams(dev, moments=False),
+                                           pack=torch.empty(ops.mlp_pack_workspace(), **f))
         ws, flat = cache['ws'], cache['flat']
         ws.rays_o, ws.rays_d, ws.viewdirs = ro, rd, vd
         ops.sample_var(cfg.pp, ro, rd, cap, ws.t_min, ws.t_max, ws.n_steps, ws.ray_start, ws.count, ws.pts, ws.ray_id, ws.step_k)
@@ -733,12 +740,14 @@ class Voxurf(torch.nn.Module):
         flat.load_reference(self.sdf_alpha, self.sdf_beta, [(mlp[2 * k], mlp[2 * k + 1]) for k in range(4)],
                             [(mlp[8 + 2 * k], mlp[8 + 2 * k + 1]) for k in range(5)])
         sdf_g = self.sdf.grid[0, 0].contiguous()
+        ops.mlp_pack(flat.view('warp'), flat.view('rgbnet'), cache['pack'], core.ctx)     # after load_reference: once per call
         ops.warp_fwd(flat.view('warp'), ws.pts, ws.count, ws.cap, cfg.out_range, ws.warp_acts, ws.warp_out, core.ctx)
         ops.geometry_fwd(cfg.pp, sdf_g, flat.view('sdf_ab'), ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
                          ws.alpha, ws.gradient, ws.sdf_final, ws.sdf_deform, ws.grad_deform)
         ops.color_feat_fwd(cfg.pp, channels_last_view(self.k0.grid), ws.pts, ws.viewdirs, ws.ray_id, ws.gradient, pe_w, ws.count,
                            ws.cap, ws.feat)
         ops.rgbnet_fwd(flat.view('rgbnet'), ws.feat, ws.count, ws.cap, ws.rgb_acts, ws.rgb, core.ctx)
+        ops.mlp_pack_invalidate(core.ctx)
         # rows past the count hold stale values: harmless, the marching kernel walks ray_start ranges only
         torch.div(ws.gradient, ws.gradient.norm(2, -1, keepdim=True) + 1e-6, out=ws.nrm)
         ops.march_fwd(ws.alpha, ws.rgb, ws.step, ws.nrm, ws.ray_start, N, cfg.bg, ws.weights, ws.T, ws.alphainv_last, ws.i_end,
