@@ -59,13 +59,12 @@ static __global__ __launch_bounds__(256) void k_pack_planes(PlanePackJobs J, con
 //     has) into the hi / lo image of the step;
 //   * weights (L2): each column half of the next step's image (16 KB) into that half's other buffer.
 //
-// PING-PONG.  Phase timers (s_memtime) on a single-phase version showed the matrix pipe busy for a third of a step: all eight
-// wavefronts sat behind the same barrier, so the two wavefronts of a SIMD converted, waited and issued loads together and then
-// competed for the pipe together.  Here the work-group is two halves of four wavefronts (one per SIMD each; half h owns the
-// output columns 128 h .. 128 h + 127 of the 128-row tile): in phase A of a step half 0 runs its 24 MFMAs per wavefront on
-// the images of step g while half 1 does the memory work for step g + 1 (waits for / converts its rows of the activation
-// chunk, issues the loads of its weight half and of the activations four steps on); phase B swaps the roles; one LDS-only
-// barrier per phase.  Every SIMD thus always has one wavefront on the matrix pipe and one doing vector / LDS / memory work.
+// SCHEDULE.  The work-group is two halves of four wavefronts (one per SIMD each; half h owns the output columns
+// 128 h .. 128 h + 127 of the 128-row tile and fetches its own weight half).  All eight wavefronts run in one phase: phase
+// timers (s_memtime) showed the matrix pipe busy for a third of a step, because the two wavefronts of a SIMD convert, wait
+// and issue loads together and then compete for the pipe together.  A two-phase ping-pong schedule (one half on the matrix
+// pipe while the other does the memory work of the next step, one barrier per phase) was tried against exactly that and
+// measured SLOWER: 113 vs 96 us at 131 k rows.
 //
 // vmcnt bookkeeping: a wavefront's memory operations complete in order (loads, stores, LDS-direct loads alike), so "these
 // loads have landed" is "at most n operations are outstanding", n = operations this wavefront issued after them.  The
@@ -73,12 +72,6 @@ static __global__ __launch_bounds__(256) void k_pack_planes(PlanePackJobs J, con
 #define PL_S_BYTES (128 * 128)      // one staging slot: 128 rows x 32 fp32
 #define PL_DEPTH 3
 #define PL_BH_BYTES (128 * 128)     // one column half of a weight chunk image
-#ifndef PL_PINGPONG
-#define PL_PINGPONG 0  // 1: two-phase ping-pong schedule (measured SLOWER: 113 vs 96 us at 131 k rows, kept for experiments)
-#endif
-#ifndef PL_DBG
-#define PL_DBG 0      // experiments only: 1 = no MFMAs, 2 = activations always from the work-group's first tile, 3 = no C stores
-#endif
 
 #define PL_VM(n) (0x0F70 | ((n) & 15) | (((n) >> 4) << 14))     // s_waitcnt immediate: vmcnt(n) only (gfx9 encoding)
 __device__ __forceinline__ void pl_wait_vm(int n) {     // waits until at most n' <= n operations are outstanding
@@ -114,19 +107,18 @@ __global__ __launch_bounds__(512, 1) void k_gemm256p(const float* __restrict__ A
   const int ntiles = (R + BM - 1) / BM;
   if ((int)blockIdx.x >= ntiles) return;
   const int tid = threadIdx.x, lane = tid & 63;
-  // the wavefront index in a SCALAR register: everything that depends on it (the role of the wavefront in a phase, the
-  // operation counters, the wait immediates) is then uniform control flow instead of exec-masked vector code
+  // the wavefront index in a SCALAR register: everything that depends on it (the operation counters, the wait immediates)
+  // is then uniform control flow instead of exec-masked vector code
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = wid >> 2, w4 = wid & 3;              // half: column half and phase of the matrix work
+  const int half = wid >> 2, w4 = wid & 3;              // half: column half of the matrix work
   const int wr = w4 >> 1, wq = w4 & 1;                  // 64 x 64 outputs per wavefront: rows 64 wr, columns 128 half + 64 wq
   const int l31 = lane & 31, lh = lane >> 5;
   const float sA = pp_split_scale(a_max[0]), sW = pp_split_scale(w_max[0]);
   const float inv = 1.0f / (sA * sW);
   const int nk = K >> 5;
-  // a half FETCHES the other half's weights (see the pipeline note at dma_b) and COMPUTES on its own
-  const unsigned char* __restrict__ Wb = reinterpret_cast<const unsigned char*>(Wimg) + (PL_PINGPONG ? half ^ 1 : half) * PL_BH_BYTES;
+  // a half fetches its own weights and computes on them
+  const unsigned char* __restrict__ Wb = reinterpret_cast<const unsigned char*>(Wimg) + half * PL_BH_BYTES;
   unsigned char* const Bmine = Bs + half * 2 * PL_BH_BYTES;
-  unsigned char* const Bother = Bs + (PL_PINGPONG ? half ^ 1 : half) * 2 * PL_BH_BYTES;   // where this wavefront's weight loads go
   const int my_tiles = (ntiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1;
   const int nsteps = my_tiles * nk;
   // loop-invariant epilogue operands are fetched before the pipeline starts
@@ -152,7 +144,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256p(const float* __restrict__ A
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int blk = wid * 2 + i;
-      const int row = min((PL_DBG == 2 ? (int)blockIdx.x : ptile) * BM + blk * 8 + (lane >> 3), R - 1);
+      const int row = min(ptile * BM + blk * 8 + (lane >> 3), R - 1);
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(A + (size_t)row * lda + pk * 32 + (lane & 7) * 4),
                                        (__attribute__((address_space(3))) void*)(St + pslot * PL_S_BYTES + blk * 1024), 16, 0, 0);
     }
@@ -183,10 +175,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm256p(const float* __restrict__ A
       *reinterpret_cast<pp_half4*>(img + pl_slot_off(row, 4 + (c4 >> 1)) + (c4 & 1) * 8) = l;
     }
   };
-  // 16 KB of a weight chunk image - the OTHER half's columns: linear copy, 4 x 1 KB per wavefront.  A half's memory phase
-  // directly precedes its own matrix phase of the next step but lies a full phase before the other half's, so the loads a
-  // half issues feed the other half: they have one and a half phases to land (L2 latency ~1000 cycles) and are waited for
-  // by their issuer at the end of its next matrix phase, in front of the barrier that opens the consumer's matrix phase.
+  // 16 KB of a weight chunk image - this half's columns: linear copy, 4 x 1 KB per wavefront, issued a step ahead of their
+  // use and waited for by their issuer in front of the barrier that opens that step (L2 latency ~1000 cycles)
   auto dma_b = [&](int kc, unsigned char* img) {
     const unsigned char* src = Wb + (size_t)kc * PL_B_BYTES;
 #pragma unroll
@@ -224,7 +214,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256p(const float* __restrict__ A
   };
 
   // ---- prologue: weights of step 0, slots of steps 0 .. 2, image of step 0, then the slot of step 3
-  dma_b(0, Bother);
+  dma_b(0, Bmine);
   prefetch_a(); f0 = f2;                                // FIFO filling: the first fetch becomes the oldest position,
   prefetch_a(); f1 = f2;                                // the second the middle one, the third stays the newest
   prefetch_a();
@@ -233,102 +223,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm256p(const float* __restrict__ A
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
   float vmax = 0.f;
-#if PL_PINGPONG
+  // ---- all eight wavefronts convert, meet at ONE barrier per step, issue the next loads and run their MFMAs together.
+  // (The prologue above has already converted step 0 and fetched slot 3.)
   int g = 0, cslot = 1;                                 // cslot: staging slot of step g + 1
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int r0 = tile * BM;
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][u][i] = 0.f;
-    for (int kc = 0; kc < nk; ++kc, ++g) {
-      const int par = g & 1;
-      unsigned char* const Acur = As + par * PL_A_BYTES;
-      unsigned char* const Bcur = Bmine + par * PL_BH_BYTES;
-#pragma unroll
-      for (int phase = 0; phase < 2; ++phase) {
-        if (phase == half) {
-          // ---- matrix phase: 24 MFMAs on the images of step g
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) {
-            pp_half8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-              const int row = wr * 64 + t * 32 + l31;
-              ah[t] = *reinterpret_cast<const pp_half8*>(Acur + pl_slot_off(row, ks * 2 + lh));
-              al[t] = *reinterpret_cast<const pp_half8*>(Acur + pl_slot_off(row, 4 + ks * 2 + lh));
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-              const int colh = wq * 64 + u * 32 + l31;  // column within the half (the swizzle only looks at its low bits)
-              bh[u] = *reinterpret_cast<const pp_half8*>(Bcur + pl_slot_off(colh, ks * 2 + lh));
-              bl[u] = *reinterpret_cast<const pp_half8*>(Bcur + pl_slot_off(colh, 4 + ks * 2 + lh));
-            }
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-              for (int u = 0; u < 2; ++u) {             // small terms first
-                if (PL_DBG == 1) { acc[t][u][0] += (float)ah[t][0] + (float)bl[u][0] + (float)al[t][1] + (float)bh[u][1]; continue; }
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[t], bh[u], acc[t][u], 0, 0, 0);
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[t], bl[u], acc[t][u], 0, 0, 0);
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[t], bh[u], acc[t][u], 0, 0, 0);
-              }
-          }
-          if (kc == nk - 1) {
-            // ---- end of a tile: outputs straight from the accumulators (same arithmetic and bit layout as k_gemm128s)
-            unsigned mw[2][2] = {{0u, 0u}, {0u, 0u}};
-            if (EPI == EPI_MASK) read_masks(mw);
-            const bool full = r0 + BM <= R;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-              for (int u = 0; u < 2; ++u) {
-                const int col = half * 128 + wq * 64 + u * 32 + l31;
-                const int rbase = r0 + wr * 64 + t * 32 + 4 * lh;
-                unsigned mbits = mw[t][u];
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                  const int row = rbase + (reg & 3) + 8 * (reg >> 2);
-                  float val = acc[t][u][reg] * inv;
-                  if (EPI == EPI_RELU) {
-                    val = fmaxf(val + bcols[u], 0.f);
-                    mbits |= (val > 0.f ? 1u : 0u) << reg;
-                  } else if (EPI == EPI_MASK) {
-                    val = ((mbits >> reg) & 1u) ? val : 0.f;
-                  }
-                  if (full || row < R) {
-                    if (PL_DBG != 3 || val == 123.456f) C[(size_t)row * ldc + col] = val;
-                    vmax = fmaxf(vmax, fabsf(val));
-                  }
-                }
-                if (EPI == EPI_RELU) bits16[(((size_t)(rbase - 4 * lh) >> 5) * 256 + col) * 2 + lh] = (uint16_t)mbits;
-              }
-            if (full) PL_ISSUED(EPI == EPI_RELU ? 68 : 64);    // a partial tile may skip stores: count none (stricter waits only)
-          }
-          pl_wait_vm(after_b);                          // the weight loads of this wavefront's last memory phase have landed
-        } else {
-          // ---- memory phase, for step g + 1: the other half's weight image, this wavefront's rows of the activation chunk,
-          // the fetch four steps on, the tile's mask words
-          if (g + 1 < nsteps) {
-            dma_b(kc + 1 < nk ? kc + 1 : 0, Bother + (par ^ 1) * PL_BH_BYTES);
-            convert_a(cslot, As + (par ^ 1) * PL_A_BYTES);
-          }
-          prefetch_a();
-          if (EPI == EPI_MASK && kc == 0) fetch_masks(tile);
-        }
-        // LDS-only barrier: __syncthreads() would add a vmcnt(0) (its memory fence) and drain the prefetch ring
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      }
-      if (++cslot == PL_DEPTH) cslot = 0;
-    }
-  }
-#else
-  // ---- single-phase schedule: all eight wavefronts convert, meet at ONE barrier per step, issue the next loads and run
-  // their MFMAs together.  (The prologue above has already converted step 0 and fetched slot 3.)
-  int g = 0, cslot = 1;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int r0 = tile * BM;
     f32x16 acc[2][2];
@@ -369,7 +266,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm256p(const float* __restrict__ A
         for (int t = 0; t < 2; ++t)
 #pragma unroll
           for (int u = 0; u < 2; ++u) {                 // small terms first
-            if (PL_DBG == 1) { acc[t][u][0] += (float)ah[t][0] + (float)bl[u][0] + (float)al[t][1] + (float)bh[u][1]; continue; }
             acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[t], bh[u], acc[t][u], 0, 0, 0);
             acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[t], bl[u], acc[t][u], 0, 0, 0);
             acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[t], bh[u], acc[t][u], 0, 0, 0);
@@ -399,7 +295,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256p(const float* __restrict__ A
                 val = ((mbits >> reg) & 1u) ? val : 0.f;
               }
               if (full || row < R) {
-                if (PL_DBG != 3 || val == 123.456f) C[(size_t)row * ldc + col] = val;
+                C[(size_t)row * ldc + col] = val;
                 vmax = fmaxf(vmax, fabsf(val));
               }
             }
@@ -409,6 +305,5 @@ __global__ __launch_bounds__(512, 1) void k_gemm256p(const float* __restrict__ A
       }
     }
   }
-#endif
   pp_record_max(c_max, vmax);
 }

@@ -15,9 +15,7 @@
 typedef _Float16 pp_half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 pp_half4 __attribute__((ext_vector_type(4)));
 
-#ifndef PP_SPLIT_WAVES
 #define PP_SPLIT_WAVES 2
-#endif
 #define LDH 40        // halfs per LDS row: 80 B (16-byte aligned fragments, rows skewed by 20 banks)
 
 __device__ __forceinline__ float pp_split_scale(float mx) {

@@ -10,19 +10,6 @@
 #pragma once
 #include "pp_split_image.h"
 
-#ifndef TN_DBG
-#define TN_DBG 0      // experiments only (k_gemm_tn_tr), bit mask: 1 no row fetches in the loop, 2 fragments read once per chunk
-#endif
-
-#ifdef TN_TIMERS      // phase timers (experiments): wave 0 of every work-group sums s_memtime deltas per phase
-#define TN_TIMERS_ON 1
-__device__ unsigned long long g_tn_t[8];
-extern "C" int pp_debug_read_tn_timers(unsigned long long* out8, int reset) {
-  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_tn_t), sizeof(g_tn_t)) != hipSuccess) return 1;
-  if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_tn_t), z, sizeof(z)) != hipSuccess) return 1; }
-  return 0;
-}
-#endif
 static __global__ __launch_bounds__(256, 2) void k_gemm_tn_tr(const float* __restrict__ Y_, int ldy, const float* __restrict__ X_, int ldx,
                                                           int Kx_, float* __restrict__ Wbar_, int ldwb, float* __restrict__ bbar_,
                                                           const int32_t* __restrict__ count, int rcap,
@@ -71,21 +58,13 @@ static __global__ __launch_bounds__(256, 2) void k_gemm_tn_tr(const float* __res
       if (i < i0 || i >= i1) continue;
       const int gr = min(r0 + rblk * 8 + i, R - 1);
       ry[i] = *reinterpret_cast<const float4*>(Y + (size_t)gr * ldy + c4 * 4);
-      if (TN_DBG & 4) rx[i] = ry[i];                        // experiment: half the bytes
-      else rx[i] = *reinterpret_cast<const float4*>(X + (size_t)gr * ldx + (c4 < kx4 ? c4 : 0) * 4);
+      rx[i] = *reinterpret_cast<const float4*>(X + (size_t)gr * ldx + (c4 < kx4 ? c4 : 0) * 4);
     }
   };
   auto frag = [&](const unsigned char* plane, int cb, int ks) { return tn_frag(plane, cb, ks, lane); };
-#ifdef TN_TIMERS_ON
-  unsigned long long tsum[8] = {0}, tprev = __builtin_readcyclecounter();
-#define TN_TICK(i) do { const unsigned long long t__ = __builtin_readcyclecounter(); tsum[i] += t__ - tprev; tprev = t__; } while (0)
-#else
-#define TN_TICK(i) do {} while (0)
-#endif
   load_rows(rb, 0, 8);
   for (int r0 = rb; r0 < re; r0 += CH) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    TN_TICK(0);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float ky = (r0 + rblk * 8 + i < re) ? 1.f : 0.f, kx = (c4 < kx4) ? ky : 0.f;
@@ -98,9 +77,7 @@ static __global__ __launch_bounds__(256, 2) void k_gemm_tn_tr(const float* __res
 #pragma unroll
       for (int i = 0; i < 8; ++i) { bsum[0] += ry[i].x; bsum[1] += ry[i].y; bsum[2] += ry[i].z; bsum[3] += ry[i].w; }
     }
-    TN_TICK(1);
     __syncthreads();
-    TN_TICK(2);
     if (wc * 64 < Kx) {                                       // (uniform per wavefront: the transposed reads need all 64 lanes)
       // fragments of the next 16 rows are on their way while the matrix instructions of these 16 issue (left in one loop
       // body, the compiler reads a step's ten fragments only after the previous step's last matrix instruction: four exposed
@@ -116,8 +93,7 @@ static __global__ __launch_bounds__(256, 2) void k_gemm_tn_tr(const float* __res
 #pragma unroll
       for (int s4 = 0; s4 < CH / 16; ++s4) {
         const int par = s4 & 1;
-        if (s4 + 1 < CH / 16 && !(TN_DBG & 2)) fetch(par ^ 1, (s4 + 1) * 16);
-        if (TN_DBG & 2) { for (int i = 0; i < 4; ++i) { fa[par ^ 1][i] = fa[par][i]; fb[par ^ 1][i] = fb[par][i]; } }
+        if (s4 + 1 < CH / 16) fetch(par ^ 1, (s4 + 1) * 16);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
@@ -126,19 +102,17 @@ static __global__ __launch_bounds__(256, 2) void k_gemm_tn_tr(const float* __res
             acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[par][2 * t], fb[par][2 * u + 1], acc[t][u], 0, 0, 0);
             acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[par][2 * t], fb[par][2 * u], acc[t][u], 0, 0, 0);
           }
-          if (t == 0 && !(TN_DBG & 1)) {                    // a quarter of the next chunk's rows behind the first six matrix instructions
+          if (t == 0) {                    // a quarter of the next chunk's rows behind the first six matrix instructions
             __builtin_amdgcn_sched_barrier(0);
             load_rows(r0 + CH, 2 * s4, 2 * s4 + 2);
             __builtin_amdgcn_sched_barrier(0);
           }
         }
       }
-    } else if (!(TN_DBG & 1)) {
+    } else {
       load_rows(r0 + CH, 0, 8);                               // a wavefront without columns in this block still stages its rows
     }
-    TN_TICK(3);
     __syncthreads();
-    TN_TICK(4);
   }
   const float inv = 1.0f / (sY * sX);
   if (wc * 64 < Kx) {
@@ -167,10 +141,4 @@ static __global__ __launch_bounds__(256, 2) void k_gemm_tn_tr(const float* __res
       atomicAdd(&bbar[tid], sum);
     }
   }
-#ifdef TN_TIMERS_ON
-  TN_TICK(5);
-  if (tid == 0)
-    for (int i = 0; i < 8; ++i) atomicAdd(&g_tn_t[i], tsum[i]);
-#endif
-#undef TN_TICK
 }

@@ -169,9 +169,7 @@ __global__ __launch_bounds__(256) void k_geometry_fwd(SceneDev sc, const float* 
 // |correction|, |sdf_deform|) are differentiated right here from the recomputed forward instead of by a separate kernel
 // that writes g_grad_deform / g_correction / g_sdf_deform to HBM first (pp_loss_samples); same expressions, same
 // order of additions, so the two routes are bit-identical.
-#ifndef GEO_BWD_THREADS
 #define GEO_BWD_THREADS 512
-#endif
 template <bool PRIORS>
 __global__ __launch_bounds__(GEO_BWD_THREADS) void k_geometry_bwd(
     SceneDev sc, const float* __restrict__ grid, const float* __restrict__ sdf_ab, const float* __restrict__ pts,

@@ -227,26 +227,7 @@ __global__ __launch_bounds__(256) void k_rgb_out_bwd(const float* __restrict__ W
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-#define RG_W0 0
-#define RG_B0 (128 * 64)
-#define RG_W1 (RG_B0 + 128)
-#define RG_B1 (RG_W1 + 128 * 128)
-#define RG_W2 (RG_B1 + 128)
-#define RG_B2 (RG_W2 + 128 * 128)
-#define RG_W3 (RG_B2 + 128)
-#define RG_B3 (RG_W3 + 3 * 128)
-
-#define WP_W0 0
-#define WP_B0 (128 * 3)
-#define WP_W1 (WP_B0 + 128)
-#define WP_B1 (WP_W1 + 128 * 128)
-#define WP_W2 (WP_B1 + 128)
-#define WP_B2 (WP_W2 + 128 * 128)
-#define WP_W3 (WP_B2 + 128)
-#define WP_B3 (WP_W3 + 128 * 128)
-#define WP_W4 (WP_B3 + 128)
-#define WP_B4 (WP_W4 + 4 * 128)
-
+// (parameter-block offsets of the two nets: WPF_* / RGF_* of pp_mlp_fused.h)
 // weight-gradient GEMM: a FIXED number of work-groups splits the (device-side) row count evenly; measured optimum on
 // MI355X ~ 450 work-groups (more: the 64 KB of contended atomics per work-group dominates; fewer: idle CUs).
 static const int TN_WGS = 448;
@@ -355,9 +336,7 @@ static inline int gemm_grid(int rows, int bm, bool shared = false) {
   int t = pp_div_up(rows, bm), cap = shared ? GEMM_MAX_WG_SHARED : GEMM_MAX_WG;
   return t < cap ? t : cap;
 }
-#ifndef PP_GEMM_BM
 #define PP_GEMM_BM 64
-#endif
 
 // Generic ReLU MLP  in_ld -> 128 -> ... -> 128 -> 3 (+ optional sigmoid), n_gemm = number of 128-wide hidden layers.
 // Parameter block: W0[128*in_ld] b0[128] | (W[128*128] b[128]) x (n_gemm-1) | Wout[3*128] bout[3].
@@ -396,6 +375,47 @@ extern "C" int pp_mlp_fwd(const float* params, const float* feat, int32_t in_ld,
   return PP_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ fused backward, two stages
+// Stage 1 of a layer-fused backward chain: the data-gradient kernel (split-precision or fp32 instructions), which also produces
+// the thin layers' gradients and leaves Ybar of the hidden layers in `scratch`.  Returns whether the hidden layers' bias
+// gradients are stage 2's to produce (the split-precision kernel leaves them to the weight-gradient kernel).
+// Stage 2: the three weight-gradient GEMMs on that Ybar, on stream `ws` with `side_wgs` work-groups (0: one per CU).
+static bool warp_bwd_stage1(const float* params, const float* pts, const float* acts, const float* out_grad, const int32_t* count,
+                            int capacity, float out_range, float* scratch, float* params_grad, float* pts_grad, void* ctx,
+                            hipStream_t st) {
+  const bool sb = (pp_opt(PP_OPT_MLP_SPLIT) & 2) != 0;
+  if (sb) pp_launch_warp_fused_bwd_s(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st,
+                                     mlp_pack_for(ctx, params, 0));
+  else pp_launch_warp_fused_bwd(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st);
+  return sb;
+}
+static void warp_bwd_stage2(const float* acts, const float* scratch, const int32_t* count, int capacity, float* params_grad, bool sb,
+                            hipStream_t ws, int side_wgs) {
+  const int rcap = capacity * 4;
+  const size_t LS = (size_t)rcap * 128;
+  pp_launch_wgrad_chain(scratch, acts + 2 * LS, params_grad + WPF_W3, scratch + LS, acts + LS, params_grad + WPF_W2,
+                        scratch + 2 * LS, acts, params_grad + WPF_W1, 128, count, 4, rcap, ws,
+                        sb ? params_grad + WPF_B3 : nullptr, sb ? params_grad + WPF_B2 : nullptr, sb ? params_grad + WPF_B1 : nullptr,
+                        side_wgs);
+}
+static bool rgb_bwd_stage1(const float* params, const float* acts, const float* rgb, const float* rgb_grad, const int32_t* count,
+                           int capacity, float* scratch, float* params_grad, float* feat_grad, float* logit_grad, int lg_ld,
+                           void* ctx, hipStream_t st) {
+  const bool sb = (pp_opt(PP_OPT_MLP_SPLIT) & 8) != 0;
+  if (sb) pp_launch_rgb_fused_bwd_s(params, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, logit_grad, lg_ld,
+                                    st, mlp_pack_for(ctx, params, 1));
+  else pp_launch_rgb_fused_bwd(params, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, logit_grad, lg_ld, st);
+  return sb;
+}
+static void rgb_bwd_stage2(const float* feat, const float* acts, const float* scratch, const int32_t* count, int capacity,
+                           float* params_grad, bool sb, hipStream_t ws, int side_wgs) {
+  const size_t FLS = (size_t)capacity * 128;
+  pp_launch_wgrad_chain(scratch, acts + FLS, params_grad + RGF_W2, scratch + FLS, acts, params_grad + RGF_W1,
+                        scratch + 2 * FLS, feat, params_grad + RGF_W0, 64, count, 1, capacity, ws,
+                        sb ? params_grad + RGF_B2 : nullptr, sb ? params_grad + RGF_B1 : nullptr, sb ? params_grad + RGF_B0 : nullptr,
+                        side_wgs);
+}
+
 extern "C" int pp_mlp_bwd(const float* params, const float* feat, int32_t in_ld, int32_t n_gemm, const float* acts,
                           const float* out, const float* out_grad, const int32_t* count, int32_t capacity,
                           float* scratch, float* params_grad, float* feat_grad, float* logit_add_grad,
@@ -405,17 +425,10 @@ extern "C" int pp_mlp_bwd(const float* params, const float* feat, int32_t in_ld,
   PP_REQUIRE(capacity > 0 && in_ld % 32 == 0 && in_ld <= 128 && n_gemm >= 1 && n_gemm <= 8, "bad sizes");
   hipStream_t st = pp_stream(stream);
   if (in_ld == 64 && n_gemm == 3 && feat_grad && mlp_fused_enabled()) {
-    const bool sb = (pp_opt(PP_OPT_MLP_SPLIT) & 8) != 0;   // split-precision data-gradient kernel: b0..b2 come from the weight-gradient kernel
-    if (sb) pp_launch_rgb_fused_bwd_s(params, acts, out, out_grad, count, capacity, scratch, params_grad, feat_grad, logit_add_grad,
-                                      logit_add_ld, st, mlp_pack_for(ctx, params, 1));
-    else pp_launch_rgb_fused_bwd(params, acts, out, out_grad, count, capacity, scratch, params_grad, feat_grad, logit_add_grad,
-                                 logit_add_ld, st);
-    const size_t FLS = (size_t)capacity * 128;
+    const bool sb = rgb_bwd_stage1(params, acts, out, out_grad, count, capacity, scratch, params_grad, feat_grad, logit_add_grad,
+                                   logit_add_ld, ctx, st);
     hipStream_t ws = deferred_fork(ctx, st);
-    pp_launch_wgrad_chain(scratch, acts + FLS, params_grad + RGF_W2, scratch + FLS, acts, params_grad + RGF_W1,
-                          scratch + 2 * FLS, feat, params_grad + RGF_W0, 64, count, 1, capacity, ws,
-                          sb ? params_grad + RGF_B2 : nullptr, sb ? params_grad + RGF_B1 : nullptr, sb ? params_grad + RGF_B0 : nullptr,
-                          ws != st ? pp_opt(PP_OPT_WGRAD_SIDE_WGS) : 0);
+    rgb_bwd_stage2(feat, acts, scratch, count, capacity, params_grad, sb, ws, ws != st ? pp_opt(PP_OPT_WGRAD_SIDE_WGS) : 0);
     deferred_forked(ctx, ws, st);
     PP_CHECK_LAUNCH();
     return PP_OK;
@@ -487,15 +500,15 @@ extern "C" int pp_warp_fwd(const float* params, const float* pts, const int32_t*
   const int rcap = capacity * 4;
   const size_t LS = (size_t)rcap * 128;
   dim3 g(gemm_grid(rcap, PP_GEMM_BM)), b(256);
-  hipLaunchKernelGGL(k_warp_l0_fwd, dim3(pp_div_up(capacity, 2)), b, 0, st, params + WP_W0, params + WP_B0, pts, count,
+  hipLaunchKernelGGL(k_warp_l0_fwd, dim3(pp_div_up(capacity, 2)), b, 0, st, params + WPF_W0, params + WPF_B0, pts, count,
                      capacity, acts);
-  hipLaunchKernelGGL((k_gemm128<MODE_NT, EPI_RELU, 4, PP_GEMM_BM>), g, b, 0, st, acts, 128, params + WP_W1, 128, 128, 128,
-                     params + WP_B1, nullptr, 0, acts + LS, 128, count, 4, rcap);
-  hipLaunchKernelGGL((k_gemm128<MODE_NT, EPI_RELU, 4, PP_GEMM_BM>), g, b, 0, st, acts + LS, 128, params + WP_W2, 128, 128, 128,
-                     params + WP_B2, nullptr, 0, acts + 2 * LS, 128, count, 4, rcap);
-  hipLaunchKernelGGL((k_gemm128<MODE_NT, EPI_RELU, 4, PP_GEMM_BM>), g, b, 0, st, acts + 2 * LS, 128, params + WP_W3, 128, 128, 128,
-                     params + WP_B3, nullptr, 0, acts + 3 * LS, 128, count, 4, rcap);
-  hipLaunchKernelGGL(k_warp_l4_fwd, dim3(pp_div_up(capacity, 4)), b, 0, st, params + WP_W4, params + WP_B4,
+  hipLaunchKernelGGL((k_gemm128<MODE_NT, EPI_RELU, 4, PP_GEMM_BM>), g, b, 0, st, acts, 128, params + WPF_W1, 128, 128, 128,
+                     params + WPF_B1, nullptr, 0, acts + LS, 128, count, 4, rcap);
+  hipLaunchKernelGGL((k_gemm128<MODE_NT, EPI_RELU, 4, PP_GEMM_BM>), g, b, 0, st, acts + LS, 128, params + WPF_W2, 128, 128, 128,
+                     params + WPF_B2, nullptr, 0, acts + 2 * LS, 128, count, 4, rcap);
+  hipLaunchKernelGGL((k_gemm128<MODE_NT, EPI_RELU, 4, PP_GEMM_BM>), g, b, 0, st, acts + 2 * LS, 128, params + WPF_W3, 128, 128, 128,
+                     params + WPF_B3, nullptr, 0, acts + 3 * LS, 128, count, 4, rcap);
+  hipLaunchKernelGGL(k_warp_l4_fwd, dim3(pp_div_up(capacity, 4)), b, 0, st, params + WPF_W4, params + WPF_B4,
                      acts + 3 * LS, count, capacity, out_range, out);
   PP_CHECK_LAUNCH();
   return PP_OK;
@@ -512,14 +525,9 @@ extern "C" int pp_warp_bwd(const float* params, const float* pts, const float* a
   const size_t LS = (size_t)rcap * 128;
   if (mlp_fused_enabled()) {
     // one fused data-gradient kernel (+ thin layers), then the three weight-gradient GEMMs on the Ybar it left behind
-    if (pp_opt(PP_OPT_MLP_SPLIT) & 2) pp_launch_warp_fused_bwd_s(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st, mlp_pack_for(ctx, params, 0));
-    else pp_launch_warp_fused_bwd(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st);
+    const bool sb = warp_bwd_stage1(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, ctx, st);
     hipStream_t ws = deferred_fork(ctx, st);
-    const bool sb = (pp_opt(PP_OPT_MLP_SPLIT) & 2) != 0;   // the split-precision data-gradient kernel leaves b1..b3 to this one
-    pp_launch_wgrad_chain(scratch, acts + 2 * LS, params_grad + WP_W3, scratch + LS, acts + LS, params_grad + WP_W2,
-                          scratch + 2 * LS, acts, params_grad + WP_W1, 128, count, 4, rcap, ws,
-                          sb ? params_grad + WP_B3 : nullptr, sb ? params_grad + WP_B2 : nullptr, sb ? params_grad + WP_B1 : nullptr,
-                          ws != st ? pp_opt(PP_OPT_WGRAD_SIDE_WGS) : 0);
+    warp_bwd_stage2(acts, scratch, count, capacity, params_grad, sb, ws, ws != st ? pp_opt(PP_OPT_WGRAD_SIDE_WGS) : 0);
     deferred_forked(ctx, ws, st);
     PP_CHECK_LAUNCH();
     return PP_OK;
@@ -529,13 +537,13 @@ extern "C" int pp_warp_bwd(const float* params, const float* pts, const float* a
   float* nxt = scratch + LS;
   float* wt = scratch + 2 * LS;          // transposed weights W3^T, W2^T, W1^T
   dim3 g(gemm_grid(rcap, PP_GEMM_BM, side.c != nullptr)), gt(TN_WGS), b(256);
-  hipLaunchKernelGGL(k_transpose, dim3(64), b, 0, st, params + WP_W3, wt, 128, 128);
-  hipLaunchKernelGGL(k_transpose, dim3(64), b, 0, st, params + WP_W2, wt + 16384, 128, 128);
-  hipLaunchKernelGGL(k_transpose, dim3(64), b, 0, st, params + WP_W1, wt + 32768, 128, 128);
-  hipLaunchKernelGGL(k_warp_l4_bwd, dim3(pp_div_up(capacity, STRIP)), b, 0, st, params + WP_W4, acts + 3 * LS, out_grad,
-                     count, capacity, out_range, cur, params_grad + WP_W4, params_grad + WP_B4);
-  const int w_off[4] = {0, WP_W1, WP_W2, WP_W3};
-  const int b_off[4] = {0, WP_B1, WP_B2, WP_B3};
+  hipLaunchKernelGGL(k_transpose, dim3(64), b, 0, st, params + WPF_W3, wt, 128, 128);
+  hipLaunchKernelGGL(k_transpose, dim3(64), b, 0, st, params + WPF_W2, wt + 16384, 128, 128);
+  hipLaunchKernelGGL(k_transpose, dim3(64), b, 0, st, params + WPF_W1, wt + 32768, 128, 128);
+  hipLaunchKernelGGL(k_warp_l4_bwd, dim3(pp_div_up(capacity, STRIP)), b, 0, st, params + WPF_W4, acts + 3 * LS, out_grad,
+                     count, capacity, out_range, cur, params_grad + WPF_W4, params_grad + WPF_B4);
+  const int w_off[4] = {0, WPF_W1, WPF_W2, WPF_W3};
+  const int b_off[4] = {0, WPF_B1, WPF_B2, WPF_B3};
   for (int l = 3; l >= 1; --l) {
     hipStream_t ss = side.fork();                      // weight gradient of layer l beside its data gradient
     hipLaunchKernelGGL((k_gemm_tn<4>), gt, b, 0, ss, cur, 128, acts + (l - 1) * LS, 128, 128, params_grad + w_off[l], 128,
@@ -547,10 +555,10 @@ extern "C" int pp_warp_bwd(const float* params, const float* pts, const float* a
     float* tmp = cur; cur = nxt; nxt = tmp;
   }
   // layer 0 (cur = Ybar1)
-  hipLaunchKernelGGL(k_warp_l0_bwd_pts, dim3(pp_div_up(capacity * 16, 256)), b, 0, st, params + WP_W0, cur, count, capacity,
+  hipLaunchKernelGGL(k_warp_l0_bwd_pts, dim3(pp_div_up(capacity * 16, 256)), b, 0, st, params + WPF_W0, cur, count, capacity,
                      pts_grad);
   hipLaunchKernelGGL(k_warp_l0_bwd_w, dim3(pp_div_up(capacity, STRIP0)), b, 0, st, pts, cur, count, capacity,
-                     params_grad + WP_W0, params_grad + WP_B0);
+                     params_grad + WPF_W0, params_grad + WPF_B0);
   side.join(0);
   PP_CHECK_LAUNCH();
   return PP_OK;
@@ -569,13 +577,9 @@ extern "C" int pp_warp_bwd_data(const float* params, const float* pts, const flo
   PP_REQUIRE(params && pts && acts && out_grad && count && scratch && params_grad && pts_grad && stage2_host, "null pointer");
   PP_REQUIRE(capacity > 0, "capacity<=0");
   if (!mlp_fused_enabled()) { pp_set_error("pp_warp_bwd_data: option mlp_fused = 0 has no two-stage form"); return PP_ERR_UNSUPPORTED; }
-  *stage2_host = (pp_opt(PP_OPT_MLP_SPLIT) & 2) ? 1 : 0;       // 1: the hidden layers' bias gradients are stage 2's to produce
-  if (pp_opt(PP_OPT_MLP_SPLIT) & 2)
-    pp_launch_warp_fused_bwd_s(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad,
-                               pp_stream(stream), mlp_pack_for(ctx, params, 0));
-  else
-    pp_launch_warp_fused_bwd(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad,
-                             pp_stream(stream));
+  // 1: the hidden layers' bias gradients are stage 2's to produce
+  *stage2_host = warp_bwd_stage1(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, ctx,
+                                 pp_stream(stream)) ? 1 : 0;
   PP_CHECK_LAUNCH();
   return PP_OK;
 }
@@ -586,12 +590,8 @@ extern "C" int pp_warp_bwd_weights(const float* acts, const float* scratch, cons
   PP_REQUIRE(acts && scratch && count && params_grad, "null pointer");
   PP_REQUIRE(capacity > 0 && (stage2 == 0 || stage2 == 1), "capacity<=0 or stage2 is not what pp_warp_bwd_data returned");
   if (!mlp_fused_enabled()) { pp_set_error("pp_warp_bwd_weights: option mlp_fused = 0 has no two-stage form"); return PP_ERR_UNSUPPORTED; }
-  const int rcap = capacity * 4;
-  const size_t LS = (size_t)rcap * 128;
-  const bool sb = stage2 != 0;     // who owns b1..b3 was decided by stage 1 and is handed over explicitly (never re-read from the options)
-  pp_launch_wgrad_chain(scratch, acts + 2 * LS, params_grad + WP_W3, scratch + LS, acts + LS, params_grad + WP_W2,
-                        scratch + 2 * LS, acts, params_grad + WP_W1, 128, count, 4, rcap, pp_stream(stream),
-                        sb ? params_grad + WP_B3 : nullptr, sb ? params_grad + WP_B2 : nullptr, sb ? params_grad + WP_B1 : nullptr);
+  // who owns b1..b3 was decided by stage 1 and is handed over explicitly (never re-read from the options)
+  warp_bwd_stage2(acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream), 0);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }
@@ -603,13 +603,8 @@ extern "C" int pp_rgbnet_bwd_data(const float* params, const float* acts, const 
   PP_REQUIRE(params && acts && rgb && rgb_grad && count && scratch && params_grad && feat_grad && stage2_host, "null pointer");
   PP_REQUIRE(capacity > 0, "capacity<=0");
   if (!mlp_fused_enabled()) { pp_set_error("pp_rgbnet_bwd_data: option mlp_fused = 0 has no two-stage form"); return PP_ERR_UNSUPPORTED; }
-  *stage2_host = (pp_opt(PP_OPT_MLP_SPLIT) & 8) ? 1 : 0;
-  if (pp_opt(PP_OPT_MLP_SPLIT) & 8)
-    pp_launch_rgb_fused_bwd_s(params, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, nullptr, 0,
-                              pp_stream(stream), mlp_pack_for(ctx, params, 1));
-  else
-    pp_launch_rgb_fused_bwd(params, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, nullptr, 0,
-                            pp_stream(stream));
+  *stage2_host = rgb_bwd_stage1(params, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, nullptr, 0, ctx,
+                                pp_stream(stream)) ? 1 : 0;
   PP_CHECK_LAUNCH();
   return PP_OK;
 }
@@ -620,11 +615,7 @@ extern "C" int pp_rgbnet_bwd_weights(const float* feat, const float* acts, const
   PP_REQUIRE(feat && acts && scratch && count && params_grad, "null pointer");
   PP_REQUIRE(capacity > 0 && (stage2 == 0 || stage2 == 1), "capacity<=0 or stage2 is not what pp_rgbnet_bwd_data returned");
   if (!mlp_fused_enabled()) { pp_set_error("pp_rgbnet_bwd_weights: option mlp_fused = 0 has no two-stage form"); return PP_ERR_UNSUPPORTED; }
-  const size_t FLS = (size_t)capacity * 128;
-  const bool sb = stage2 != 0;     // see pp_warp_bwd_weights
-  pp_launch_wgrad_chain(scratch, acts + FLS, params_grad + RGF_W2, scratch + FLS, acts, params_grad + RGF_W1,
-                        scratch + 2 * FLS, feat, params_grad + RGF_W0, 64, count, 1, capacity, pp_stream(stream),
-                        sb ? params_grad + RGF_B2 : nullptr, sb ? params_grad + RGF_B1 : nullptr, sb ? params_grad + RGF_B0 : nullptr);
+  rgb_bwd_stage2(feat, acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream), 0);   // see pp_warp_bwd_weights
   PP_CHECK_LAUNCH();
   return PP_OK;
 }

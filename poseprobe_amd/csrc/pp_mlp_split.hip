@@ -44,20 +44,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define TILE_ROWS 64
 #define LDH2 136                // halfs per row of a split tile
 #define PLANE (TILE_ROWS * LDH2)
-#ifndef MS_DBG
-#define MS_DBG 0      // experiments only (forward kernels): 1 = no MFMAs, 2 = no HBM activation stores, 3 = no LDS image writes
-#endif
-#ifdef MS_TIMERS      // phase timers (experiments): wave 0 of every work-group sums s_memtime deltas per phase
-__device__ unsigned long long g_ms_t[16];
-extern "C" int pp_debug_read_timers(unsigned long long* out16, int reset) {
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_ms_t), sizeof(g_ms_t)) != hipSuccess) return 1;
-  if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_ms_t), z, sizeof(z)) != hipSuccess) return 1; }
-  return 0;
-}
-#define TICK(i) do { const unsigned long long t__ = __builtin_readcyclecounter(); tsum[i] += t__ - tprev; tprev = t__; } while (0)
-#else
-#define TICK(i) do {} while (0)
-#endif
 #define PP_WAIT_VMEM() do { __builtin_amdgcn_s_waitcnt(0x0F70); asm volatile("" ::: "memory"); } while (0)
 
 namespace {
@@ -69,16 +55,25 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// maximum over the 16 lanes of a DPP row (all 16 lanes receive it): four VALU instructions, no LDS round trip
+template <int CTRL>
+__device__ __forceinline__ float dpp_f(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float row_max16(float v) {       // v >= 0
+  v = fmaxf(v, dpp_f<0xB1>(v));      // quad_perm [1,0,3,2]
+  v = fmaxf(v, dpp_f<0x4E>(v));      // quad_perm [2,3,0,1]
+  v = fmaxf(v, dpp_f<0x141>(v));     // row_half_mirror
+  v = fmaxf(v, dpp_f<0x140>(v));     // row_mirror
+  return v;
+}
 // block-wide maximum of a non-negative value (prologues): DPP row maxima, sixteen partials through LDS, ONE barrier per call - the
 // calls alternate between two slot sets (`red`: [2][16] floats, `phase` counts the calls), so the readers of one call are done
 // with their set before the call after the next writes it again
 __device__ __forceinline__ float block_max(float v, float* red, int tid, int& phase) {
   float* set = red + 16 * (phase & 1);
   ++phase;
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, true)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, true)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, true)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, true)));
+  v = row_max16(v);
   if ((tid & 15) == 0) set[tid >> 4] = v;
   __syncthreads();
   const float4 a = *reinterpret_cast<const float4*>(set), b = *reinterpret_cast<const float4*>(set + 4),
@@ -160,7 +155,7 @@ __device__ __forceinline__ void mma_half(const _Float16* __restrict__ rows, cons
   const _Float16* p = rows + l31 * LD + 8 * lh;
   pp_half8 h = *reinterpret_cast<const pp_half8*>(p), l = *reinterpret_cast<const pp_half8*>(p + PL);
 #pragma unroll
-  for (int ks = 0; ks < (MS_DBG == 1 ? 0 : KS); ++ks) {
+  for (int ks = 0; ks < KS; ++ks) {
     pp_half8 nh = h, nl = l;
     if (ks + 1 < KS) {
       nh = *reinterpret_cast<const pp_half8*>(p + 16 * (ks + 1));
@@ -244,20 +239,19 @@ struct HalfEpilogue {
         asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l[k]) : "v"(h[k]), "v"(p[2 * k + 1]));
     } else if (i == 5) {
       // the LDS image two steps before the end of the stage: its writes have retired when the barrier's lgkmcnt(0) comes
-      if (SPLIT && MS_DBG != 3) {
+      if (SPLIT) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           *reinterpret_cast<uint2*>(Arow + 8 * q) = make_uint2(h[2 * q], h[2 * q + 1]);
           *reinterpret_cast<uint2*>(Arow + 8 * q + PLANE) = make_uint2(l[2 * q], l[2 * q + 1]);
         }
-      }
-      if (!SPLIT) {
+      } else {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           *reinterpret_cast<float4*>(reinterpret_cast<float*>(Arow) + 8 * q) = make_float4(y[4 * q], y[4 * q + 1], y[4 * q + 2], y[4 * q + 3]);
       }
     } else if (i == 6) {
-      if (ok && MS_DBG != 2) {
+      if (ok) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(Crow + 8 * q) = make_float4(y[4 * q], y[4 * q + 1], y[4 * q + 2], y[4 * q + 3]);
       }
@@ -272,18 +266,6 @@ struct HalfEpilogue {
   __device__ __forceinline__ float vmax(float ninv) const { return xmax * ninv; }
 };
 
-// maximum over the 16 lanes of a DPP row (all 16 lanes receive it): four VALU instructions, no LDS round trip
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float row_max16(float v) {       // v >= 0
-  v = fmaxf(v, dpp_f<0xB1>(v));      // quad_perm [1,0,3,2]
-  v = fmaxf(v, dpp_f<0x4E>(v));      // quad_perm [2,3,0,1]
-  v = fmaxf(v, dpp_f<0x141>(v));     // row_half_mirror
-  v = fmaxf(v, dpp_f<0x140>(v));     // row_mirror
-  return v;
-}
 // fold a lane's non-negative value into an LDS slot (float bits as unsigned).  Written as one ds_max_u32 from four lanes
 // in inline assembly: the compiler's atomic optimiser would turn a plain atomicMax into a 64-iteration scalar readlane loop.
 __device__ __forceinline__ void slot_max(unsigned* slot, float v, int lane) {
@@ -379,13 +361,9 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
   if (tid < 16) Mx[tid >> 3][tid & 7] = 0u;
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
-#ifdef MS_TIMERS
-  unsigned long long tsum[16] = {0}, tprev = __builtin_readcyclecounter();
-#endif
   int par = 0;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, par ^= 1) {
     const int s0 = tile * 16, r0 = tile * TILE_ROWS;
-    TICK(15);
     {
       const int nt = tile + gridDim.x;
       pnext = 0.f;
@@ -424,9 +402,7 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
     ea.begin(brow(3));
     ea.all(acc0, inv0, sc0, ok0, crow, arow0);
     slot_max(&Mx[par][0], ea.vmax(ninv0), lane);
-    TICK(0);
     __syncthreads();
-    TICK(1);
     if (tid < 8) Mx[par ^ 1][tid] = 0u;                   // the next tile's slots (last read a tile ago)
     // ---- stage A1: layer 1 on half 0  ||  epilogue of (layer 0, half 1)
     zero16(acc0);
@@ -434,9 +410,7 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
     mma_half(&At[0][0], w1, acc0, l31, lh, [&](int ks) { ea.step(ks, acc1, inv0, sc0, ok1, crow + 32 * 128, arow0 + 32 * LDH2); });
     slot_max(&Mx[par][1], ea.vmax(ninv0), lane);
     park(par ^ 1, pnext);                                  // next tile's positions (read after >= 3 barriers)
-    TICK(2);
     __syncthreads();
-    TICK(3);
     // ---- stage B1: layer 1 on half 1  ||  epilogue of (layer 1, half 0)
     const int e10 = scale_exp(fmaf(slot_get(&Mx[par][0]), l1_1, b1mx));
     const float sc10 = pow2(e10), inv1 = pow2(-(e0 + ew1));
@@ -444,9 +418,7 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
     ea.begin(brow(0));
     mma_half(&At[0][32 * LDH2], w1, acc1, l31, lh, [&](int ks) { ea.step(ks, acc0, inv1, sc10, ok0, crow + LS, arow1); });
     slot_max(&Mx[par][2], ea.vmax(pow2(-e10)), lane);
-    TICK(4);
     __syncthreads();
-    TICK(5);
     // ---- stage A2: layer 2 on half 0  ||  epilogue of (layer 1, half 1)
     const int e11 = scale_exp(fmaf(slot_get(&Mx[par][1]), l1_1, b1mx));
     const float sc11 = pow2(e11);
@@ -454,27 +426,21 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
     ea.begin(brow(0));
     mma_half(&At[1][0], w2, acc0, l31, lh, [&](int ks) { ea.step(ks, acc1, inv1, sc11, ok1, crow + LS + 32 * 128, arow1 + 32 * LDH2); });
     slot_max(&Mx[par][3], ea.vmax(pow2(-e11)), lane);
-    TICK(6);
     __syncthreads();
-    TICK(7);
     // ---- stage B2: layer 2 on half 1  ||  epilogue of (layer 2, half 0)
     const int e20 = scale_exp(fmaf(slot_get(&Mx[par][2]), l1_2, b2mx));
     const float sc20 = pow2(e20), inv20 = pow2(-(e10 + ew2)), inv21 = pow2(-(e11 + ew2));
     zero16(acc1);
     ea.begin(brow(1));
     mma_half(&At[1][32 * LDH2], w2, acc1, l31, lh, [&](int ks) { ea.step(ks, acc0, inv20, sc20, ok0, crow + 2 * LS, arow0); });
-    TICK(8);
     __syncthreads();
-    TICK(9);
     // ---- stage A3: layer 3 on half 0  ||  epilogue of (layer 2, half 1)
     const int e21 = scale_exp(fmaf(slot_get(&Mx[par][3]), l1_2, b2mx));
     const float sc21 = pow2(e21);
     zero16(acc0);
     ea.begin(brow(1));
     mma_half(&At[0][0], w3, acc0, l31, lh, [&](int ks) { ea.step(ks, acc1, inv21, sc21, ok1, crow + 2 * LS + 32 * 128, arow0 + 32 * LDH2); });
-    TICK(10);
     __syncthreads();
-    TICK(11);
     // ---- stage B3: layer 3 on half 1  ||  epilogue of (layer 3, half 0) into the fp32 view, then that of half 1
     HalfEpilogue<4, false> ef;
     const float inv30 = pow2(-(e20 + ew3)), inv31 = pow2(-(e21 + ew3));
@@ -483,9 +449,7 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
     mma_half(&At[0][32 * LDH2], w3, acc1, l31, lh, [&](int ks) { ef.step(ks, acc0, inv30, 1.f, ok0, crow + 3 * LS, reinterpret_cast<_Float16*>(frow1)); });
     ef.begin(brow(2));
     ef.all(acc1, inv31, 1.f, ok1, crow + 3 * LS + 32 * 128, reinterpret_cast<_Float16*>(frow1 + 32 * LDA));
-    TICK(12);
     __syncthreads();
-    TICK(13);
     // ---- output layer (128 -> 4) on v_mfma_f32_4x4x1, fp32 view of tile 1 (as in k_warp_fused_fwd)
     {
       const float* As1 = reinterpret_cast<const float*>(At[1]);
@@ -514,21 +478,21 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
       const float sum = (Red[idx] + Red[256 + idx]) + (Red[512 + idx] + Red[768 + idx]);
       if (r0 + row < R) out[(size_t)r0 * 4 + tid] = (sum + b4) * out_range;
     }
-    TICK(14);
     // the next tile's first barrier orders these reads of tile 1 / Red before they are overwritten
   }
-#ifdef MS_TIMERS
-  if (tid == 0)
-    for (int i = 0; i < 16; ++i) atomicAdd(&g_ms_t[i], tsum[i]);
-#endif
+}
+
+// launches the variant of a kernel that reads the weight pack, or (pack == nullptr) the one that derives its content itself
+template <class... P, class... A>
+static void launch_pack_variant(void (*with_pack)(P...), void (*without)(P...), int grid, hipStream_t st, const float* pack, A... args) {
+  hipLaunchKernelGGL(pack ? with_pack : without, dim3(grid), dim3(256), 0, st, args..., pack);
 }
 
 int pp_launch_warp_fused_fwd_s(const float* params, const float* pts, const int32_t* count, int capacity, float out_range,
                                float* acts, float* out, hipStream_t st, const float* pack) {
   const int ntiles = pp_div_up(capacity, 16);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
-  if (pack) hipLaunchKernelGGL(k_warp_fused_fwd_s<true>, dim3(grid), dim3(256), 0, st, params, pts, count, capacity, out_range, acts, out, pack);
-  else hipLaunchKernelGGL(k_warp_fused_fwd_s<false>, dim3(grid), dim3(256), 0, st, params, pts, count, capacity, out_range, acts, out, pack);
+  launch_pack_variant(k_warp_fused_fwd_s<true>, k_warp_fused_fwd_s<false>, grid, st, pack, params, pts, count, capacity, out_range, acts, out);
   return 0;
 }
 
@@ -944,10 +908,8 @@ int pp_launch_warp_fused_bwd_s(const float* params, const float* pts, const floa
                                float* pts_grad, hipStream_t st, const float* pack) {
   const int ntiles = pp_div_up(capacity, 16);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
-  if (pack) hipLaunchKernelGGL(k_warp_fused_bwd_s<true>, dim3(grid), dim3(256), 0, st, params, pts, acts, out_grad, count, capacity, out_range,
-                               ybar, params_grad, pts_grad, pack);
-  else hipLaunchKernelGGL(k_warp_fused_bwd_s<false>, dim3(grid), dim3(256), 0, st, params, pts, acts, out_grad, count, capacity, out_range,
-                          ybar, params_grad, pts_grad, pack);
+  launch_pack_variant(k_warp_fused_bwd_s<true>, k_warp_fused_bwd_s<false>, grid, st, pack, params, pts, acts, out_grad, count, capacity,
+                      out_range, ybar, params_grad, pts_grad);
   return 0;
 }
 
@@ -1182,8 +1144,7 @@ int pp_launch_rgb_fused_fwd_s(const float* params, const float* feat, const int3
                               const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st, const float* pack) {
   const int ntiles = pp_div_up(capacity, TILE_ROWS);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
-  if (pack) hipLaunchKernelGGL(k_rgb_fused_fwd_s<true>, dim3(grid), dim3(256), 0, st, params, feat, count, capacity, logit_add, add_ld, acts, rgb, pack);
-  else hipLaunchKernelGGL(k_rgb_fused_fwd_s<false>, dim3(grid), dim3(256), 0, st, params, feat, count, capacity, logit_add, add_ld, acts, rgb, pack);
+  launch_pack_variant(k_rgb_fused_fwd_s<true>, k_rgb_fused_fwd_s<false>, grid, st, pack, params, feat, count, capacity, logit_add, add_ld, acts, rgb);
   return 0;
 }
 
@@ -1427,10 +1388,8 @@ int pp_launch_rgb_fused_bwd_s(const float* params, const float* acts, const floa
                               float* logit_grad, int lg_ld, hipStream_t st, const float* pack) {
   const int ntiles = pp_div_up(capacity, TILE_ROWS);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
-  if (pack) hipLaunchKernelGGL(k_rgb_fused_bwd_s<true>, dim3(grid), dim3(256), 0, st, params, acts, rgb, rgb_grad, count, capacity, ybar,
-                               params_grad, feat_grad, logit_grad, lg_ld, pack);
-  else hipLaunchKernelGGL(k_rgb_fused_bwd_s<false>, dim3(grid), dim3(256), 0, st, params, acts, rgb, rgb_grad, count, capacity, ybar,
-                          params_grad, feat_grad, logit_grad, lg_ld, pack);
+  launch_pack_variant(k_rgb_fused_bwd_s<true>, k_rgb_fused_bwd_s<false>, grid, st, pack, params, acts, rgb, rgb_grad, count, capacity, ybar,
+                      params_grad, feat_grad, logit_grad, lg_ld);
   return 0;
 }
 

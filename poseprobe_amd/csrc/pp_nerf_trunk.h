@@ -36,25 +36,7 @@
 
 #define TR_IMG_BYTES (8 * PL_A_BYTES)
 #define TR_STEPS 60                     // K-chunks of a chain: forward 2 + 8 + 8 + 8 + (2 + 8) + 8 + 8 + 8, backward 4 + 7 x 8
-#ifndef TR_DBG
-#define TR_DBG 0      // experiments only, bit mask: 1 no matrix instructions, 2 no output stores, 4 no mask words, 8 no weight fetches in the loop, 16 no activation reads
-#endif
-#ifndef TR_NT
-#define TR_NT 1       // output stores non-temporal: the 1 GB of activations a pass writes should not push the 2 MB of weights out of L2 (508 -> 434 us)
-#endif
 #define TR_WSTEP 32768                  // bytes of one step's weights: 256 columns x 32 k x (hi | lo) halfs
-
-#ifdef TR_TIMERS      // phase timers (experiments): wave 0 of every work-group sums s_memtime deltas per phase
-__device__ unsigned long long g_tr_t[16];
-extern "C" int pp_debug_read_trunk_timers(unsigned long long* out16, int reset) {
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_tr_t), sizeof(g_tr_t)) != hipSuccess) return 1;
-  if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_tr_t), z, sizeof(z)) != hipSuccess) return 1; }
-  return 0;
-}
-#define TR_TICK(i) do { const unsigned long long t__ = __builtin_readcyclecounter(); tsum[i] += t__ - tprev; tprev = t__; } while (0)
-#else
-#define TR_TICK(i) do {} while (0)
-#endif
 
 struct TrunkArgs {
   const float* in;                      // what the chain reads from HBM: forward [M][64] encoded points, backward [M][128] d(hidden of the colour head)
@@ -140,14 +122,8 @@ __device__ __forceinline__ void tr_step(const unsigned char* img, const pp_half8
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
       const int row = t * 32 + l31;
-      if (TR_DBG & 16) { ah[t] = wb[t & 3]; al[t] = wb[3 - (t & 3)]; continue; }
       ah[t] = *reinterpret_cast<const pp_half8*>(img + pl_slot_off(row, ks * 2 + lh));
       al[t] = *reinterpret_cast<const pp_half8*>(img + pl_slot_off(row, 4 + ks * 2 + lh));
-    }
-    if (TR_DBG & 1) {
-#pragma unroll
-      for (int t = 0; t < TM; ++t) acc[t][0][ks] += (float)ah[t][0] + (float)al[t][1] + (float)wb[ks * 2][2] + (float)wb[ks * 2 + 1][3];
-      continue;
     }
     // small terms first; the three products of one block are TM x TU instructions apart
 #pragma unroll
@@ -220,14 +196,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkAr
 #define TR_WLOAD(wb)                                                                                      \
   do {                                                                                                    \
     const unsigned char* p_ = wbase + (size_t)gs * TR_WSTEP;                                              \
-    if (!(TR_DBG & 8) || first_)                                                                          \
     _Pragma("unroll") for (int i_ = 0; i_ < TU * 4; ++i_) (wb)[i_] = *reinterpret_cast<const pp_half8*>(p_ + i_ * 1024); \
     gs = gs + 1 == nsteps ? 0 : gs + 1;                                                                   \
   } while (0)
-  bool first_ = true;
   TR_WLOAD(wb0);
   TR_WLOAD(wb1);
-  first_ = false;
 
   // streamed input of a tile: thread -> row tid / 4, eight columns at 8 (tid & 3) of a 32-wide chunk; pe holds two chunks
   float4 pe[4];
@@ -260,9 +233,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkAr
   TR_ELOAD((int)blockIdx.x);
   TR_BARRIER();
   int bp = 0;                                           // which half of bl holds the current stage's bias
-#ifdef TR_TIMERS
-  unsigned long long tsum[8] = {0}, tprev = __builtin_readcyclecounter();
-#endif
 
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int r0 = tile * TR;
@@ -278,7 +248,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkAr
       // forward: the next stage's bias on its way to LDS (fetched here, written behind barrier A, read a stage later)
       float bnext = 0.f;
       if (!BWD && tid < (l == 7 && head ? 128 : 256)) bnext = T.bias[l + 1 == NS ? 0 : l + 1][tid];
-      TR_TICK(6);
       if (!BWD && l == 8) {                             // head: the view columns through E, then a zero-weight step (keeps the two weight register sets in step)
         const float v_[8] = {pv[0].x, pv[0].y, pv[0].z, pv[0].w, pv[1].x, pv[1].y, pv[1].z, pv[1].w};
         pp_half8 h_, l_;
@@ -318,7 +287,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkAr
           TR_BARRIER();
         }
       }
-      TR_TICK(0);
       if (!BWD && l == 3) TR_ELOAD(tile);               // for layer 4 of this tile
       if (l == 7) TR_ELOAD(tile + (int)gridDim.x);      // for stage 0 of the next one (rows are clamped)
       if (!BWD && head && l == 6) TR_VLOAD(tile);       // for the head stage of this one
@@ -342,7 +310,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkAr
         // matrix instructions the wavefront also sends 16 rows of that chunk - the PREVIOUS stage's output - to HBM from the
         // image: x = (hi + lo) / s, exactly the operand the matrix instructions consume (22 significant bits), as 128-byte
         // rows; the write traffic is thereby spread evenly over the kernel instead of arriving in one burst per stage that
-        // every later weight fetch would have to wait behind (vmcnt retires in order): 712 -> 553 us.
+        // every later weight fetch would have to wait behind (vmcnt retires in order): 712 -> 553 us.  The stores are
+        // non-temporal: the 1 GB of activations a pass writes should not push the 2 MB of weights out of L2 (508 -> 434 us).
         float* __restrict__ outp = T.out[l - 1];
         const int ldp = T.ld[l - 1];
         const float invs = 1.0f / sA;
@@ -351,25 +320,18 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkAr
         float* const dptr = outp + (size_t)(r0 + drow) * ldp + 8 * dc8;
 #define TR_DRAIN(kc)                                                                                      \
         do {                                                                                              \
-            if (!(TR_DBG & 2)) {                                                                        \
-              const pp_half8 h = *reinterpret_cast<const pp_half8*>(Img + kc * CH + pl_slot_off(drow, dc8));\
-              const pp_half8 lo = *reinterpret_cast<const pp_half8*>(Img + kc * CH + pl_slot_off(drow, 4 + dc8));\
-              typedef float tr_f4 __attribute__((ext_vector_type(4)));                                  \
-              tr_f4 a, b;                                                                               \
-              a.x = ((float)h[0] + (float)lo[0]) * invs; a.y = ((float)h[1] + (float)lo[1]) * invs;     \
-              a.z = ((float)h[2] + (float)lo[2]) * invs; a.w = ((float)h[3] + (float)lo[3]) * invs;     \
-              b.x = ((float)h[4] + (float)lo[4]) * invs; b.y = ((float)h[5] + (float)lo[5]) * invs;     \
-              b.z = ((float)h[6] + (float)lo[6]) * invs; b.w = ((float)h[7] + (float)lo[7]) * invs;     \
-              if (dok) {                                                                                \
-                if (TR_NT) {                                                                            \
-                  __builtin_nontemporal_store(a, reinterpret_cast<tr_f4*>(dptr + 32 * kc));             \
-                  __builtin_nontemporal_store(b, reinterpret_cast<tr_f4*>(dptr + 32 * kc + 4));         \
-                } else {                                                                                \
-                  *reinterpret_cast<tr_f4*>(dptr + 32 * kc) = a;                                        \
-                  *reinterpret_cast<tr_f4*>(dptr + 32 * kc + 4) = b;                                    \
-                }                                                                                       \
-              }                                                                                         \
-            }                                                                                           \
+            const pp_half8 h = *reinterpret_cast<const pp_half8*>(Img + kc * CH + pl_slot_off(drow, dc8));\
+            const pp_half8 lo = *reinterpret_cast<const pp_half8*>(Img + kc * CH + pl_slot_off(drow, 4 + dc8));\
+            typedef float tr_f4 __attribute__((ext_vector_type(4)));                                      \
+            tr_f4 a, b;                                                                                   \
+            a.x = ((float)h[0] + (float)lo[0]) * invs; a.y = ((float)h[1] + (float)lo[1]) * invs;         \
+            a.z = ((float)h[2] + (float)lo[2]) * invs; a.w = ((float)h[3] + (float)lo[3]) * invs;         \
+            b.x = ((float)h[4] + (float)lo[4]) * invs; b.y = ((float)h[5] + (float)lo[5]) * invs;         \
+            b.z = ((float)h[6] + (float)lo[6]) * invs; b.w = ((float)h[7] + (float)lo[7]) * invs;         \
+            if (dok) {                                                                                    \
+              __builtin_nontemporal_store(a, reinterpret_cast<tr_f4*>(dptr + 32 * kc));                   \
+              __builtin_nontemporal_store(b, reinterpret_cast<tr_f4*>(dptr + 32 * kc + 4));               \
+            }                                                                                             \
         } while (0)
         // (the head stage runs like every other one - its 128 columns sit in the wavefronts' first slots, the other slots multiply
         // zero weights: a narrower variant of the step for that stage alone, as a second unrolled loop or as a test inside this
@@ -382,7 +344,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkAr
         }
 #undef TR_DRAIN
       }
-      TR_TICK(1);
       // ---- epilogue.  forward: bias, ReLU, masks; backward: mask (+ the density term); then the tile maximum
       const float inv = 1.0f / (sA * swl[l]);
       float* __restrict__ out = T.out[l];
@@ -427,11 +388,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkAr
             }
             acc[t][u][4 * q] = v.x; acc[t][u][4 * q + 1] = v.y; acc[t][u][4 * q + 2] = v.z; acc[t][u][4 * q + 3] = v.w;
             const int row = r0 + t * 32 + l31;
-            if (last && live && row < R && (!(TR_DBG & 2) || v.x == 123.456f)) *reinterpret_cast<float4*>(out + (size_t)row * ld + 32 * cb + 8 * q + 4 * lh) = v;   // (the other stages leave through the image)
+            if (last && live && row < R) *reinterpret_cast<float4*>(out + (size_t)row * ld + 32 * cb + 8 * q + 4 * lh) = v;   // (the other stages leave through the image)
           }
         }
       }
-      if (!BWD && !hstage && !(TR_DBG & 4)) {
+      if (!BWD && !hstage) {
         if (MROW) {
           uint16_t* __restrict__ br = T.bitsr[l];
 #pragma unroll
@@ -505,9 +466,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkAr
           }
         }
       }
-      TR_TICK(2);
       TR_BARRIER();                                     // A: every wavefront is done with the image; maximum and partials complete
-      TR_TICK(3);
       const float tm = hstage ? 0.f : tmax[l];
       if (tid == 0 && !hstage) lmax[l] = fmaxf(lmax[l], tm);
       if (!BWD && tid < 256) bl[(bp ^ 1) * 256 + tid] = bnext;
@@ -536,16 +495,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkAr
             }
         }
       }
-      TR_TICK(4);
       TR_BARRIER();                                     // B: the next stage's image is complete
-      TR_TICK(5);
     }
   }
   if (tid < 8) pp_record_max_lane(T.mx + T.mx_out[tid], lmax[tid]);      // (skips the atomic when the slot already holds as much: 512 work-groups end together)
-#ifdef TR_TIMERS
-  if (tid == 0)
-    for (int i = 0; i < 8; ++i) atomicAdd(&g_tr_t[(BWD ? 8 : 0) + i], tsum[i]);
-#endif
 #undef TR_WLOAD
 #undef TR_ELOAD
 #undef TR_ELOAD1

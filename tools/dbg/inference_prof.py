@@ -1,4 +1,5 @@
-"""Whole-view inference under rocprofv3: prints wall time per view; the kernel stats come from the profiler (tools/r3_inf_prof.sh)."""
+"""Whole-view inference under rocprofv3: prints wall time per view; the kernel stats come from the profiler
+(rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 tools/dbg/inference_prof.py; tools/show_stats.py DIR)."""
 import sys, time
 sys.path.insert(0, '/root/repo')
 import torch, bench

@@ -1,4 +1,4 @@
-"""Time pp_color_feat_fwd at the train step's shape with a given build of the library (experiments: CF_DBG variants).
+"""Time pp_color_feat_fwd at the train step's shape with a given build of the library.
     python tools/dbg/time_cf.py [path/to/lib.so]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

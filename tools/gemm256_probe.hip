@@ -1,7 +1,6 @@
 // Probe (not product) for csrc/pp_gemm_planes.h: runs k_pack_planes + k_gemm256p<EPI_RELU> on one 256 -> 256 layer at M rows,
-// checks the result against an fp64 host product on sampled rows and prints time / bandwidth; with -DPL_TIMERS the kernel's
-// phase timers (s_memtime, summed per work-group) are printed for a few work-groups.
-//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off [-DPL_TIMERS] -I poseprobe_amd/csrc -o tools/_build/gemm256_probe tools/gemm256_probe.hip poseprobe_amd/csrc/pp_error.hip
+// checks the result against an fp64 host product on sampled rows and prints time / bandwidth.
+//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I poseprobe_amd/csrc -o tools/_build/gemm256_probe tools/gemm256_probe.hip poseprobe_amd/csrc/pp_error.hip
 //   tools/_build/gemm256_probe [M]
 #include <hip/hip_runtime.h>
 #include <math.h>
