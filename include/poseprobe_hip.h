@@ -304,6 +304,46 @@ int pp_mlp_pack_workspace(int64_t* pack_floats);
 int pp_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, void* ctx, void* stream);
 int pp_mlp_pack_invalidate(void* ctx);
 
+/* ---------------------------------------------------------------- ordered gradient flushes: a bit-reproducible train step.
+ * By default the parameter gradients of the object branch are accumulated with float atomics wherever several work-groups (or
+ * lanes) contribute to one address: the hidden layers' weight and bias gradients of both MLPs (pp_warp_bwd, pp_rgbnet_bwd /
+ * pp_mlp_bwd and their two-stage forms), their thin layers, sdf_ab_grad of the geometry backward and c2w_grad of the ray
+ * backward.  Float addition is not associative, so the result depends on the order in which the hardware retires them.
+ * With an ordered-flush workspace ATTACHED to a context, the MLP backward calls that are handed this context write per-work-group
+ * partial sums with plain stores into `work` instead and add them up in ascending work-group order in a small reduction behind
+ * each kernel (same stream), one writer per address; pp_geometry_bwd_priors_ordered and pp_raygen_select_bwd_ordered do the same
+ * for the two calls that take no context otherwise (rows = work-groups / rays).  Guarantee: for one build of the library, equal
+ * option values, equal shapes (capacity, n_rays, n_views, work-group counts) and the same device model, identical inputs give
+ * bit-identical gradients.  NOT across different mlp_wgs values, builds or chips.  The surplus work-groups a persistent kernel
+ * retires on the device when `count` is small are never read: the reduction derives the same active count from `count`.
+ * Only the split-precision layer-fused kernels have this path: while a workspace is attached, the MLP backward entry points
+ * refuse (PP_ERR_INVALID_ARG) option values that select other kernels (mlp_fused = 0, mlp_split without bits 2 / 8 / 16, generic
+ * MLP shapes) and side_stream = 1, rather than fall back to atomics.  The reported scalars (loss_out, tv_out) stay on atomics:
+ * they feed no update.  The k0 scatter has its own ordered form (pp_k0_scatter_samples_sorted).
+ * pp_ordered_workspace: bytes (a multiple of 16) for `work_groups` = the largest persistent grid the calls will use (the device's
+ * compute-unit count, or option mlp_wgs when that is set; at least 16 are assumed), sample capacity and ray count; a pure host
+ * function.  pp_ordered_attach records `work` (16-byte aligned, at least that many bytes, caller-owned, alive and untouched by
+ * others while calls with this context are in flight) and the three sizes in `ctx`; calls that need more than was attached are
+ * refused.  work = NULL detaches: back to atomics.  Order of magnitude: 2 x 2 x 256 x 64.5 KB = 66 MB on an MI355X. */
+int pp_ordered_workspace(int32_t work_groups, int32_t capacity, int32_t n_rays, int64_t* bytes);
+int pp_ordered_attach(void* ctx, void* work, int64_t work_bytes, int32_t work_groups, int32_t capacity, int32_t n_rays);
+/* pp_geometry_bwd_priors / pp_raygen_select_bwd (same arguments, same kernels, same results up to summation order) with
+ * sdf_ab_grad (+=, required) / c2w_grad (overwritten, required) added up in work-group / ray order through the workspace attached
+ * to `ctx` (required). */
+int pp_geometry_bwd_priors_ordered(const pp_scene* sc, const float* sdf_grid, const float* sdf_ab, const float* pts,
+                                   const float* warp_out, const float* viewdirs, const int32_t* ray_id, const int32_t* count,
+                                   int32_t capacity, float inv_s, const float* g_alpha, const float* g_gradient, float w_eikonal,
+                                   float w_deform, float loss_scale, int32_t accumulate, float* warp_out_grad, float* pts_grad,
+                                   float* viewdir_grad_s, float* sdf_ab_grad, float* loss_out, const float* batch_norm,
+                                   void* ctx, void* stream);
+int pp_raygen_select_bwd_ordered(const pp_scene* sc, const int32_t* ray_idx, int32_t n_rays, const float* c2w,
+                                 const float* intr, int32_t n_views, int32_t H, int32_t W, int32_t inverse_y,
+                                 const float* rays_o, const float* rays_d, const float* t_min,
+                                 const int32_t* ray_start, const float* pts_grad, const float* step,
+                                 const float* viewdir_grad_s, const float* rays_o_grad, const float* rays_d_grad,
+                                 const float* viewdirs_grad, const float* depth_grad, float* rays_o_grad_out,
+                                 float* rays_d_grad_out, float* viewdirs_grad_out, float* c2w_grad, void* ctx, void* stream);
+
 /* ---------------------------------------------------------------- losses: lib/losses.py:6-74 (object_losses),
  * forward values + gradients w.r.t. the render outputs in one pass.  loss_scale multiplies every gradient
  * (recon_scene.py:648 scales the object loss by 0.1).

@@ -45,6 +45,10 @@ struct PPContext {
   // ([0] warp net, [1] rgbnet); pack == nullptr: none
   const float* pack;
   const float* pack_params[2];
+  // workspace of the ordered gradient flushes (pp_ordered_attach, pp_ordered.h) and the sizes it was attached for;
+  // ord == nullptr: none, every flush uses float atomics
+  float* ord;
+  int ord_wgs, ord_cap, ord_rays;
 };
 bool pp_context_aux(PPContext* c);   // creates the auxiliary stream + events on first use; false when HIP refuses
 

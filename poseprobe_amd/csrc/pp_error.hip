@@ -58,6 +58,8 @@ extern "C" int pp_context_create(void** ctx) {
   c->pending = 0;
   c->pack = nullptr;
   c->pack_params[0] = c->pack_params[1] = nullptr;
+  c->ord = nullptr;
+  c->ord_wgs = c->ord_cap = c->ord_rays = 0;
   *ctx = c;
   return PP_OK;
 }

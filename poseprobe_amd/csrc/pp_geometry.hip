@@ -4,6 +4,7 @@
 // :968-984), NeuS alpha (:483-519).  The sdf template is [X][Y][Z] fp32 (4 B gathers, L2/Infinity-Cache resident:
 // 3.5 MB at 96^3, 16 MB at 160^3).
 #include "pp_common.h"
+#include "pp_ordered.h"
 
 struct Tri {
   float w0[3], w1[3];
@@ -170,6 +171,7 @@ __global__ __launch_bounds__(256) void k_geometry_fwd(SceneDev sc, const float* 
 // that writes g_grad_deform / g_correction / g_sdf_deform to HBM first (pp_loss_samples); same expressions, same
 // order of additions, so the two routes are bit-identical.
 #define GEO_BWD_THREADS 512
+static_assert(GEO_BWD_THREADS == ORD_GEO_THREADS, "the ordered-flush workspace is sized by this block size");
 template <bool PRIORS>
 __global__ __launch_bounds__(GEO_BWD_THREADS) void k_geometry_bwd(
     SceneDev sc, const float* __restrict__ grid, const float* __restrict__ sdf_ab, const float* __restrict__ pts,
@@ -179,7 +181,7 @@ __global__ __launch_bounds__(GEO_BWD_THREADS) void k_geometry_bwd(
     const float* __restrict__ g_grad_deform, const float* __restrict__ g_correction, int accumulate,
     float* __restrict__ warp_out_grad, float* __restrict__ pts_grad, float* __restrict__ vgrad_s,
     float* __restrict__ sdf_ab_grad, float w_eik, float w_dyn, float ls, float* __restrict__ loss_out,
-    const float* __restrict__ batch_norm) {
+    const float* __restrict__ batch_norm, float* __restrict__ part) {
   __shared__ float red[6][GEO_BWD_THREADS / 64];
   int m = blockIdx.x * blockDim.x + threadIdx.x;
   int M = min(count[0], capacity);
@@ -307,7 +309,9 @@ __global__ __launch_bounds__(GEO_BWD_THREADS) void k_geometry_bwd(
     for (int w = 0; w < nw; ++w) s += red[threadIdx.x][w];
     const int k = threadIdx.x;
     if (k < 2) {
-      if (sdf_ab_grad && s != 0.f) atomicAdd(&sdf_ab_grad[k], s);
+      // part != nullptr (ordered flush, pp_ordered.h): the work-group's sums go to its row, every work-group writes one
+      if (part) part[blockIdx.x * ORD_GEO_ROW + k] = s;
+      else if (sdf_ab_grad && s != 0.f) atomicAdd(&sdf_ab_grad[k], s);
     } else if (PRIORS && loss_out && blockIdx.x * blockDim.x < M) {
       atomicAdd(&loss_out[k], k == 3 ? s * invM / 3.f : s * invM);
     }
@@ -341,7 +345,7 @@ extern "C" int pp_geometry_bwd(const pp_scene* sc, const float* sdf_grid, const 
   hipLaunchKernelGGL(k_geometry_bwd<false>, dim3(pp_div_up(capacity, GEO_BWD_THREADS)), dim3(GEO_BWD_THREADS), 0, pp_stream(stream), pp_scene_dev(sc),
                      sdf_grid, sdf_ab, pts, warp_out, viewdirs, ray_id, count, capacity, inv_s, g_alpha, g_gradient,
                      g_sdf_final, g_sdf_deform, g_grad_deform, g_correction, accumulate, warp_out_grad, pts_grad,
-                     viewdir_grad_s, sdf_ab_grad, 0.f, 0.f, 0.f, (float*)nullptr, (const float*)nullptr);
+                     viewdir_grad_s, sdf_ab_grad, 0.f, 0.f, 0.f, (float*)nullptr, (const float*)nullptr, (float*)nullptr);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }
@@ -358,7 +362,34 @@ extern "C" int pp_geometry_bwd_priors(const pp_scene* sc, const float* sdf_grid,
   hipLaunchKernelGGL(k_geometry_bwd<true>, dim3(pp_div_up(capacity, GEO_BWD_THREADS)), dim3(GEO_BWD_THREADS), 0, pp_stream(stream), pp_scene_dev(sc),
                      sdf_grid, sdf_ab, pts, warp_out, viewdirs, ray_id, count, capacity, inv_s, g_alpha, g_gradient,
                      nullptr, nullptr, nullptr, nullptr, accumulate, warp_out_grad, pts_grad, viewdir_grad_s, sdf_ab_grad,
-                     w_eikonal, w_deform, loss_scale, loss_out, batch_norm);
+                     w_eikonal, w_deform, loss_scale, loss_out, batch_norm, (float*)nullptr);
+  PP_CHECK_LAUNCH();
+  return PP_OK;
+}
+
+// pp_geometry_bwd_priors with sdf_ab_grad added up in a fixed order: every work-group writes its two sums to its row of the
+// context's ordered-flush workspace, one small reduction adds the rows (pp_ordered.h).  Everything else is the same kernel.
+extern "C" int pp_geometry_bwd_priors_ordered(const pp_scene* sc, const float* sdf_grid, const float* sdf_ab, const float* pts,
+                                              const float* warp_out, const float* viewdirs, const int32_t* ray_id,
+                                              const int32_t* count, int32_t capacity, float inv_s, const float* g_alpha,
+                                              const float* g_gradient, float w_eikonal, float w_deform, float loss_scale,
+                                              int32_t accumulate, float* warp_out_grad, float* pts_grad, float* viewdir_grad_s,
+                                              float* sdf_ab_grad, float* loss_out, const float* batch_norm, void* ctx, void* stream) {
+  PP_REQUIRE(sc && sdf_grid && sdf_ab && pts && warp_out && viewdirs && ray_id && count && warp_out_grad && pts_grad && sdf_ab_grad,
+             "null pointer");
+  PP_REQUIRE(capacity > 0, "capacity<=0");
+  const PPContext* c = static_cast<const PPContext*>(ctx);
+  PP_REQUIRE(c && c->ord, "no ordered-flush workspace attached to the context (pp_ordered_attach)");
+  PP_REQUIRE(capacity <= c->ord_cap, "the attached ordered-flush workspace is too small for this capacity");
+  float* part = c->ord + pp_ord_layout(c->ord_wgs, c->ord_cap, c->ord_rays).geo;
+  const int grid = pp_div_up(capacity, GEO_BWD_THREADS);
+  hipStream_t st = pp_stream(stream);
+  hipLaunchKernelGGL(k_geometry_bwd<true>, dim3(grid), dim3(GEO_BWD_THREADS), 0, st, pp_scene_dev(sc),
+                     sdf_grid, sdf_ab, pts, warp_out, viewdirs, ray_id, count, capacity, inv_s, g_alpha, g_gradient,
+                     nullptr, nullptr, nullptr, nullptr, accumulate, warp_out_grad, pts_grad, viewdir_grad_s, sdf_ab_grad,
+                     w_eikonal, w_deform, loss_scale, loss_out, batch_norm, part);
+  const OrdSegs segs{1, {2, 0, 0, 0}, {0, 0, 0, 0}};
+  pp_launch_ordered_flush(part, ORD_GEO_ROW, grid, nullptr, 0, 1, segs, sdf_ab_grad, st);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }

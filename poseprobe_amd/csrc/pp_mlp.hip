@@ -20,6 +20,7 @@
 #include "pp_common.h"
 #include "pp_mlp_fused.h"
 #include "pp_mlp_pack.h"
+#include "pp_ordered.h"
 #include <stdlib.h>
 
 #include "pp_gemm.h"
@@ -299,6 +300,34 @@ static const float* mlp_pack_for(const void* ctx, const float* params, int net) 
   return c->pack;
 }
 
+// Ordered flushes (pp_ordered_attach): with a workspace recorded in the call's context the parameter gradients of the backward
+// chains are added up in a fixed order instead of by float atomics.  Only the split-precision layer-fused kernels have that
+// path, and only on the caller's stream: everything else is refused while a workspace is attached rather than left on atomics.
+// `bits`: the mlp_split bits of the kernels the call runs.  Returns the reason for a refusal, or nullptr.
+static const char* ordered_refusal(const void* ctx, int capacity, int bits, bool fused_shape = true) {
+  const PPContext* c = static_cast<const PPContext*>(ctx);
+  if (!c || !c->ord) return nullptr;
+  if (!fused_shape || !mlp_fused_enabled() || (pp_opt(PP_OPT_MLP_SPLIT) & bits) != bits)
+    return "an ordered-flush workspace is attached to the context: only the split-precision layer-fused kernels have ordered "
+           "flushes (options mlp_fused = 1, mlp_split bits 2, 8 and 16; the Voxurf network shapes)";
+  if (pp_opt(PP_OPT_SIDE_STREAM) != 0) return "an ordered-flush workspace is attached to the context: option side_stream must be 0";
+  if (capacity > c->ord_cap || pp_fused_wgs() > c->ord_wgs)
+    return "the attached ordered-flush workspace is too small for this capacity / work-group count";
+  return nullptr;
+}
+#define PP_REQUIRE_ORDERED(ctx, capacity, ...)                                  \
+  do {                                                                          \
+    const char* why__ = ordered_refusal(ctx, capacity, __VA_ARGS__);            \
+    PP_REQUIRE(why__ == nullptr, why__);                                        \
+  } while (0)
+// region of the attached workspace: 0 / 1 = weight-gradient chain of the warp net / rgbnet, 2 / 3 = their thin layers; nullptr: none
+static float* ordered_part(const void* ctx, int region) {
+  const PPContext* c = static_cast<const PPContext*>(ctx);
+  if (!c || !c->ord) return nullptr;
+  const OrdLayout L = pp_ord_layout(c->ord_wgs, c->ord_cap, c->ord_rays);
+  return c->ord + (region < 2 ? L.wgrad[region] : L.thin[region - 2]);
+}
+
 extern "C" int pp_mlp_pack_workspace(int64_t* pack_floats) {
   PP_REQUIRE(pack_floats, "null pointer");
   *pack_floats = PK_FLOATS;
@@ -385,35 +414,35 @@ static bool warp_bwd_stage1(const float* params, const float* pts, const float* 
                             hipStream_t st) {
   const bool sb = (pp_opt(PP_OPT_MLP_SPLIT) & 2) != 0;
   if (sb) pp_launch_warp_fused_bwd_s(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st,
-                                     mlp_pack_for(ctx, params, 0));
+                                     mlp_pack_for(ctx, params, 0), ordered_part(ctx, 2));
   else pp_launch_warp_fused_bwd(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st);
   return sb;
 }
 static void warp_bwd_stage2(const float* acts, const float* scratch, const int32_t* count, int capacity, float* params_grad, bool sb,
-                            hipStream_t ws, int side_wgs) {
+                            hipStream_t ws, int side_wgs, const void* ctx) {
   const int rcap = capacity * 4;
   const size_t LS = (size_t)rcap * 128;
   pp_launch_wgrad_chain(scratch, acts + 2 * LS, params_grad + WPF_W3, scratch + LS, acts + LS, params_grad + WPF_W2,
                         scratch + 2 * LS, acts, params_grad + WPF_W1, 128, count, 4, rcap, ws,
                         sb ? params_grad + WPF_B3 : nullptr, sb ? params_grad + WPF_B2 : nullptr, sb ? params_grad + WPF_B1 : nullptr,
-                        side_wgs);
+                        side_wgs, ordered_part(ctx, 0));
 }
 static bool rgb_bwd_stage1(const float* params, const float* acts, const float* rgb, const float* rgb_grad, const int32_t* count,
                            int capacity, float* scratch, float* params_grad, float* feat_grad, float* logit_grad, int lg_ld,
                            void* ctx, hipStream_t st) {
   const bool sb = (pp_opt(PP_OPT_MLP_SPLIT) & 8) != 0;
   if (sb) pp_launch_rgb_fused_bwd_s(params, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, logit_grad, lg_ld,
-                                    st, mlp_pack_for(ctx, params, 1));
+                                    st, mlp_pack_for(ctx, params, 1), ordered_part(ctx, 3));
   else pp_launch_rgb_fused_bwd(params, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, logit_grad, lg_ld, st);
   return sb;
 }
 static void rgb_bwd_stage2(const float* feat, const float* acts, const float* scratch, const int32_t* count, int capacity,
-                           float* params_grad, bool sb, hipStream_t ws, int side_wgs) {
+                           float* params_grad, bool sb, hipStream_t ws, int side_wgs, const void* ctx) {
   const size_t FLS = (size_t)capacity * 128;
   pp_launch_wgrad_chain(scratch, acts + FLS, params_grad + RGF_W2, scratch + FLS, acts, params_grad + RGF_W1,
                         scratch + 2 * FLS, feat, params_grad + RGF_W0, 64, count, 1, capacity, ws,
                         sb ? params_grad + RGF_B2 : nullptr, sb ? params_grad + RGF_B1 : nullptr, sb ? params_grad + RGF_B0 : nullptr,
-                        side_wgs);
+                        side_wgs, ordered_part(ctx, 1));
 }
 
 extern "C" int pp_mlp_bwd(const float* params, const float* feat, int32_t in_ld, int32_t n_gemm, const float* acts,
@@ -423,12 +452,13 @@ extern "C" int pp_mlp_bwd(const float* params, const float* feat, int32_t in_ld,
   PPOptScope scope(ctx);
   PP_REQUIRE(params && feat && acts && out && out_grad && count && scratch && params_grad, "null pointer");
   PP_REQUIRE(capacity > 0 && in_ld % 32 == 0 && in_ld <= 128 && n_gemm >= 1 && n_gemm <= 8, "bad sizes");
+  PP_REQUIRE_ORDERED(ctx, capacity, 8 | 16, in_ld == 64 && n_gemm == 3 && feat_grad != nullptr);
   hipStream_t st = pp_stream(stream);
   if (in_ld == 64 && n_gemm == 3 && feat_grad && mlp_fused_enabled()) {
     const bool sb = rgb_bwd_stage1(params, acts, out, out_grad, count, capacity, scratch, params_grad, feat_grad, logit_add_grad,
                                    logit_add_ld, ctx, st);
     hipStream_t ws = deferred_fork(ctx, st);
-    rgb_bwd_stage2(feat, acts, scratch, count, capacity, params_grad, sb, ws, ws != st ? pp_opt(PP_OPT_WGRAD_SIDE_WGS) : 0);
+    rgb_bwd_stage2(feat, acts, scratch, count, capacity, params_grad, sb, ws, ws != st ? pp_opt(PP_OPT_WGRAD_SIDE_WGS) : 0, ctx);
     deferred_forked(ctx, ws, st);
     PP_CHECK_LAUNCH();
     return PP_OK;
@@ -520,6 +550,7 @@ extern "C" int pp_warp_bwd(const float* params, const float* pts, const float* a
   PPOptScope scope(ctx);
   PP_REQUIRE(params && pts && acts && out_grad && count && scratch && params_grad && pts_grad, "null pointer");
   PP_REQUIRE(capacity > 0, "capacity<=0");
+  PP_REQUIRE_ORDERED(ctx, capacity, 2 | 16);
   hipStream_t st = pp_stream(stream);
   const int rcap = capacity * 4;
   const size_t LS = (size_t)rcap * 128;
@@ -527,7 +558,7 @@ extern "C" int pp_warp_bwd(const float* params, const float* pts, const float* a
     // one fused data-gradient kernel (+ thin layers), then the three weight-gradient GEMMs on the Ybar it left behind
     const bool sb = warp_bwd_stage1(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, ctx, st);
     hipStream_t ws = deferred_fork(ctx, st);
-    warp_bwd_stage2(acts, scratch, count, capacity, params_grad, sb, ws, ws != st ? pp_opt(PP_OPT_WGRAD_SIDE_WGS) : 0);
+    warp_bwd_stage2(acts, scratch, count, capacity, params_grad, sb, ws, ws != st ? pp_opt(PP_OPT_WGRAD_SIDE_WGS) : 0, ctx);
     deferred_forked(ctx, ws, st);
     PP_CHECK_LAUNCH();
     return PP_OK;
@@ -577,6 +608,7 @@ extern "C" int pp_warp_bwd_data(const float* params, const float* pts, const flo
   PP_REQUIRE(params && pts && acts && out_grad && count && scratch && params_grad && pts_grad && stage2_host, "null pointer");
   PP_REQUIRE(capacity > 0, "capacity<=0");
   if (!mlp_fused_enabled()) { pp_set_error("pp_warp_bwd_data: option mlp_fused = 0 has no two-stage form"); return PP_ERR_UNSUPPORTED; }
+  PP_REQUIRE_ORDERED(ctx, capacity, 2);
   // 1: the hidden layers' bias gradients are stage 2's to produce
   *stage2_host = warp_bwd_stage1(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, ctx,
                                  pp_stream(stream)) ? 1 : 0;
@@ -590,8 +622,9 @@ extern "C" int pp_warp_bwd_weights(const float* acts, const float* scratch, cons
   PP_REQUIRE(acts && scratch && count && params_grad, "null pointer");
   PP_REQUIRE(capacity > 0 && (stage2 == 0 || stage2 == 1), "capacity<=0 or stage2 is not what pp_warp_bwd_data returned");
   if (!mlp_fused_enabled()) { pp_set_error("pp_warp_bwd_weights: option mlp_fused = 0 has no two-stage form"); return PP_ERR_UNSUPPORTED; }
+  PP_REQUIRE_ORDERED(ctx, capacity, 16);
   // who owns b1..b3 was decided by stage 1 and is handed over explicitly (never re-read from the options)
-  warp_bwd_stage2(acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream), 0);
+  warp_bwd_stage2(acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream), 0, ctx);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }
@@ -603,6 +636,7 @@ extern "C" int pp_rgbnet_bwd_data(const float* params, const float* acts, const 
   PP_REQUIRE(params && acts && rgb && rgb_grad && count && scratch && params_grad && feat_grad && stage2_host, "null pointer");
   PP_REQUIRE(capacity > 0, "capacity<=0");
   if (!mlp_fused_enabled()) { pp_set_error("pp_rgbnet_bwd_data: option mlp_fused = 0 has no two-stage form"); return PP_ERR_UNSUPPORTED; }
+  PP_REQUIRE_ORDERED(ctx, capacity, 8);
   *stage2_host = rgb_bwd_stage1(params, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, nullptr, 0, ctx,
                                 pp_stream(stream)) ? 1 : 0;
   PP_CHECK_LAUNCH();
@@ -615,7 +649,8 @@ extern "C" int pp_rgbnet_bwd_weights(const float* feat, const float* acts, const
   PP_REQUIRE(feat && acts && scratch && count && params_grad, "null pointer");
   PP_REQUIRE(capacity > 0 && (stage2 == 0 || stage2 == 1), "capacity<=0 or stage2 is not what pp_rgbnet_bwd_data returned");
   if (!mlp_fused_enabled()) { pp_set_error("pp_rgbnet_bwd_weights: option mlp_fused = 0 has no two-stage form"); return PP_ERR_UNSUPPORTED; }
-  rgb_bwd_stage2(feat, acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream), 0);   // see pp_warp_bwd_weights
+  PP_REQUIRE_ORDERED(ctx, capacity, 16);
+  rgb_bwd_stage2(feat, acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream), 0, ctx);   // see pp_warp_bwd_weights
   PP_CHECK_LAUNCH();
   return PP_OK;
 }

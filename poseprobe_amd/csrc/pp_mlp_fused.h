@@ -34,21 +34,24 @@ struct WgradOperands {
 };
 int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                             const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                            hipStream_t st, float* bA, float* bB, float* bC, int wgs = 0);
+                            hipStream_t st, float* bA, float* bB, float* bC, int wgs = 0, float* part = nullptr);
 // split-precision variants (pp_mlp_split.hip, option "mlp_split"): same contracts.  pack: the weight pack written by
-// pp_launch_mlp_pack FOR THESE params (pp_mlp_pack.h), or nullptr = the kernel derives the same quantities in its prologue
+// pp_launch_mlp_pack FOR THESE params (pp_mlp_pack.h), or nullptr = the kernel derives the same quantities in its prologue.
+// part (backward kernels, weight-gradient chain): this launch's region of the ordered-flush workspace (pp_ordered.h) - the
+// parameter gradients are then added up in a fixed order by a reduction launched behind the kernel; nullptr = float atomics
 int pp_launch_warp_fused_fwd_s(const float* params, const float* pts, const int32_t* count, int capacity, float out_range,
                                float* acts, float* out, hipStream_t st, const float* pack);
 int pp_launch_warp_fused_bwd_s(const float* params, const float* pts, const float* acts, const float* out_grad,
                                const int32_t* count, int capacity, float out_range, float* ybar, float* params_grad,
-                               float* pts_grad, hipStream_t st, const float* pack);
+                               float* pts_grad, hipStream_t st, const float* pack, float* part = nullptr);
 int pp_launch_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, hipStream_t st);
 // weight gradients of three layers (Y_l^T X_l accumulated into W_l) in one persistent kernel; kxc = width of X of layer C;
 // bA / bB / bC: also accumulate the bias gradients = column sums of Y over the primal rows (kxc == 128: the warp net's 4-row
 // form, every fourth row) or over all rows (kxc == 64: rgbnet)
 int pp_launch_wgrad_chain(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                           const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                          hipStream_t st, float* bA = nullptr, float* bB = nullptr, float* bC = nullptr, int wgs = 0 /* 0: one per CU */);
+                          hipStream_t st, float* bA = nullptr, float* bB = nullptr, float* bC = nullptr, int wgs = 0 /* 0: one per CU */,
+                          float* part = nullptr /* split-precision kernel only */);
 
 // parameter block of rgbnet (64-wide padded input): W0[128x64] b0 | W1[128x128] b1 | W2[128x128] b2 | W3[3x128] b3
 #define RGF_W0 0
@@ -66,7 +69,7 @@ int pp_launch_rgb_fused_fwd_s(const float* params, const float* feat, const int3
                               const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st, const float* pack);
 int pp_launch_rgb_fused_bwd_s(const float* params, const float* acts, const float* rgb, const float* rgb_grad,
                               const int32_t* count, int capacity, float* ybar, float* params_grad, float* feat_grad,
-                              float* logit_grad, int lg_ld, hipStream_t st, const float* pack);
+                              float* logit_grad, int lg_ld, hipStream_t st, const float* pack, float* part = nullptr);
 int pp_launch_rgb_fused_bwd(const float* params, const float* acts, const float* rgb, const float* rgb_grad,
                             const int32_t* count, int capacity, float* ybar, float* params_grad, float* feat_grad,
                             float* logit_grad, int lg_ld, hipStream_t st);

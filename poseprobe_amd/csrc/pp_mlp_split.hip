@@ -37,6 +37,7 @@
 #include "pp_gemm_split.h"
 #include "pp_split_image.h"
 #include "pp_mlp_pack.h"
+#include "pp_ordered.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -617,7 +618,8 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
                                                           const float* __restrict__ acts, const float* __restrict__ out_grad,
                                                           const int32_t* __restrict__ count, int capacity, float out_range,
                                                           float* __restrict__ ybar, float* __restrict__ params_grad,
-                                                          float* __restrict__ pts_grad, const float* __restrict__ pack) {
+                                                          float* __restrict__ pts_grad, float* __restrict__ part,
+                                                          const float* __restrict__ pack) {
   __shared__ __attribute__((aligned(16))) _Float16 At[2][2 * PLANE];      // tile 1 doubles as the fp32 [64][LDA] view (Ybar0)
   __shared__ __attribute__((aligned(16))) float XS[TILE_ROWS * 128];      // X3 rows of the NEXT tile (unpadded, lane-contiguous)
   __shared__ __attribute__((aligned(16))) float GT[2][16 * 128];          // primal rows of the gating activation of a layer
@@ -881,7 +883,8 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
     }
   }
 
-  // ---- flush the thin-layer weight gradients (one atomic per entry and work-group)
+  // ---- flush the thin-layer weight gradients: one atomic per entry and work-group, or (part != nullptr: ordered flush,
+  // pp_ordered.h) this work-group's row of `part`, W0 already in the layout of the parameter block
   __syncthreads();
   float* red = reinterpret_cast<float*>(At[0]);
   if (h0 == 1) {
@@ -893,7 +896,15 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
     if (j0 < 4) red[8 * 128 + j0] = bacc4;
   }
   __syncthreads();
-  if (h0 == 0) {
+  if (h0 == 0 && part != nullptr) {
+    float* __restrict__ row = part + (size_t)blockIdx.x * ORD_WARP_THIN;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) row[o * 128 + j0] = (wacc4[o] + red[o * 128 + j0]) * out_range;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) row[512 + j0 * 3 + i] = wacc0[i] + red[(4 + i) * 128 + j0];
+    row[896 + j0] = bacc0 + red[7 * 128 + j0];
+    if (j0 < 4) row[1024 + j0] = (bacc4 + red[8 * 128 + j0]) * out_range;
+  } else if (h0 == 0) {
 #pragma unroll
     for (int o = 0; o < 4; ++o) atomicAdd(&params_grad[WPF_W4 + o * 128 + j0], (wacc4[o] + red[o * 128 + j0]) * out_range);
 #pragma unroll
@@ -905,11 +916,15 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
 
 int pp_launch_warp_fused_bwd_s(const float* params, const float* pts, const float* acts, const float* out_grad,
                                const int32_t* count, int capacity, float out_range, float* ybar, float* params_grad,
-                               float* pts_grad, hipStream_t st, const float* pack) {
+                               float* pts_grad, hipStream_t st, const float* pack, float* part) {
   const int ntiles = pp_div_up(capacity, 16);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
   launch_pack_variant(k_warp_fused_bwd_s<true>, k_warp_fused_bwd_s<false>, grid, st, pack, params, pts, acts, out_grad, count, capacity,
-                      out_range, ybar, params_grad, pts_grad);
+                      out_range, ybar, params_grad, pts_grad, part);
+  if (part) {       // work-groups past the tile count retired at once: the rows of the first min(grid, tiles) are added up
+    const OrdSegs segs{4, {512, 896, 1024, ORD_WARP_THIN_N}, {WPF_W4, WPF_W0, WPF_B0, WPF_B4}};
+    pp_launch_ordered_flush(part, ORD_WARP_THIN, grid, count, capacity, 16, segs, params_grad, st);
+  }
   return 0;
 }
 
@@ -1161,7 +1176,7 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
                                                          const int32_t* __restrict__ count, int capacity,
                                                          float* __restrict__ ybar, float* __restrict__ params_grad,
                                                          float* __restrict__ feat_grad, float* __restrict__ logit_grad, int lg_ld,
-                                                         const float* __restrict__ pack) {
+                                                         float* __restrict__ part, const float* __restrict__ pack) {
   __shared__ __attribute__((aligned(16))) _Float16 At[2][2 * PLANE];
   __shared__ __attribute__((aligned(16))) float XS[TILE_ROWS * 128];      // H2 of the NEXT tile
   __shared__ __attribute__((aligned(16))) float GT[TILE_ROWS * 128];      // gates of the current layer (H1, then H0)
@@ -1367,7 +1382,7 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
     __syncthreads();
   }
 
-  // ---- flush W3bar, b3bar (thread = feature / output)
+  // ---- flush W3bar, b3bar (thread = feature / output): atomics, or this work-group's row of `part` (ordered flush, pp_ordered.h)
   float* red = reinterpret_cast<float*>(At[0]);
   __syncthreads();
   if (h0 == 1) {
@@ -1376,7 +1391,12 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
     if (j0 < 3) red[4 * 128 + j0] = bacc3;
   }
   __syncthreads();
-  if (h0 == 0) {
+  if (h0 == 0 && part != nullptr) {
+    float* __restrict__ row = part + (size_t)blockIdx.x * ORD_RGB_THIN;
+#pragma unroll
+    for (int o = 0; o < 3; ++o) row[o * 128 + j0] = wacc3[o] + red[o * 128 + j0];
+    if (j0 < 3) row[384 + j0] = bacc3 + red[4 * 128 + j0];
+  } else if (h0 == 0) {
 #pragma unroll
     for (int o = 0; o < 3; ++o) atomicAdd(&params_grad[RGF_W3 + o * 128 + j0], wacc3[o] + red[o * 128 + j0]);
     if (j0 < 3) atomicAdd(&params_grad[RGF_B3 + j0], bacc3 + red[4 * 128 + j0]);
@@ -1385,11 +1405,15 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
 
 int pp_launch_rgb_fused_bwd_s(const float* params, const float* acts, const float* rgb, const float* rgb_grad,
                               const int32_t* count, int capacity, float* ybar, float* params_grad, float* feat_grad,
-                              float* logit_grad, int lg_ld, hipStream_t st, const float* pack) {
+                              float* logit_grad, int lg_ld, hipStream_t st, const float* pack, float* part) {
   const int ntiles = pp_div_up(capacity, TILE_ROWS);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
   launch_pack_variant(k_rgb_fused_bwd_s<true>, k_rgb_fused_bwd_s<false>, grid, st, pack, params, acts, rgb, rgb_grad, count, capacity, ybar,
-                      params_grad, feat_grad, logit_grad, lg_ld);
+                      params_grad, feat_grad, logit_grad, lg_ld, part);
+  if (part) {
+    const OrdSegs segs{2, {384, ORD_RGB_THIN_N, 0, 0}, {RGF_W3, RGF_B3, 0, 0}};
+    pp_launch_ordered_flush(part, ORD_RGB_THIN, grid, count, capacity, TILE_ROWS, segs, params_grad, st);
+  }
   return 0;
 }
 
@@ -1496,9 +1520,19 @@ __device__ __forceinline__ WgsUnit wgs_unit(int k, int full, int wg, int nwg, in
   return {max(hi - q, 0), hi};
 }
 
+// the work-groups of the chain kernel that take part at `ntiles` tiles: with fewer than 8 tiles per work-group only the first half
+// of the grid works (k_wgrad_chain_s explains); the ordered reduction derives its row counts from the same rule
+__device__ __forceinline__ void wgs_active(int ntiles, int& nwg_ab, int& nwg_c) {
+  if (ntiles < 8 * nwg_ab) {
+    nwg_ab = max(nwg_ab / 2, 1);
+    nwg_c = max(nwg_c / 2, 1);
+  }
+}
+
+// slot: this work-group's slot of the ordered flush (pp_ordered.h), or nullptr = flush with atomics
 template <int KX, int CSTEP>
 __device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int ntiles, int wg, int nwg, unsigned char* __restrict__ img,
-                                          float2* __restrict__ flags) {
+                                          float2* __restrict__ flags, float* __restrict__ slot) {
   constexpr int NB = KX / 64;            // 32-column X blocks per wavefront
   constexpr int XR = KX / 16;            // X rows per thread: 8 (KX = 128) or 4 (KX = 64)
   constexpr int XC = KX / 4;             // threads per X row
@@ -1506,7 +1540,11 @@ __device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int nti
   const int rem_rows = min((ntiles - full * nwg) * TILE_ROWS, R);
   const int q = ((rem_rows + nwg - 1) / nwg + 15) & ~15;
   const int nunits = full + (rem_rows - wg * q > 0 ? 1 : 0);
-  if (nunits == 0) return;
+  if (nunits == 0) {                     // no rows for this work-group: its slot holds zeros
+    if (slot != nullptr)
+      for (int i = threadIdx.x; i < ORD_WGRAD_SLOT / 4; i += 256) reinterpret_cast<float4*>(slot)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
   unsigned char* const Yh = img;
   unsigned char* const Yl = img + TILE_ROWS * 256;
   unsigned char* const Xh = img + 2 * TILE_ROWS * 256;
@@ -1651,19 +1689,33 @@ __device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int nti
     __syncthreads();                                           // the images are free
     cur = nxt;
   }
-  // flush: one atomic per entry, scaled back
+  // flush, scaled back: one atomic per entry, or (ordered flush) the block as it lies in the accumulators into the work-group's
+  // slot - float4 number ((t NB + u) 4 + q) 256 + tid holds registers 4 q .. 4 q + 3 of acc[t][u]: every store instruction of a
+  // wavefront covers 1 KB; k_wgrad_reduce_s undoes the layout
   const float f = pow2(-(eY + eX));
+  if (slot != nullptr) {
+    float4* __restrict__ s4 = reinterpret_cast<float4*>(slot) + tid;
 #pragma unroll
-  for (int t = 0; t < 2; ++t)
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      const int k = 32 * NB * wc + u * 32 + l31;
+      for (int u = 0; u < NB; ++u)
 #pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int n = wr * 64 + t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-        atomicAdd(&L.Wbar[(size_t)n * KX + k], acc[t][u][reg] * f);
+        for (int qq = 0; qq < 4; ++qq)
+          s4[((t * NB + u) * 4 + qq) * 256] = make_float4(acc[t][u][4 * qq] * f, acc[t][u][4 * qq + 1] * f, acc[t][u][4 * qq + 2] * f,
+                                                          acc[t][u][4 * qq + 3] * f);
+  } else {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int u = 0; u < NB; ++u) {
+        const int k = 32 * NB * wc + u * 32 + l31;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+          const int n = wr * 64 + t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+          atomicAdd(&L.Wbar[(size_t)n * KX + k], acc[t][u][reg] * f);
+        }
       }
-    }
+  }
   if (bias) {                              // 8 row blocks x 128 columns of partial sums -> one atomic per column
     float* red = reinterpret_cast<float*>(img);               // the images are dead (the last step ended with a barrier)
 #pragma unroll
@@ -1673,7 +1725,8 @@ __device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int nti
       float sum = 0.f;
 #pragma unroll
       for (int i = 0; i < 8; ++i) sum += red[i * 128 + tid];
-      atomicAdd(&L.bbar[tid], sum);
+      if (slot != nullptr) slot[ORD_WGRAD_BIAS + tid] = sum;
+      else atomicAdd(&L.bbar[tid], sum);
     }
   }
 }
@@ -1682,7 +1735,8 @@ __device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int nti
 
 template <int KXC, int CSTEP>
 __global__ __launch_bounds__(256, 2) void k_wgrad_chain_s(WgradOperands LA, WgradOperands LB, WgradOperands LC,
-                                                          const int32_t* __restrict__ count, int rmul, int rcap, int nwg_ab, int nwg_c) {
+                                                          const int32_t* __restrict__ count, int rmul, int rcap, int nwg_ab, int nwg_c,
+                                                          float* __restrict__ part) {
   __shared__ __attribute__((aligned(1024))) unsigned char img[4 * TILE_ROWS * 256];      // Yh | Yl | Xh | Xl
   __shared__ __attribute__((aligned(16))) float2 flags[8];                                // [2 sets][4 wavefronts]
   const int R = min(count[0] * rmul, rcap);
@@ -1691,10 +1745,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_chain_s(WgradOperands LA, Wgra
   // CU pays only where each gets many tiles (warp net at 55 k samples: 20 tiles each, 159 us against 166 us with one per CU;
   // rgbnet: 1.7 tiles each, 56 us against 47 us).  With fewer than 8 tiles per work-group only the first half of the grid works:
   // the work-groups dispatched first, one per CU.
-  if (ntiles < 8 * nwg_ab) {
-    nwg_ab = max(nwg_ab / 2, 1);
-    nwg_c = max(nwg_c / 2, 1);
-  }
+  wgs_active(ntiles, nwg_ab, nwg_c);
   // work-groups 0 .. nwg_ab - 1: layer A, the next nwg_ab: layer B, the next nwg_c: layer C (fewer when its operand is narrower)
   const int bx = blockIdx.x;
   if (bx >= 2 * nwg_ab + nwg_c) return;
@@ -1702,13 +1753,50 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_chain_s(WgradOperands LA, Wgra
   const int wg = bx - layer * nwg_ab, nwg = layer < 2 ? nwg_ab : nwg_c;
   // one copy of the layer code per operand width (three calls would triple the instruction footprint)
   const WgradOperands L = layer == 0 ? LA : (layer == 1 ? LB : LC);
-  if (KXC == 128 || layer < 2) wgs_layer<128, CSTEP>(L, R, ntiles, wg, nwg, img, flags);
-  else wgs_layer<KXC, CSTEP>(L, R, ntiles, wg, nwg, img, flags);
+  float* const slot = part != nullptr ? part + (size_t)bx * ORD_WGRAD_SLOT : nullptr;      // slot = work-group of the grid
+  if (KXC == 128 || layer < 2) wgs_layer<128, CSTEP>(L, R, ntiles, wg, nwg, img, flags, slot);
+  else wgs_layer<KXC, CSTEP>(L, R, ntiles, wg, nwg, img, flags, slot);
+}
+
+// Ordered flush of k_wgrad_chain_s: grid (65, 3) - blockIdx.y = layer, blockIdx.x = 64 consecutive float4s of the layer's block
+// (64 of them at KX = 128, 32 at KX = 64), block 64 = the 128 bias sums.  The rows of a layer are the slots of its work-groups in
+// ascending order; how many took part is derived from `count` exactly as the chain kernel does, on the device.
+template <int KXC>
+__global__ __launch_bounds__(ORD_RED_THREADS) void k_wgrad_reduce_s(WgradOperands LA, WgradOperands LB, WgradOperands LC,
+                                                                    const int32_t* __restrict__ count, int rmul, int rcap, int nwg_ab,
+                                                                    int nwg_c, const float* __restrict__ part) {
+  __shared__ float4 lds[ORD_RED_GROUPS * 64];
+  const int R = min(count[0] * rmul, rcap);
+  const int ntiles = (R + TILE_ROWS - 1) / TILE_ROWS;
+  wgs_active(ntiles, nwg_ab, nwg_c);
+  const int layer = blockIdx.y;
+  const WgradOperands L = layer == 0 ? LA : (layer == 1 ? LB : LC);
+  const int KX = layer < 2 ? 128 : KXC, NB = KX / 64;
+  const int row0 = layer * nwg_ab, rows = layer < 2 ? nwg_ab : nwg_c;
+  const bool bias_block = blockIdx.x == 64;
+  if ((!bias_block && (int)blockIdx.x * 64 >= 32 * KX) || (bias_block && L.bbar == nullptr)) return;
+  const int el = threadIdx.x & 63;
+  const int e4 = bias_block ? ORD_WGRAD_BIAS / 4 + el : blockIdx.x * 64 + el;
+  float4 s;
+  if (!pp_ordered_rows_sum(reinterpret_cast<const float4*>(part), ORD_WGRAD_SLOT / 4, row0, rows, e4, !bias_block || el < 32, lds, s)) return;
+  if (bias_block) {
+    float4* b4 = reinterpret_cast<float4*>(L.bbar) + el;
+    float4 v = *b4;
+    v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w;
+    *b4 = v;
+    return;
+  }
+  // float4 e4 of a slot = registers 4 qq .. 4 qq + 3 of acc[t][u] of thread tid (wgs_layer): column k, rows n .. n + 3
+  const int tid = e4 & 255, qq = (e4 >> 8) & 3, tu = e4 >> 10, u = tu % NB, t = tu / NB;
+  const int lane = tid & 63, wid = tid >> 6, wr = wid >> 1, wc = wid & 1, l31 = lane & 31, lh = lane >> 5;
+  const int k = 32 * NB * wc + u * 32 + l31, n = wr * 64 + t * 32 + 8 * qq + 4 * lh;
+  float* __restrict__ w = L.Wbar + (size_t)n * KX + k;
+  w[0] += s.x; w[KX] += s.y; w[2 * KX] += s.z; w[3 * KX] += s.w;
 }
 
 int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                             const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                            hipStream_t st, float* bA, float* bB, float* bC, int wgs_) {
+                            hipStream_t st, float* bA, float* bB, float* bC, int wgs_, float* part) {
   WgradOperands LA{YA, XA, WA, bA}, LB{YB, XB, WB, bB}, LC{YC, XC, WC, bC};
   const int ntiles = pp_div_up(rcap, TILE_ROWS);
   // persistent work-groups, two per CU over the three layers, shared out in proportion to the layers' work (wgs_ > 0: the caller's
@@ -1720,8 +1808,14 @@ int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const f
   if (nab > ntiles) nab = ntiles;
   if (nc > ntiles) nc = ntiles;
   if (kxc == 128)
-    hipLaunchKernelGGL((k_wgrad_chain_s<128, 4>), dim3(2 * nab + nc), dim3(256), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc);
+    hipLaunchKernelGGL((k_wgrad_chain_s<128, 4>), dim3(2 * nab + nc), dim3(256), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc, part);
   else
-    hipLaunchKernelGGL((k_wgrad_chain_s<64, 1>), dim3(2 * nab + nc), dim3(256), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc);
+    hipLaunchKernelGGL((k_wgrad_chain_s<64, 1>), dim3(2 * nab + nc), dim3(256), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc, part);
+  if (part) {
+    if (kxc == 128)
+      hipLaunchKernelGGL((k_wgrad_reduce_s<128>), dim3(65, 3), dim3(ORD_RED_THREADS), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc, part);
+    else
+      hipLaunchKernelGGL((k_wgrad_reduce_s<64>), dim3(65, 3), dim3(ORD_RED_THREADS), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc, part);
+  }
   return 0;
 }

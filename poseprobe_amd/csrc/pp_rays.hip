@@ -2,6 +2,7 @@
 // Reference behaviour restated (not translated) from: lib/camera.py:76-99,127-188; lib/recon_scene.py:62-74;
 // lib/voxurf_coarse.py:1339-1368,1402-1407,697-719,936-945,661-695; lib/cuda/render_utils_kernel.cu:12-242.
 #include "pp_common.h"
+#include "pp_ordered.h"
 
 // ------------------------------------------------------------------------------------------------
 // forward-mode dual numbers with 6 tangents (d/d se3) - one thread per view, a few hundred ops.
@@ -441,7 +442,7 @@ __global__ __launch_bounds__(256) void k_raygen_bwd(
     const float* __restrict__ pts_grad, const float* __restrict__ step, const float* __restrict__ vgrad_s,
     const float* __restrict__ g_o_in, const float* __restrict__ g_d_in, const float* __restrict__ g_v_in,
     const float* __restrict__ g_depth, float* __restrict__ g_o_out, float* __restrict__ g_d_out,
-    float* __restrict__ g_v_out, float* __restrict__ c2w_grad) {
+    float* __restrict__ g_v_out, float* __restrict__ c2w_grad, float* __restrict__ part) {
   extern __shared__ float s_c2w[];  // [n_views*12]
   for (int i = threadIdx.x; i < n_views * 12; i += blockDim.x) s_c2w[i] = 0.f;
   __syncthreads();
@@ -519,19 +520,68 @@ __global__ __launch_bounds__(256) void k_raygen_bwd(
         float Dn = sqrtf(Du[0] * Du[0] + Du[1] * Du[1] + Du[2] * Du[2]);
         float nh[3] = {Du[0] / Dn, Du[1] / Dn, Du[2] / Dn};
         float dot = nh[0] * gt[0] + nh[1] * gt[1] + nh[2] * gt[2];
+        // part != nullptr (ordered flush, pp_ordered.h): the ray's twelve contributions and its view go to the ray's row,
+        // k_raygen_c2w_reduce adds the rows of a view in ray order
+        float* __restrict__ row = part ? part + (size_t)r * ORD_RAY_ROW : nullptr;
         for (int k = 0; k < 3; ++k) {
           float Db = (gt[k] - nh[k] * dot) / Dn;
-          for (int j = 0; j < 3; ++j) atomicAdd(&s_c2w[view * 12 + k * 4 + j], Db * dirs[j]);
-          atomicAdd(&s_c2w[view * 12 + k * 4 + 3], ob[k]);
+          if (row) {
+            for (int j = 0; j < 3; ++j) row[k * 4 + j] = Db * dirs[j];
+            row[k * 4 + 3] = ob[k];
+          } else {
+            for (int j = 0; j < 3; ++j) atomicAdd(&s_c2w[view * 12 + k * 4 + j], Db * dirs[j]);
+            atomicAdd(&s_c2w[view * 12 + k * 4 + 3], ob[k]);
+          }
         }
+        if (row) row[12] = __int_as_float(view);
       }
     }
   }
   __syncthreads();
-  if (c2w_grad)
+  if (c2w_grad && !part)
     for (int i = threadIdx.x; i < n_views * 12; i += blockDim.x)
       if (s_c2w[i] != 0.f) atomicAdd(&c2w_grad[i], s_c2w[i]);
 }
+
+// Ordered flush of k_raygen_bwd: one work-group per view.  Thread t adds the rows (one per ray) of rays t, t + 256, ... that belong
+// to its view, in ascending order, into twelve sums; the 256 x 12 partial sums are then folded by a tree with fixed pairs
+// (t += t + 128, t += t + 64, ...), so the order of every addition is a function of n_rays alone.  Overwrites c2w_grad.
+__global__ __launch_bounds__(256) void k_raygen_c2w_reduce(const float* __restrict__ part, int n_rays, int n_views,
+                                                           float* __restrict__ c2w_grad) {
+  __shared__ float sums[256][13];              // 13: the twelve columns of consecutive threads fall into different banks
+  const int view = blockIdx.x, t = threadIdx.x;
+  float s[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) s[e] = 0.f;
+  const float4* __restrict__ rows = reinterpret_cast<const float4*>(part);
+  for (int r = t; r < n_rays; r += 256) {
+    const float4 tail = rows[(size_t)r * (ORD_RAY_ROW / 4) + 3];                    // | view | pad
+    if (__float_as_int(tail.x) != view) continue;
+    const float4 a = rows[(size_t)r * (ORD_RAY_ROW / 4)], b = rows[(size_t)r * (ORD_RAY_ROW / 4) + 1],
+                 c = rows[(size_t)r * (ORD_RAY_ROW / 4) + 2];
+    s[0] += a.x; s[1] += a.y; s[2] += a.z; s[3] += a.w;
+    s[4] += b.x; s[5] += b.y; s[6] += b.z; s[7] += b.w;
+    s[8] += c.x; s[9] += c.y; s[10] += c.z; s[11] += c.w;
+  }
+#pragma unroll
+  for (int e = 0; e < 12; ++e) sums[t][e] = s[e];
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (t < h) {
+#pragma unroll
+      for (int e = 0; e < 12; ++e) sums[t][e] += sums[t + h][e];
+    }
+    __syncthreads();
+  }
+  if (t < 12) c2w_grad[view * 12 + t] = sums[0][t];
+}
+
+static int raygen_select_bwd(const pp_scene* sc, const int32_t* ray_idx, int32_t n_rays, const float* c2w, const float* intr,
+                             int32_t n_views, int32_t H, int32_t W, int32_t inverse_y, const float* rays_o, const float* rays_d,
+                             const float* t_min, const int32_t* ray_start, const float* pts_grad, const float* step,
+                             const float* viewdir_grad_s, const float* rays_o_grad, const float* rays_d_grad,
+                             const float* viewdirs_grad, const float* depth_grad, float* rays_o_grad_out, float* rays_d_grad_out,
+                             float* viewdirs_grad_out, float* c2w_grad, float* part, void* stream);
 
 extern "C" int pp_raygen_select_bwd(const pp_scene* sc, const int32_t* ray_idx, int32_t n_rays, const float* c2w,
                                     const float* intr, int32_t n_views, int32_t H, int32_t W, int32_t inverse_y,
@@ -543,6 +593,37 @@ extern "C" int pp_raygen_select_bwd(const pp_scene* sc, const int32_t* ray_idx, 
   PP_REQUIRE(sc && rays_o && rays_d && t_min && ray_start && pts_grad && step, "null pointer");
   PP_REQUIRE(!c2w_grad || (ray_idx && c2w && intr && n_views > 0), "c2w_grad requested without camera data");
   PP_REQUIRE(n_rays > 0, "n_rays<=0");
+  return raygen_select_bwd(sc, ray_idx, n_rays, c2w, intr, n_views, H, W, inverse_y, rays_o, rays_d, t_min, ray_start, pts_grad, step,
+                           viewdir_grad_s, rays_o_grad, rays_d_grad, viewdirs_grad, depth_grad, rays_o_grad_out, rays_d_grad_out,
+                           viewdirs_grad_out, c2w_grad, nullptr, stream);
+}
+
+// pp_raygen_select_bwd with c2w_grad added up in ray order (required here) through the context's ordered-flush workspace
+extern "C" int pp_raygen_select_bwd_ordered(const pp_scene* sc, const int32_t* ray_idx, int32_t n_rays, const float* c2w,
+                                            const float* intr, int32_t n_views, int32_t H, int32_t W, int32_t inverse_y,
+                                            const float* rays_o, const float* rays_d, const float* t_min,
+                                            const int32_t* ray_start, const float* pts_grad, const float* step,
+                                            const float* viewdir_grad_s, const float* rays_o_grad, const float* rays_d_grad,
+                                            const float* viewdirs_grad, const float* depth_grad, float* rays_o_grad_out,
+                                            float* rays_d_grad_out, float* viewdirs_grad_out, float* c2w_grad, void* ctx,
+                                            void* stream) {
+  PP_REQUIRE(sc && rays_o && rays_d && t_min && ray_start && pts_grad && step && c2w_grad, "null pointer");
+  PP_REQUIRE(ray_idx && c2w && intr && n_views > 0, "c2w_grad requested without camera data");
+  PP_REQUIRE(n_rays > 0, "n_rays<=0");
+  const PPContext* c = static_cast<const PPContext*>(ctx);
+  PP_REQUIRE(c && c->ord, "no ordered-flush workspace attached to the context (pp_ordered_attach)");
+  PP_REQUIRE(n_rays <= c->ord_rays, "the attached ordered-flush workspace is too small for this ray count");
+  return raygen_select_bwd(sc, ray_idx, n_rays, c2w, intr, n_views, H, W, inverse_y, rays_o, rays_d, t_min, ray_start, pts_grad, step,
+                           viewdir_grad_s, rays_o_grad, rays_d_grad, viewdirs_grad, depth_grad, rays_o_grad_out, rays_d_grad_out,
+                           viewdirs_grad_out, c2w_grad, c->ord + pp_ord_layout(c->ord_wgs, c->ord_cap, c->ord_rays).ray, stream);
+}
+
+static int raygen_select_bwd(const pp_scene* sc, const int32_t* ray_idx, int32_t n_rays, const float* c2w, const float* intr,
+                             int32_t n_views, int32_t H, int32_t W, int32_t inverse_y, const float* rays_o, const float* rays_d,
+                             const float* t_min, const int32_t* ray_start, const float* pts_grad, const float* step,
+                             const float* viewdir_grad_s, const float* rays_o_grad, const float* rays_d_grad,
+                             const float* viewdirs_grad, const float* depth_grad, float* rays_o_grad_out, float* rays_d_grad_out,
+                             float* viewdirs_grad_out, float* c2w_grad, float* part, void* stream) {
   SceneDev d = pp_scene_dev(sc);
   hipStream_t st = pp_stream(stream);
   if (c2w_grad) {
@@ -555,7 +636,8 @@ extern "C" int pp_raygen_select_bwd(const pp_scene* sc, const int32_t* ray_idx, 
   hipLaunchKernelGGL(k_raygen_bwd, dim3(pp_div_up(n_rays, 4)), dim3(256), sizeof(float) * 12 * nv, st, d, ray_idx,
                      n_rays, c2w, intr, nv, H, W, inverse_y, rays_o, rays_d, t_min, ray_start, pts_grad, step,
                      viewdir_grad_s, rays_o_grad, rays_d_grad, viewdirs_grad, depth_grad, rays_o_grad_out,
-                     rays_d_grad_out, viewdirs_grad_out, c2w_grad);
+                     rays_d_grad_out, viewdirs_grad_out, c2w_grad, part);
+  if (part) hipLaunchKernelGGL(k_raygen_c2w_reduce, dim3(nv), dim3(256), 0, st, part, n_rays, nv, c2w_grad);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }

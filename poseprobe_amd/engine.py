@@ -207,8 +207,10 @@ class RenderCore:
     """Forward and backward kernel chains over a Workspace.  Parameters are passed as raw device tensors:
     k0_cl [X,Y,Z,C] (channels-last), sdf [X,Y,Z], flat (FlatParams-like with .view)."""
 
-    def __init__(self, cfg: SceneConfig, ctx=None):
-        """ctx: the pp_context (ops.Context) every option-dependent kernel of this core is called with; None = the host's
+    def __init__(self, cfg: SceneConfig, ctx=None, ordered=False):
+        """ordered: `ctx` (required then) has an ordered-flush workspace attached (ops.ordered_attach) - the fused step's backward
+        uses the ordered form of the geometry backward as well (the MLP calls pick the workspace up from the context).
+        ctx: the pp_context (ops.Context) every option-dependent kernel of this core is called with; None = the host's
         default context.  Its option `side_stream` = 1 runs the weight-gradient kernel of each MLP chain on the context's
         auxiliary stream beside the small, latency-bound kernels that follow the chain's data-gradient kernel and joins it before
         the next register-hungry MLP kernel.  Measured on MI355X (kernel trace): the overlap happens, but the small kernels only
@@ -216,6 +218,9 @@ class RenderCore:
         off by default (PP_SIDE_STREAM=1 in the host's environment turns it on in the default context)."""
         self.cfg = cfg
         self.ctx = ctx
+        self.ordered = bool(ordered)
+        if self.ordered and ctx is None:
+            raise ValueError('an ordered RenderCore needs its own context (the workspace is attached to it)')
 
     # -- forward -------------------------------------------------------------------------------------------
     def sample(self, ws, jitter):
@@ -258,10 +263,18 @@ class RenderCore:
         if priors is not None:
             # fused step: the sample-level priors (eikonal, deformation) are differentiated inside the geometry backward
             w_eik, w_dyn, ls, loss_out, batch_norm = priors
-            ops.geometry_bwd_priors(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
-                                    ws.g_alpha, ws.g_gradient, w_eik, w_dyn, ls, 1, ws.g_warp_out, ws.g_pts, ws.g_view_s,
-                                    sdf_ab_grad, loss_out, batch_norm)
+            if self.ordered:
+                ops.geometry_bwd_priors_ordered(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap,
+                                                inv_s, ws.g_alpha, ws.g_gradient, w_eik, w_dyn, ls, 1, ws.g_warp_out, ws.g_pts,
+                                                ws.g_view_s, sdf_ab_grad, loss_out, batch_norm, self.ctx)
+            else:
+                ops.geometry_bwd_priors(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
+                                        ws.g_alpha, ws.g_gradient, w_eik, w_dyn, ls, 1, ws.g_warp_out, ws.g_pts, ws.g_view_s,
+                                        sdf_ab_grad, loss_out, batch_norm)
         else:
+            if self.ordered:
+                raise ValueError('an ordered RenderCore differentiates the fused step only (priors=...): the separate '
+                                 'geometry backward keeps its float atomics')
             if g_gradient_ext is not None:
                 g_gradient_ext(ws)      # callable adding loss terms into ws.g_gradient etc.
             ops.geometry_bwd(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
@@ -282,20 +295,51 @@ class TrainEngine:
 
     def __init__(self, cfg: SceneConfig, n_views, H, W, n_rand, device='cuda', lr_pose=1e-3, lr_pose_end=1e-4,
                  pose_iters=1, lrate_decay=10, loss_scale=0.1, weight_main=1.0, weight_tv_k0=0.01, weight_mask=0.1,
-                 fix_first=True, capacity=None, x_slab=None, dist_ctx=None, deterministic_scatter=False, options=None):
-        """deterministic_scatter: the k0 gradient is accumulated per voxel in sample order (sorted scatter, ~0.2 ms instead of
+                 fix_first=True, capacity=None, x_slab=None, dist_ctx=None, deterministic_scatter=False, options=None,
+                 deterministic=False):
+        """deterministic: bit-reproducible train step.  Implies deterministic_scatter and additionally replaces every other
+        floating-point sum of the object-branch step that feeds a parameter update and depends on the order in which work-groups
+        or lanes finish - the weight and bias gradients of both MLPs, their thin layers, the alpha / beta gradient of the geometry
+        backward, the pose gradient of the ray backward - by per-work-group (per-ray) partial sums in a workspace and a reduction
+        in a fixed order (ops.ordered_attach; sized by ops.ordered_workspace, allocated at the first step and kept).
+        GUARANTEE: for a fixed build, fixed option values, fixed shapes and the same device model, identical inputs (state,
+        ray_idx, jitter, global_step sequence) give bit-identical k0, k0_m, k0_v, flat.data, flat.m, flat.v, se3, se3_m, se3_v
+        after every step.  It is NOT a promise of equal bits across different mlp_wgs values, builds or chips, and it covers the
+        single-GPU object branch only: the scene branch (joint.DualBranchEngine) and multi-rank runs (dist) work with such an
+        engine but keep their own atomics and reductions.  The reported scalars (ws.loss_out, ws.tv_out) stay on float atomics:
+        they feed no update and may differ in the last bits between runs.
+        The engine then always owns a private context (the host's default context's values + `options`).  Only the default,
+        split-precision layer-fused MLP kernels have ordered flushes: options mlp_fused = 0, mlp_split without bits 2, 8 and 16
+        (e.g. mlp_split = 0), side_stream = 1 and wgrad_side_wgs != 0 are refused with ValueError.  Off (default): nothing
+        changes - same kernels, same launches.
+        deterministic_scatter: the k0 gradient is accumulated per voxel in sample order (sorted scatter, ~0.2 ms instead of
         0.04 ms per step) instead of by float atomics - bit-identical gradient grids for identical inputs, and bit-identical
         replicas in the multi-GPU "samples" mode without the periodic re-broadcast.
         options: {name: value} of a PRIVATE pp_context for this engine's kernels (e.g. {'mlp_split': 0}: every MLP product on the
         fp32 MFMA instructions); None = the host's default context.  Engines with different options coexist in one process."""
         self.cfg, self.dev = cfg, torch.device(device)
+        self.deterministic = bool(deterministic)
+        if self.deterministic:
+            from . import _lib
+            opts = dict(_lib.default_context().options(), **(options or {}))
+            refused = [('mlp_fused = 0: the layer-by-layer kernels', opts['mlp_fused'] != 1),
+                       (f"mlp_split = {opts['mlp_split']} (bits 2, 8 and 16 are needed): the fp32-instruction kernels",
+                        opts['mlp_split'] & 26 != 26),
+                       ('side_stream = 1: the deferred weight-gradient launches', opts['side_stream'] != 0),
+                       ('wgrad_side_wgs != 0: the side-stream launches it sizes', opts['wgrad_side_wgs'] != 0)]
+            for what, bad in refused:
+                if bad:
+                    raise ValueError(f'deterministic=True with {what} have no ordered gradient flush (they keep float atomics)')
+            options = opts
+            deterministic_scatter = True
         self.ctx = ops.Context(**options) if options else None
         self.deterministic_scatter = bool(deterministic_scatter)
         self._scatter_work = None
+        self._ordered_work = None
         self.V, self.H, self.W, self.N = n_views, H, W, n_rand
         cap = capacity or n_rand * cfg.n_samples
         self.ws = Workspace(n_rand, cap, self.dev, ctx=self.ctx)
-        self.core = RenderCore(cfg, ctx=self.ctx)
+        self.core = RenderCore(cfg, ctx=self.ctx, ordered=self.deterministic)
         X, Y, Z = cfg.world_size
         f = dict(dtype=torch.float32, device=self.dev)
         self.k0 = [torch.zeros(X, Y, Z, cfg.k0_dim, **f), torch.zeros(X, Y, Z, cfg.k0_dim, **f)]   # ping-pong
@@ -383,6 +427,17 @@ class TrainEngine:
             self._scatter_work = torch.empty(need, dtype=torch.uint8, device=self.dev)
         return self._scatter_work
 
+    def ordered_work(self):
+        """Workspace of the ordered gradient flushes (deterministic=True): allocated on first use for this engine's shapes, attached
+        to its context and kept."""
+        mlp_wgs = self.ctx.get('mlp_wgs')
+        wgs = max(16, mlp_wgs) if mlp_wgs > 0 else torch.cuda.get_device_properties(self.dev).multi_processor_count
+        need = ops.ordered_workspace(wgs, self.ws.cap, self.N)
+        if self._ordered_work is None or self._ordered_work.numel() < need:
+            self._ordered_work = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            ops.ordered_attach(self.ctx, self._ordered_work, wgs, self.ws.cap, self.N)
+        return self._ordered_work
+
     def zero_grads(self):
         self.k0_grad.zero_()
         self.k0_touched.zero_()
@@ -394,6 +449,8 @@ class TrainEngine:
         """pose -> rays -> forward -> losses -> full backward.  Gradients are accumulated into k0_grad / flat.grad /
         se3_grad (which must be zero on entry)."""
         cfg, ws, sc = self.cfg, self.ws, self.cfg.pp
+        if self.deterministic:
+            self.ordered_work()
         ops.pose_fwd(self.se3, self.w2c_init, self.refine_mask, self.w2c, self.c2w, self.jac)
         ops.raygen_select_fwd(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, True, self.images, self.masks,
                               ws.rays_o, ws.rays_d, ws.viewdirs, ws.target, ws.mask_px)
@@ -441,9 +498,14 @@ class TrainEngine:
                            priors=(1.0, w_dyn, ls, ws.loss_out, batch_norm),
                            after_k0_grad=after_k0, defer_join=True)
         ctx = self.ctx
-        ops.raygen_select_bwd(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, ws.rays_o, ws.rays_d,
-                              ws.t_min, ws.ray_start, ws.g_pts, ws.step, ws.g_view_s, None, None, None, None, None, None,
-                              None, self.c2w_grad)
+        if self.deterministic:
+            ops.raygen_select_bwd_ordered(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, ws.rays_o, ws.rays_d,
+                                          ws.t_min, ws.ray_start, ws.g_pts, ws.step, ws.g_view_s, None, None, None, None, None,
+                                          None, None, self.c2w_grad, ctx)
+        else:
+            ops.raygen_select_bwd(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, ws.rays_o, ws.rays_d,
+                                  ws.t_min, ws.ray_start, ws.g_pts, ws.step, ws.g_view_s, None, None, None, None, None, None,
+                                  None, self.c2w_grad)
         ops.pose_bwd(self.jac, self.c2w_grad, self.se3_grad)
         ops.context_join(ctx)           # the warp net's weight gradients (side stream) before anything reads flat.grad
         ops.mlp_pack_invalidate(ctx)

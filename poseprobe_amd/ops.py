@@ -172,6 +172,42 @@ def geometry_bwd_priors(sc, sdf_grid, sdf_ab, pts, warp_out, viewdirs, ray_id, c
               _f(loss_out), _f(batch_norm), _stream())
 
 
+# ------------------------------------------------------------------------------------------- ordered gradient flushes
+def ordered_workspace(work_groups, capacity, n_rays):
+    """Bytes of the ordered-flush workspace (pp_ordered_workspace): work_groups = the largest persistent grid the MLP kernels
+    will use (the device's compute-unit count, or option mlp_wgs when set)."""
+    b = ctypes.c_int64()
+    _lib.call('pp_ordered_workspace', int(work_groups), int(capacity), int(n_rays), ctypes.byref(b))
+    return b.value
+
+
+def ordered_attach(ctx, work, work_groups, capacity, n_rays):
+    """Record `work` (uint8 tensor of ordered_workspace(...) bytes; None = detach) in `ctx` (an _lib.Context, required): the MLP
+    backward calls handed this context, geometry_bwd_priors_ordered and raygen_select_bwd_ordered then add the parameter
+    gradients up in a fixed order instead of by float atomics.  The caller keeps `work` alive while such calls are in flight."""
+    if ctx is None:
+        raise ValueError('ordered_attach needs a context of its own (the default context is shared by everybody)')
+    _lib.call('pp_ordered_attach', ctx.handle, _u8(work), 0 if work is None else int(work.numel()), int(work_groups),
+              int(capacity), int(n_rays))
+
+
+def geometry_bwd_priors_ordered(sc, sdf_grid, sdf_ab, pts, warp_out, viewdirs, ray_id, count, capacity, inv_s, g_alpha, g_gradient,
+                                w_eikonal, w_deform, loss_scale, accumulate, warp_out_grad, pts_grad, vgrad_s, sdf_ab_grad, loss_out,
+                                batch_norm, ctx):
+    _lib.call('pp_geometry_bwd_priors_ordered', ctypes.byref(sc), _f(sdf_grid), _f(sdf_ab), _f(pts), _f(warp_out), _f(viewdirs),
+              _i(ray_id), _i(count), capacity, float(inv_s), _f(g_alpha), _f(g_gradient), float(w_eikonal), float(w_deform),
+              float(loss_scale), int(accumulate), _f(warp_out_grad), _f(pts_grad), _f(vgrad_s), _f(sdf_ab_grad),
+              _f(loss_out), _f(batch_norm), ctx.handle, _stream())
+
+
+def raygen_select_bwd_ordered(sc, ray_idx, c2w, intr, H, W, inverse_y, rays_o, rays_d, t_min, ray_start, pts_grad, step,
+                              vgrad_s, g_o, g_d, g_v, g_depth, g_o_out, g_d_out, g_v_out, c2w_grad, ctx):
+    _lib.call('pp_raygen_select_bwd_ordered', ctypes.byref(sc), _i(ray_idx), rays_o.shape[0], _f(c2w), _f(intr), c2w.shape[0],
+              H, W, int(inverse_y), _f(rays_o), _f(rays_d), _f(t_min), _i(ray_start), _f(pts_grad), _f(step),
+              _f(vgrad_s), _f(g_o), _f(g_d), _f(g_v), _f(g_depth), _f(g_o_out), _f(g_d_out), _f(g_v_out),
+              _f(c2w_grad), ctx.handle, _stream())
+
+
 def k0_pack_samples(pts, feat_grad, count, capacity, k0_dim, packed):
     _lib.call('pp_k0_pack_samples', _f(pts), _f(feat_grad), _i(count), capacity, int(k0_dim), _f(packed), _stream())
 
