@@ -225,7 +225,8 @@ int pp_color_feat_bwd(const pp_scene* sc, const float* k0_cl, const float* pts, 
  * Names (meaning and ranges: csrc/pp_common.h, csrc/pp_error.hip):
  *   arithmetic   mlp_split (bit mask: object-branch MLP kernels as 3 fp16 products per fp32 product; 0 = fp32 MFMA instructions),
  *                nerf_split (scene branch likewise), mlp_fused, nerf_chain
- *   scheduling   side_stream, mlp_wgs, wgrad_side_wgs, grid_chunks, nerf_chain_nw, nerf_chain_head, mlp_pack (see pp_mlp_pack)
+ *   scheduling   side_stream, mlp_wgs, wgrad_side_wgs, grid_chunks, nerf_chain_nw, nerf_chain_head, mlp_pack (see pp_mlp_pack),
+ *                warp_lean (see pp_warp_lean_begin)
  * pp_nerf_fwd and pp_nerf_bwd of one pass (and the two stages of a two-stage backward) must see the same option values.
  * Unknown names / out-of-range values are refused; pp_context_get_option(NULL, ...) reads the defaults. */
 int pp_context_create(void** ctx);
@@ -303,6 +304,26 @@ int pp_rgbnet_bwd_weights(const float* feat, const float* acts, const float* scr
 int pp_mlp_pack_workspace(int64_t* pack_floats);
 int pp_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, void* ctx, void* stream);
 int pp_mlp_pack_invalidate(void* ctx);
+
+/* Lean scope of the warp net (option warp_lean, default 1).  Two of the per-sample blocks that the warp net's three kernels
+ * exchange through `acts` and `scratch` can be rebuilt by their only reader, the weight-gradient kernel, from a few bytes:
+ *   - the tangent rows of X0 (rows 4 s + 1 .. 4 s + 3 of acts slot 0) are  X0[4 s][n] > 0 ? W0[n][i] : 0;
+ *   - Ybar3 (scratch slot 0) is  X3[4 s][n] > 0 ? sum_j W4[j][n] * out_range * out_grad[s][r][j] : 0.
+ * pp_warp_lean_begin records `acts`, `scratch` and `params` in `ctx` (required); until pp_warp_lean_end(ctx), or the next
+ * pp_warp_lean_begin, calls of pp_warp_fwd / pp_warp_bwd / pp_warp_bwd_data / pp_warp_bwd_weights with THAT context and exactly
+ * THOSE acts (and scratch) pointers use the LEAN IMAGE of the two buffers:
+ *   acts     slot 0: only the primal rows 4 s are written, the tangent rows are left untouched; slots 1 - 3 as always.
+ *   scratch  slot 0: floats [0, 16 M) hold out_range * out_grad[s][r][j] at 16 s + 4 r + j, the rest of the slot is left
+ *            untouched; slots 1 and 2 (Ybar2, Ybar1) as always.
+ * out, pts_grad and everything else the data-path kernels write are bit-identical to the full form; the weight gradients of the
+ * hidden layers agree with it to fp32 rounding.  All calls of one pass (forward, data gradients, weight gradients; one-shot or
+ * staged) must be made inside one scope, with the recorded params: the weight-gradient stage reads W0 and W4 from that block.
+ * A call with ctx = NULL, with another context or with any other acts / scratch pointer takes the full form, untouched, as does
+ * every call after pp_warp_lean_end.  Only the split-precision kernels have a lean form: pp_warp_lean_begin records nothing
+ * unless options mlp_fused = 1 and mlp_split bits 1, 2 and 16 are set, or when option warp_lean = 0.  Neither call launches
+ * anything; ordered flushes (pp_ordered_attach) and the weight pack work inside a scope as outside. */
+int pp_warp_lean_begin(const float* acts, const float* scratch, const float* params, void* ctx);
+int pp_warp_lean_end(void* ctx);
 
 /* ---------------------------------------------------------------- ordered gradient flushes: a bit-reproducible train step.
  * By default the parameter gradients of the object branch are accumulated with float atomics wherever several work-groups (or

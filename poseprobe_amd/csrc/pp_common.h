@@ -30,6 +30,8 @@ enum PPOption {
   PP_OPT_NERF_CHAIN_HEAD,      // scene branch: 1 = the colour head's hidden layer as a ninth stage of the fused forward chain
   PP_OPT_MLP_PACK,             // 1: the split-precision object-branch MLP kernels read a weight pack recorded in the context by pp_mlp_pack
                                // for the params pointer they are given, 0: they always derive it in their prologues
+  PP_OPT_WARP_LEAN,            // 1: pp_warp_lean_begin records a lean scope (the warp net's kernels then leave out what the weight-gradient
+                               // kernel can rebuild), 0: it records nothing - every call takes the full form (A/B runs)
   PP_OPT_COUNT
 };
 
@@ -45,6 +47,10 @@ struct PPContext {
   // ([0] warp net, [1] rgbnet); pack == nullptr: none
   const float* pack;
   const float* pack_params[2];
+  // lean scope of the warp net (pp_warp_lean_begin): the buffers and the parameter block it was opened for; lean_acts == nullptr: none
+  const float* lean_acts;
+  const float* lean_scratch;
+  const float* lean_params;
   // workspace of the ordered gradient flushes (pp_ordered_attach, pp_ordered.h) and the sizes it was attached for;
   // ord == nullptr: none, every flush uses float atomics
   float* ord;

@@ -21,7 +21,7 @@ static const PPOptionDef g_opt_def[PP_OPT_COUNT] = {
     {"mlp_fused", 1, 0, 1},          {"grid_chunks", 0, 0, 4096},  {"nerf_split", 1, 0, 1},
     {"mlp_split", 31, 0, 31},        {"mlp_wgs", 0, 0, 4096},      {"wgrad_side_wgs", 0, 0, 4096},
     {"side_stream", 0, 0, 1},        {"nerf_chain", 3, 0, 3},      {"nerf_chain_nw", 4, 4, 8},
-    {"nerf_chain_head", 1, 0, 1},    {"mlp_pack", 1, 0, 1},
+    {"nerf_chain_head", 1, 0, 1},    {"mlp_pack", 1, 0, 1},        {"warp_lean", 1, 0, 1},
 };
 // compiled-in defaults: constants, never written after static initialisation
 static const struct PPDefaults {
@@ -58,6 +58,7 @@ extern "C" int pp_context_create(void** ctx) {
   c->pending = 0;
   c->pack = nullptr;
   c->pack_params[0] = c->pack_params[1] = nullptr;
+  c->lean_acts = c->lean_scratch = c->lean_params = nullptr;
   c->ord = nullptr;
   c->ord_wgs = c->ord_cap = c->ord_rays = 0;
   *ctx = c;

@@ -300,6 +300,37 @@ static const float* mlp_pack_for(const void* ctx, const float* params, int net) 
   return c->pack;
 }
 
+// Lean scope of the warp net (pp_warp_lean_begin): a call takes the lean form only with the context that holds the record, for
+// exactly the recorded buffers (scratch == nullptr: the forward pass, which has none) and while all three kernels are the
+// split-precision ones - the other paths cannot honour a lean image.  Returns the recorded params pointer (the block the scope's
+// calls are made with: the weight-gradient stage, which is not handed one, reads W0 and W4 from it), or nullptr = full form.
+static bool warp_lean_capable() { return mlp_fused_enabled() && (pp_opt(PP_OPT_MLP_SPLIT) & (1 | 2 | 16)) == (1 | 2 | 16); }
+static const float* warp_lean_for(const void* ctx, const float* acts, const float* scratch) {
+  const PPContext* c = static_cast<const PPContext*>(ctx);
+  if (!c || !c->lean_acts || c->lean_acts != acts || (scratch && c->lean_scratch != scratch) || !warp_lean_capable()) return nullptr;
+  return c->lean_params;
+}
+
+extern "C" int pp_warp_lean_end(void* ctx) {
+  PP_REQUIRE(ctx, "null context");
+  PPContext* c = static_cast<PPContext*>(ctx);
+  c->lean_acts = c->lean_scratch = c->lean_params = nullptr;
+  return PP_OK;
+}
+
+extern "C" int pp_warp_lean_begin(const float* acts, const float* scratch, const float* params, void* ctx) {
+  PPOptScope scope(ctx);
+  PP_REQUIRE(ctx, "null context (the scope is recorded in a context: create one)");
+  PP_REQUIRE(acts && scratch && params, "null pointer");
+  pp_warp_lean_end(ctx);
+  if (pp_opt(PP_OPT_WARP_LEAN) != 1 || !warp_lean_capable()) return PP_OK;
+  PPContext* c = static_cast<PPContext*>(ctx);
+  c->lean_acts = acts;
+  c->lean_scratch = scratch;
+  c->lean_params = params;
+  return PP_OK;
+}
+
 // Ordered flushes (pp_ordered_attach): with a workspace recorded in the call's context the parameter gradients of the backward
 // chains are added up in a fixed order instead of by float atomics.  Only the split-precision layer-fused kernels have that
 // path, and only on the caller's stream: everything else is refused while a workspace is attached rather than left on atomics.
@@ -414,7 +445,7 @@ static bool warp_bwd_stage1(const float* params, const float* pts, const float* 
                             hipStream_t st) {
   const bool sb = (pp_opt(PP_OPT_MLP_SPLIT) & 2) != 0;
   if (sb) pp_launch_warp_fused_bwd_s(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st,
-                                     mlp_pack_for(ctx, params, 0), ordered_part(ctx, 2));
+                                     mlp_pack_for(ctx, params, 0), ordered_part(ctx, 2), warp_lean_for(ctx, acts, scratch) != nullptr);
   else pp_launch_warp_fused_bwd(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st);
   return sb;
 }
@@ -422,10 +453,13 @@ static void warp_bwd_stage2(const float* acts, const float* scratch, const int32
                             hipStream_t ws, int side_wgs, const void* ctx) {
   const int rcap = capacity * 4;
   const size_t LS = (size_t)rcap * 128;
+  // inside a lean scope slot 0 of `scratch` holds the output gradients and X0 only its primal rows: the kernel rebuilds the rest
+  const float* lp = warp_lean_for(ctx, acts, scratch);
+  const WgradLean lean{acts + 3 * LS, lp ? lp + WPF_W4 : nullptr, lp ? lp + WPF_W0 : nullptr};
   pp_launch_wgrad_chain(scratch, acts + 2 * LS, params_grad + WPF_W3, scratch + LS, acts + LS, params_grad + WPF_W2,
                         scratch + 2 * LS, acts, params_grad + WPF_W1, 128, count, 4, rcap, ws,
                         sb ? params_grad + WPF_B3 : nullptr, sb ? params_grad + WPF_B2 : nullptr, sb ? params_grad + WPF_B1 : nullptr,
-                        side_wgs, ordered_part(ctx, 0));
+                        side_wgs, ordered_part(ctx, 0), lp ? &lean : nullptr);
 }
 static bool rgb_bwd_stage1(const float* params, const float* acts, const float* rgb, const float* rgb_grad, const int32_t* count,
                            int capacity, float* scratch, float* params_grad, float* feat_grad, float* logit_grad, int lg_ld,
@@ -522,7 +556,9 @@ extern "C" int pp_warp_fwd(const float* params, const float* pts, const int32_t*
              "acts may be NULL (forward only) only with the split-precision forward kernel (option mlp_split bit 1)");
   hipStream_t st = pp_stream(stream);
   if (mlp_fused_enabled()) {
-    if (pp_opt(PP_OPT_MLP_SPLIT) & 1) pp_launch_warp_fused_fwd_s(params, pts, count, capacity, out_range, acts, out, st, mlp_pack_for(ctx, params, 0));
+    if (pp_opt(PP_OPT_MLP_SPLIT) & 1)
+      pp_launch_warp_fused_fwd_s(params, pts, count, capacity, out_range, acts, out, st, mlp_pack_for(ctx, params, 0),
+                                 acts && warp_lean_for(ctx, acts, nullptr) != nullptr);
     else pp_launch_warp_fused_fwd(params, pts, count, capacity, out_range, acts, out, st);
     PP_CHECK_LAUNCH();
     return PP_OK;

@@ -32,18 +32,28 @@ struct WgradOperands {
   float* Wbar;         // [128][KX]
   float* bbar;         // [128] or nullptr: += column sums of Y (every row, or the primal rows of the 4-row form)
 };
+// what the lean form of the warp net's chain (pp_warp_lean_begin) needs beside the operands: layer A's Y then holds the 16 output
+// gradients per sample and Ybar3 is rebuilt from them, W4 and the gate; layer C's tangent rows of X0 are rebuilt from W0
+struct WgradLean {
+  const float* gate3;  // X3 [R][128]: its primal rows gate the rebuilt Ybar3
+  const float* w4;     // W4 [4][128]
+  const float* w0;     // W0 [128][3]
+};
 int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                             const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                            hipStream_t st, float* bA, float* bB, float* bC, int wgs = 0, float* part = nullptr);
+                            hipStream_t st, float* bA, float* bB, float* bC, int wgs = 0, float* part = nullptr,
+                            const WgradLean* lean = nullptr);
 // split-precision variants (pp_mlp_split.hip, option "mlp_split"): same contracts.  pack: the weight pack written by
 // pp_launch_mlp_pack FOR THESE params (pp_mlp_pack.h), or nullptr = the kernel derives the same quantities in its prologue.
 // part (backward kernels, weight-gradient chain): this launch's region of the ordered-flush workspace (pp_ordered.h) - the
 // parameter gradients are then added up in a fixed order by a reduction launched behind the kernel; nullptr = float atomics
+// lean (warp net, pp_warp_lean_begin): the forward kernel leaves the tangent rows of X0 unwritten, the backward kernel writes the
+// scaled output gradients to the start of `ybar` instead of Ybar3
 int pp_launch_warp_fused_fwd_s(const float* params, const float* pts, const int32_t* count, int capacity, float out_range,
-                               float* acts, float* out, hipStream_t st, const float* pack);
+                               float* acts, float* out, hipStream_t st, const float* pack, bool lean = false);
 int pp_launch_warp_fused_bwd_s(const float* params, const float* pts, const float* acts, const float* out_grad,
                                const int32_t* count, int capacity, float out_range, float* ybar, float* params_grad,
-                               float* pts_grad, hipStream_t st, const float* pack, float* part = nullptr);
+                               float* pts_grad, hipStream_t st, const float* pack, float* part = nullptr, bool lean = false);
 int pp_launch_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, hipStream_t st);
 // weight gradients of three layers (Y_l^T X_l accumulated into W_l) in one persistent kernel; kxc = width of X of layer C;
 // bA / bB / bC: also accumulate the bias gradients = column sums of Y over the primal rows (kxc == 128: the warp net's 4-row
@@ -51,7 +61,7 @@ int pp_launch_mlp_pack(const float* warp_params, const float* rgbnet_params, flo
 int pp_launch_wgrad_chain(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                           const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
                           hipStream_t st, float* bA = nullptr, float* bB = nullptr, float* bC = nullptr, int wgs = 0 /* 0: one per CU */,
-                          float* part = nullptr /* split-precision kernel only */);
+                          float* part = nullptr /* split-precision kernel only */, const WgradLean* lean = nullptr /* likewise */);
 
 // parameter block of rgbnet (64-wide padded input): W0[128x64] b0 | W1[128x128] b1 | W2[128x128] b2 | W3[3x128] b3
 #define RGF_W0 0

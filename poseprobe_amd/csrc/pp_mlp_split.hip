@@ -283,7 +283,9 @@ __device__ __forceinline__ float slot_get(const unsigned* slot) { return __uint_
 // ------------------------------------------------------------------------------------------------ warp net, forward
 // Same contract as k_warp_fused_fwd: pts[M][3] -> out[M][4][4], hidden activations X0..X3 ([4M][128] fp32 each) for backward.
 // PACK: the prologue reads the hidden layers' registers and every scalar from the weight pack instead of deriving them
-template <bool PACK>
+// LEAN: the tangent rows of X0 (rows 1-3 of every sample: gate0[n] * W0[n][i]) are NOT stored - the quad's three tangent lanes skip
+// their stores and leave those rows of `acts` untouched; the weight-gradient kernel rebuilds them (pp_warp_lean_begin)
+template <bool PACK, bool LEAN>
 __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restrict__ params, const float* __restrict__ pts,
                                                           const int32_t* __restrict__ count, int capacity, float out_range,
                                                           float* __restrict__ acts, float* __restrict__ out,
@@ -401,14 +403,14 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
     const float inv0 = pow2(-(ein + ew0)), ninv0 = pow2(-e0);
     HalfEpilogue<4, true> ea;          // epilogue state of the half that is being written out
     ea.begin(brow(3));
-    ea.all(acc0, inv0, sc0, ok0, crow, arow0);
+    ea.all(acc0, inv0, sc0, ok0 && (!LEAN || primal), crow, arow0);
     slot_max(&Mx[par][0], ea.vmax(ninv0), lane);
     __syncthreads();
     if (tid < 8) Mx[par ^ 1][tid] = 0u;                   // the next tile's slots (last read a tile ago)
     // ---- stage A1: layer 1 on half 0  ||  epilogue of (layer 0, half 1)
     zero16(acc0);
     ea.begin(brow(3));
-    mma_half(&At[0][0], w1, acc0, l31, lh, [&](int ks) { ea.step(ks, acc1, inv0, sc0, ok1, crow + 32 * 128, arow0 + 32 * LDH2); });
+    mma_half(&At[0][0], w1, acc0, l31, lh, [&](int ks) { ea.step(ks, acc1, inv0, sc0, ok1 && (!LEAN || primal), crow + 32 * 128, arow0 + 32 * LDH2); });
     slot_max(&Mx[par][1], ea.vmax(ninv0), lane);
     park(par ^ 1, pnext);                                  // next tile's positions (read after >= 3 barriers)
     __syncthreads();
@@ -490,10 +492,13 @@ static void launch_pack_variant(void (*with_pack)(P...), void (*without)(P...), 
 }
 
 int pp_launch_warp_fused_fwd_s(const float* params, const float* pts, const int32_t* count, int capacity, float out_range,
-                               float* acts, float* out, hipStream_t st, const float* pack) {
+                               float* acts, float* out, hipStream_t st, const float* pack, bool lean) {
   const int ntiles = pp_div_up(capacity, 16);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
-  launch_pack_variant(k_warp_fused_fwd_s<true>, k_warp_fused_fwd_s<false>, grid, st, pack, params, pts, count, capacity, out_range, acts, out);
+  if (lean)
+    launch_pack_variant(k_warp_fused_fwd_s<true, true>, k_warp_fused_fwd_s<false, true>, grid, st, pack, params, pts, count, capacity, out_range, acts, out);
+  else
+    launch_pack_variant(k_warp_fused_fwd_s<true, false>, k_warp_fused_fwd_s<false, false>, grid, st, pack, params, pts, count, capacity, out_range, acts, out);
   return 0;
 }
 
@@ -613,7 +618,9 @@ struct HalfEpilogueB {
 
 }  // namespace
 
-template <bool PACK>
+// LEAN: Ybar3 is NOT stored.  Instead the tile's 16 output gradients per sample, times out_range, go to the start of `ybar`
+// (float 16 s + 4 r + j: 64 B per sample, contiguous); the weight-gradient kernel rebuilds Ybar3 from them (pp_warp_lean_begin)
+template <bool PACK, bool LEAN>
 __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restrict__ params, const float* __restrict__ pts,
                                                           const float* __restrict__ acts, const float* __restrict__ out_grad,
                                                           const int32_t* __restrict__ count, int capacity, float out_range,
@@ -742,12 +749,13 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
     out_layer(b, 0, sg, a0);
     out_layer(b, 1, sg, a1);
     HalfEpilogueB<true> eb;
-    float* crow = ybar + (size_t)(r0 + l31) * 128 + fb;
+    float* crow = LEAN ? nullptr : ybar + (size_t)(r0 + l31) * 128 + fb;
+    if (LEAN && t * 16 + (tid >> 4) < M) ybar[(size_t)t * 256 + tid] = G[b][tid] * out_range;
     eb.begin(&XS[(4 * pr) * 128 + fb]);
     eb.all(a0, inv, s3, r0 + l31 < R, crow, &At[0][l31 * LDH2 + fb]);
     slot_max(&Mx[b][0], eb.vmax(n3), lane);
     eb.begin(&XS[(32 + 4 * pr) * 128 + fb]);
-    eb.all(a1, inv, s3, r0 + 32 + l31 < R, crow + 32 * 128, &At[0][(32 + l31) * LDH2 + fb]);
+    eb.all(a1, inv, s3, r0 + 32 + l31 < R, LEAN ? nullptr : crow + 32 * 128, &At[0][(32 + l31) * LDH2 + fb]);
     slot_max(&Mx[b][1], eb.vmax(n3), lane);
     e3n0 = e3; e3n1 = e3;
   };
@@ -916,11 +924,15 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
 
 int pp_launch_warp_fused_bwd_s(const float* params, const float* pts, const float* acts, const float* out_grad,
                                const int32_t* count, int capacity, float out_range, float* ybar, float* params_grad,
-                               float* pts_grad, hipStream_t st, const float* pack, float* part) {
+                               float* pts_grad, hipStream_t st, const float* pack, float* part, bool lean) {
   const int ntiles = pp_div_up(capacity, 16);
   const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
-  launch_pack_variant(k_warp_fused_bwd_s<true>, k_warp_fused_bwd_s<false>, grid, st, pack, params, pts, acts, out_grad, count, capacity,
-                      out_range, ybar, params_grad, pts_grad, part);
+  if (lean)
+    launch_pack_variant(k_warp_fused_bwd_s<true, true>, k_warp_fused_bwd_s<false, true>, grid, st, pack, params, pts, acts, out_grad, count,
+                        capacity, out_range, ybar, params_grad, pts_grad, part);
+  else
+    launch_pack_variant(k_warp_fused_bwd_s<true, false>, k_warp_fused_bwd_s<false, false>, grid, st, pack, params, pts, acts, out_grad, count,
+                        capacity, out_range, ybar, params_grad, pts_grad, part);
   if (part) {       // work-groups past the tile count retired at once: the rows of the first min(grid, tiles) are added up
     const OrdSegs segs{4, {512, 896, 1024, ORD_WARP_THIN_N}, {WPF_W4, WPF_W0, WPF_B0, WPF_B4}};
     pp_launch_ordered_flush(part, ORD_WARP_THIN, grid, count, capacity, 16, segs, params_grad, st);
@@ -1530,9 +1542,19 @@ __device__ __forceinline__ void wgs_active(int ntiles, int& nwg_ab, int& nwg_c) 
 }
 
 // slot: this work-group's slot of the ordered flush (pp_ordered.h), or nullptr = flush with atomics
-template <int KX, int CSTEP>
-__device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int ntiles, int wg, int nwg, unsigned char* __restrict__ img,
+// LEAN (the warp net inside a lean scope, pp_warp_lean_begin; Z: what the rebuild needs): two operands are not read whole but
+// rebuilt in registers before the tile is checked, split and converted -
+//   layer 0: L.Y holds the 16 output gradients per sample (float 4 row + j); Y[row][n] = X3[primal row][n] > 0 ?
+//            sum_j W4[j][n] * g[row][j] : 0 - eight 16-byte loads that a half-wavefront shares + the two primal rows of X3
+//   layer 2: only the primal rows of L.X (= X0) are loaded; tangent row i of a sample is X0[primal row][n] > 0 ? W0[n][i] : 0
+// (the gate predicates are those of the data-gradient kernel).  Rows of a thread are 8-aligned + a multiple of 4: two samples.
+// wls: the layer's thin weights in LDS (layer 0: W4 [4][128], layer 2: W0 [128][3]) - read at every rebuild instead of held in
+// registers, of which the matrix loop leaves none
+template <int KX, int CSTEP, bool LEAN>
+__device__ __forceinline__ void wgs_layer(const WgradOperands& L, const float* __restrict__ gate3, const float* __restrict__ wls,
+                                          int layer, int R, int ntiles, int wg, int nwg, unsigned char* __restrict__ img,
                                           float2* __restrict__ flags, float* __restrict__ slot) {
+  static_assert(!LEAN || KX == 128, "the lean form is the warp net's");
   constexpr int NB = KX / 64;            // 32-column X blocks per wavefront
   constexpr int XR = KX / 16;            // X rows per thread: 8 (KX = 128) or 4 (KX = 64)
   constexpr int XC = KX / 4;             // threads per X row
@@ -1554,6 +1576,8 @@ __device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int nti
   const int c4 = tid & 31, rblk = tid >> 5;                   // Y: columns 4 c4 .. 4 c4 + 3 of rows 8 rblk .. 8 rblk + 7
   const int xc4 = c4 % XC, xrow = 8 * rblk + (c4 / XC) * XR;  // X: columns 4 xc4 .. 4 xc4 + 3 of rows xrow .. xrow + XR - 1
   const bool bias = L.bbar != nullptr;
+  const bool lean_y = LEAN && layer == 0, lean_x = LEAN && layer == 2;
+  float4 rg[2];                          // lean_y: primal rows of X3 of this thread's two samples
   f32x16 acc[2][NB];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
@@ -1569,8 +1593,44 @@ __device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int nti
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       if (i < i0 || i >= i1) continue;
-      ry[i] = *reinterpret_cast<const float4*>(L.Y + (size_t)min(r0 + 8 * rblk + i, R - 1) * 128 + c4 * 4);
-      if (i < XR) rx[i] = *reinterpret_cast<const float4*>(L.X + (size_t)min(r0 + xrow + i, R - 1) * KX + xc4 * 4);
+      if (lean_y) {
+        const size_t row = (size_t)min(r0 + 8 * rblk + i, R - 1);
+        ry[i] = *reinterpret_cast<const float4*>(L.Y + row * 4);
+        if ((i & 3) == 0) rg[i >> 2] = *reinterpret_cast<const float4*>(gate3 + row * 128 + c4 * 4);
+      } else {
+        ry[i] = *reinterpret_cast<const float4*>(L.Y + (size_t)min(r0 + 8 * rblk + i, R - 1) * 128 + c4 * 4);
+      }
+      if (i < XR && !(lean_x && (i & 3) != 0))
+        rx[i] = *reinterpret_cast<const float4*>(L.X + (size_t)min(r0 + xrow + i, R - 1) * KX + xc4 * 4);
+    }
+  };
+  // lean form: what was loaded -> the rows the full form loads (once per step, before mask / check / convert)
+  auto rebuild = [&]() {
+    if (lean_y) {                        // w[j] = W4[j][4 c4 ..]
+      const float4 w0 = *reinterpret_cast<const float4*>(wls + c4 * 4), w1 = *reinterpret_cast<const float4*>(wls + 128 + c4 * 4),
+                   w2 = *reinterpret_cast<const float4*>(wls + 256 + c4 * 4), w3 = *reinterpret_cast<const float4*>(wls + 384 + c4 * 4);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float4 g = ry[i], q = rg[i >> 2];
+        const float y0 = fmaf(g.w, w3.x, fmaf(g.z, w2.x, fmaf(g.y, w1.x, g.x * w0.x)));
+        const float y1 = fmaf(g.w, w3.y, fmaf(g.z, w2.y, fmaf(g.y, w1.y, g.x * w0.y)));
+        const float y2 = fmaf(g.w, w3.z, fmaf(g.z, w2.z, fmaf(g.y, w1.z, g.x * w0.z)));
+        const float y3 = fmaf(g.w, w3.w, fmaf(g.z, w2.w, fmaf(g.y, w1.w, g.x * w0.w)));
+        ry[i] = make_float4(q.x > 0.f ? y0 : 0.f, q.y > 0.f ? y1 : 0.f, q.z > 0.f ? y2 : 0.f, q.w > 0.f ? y3 : 0.f);
+      }
+    }
+    if (lean_x) {                        // W0[4 c4 + c][i] at 3 c + i of the thread's twelve floats
+      const float4 a = *reinterpret_cast<const float4*>(wls + c4 * 12), b = *reinterpret_cast<const float4*>(wls + c4 * 12 + 4),
+                   c = *reinterpret_cast<const float4*>(wls + c4 * 12 + 8);
+      const float wl[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+      for (int s = 0; s < 8; s += 4) {
+        const float4 p = rx[s];
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+          rx[s + 1 + t] = make_float4(p.x > 0.f ? wl[t] : 0.f, p.y > 0.f ? wl[3 + t] : 0.f, p.z > 0.f ? wl[6 + t] : 0.f,
+                                      p.w > 0.f ? wl[9 + t] : 0.f);
+      }
     }
   };
   auto mask = [&](const WgsUnit& u) {
@@ -1628,6 +1688,7 @@ __device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int nti
   WgsUnit cur = wgs_unit(0, full, wg, nwg, ntiles, R, rem_rows, q);
   load_rows(cur.r0, 0, 8);
   PP_WAIT_VMEM();
+  if (LEAN) rebuild();
   mask(cur);
   check(flags + 4);
   __syncthreads();
@@ -1637,6 +1698,7 @@ __device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int nti
     const WgsUnit nxt = has_next ? wgs_unit(k + 1, full, wg, nwg, ntiles, R, rem_rows, q) : cur;
     if (k > 0) {
       PP_WAIT_VMEM();
+      if (LEAN) rebuild();
       mask(cur);
     }
     check(flags);
@@ -1733,12 +1795,13 @@ __device__ __forceinline__ void wgs_layer(const WgradOperands& L, int R, int nti
 
 }  // namespace
 
-template <int KXC, int CSTEP>
+template <int KXC, int CSTEP, bool LEAN>
 __global__ __launch_bounds__(256, 2) void k_wgrad_chain_s(WgradOperands LA, WgradOperands LB, WgradOperands LC,
                                                           const int32_t* __restrict__ count, int rmul, int rcap, int nwg_ab, int nwg_c,
-                                                          float* __restrict__ part) {
+                                                          float* __restrict__ part, WgradLean Z) {
   __shared__ __attribute__((aligned(1024))) unsigned char img[4 * TILE_ROWS * 256];      // Yh | Yl | Xh | Xl
   __shared__ __attribute__((aligned(16))) float2 flags[8];                                // [2 sets][4 wavefronts]
+  __shared__ __attribute__((aligned(16))) float wls[LEAN ? 512 : 4];                     // lean form: W4 (layer 0) or W0 (layer 2)
   const int R = min(count[0] * rmul, rcap);
   const int ntiles = (R + TILE_ROWS - 1) / TILE_ROWS;
   // Every work-group ends in one atomic per entry of its 128 x KX block (64 KB at 1.3 TB/s chip-wide), so the second work-group per
@@ -1754,8 +1817,13 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_chain_s(WgradOperands LA, Wgra
   // one copy of the layer code per operand width (three calls would triple the instruction footprint)
   const WgradOperands L = layer == 0 ? LA : (layer == 1 ? LB : LC);
   float* const slot = part != nullptr ? part + (size_t)bx * ORD_WGRAD_SLOT : nullptr;      // slot = work-group of the grid
-  if (KXC == 128 || layer < 2) wgs_layer<128, CSTEP>(L, R, ntiles, wg, nwg, img, flags, slot);
-  else wgs_layer<KXC, CSTEP>(L, R, ntiles, wg, nwg, img, flags, slot);
+  if (LEAN) {
+    if (layer == 0) { wls[threadIdx.x] = Z.w4[threadIdx.x]; wls[256 + threadIdx.x] = Z.w4[256 + threadIdx.x]; }
+    else if (layer == 2) { wls[threadIdx.x] = Z.w0[threadIdx.x]; if (threadIdx.x < 128) wls[256 + threadIdx.x] = Z.w0[256 + threadIdx.x]; }
+    __syncthreads();
+  }
+  if (KXC == 128 || layer < 2) wgs_layer<128, CSTEP, LEAN>(L, Z.gate3, wls, layer, R, ntiles, wg, nwg, img, flags, slot);
+  else wgs_layer<KXC, CSTEP, false>(L, Z.gate3, wls, layer, R, ntiles, wg, nwg, img, flags, slot);
 }
 
 // Ordered flush of k_wgrad_chain_s: grid (65, 3) - blockIdx.y = layer, blockIdx.x = 64 consecutive float4s of the layer's block
@@ -1796,8 +1864,9 @@ __global__ __launch_bounds__(ORD_RED_THREADS) void k_wgrad_reduce_s(WgradOperand
 
 int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                             const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                            hipStream_t st, float* bA, float* bB, float* bC, int wgs_, float* part) {
+                            hipStream_t st, float* bA, float* bB, float* bC, int wgs_, float* part, const WgradLean* lean) {
   WgradOperands LA{YA, XA, WA, bA}, LB{YB, XB, WB, bB}, LC{YC, XC, WC, bC};
+  const WgradLean Z = lean ? *lean : WgradLean{nullptr, nullptr, nullptr};
   const int ntiles = pp_div_up(rcap, TILE_ROWS);
   // persistent work-groups, two per CU over the three layers, shared out in proportion to the layers' work (wgs_ > 0: the caller's
   // number of CUs - a launch on an auxiliary stream that leaves CUs to the kernels running beside it); the kernel idles half of
@@ -1807,10 +1876,12 @@ int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const f
   int nab = kxc == 128 ? wgs / 3 : (wgs * 4) / 11, nc = kxc == 128 ? wgs / 3 : wgs - 2 * ((wgs * 4) / 11);
   if (nab > ntiles) nab = ntiles;
   if (nc > ntiles) nc = ntiles;
-  if (kxc == 128)
-    hipLaunchKernelGGL((k_wgrad_chain_s<128, 4>), dim3(2 * nab + nc), dim3(256), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc, part);
+  if (kxc == 128 && lean)
+    hipLaunchKernelGGL((k_wgrad_chain_s<128, 4, true>), dim3(2 * nab + nc), dim3(256), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc, part, Z);
+  else if (kxc == 128)
+    hipLaunchKernelGGL((k_wgrad_chain_s<128, 4, false>), dim3(2 * nab + nc), dim3(256), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc, part, Z);
   else
-    hipLaunchKernelGGL((k_wgrad_chain_s<64, 1>), dim3(2 * nab + nc), dim3(256), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc, part);
+    hipLaunchKernelGGL((k_wgrad_chain_s<64, 1, false>), dim3(2 * nab + nc), dim3(256), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc, part, Z);
   if (part) {
     if (kxc == 128)
       hipLaunchKernelGGL((k_wgrad_reduce_s<128>), dim3(65, 3), dim3(ORD_RED_THREADS), 0, st, LA, LB, LC, count, rmul, rcap, nab, nc, part);

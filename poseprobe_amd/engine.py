@@ -123,7 +123,9 @@ class Workspace:
         self.g_gradient, self.g_pts, self.g_view_s = e(capacity, 3, **f), e(capacity, 3, **f), e(capacity, 3, **f)
         self.g_grad_deform, self.g_corr, self.g_sdf_deform = e(capacity, 9, **f), e(capacity, **f), e(capacity, **f)
         self.g_warp_out = e(capacity, 16, **f)
-        self.scratch = e(wsz['warp'][1], **f)              # Ybar of the warp chain (+ transposed weights, layered path)
+        # Ybar of the warp chain (+ transposed weights, layered path).  Zeroed once, here: inside a lean scope (ops.warp_lean_begin)
+        # most of slot 0 is never written, and two engines that went through the same steps must hold the same bytes there
+        self.scratch = torch.zeros(wsz['warp'][1], **f)
         self.scratch_rgb = e(wsz['rgbnet'][1], **f)   # Ybar of rgbnet: its weight-gradient kernel may still be
         #                                                         reading it on the side stream while the warp chain runs
         self.g_rays_o, self.g_rays_d, self.g_viewdirs = e(N, 3, **f), e(N, 3, **f), e(N, 3, **f)
@@ -468,6 +470,10 @@ class TrainEngine:
         # every writer of flat.data (the optimiser, load_reference_params, a checkpoint load, an in-place copy from outside)
         # runs between two calls of this function, so no kernel can read a pack older than its parameters.
         ops.mlp_pack(P.view('warp'), P.view('rgbnet'), self.mlp_pack, self.ctx)
+        # Lean scope of the warp net, for this step's buffers and closed with the pack record: the forward kernel leaves out the
+        # tangent rows of X0, the data-gradient kernel Ybar3, and the weight-gradient kernel rebuilds both (option warp_lean)
+        if ws.warp_acts is not None:
+            ops.warp_lean_begin(ws.warp_acts, ws.scratch, P.view('warp'), self.ctx)
         self.core.forward(ws, self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w,
                           before_k0_use=None if self.dist is None else (lambda: self.dist.wait_parameters(self)))
         ws.zero_block.zero_()
@@ -509,6 +515,7 @@ class TrainEngine:
         ops.pose_bwd(self.jac, self.c2w_grad, self.se3_grad)
         ops.context_join(ctx)           # the warp net's weight gradients (side stream) before anything reads flat.grad
         ops.mlp_pack_invalidate(ctx)
+        ops.warp_lean_end(ctx)
         return s_val, w_dyn
 
     def _upload_step_scalars(self, progress):

@@ -263,6 +263,17 @@ def mlp_pack_invalidate(ctx=None):
     _lib.call('pp_mlp_pack_invalidate', _h(ctx))
 
 
+def warp_lean_begin(acts, scratch, params, ctx=None):
+    """Open a lean scope of the warp net for these buffers (pp_warp_lean_begin): until warp_lean_end, warp_fwd / warp_bwd /
+    warp_bwd_data / warp_bwd_weights called with `ctx` and exactly these tensors leave out the tangent rows of X0 and Ybar3,
+    which the weight-gradient kernel rebuilds.  Records nothing with option warp_lean = 0 or without the split-precision kernels."""
+    _lib.call('pp_warp_lean_begin', _f(acts), _f(scratch), _f(params), _h(ctx))
+
+
+def warp_lean_end(ctx=None):
+    _lib.call('pp_warp_lean_end', _h(ctx))
+
+
 def rgbnet_fwd(params, feat, count, capacity, acts, rgb, ctx=None):
     _lib.call('pp_rgbnet_fwd', _f(params), _f(feat), _i(count), capacity, _f(acts), _f(rgb), _h(ctx), _stream())
 
