@@ -39,14 +39,15 @@ typedef enum {
 
 const char* pp_last_error(void);
 /* ABI history.  1: round 1.  2: pp_loss_rays / pp_loss_samples / pp_geometry_bwd_priors gained `const float* batch_norm`
- * in front of `stream` (the library kept answering 1 for it by mistake).  3 (this header): options moved from process-wide
+ * in front of `stream` (the library kept answering 1 for it by mistake).  3: options moved from process-wide
  * pp_set_option / pp_get_option into the caller-owned pp_context, which every option-dependent entry point now takes in front
  * of `stream` (pp_rgbnet_fwd, pp_warp_fwd, pp_mlp_fwd, the four two-stage backward entry points - which also hand the bias
  * ownership from stage 1 to stage 2 explicitly -, pp_nerf_fwd / pp_nerf_bwd, pp_grid_tv_adam_step{,_sparse});
- * pp_scene gained `sdf_index_exact`; new: pp_sdf_crossing_dense_bwd, pp_context_set_option / pp_context_get_option.
+ * pp_scene gained `sdf_index_exact`; new: pp_sdf_crossing_dense_bwd, pp_context_set_option / pp_context_get_option.  4 (this header): the
+ * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
  * (poseprobe_amd/_lib.py does): the signatures changed, so a stale caller would pass a stream where a pointer is read. */
-#define PP_ABI_VERSION 3
+#define PP_ABI_VERSION 4
 int pp_abi_version(void);
 
 /* Static description of the voxel scene; mirrors the attributes Voxurf derives in __init__ /
@@ -218,14 +219,14 @@ int pp_color_feat_bwd(const pp_scene* sc, const float* k0_cl, const float* pts, 
                       int32_t capacity, const float* feat_grad, float* k0_grad_cl, float* pts_grad,
                       float* gradient_grad, float* viewdir_grad_s, void* stream);
 
-/* Caller-owned context = the option values of the calls it is handed to (+ one auxiliary HIP stream with its events, created
- * on first use).  NULL everywhere = the compiled-in defaults (the measured best on MI355X).  Options are plain integers
+/* Caller-owned context = the option values of the calls it is handed to.  NULL everywhere = the compiled-in defaults (the
+ * measured best on MI355X).  Options are plain integers
  * set by name; a call reads them from ITS context for the duration of the call only, so contexts with different arithmetic
  * coexist in one process and on concurrent threads (a context itself must not be modified while a call uses it).
  * Names (meaning and ranges: csrc/pp_common.h, csrc/pp_error.hip):
  *   arithmetic   mlp_split (bit mask: object-branch MLP kernels as 3 fp16 products per fp32 product; 0 = fp32 MFMA instructions),
  *                nerf_split (scene branch likewise), mlp_fused, nerf_chain
- *   scheduling   side_stream, mlp_wgs, wgrad_side_wgs, grid_chunks, nerf_chain_nw, nerf_chain_head, mlp_pack (see pp_mlp_pack),
+ *   scheduling   mlp_wgs, grid_chunks, nerf_chain_nw, nerf_chain_head, mlp_pack (see pp_mlp_pack),
  *                warp_lean (see pp_warp_lean_begin)
  * pp_nerf_fwd and pp_nerf_bwd of one pass (and the two stages of a two-stage backward) must see the same option values.
  * Unknown names / out-of-range values are refused; pp_context_get_option(NULL, ...) reads the defaults. */
@@ -233,12 +234,6 @@ int pp_context_create(void** ctx);
 int pp_context_destroy(void* ctx);
 int pp_context_set_option(void* ctx, const char* name, int32_t value);
 int pp_context_get_option(const void* ctx, const char* name, int32_t* value);
-/* Option side_stream = 1: the weight-gradient kernel of pp_rgbnet_bwd / pp_mlp_bwd / pp_warp_bwd is launched
- * on the context's auxiliary stream and NOT joined before the call returns, so that the caller's next (small) kernels run
- * beside it (fork / join are event edges: the sequence stays hipGraph-capturable).  Call pp_context_join before `scratch` is
- * reused, before params_grad is read, and at most 4 forks apart: it makes `stream` wait for every deferred launch issued so
- * far.  With side_stream = 0 (default) everything is strictly sequential on `stream` and pp_context_join does nothing. */
-int pp_context_join(void* ctx, void* stream);
 
 /* ---------------------------------------------------------------- MLPs on the matrix cores (fp32 MFMA).
  * rgbnet (voxurf_coarse.py:208-216, :1032-1033): 64(57)->128->128->128->3, sigmoid.
@@ -339,7 +334,7 @@ int pp_warp_lean_end(void* ctx);
  * retires on the device when `count` is small are never read: the reduction derives the same active count from `count`.
  * Only the split-precision layer-fused kernels have this path: while a workspace is attached, the MLP backward entry points
  * refuse (PP_ERR_INVALID_ARG) option values that select other kernels (mlp_fused = 0, mlp_split without bits 2 / 8 / 16, generic
- * MLP shapes) and side_stream = 1, rather than fall back to atomics.  The reported scalars (loss_out, tv_out) stay on atomics:
+ * MLP shapes), rather than fall back to atomics.  The reported scalars (loss_out, tv_out) stay on atomics:
  * they feed no update.  The k0 scatter has its own ordered form (pp_k0_scatter_samples_sorted).
  * pp_ordered_workspace: bytes (a multiple of 16) for `work_groups` = the largest persistent grid the calls will use (the device's
  * compute-unit count, or option mlp_wgs when that is set; at least 16 are assumed), sample capacity and ray count; a pure host

@@ -20,10 +20,6 @@ enum PPOption {
   PP_OPT_NERF_SPLIT,           // scene branch: every matrix product as three fp16 products (1) or on the fp32 instructions (0)
   PP_OPT_MLP_SPLIT,            // bit mask: layer-fused object-branch MLP kernels with three fp16 products per fp32 product (pp_mlp_split.hip); 1 warp fwd, 2 warp bwd, 4 rgb fwd, 8 rgb bwd, 16 weight-gradient chains
   PP_OPT_MLP_WGS,              // work-groups of the persistent object-branch MLP kernels (0 = one per CU); fewer leave CUs to a concurrent HBM-bound kernel
-  PP_OPT_WGRAD_SIDE_WGS,       // work-groups of a weight-gradient chain kernel launched on a pp_context's auxiliary stream (0 = as on the main stream):
-                               // fewer leave whole CUs to the small kernels that run beside it
-  PP_OPT_SIDE_STREAM,          // 1: the weight-gradient kernels of both object-branch MLP chains are forked onto the context's auxiliary stream
-                               // (joined by pp_context_join), 0 (default): strictly sequential on the caller's stream
   PP_OPT_NERF_CHAIN,           // scene branch: bit 1 = the eight feature layers + density head of the forward pass as one kernel with the tile resident in LDS
                                // (pp_nerf_trunk.h), 3 = the data-gradient chain of the backward pass too (0 = one GEMM per layer)
   PP_OPT_NERF_CHAIN_NW,        // scene branch: wavefronts per work-group of the fused chains (8: one 128-sample tile per CU, 4: two 64-sample tiles per CU)
@@ -35,14 +31,10 @@ enum PPOption {
   PP_OPT_COUNT
 };
 
-// Caller-owned context: the option values + (created on first use) one auxiliary HIP stream with its fork / join events.
+// Caller-owned context: the option values + three records (weight pack, lean scope, ordered-flush workspace).  It owns no HIP
+// object: every kernel runs on the stream the call is given.
 struct PPContext {
   int opt[PP_OPT_COUNT];
-  bool have_aux;
-  hipStream_t aux;
-  hipEvent_t fork[16], join[16];
-  int pending;                      // deferred side launches of the fused paths not yet joined (pp_context_join)
-  hipEvent_t dfork[4], djoin[4];
   // weight pack of the object-branch MLPs (pp_mlp_pack): the buffer and the two parameter blocks it was computed from
   // ([0] warp net, [1] rgbnet); pack == nullptr: none
   const float* pack;
@@ -56,7 +48,6 @@ struct PPContext {
   float* ord;
   int ord_wgs, ord_cap, ord_rays;
 };
-bool pp_context_aux(PPContext* c);   // creates the auxiliary stream + events on first use; false when HIP refuses
 
 // Every entry point that takes a `ctx` opens a scope over ITS options for the duration of the call on the calling thread;
 // the launch helpers below it read them through pp_opt().  Nothing outlives the call: two contexts with different

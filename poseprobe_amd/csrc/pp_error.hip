@@ -19,9 +19,9 @@ extern "C" int pp_abi_version(void) { return PP_ABI_VERSION; }
 struct PPOptionDef { const char* name; int dflt, lo, hi; };
 static const PPOptionDef g_opt_def[PP_OPT_COUNT] = {
     {"mlp_fused", 1, 0, 1},          {"grid_chunks", 0, 0, 4096},  {"nerf_split", 1, 0, 1},
-    {"mlp_split", 31, 0, 31},        {"mlp_wgs", 0, 0, 4096},      {"wgrad_side_wgs", 0, 0, 4096},
-    {"side_stream", 0, 0, 1},        {"nerf_chain", 3, 0, 3},      {"nerf_chain_nw", 4, 4, 8},
-    {"nerf_chain_head", 1, 0, 1},    {"mlp_pack", 1, 0, 1},        {"warp_lean", 1, 0, 1},
+    {"mlp_split", 31, 0, 31},        {"mlp_wgs", 0, 0, 4096},      {"nerf_chain", 3, 0, 3},
+    {"nerf_chain_nw", 4, 4, 8},      {"nerf_chain_head", 1, 0, 1}, {"mlp_pack", 1, 0, 1},
+    {"warp_lean", 1, 0, 1},
 };
 // compiled-in defaults: constants, never written after static initialisation
 static const struct PPDefaults {
@@ -54,8 +54,6 @@ extern "C" int pp_context_create(void** ctx) {
   PP_REQUIRE(ctx, "null pointer");
   PPContext* c = new PPContext;
   for (int i = 0; i < PP_OPT_COUNT; ++i) c->opt[i] = g_opt_def[i].dflt;
-  c->have_aux = false;
-  c->pending = 0;
   c->pack = nullptr;
   c->pack_params[0] = c->pack_params[1] = nullptr;
   c->lean_acts = c->lean_scratch = c->lean_params = nullptr;
@@ -65,31 +63,9 @@ extern "C" int pp_context_create(void** ctx) {
   return PP_OK;
 }
 
-bool pp_context_aux(PPContext* c) {
-  if (c->have_aux) return true;
-  if (hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) != hipSuccess) return false;
-  for (int i = 0; i < 16; ++i) {
-    hipEventCreateWithFlags(&c->fork[i], hipEventDisableTiming);
-    hipEventCreateWithFlags(&c->join[i], hipEventDisableTiming);
-  }
-  for (int i = 0; i < 4; ++i) {
-    hipEventCreateWithFlags(&c->dfork[i], hipEventDisableTiming);
-    hipEventCreateWithFlags(&c->djoin[i], hipEventDisableTiming);
-  }
-  c->have_aux = true;
-  return true;
-}
-
 extern "C" int pp_context_destroy(void* ctx) {
   if (!ctx) return PP_OK;
-  PPContext* c = static_cast<PPContext*>(ctx);
-  if (c->have_aux) {
-    hipStreamSynchronize(c->aux);
-    for (int i = 0; i < 16; ++i) { hipEventDestroy(c->fork[i]); hipEventDestroy(c->join[i]); }
-    for (int i = 0; i < 4; ++i) { hipEventDestroy(c->dfork[i]); hipEventDestroy(c->djoin[i]); }
-    hipStreamDestroy(c->aux);
-  }
-  delete c;
+  delete static_cast<PPContext*>(ctx);
   return PP_OK;
 }
 

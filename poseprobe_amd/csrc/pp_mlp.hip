@@ -233,61 +233,6 @@ __global__ __launch_bounds__(256) void k_rgb_out_bwd(const float* __restrict__ W
 // MI355X ~ 450 work-groups (more: the 64 KB of contended atomics per work-group dominates; fewer: idle CUs).
 static const int TN_WGS = 448;
 
-// ------------------------------------------------------------------------------------------------ side-stream context
-// The weight-gradient GEMM (k_gemm_tn) and the data-gradient GEMM of one layer both consume Ybar_k and are otherwise
-// independent; each keeps the matrix pipe only ~55 % busy on its own (K = 128 leaves a tile prologue / epilogue per
-// 128 MFMAs).  With a context the backward chains fork the weight-gradient GEMM onto an auxiliary HIP stream so the
-// two kernels co-reside on the CUs and fill each other's MFMA bubbles.  The context is explicit caller-owned state
-// (no globals); fork / join are event edges, so the sequence stays capturable in a hipGraph.
-// Fused paths: the weight-gradient kernel of a chain depends only on what the data-gradient kernel left in `scratch` and
-// nothing downstream needs it before the optimiser, so with a context it is launched on the auxiliary stream and NOT
-// joined here: the caller's next kernels (small, latency-bound ones: colour-feature / geometry backward, ray and pose
-// backward) run beside it, and pp_context_join() is called before the scratch buffer or the gradients are touched again.
-static hipStream_t deferred_fork(void* ctx, hipStream_t main) {
-  PPContext* c = static_cast<PPContext*>(ctx);
-  if (!c || c->opt[PP_OPT_SIDE_STREAM] == 0 || c->pending >= 4 || !pp_context_aux(c)) return main;
-  hipEventRecord(c->dfork[c->pending], main);
-  hipStreamWaitEvent(c->aux, c->dfork[c->pending], 0);
-  return c->aux;
-}
-static void deferred_forked(void* ctx, hipStream_t used, hipStream_t main) {
-  PPContext* c = static_cast<PPContext*>(ctx);
-  if (!c || used == main) return;
-  hipEventRecord(c->djoin[c->pending], c->aux);
-  ++c->pending;
-}
-
-extern "C" int pp_context_join(void* ctx, void* stream) {
-  PPContext* c = static_cast<PPContext*>(ctx);
-  if (!c || !c->have_aux) return PP_OK;
-  for (int i = 0; i < c->pending; ++i) hipStreamWaitEvent(pp_stream(stream), c->djoin[i], 0);
-  c->pending = 0;
-  return PP_OK;
-}
-
-struct SideLane {
-  PPContext* c;
-  hipStream_t main;
-  int n = 0;        // forks issued
-  int waited = 0;   // joins already waited for
-  SideLane(void* ctx, hipStream_t m) : c(static_cast<PPContext*>(ctx)), main(m) {
-    if (c && (c->opt[PP_OPT_SIDE_STREAM] == 0 || !pp_context_aux(c))) c = nullptr;
-  }
-  // stream on which the next side kernel must be launched (after everything enqueued on `main` so far)
-  hipStream_t fork() {
-    if (!c) return main;
-    hipEventRecord(c->fork[n], main);
-    hipStreamWaitEvent(c->aux, c->fork[n], 0);
-    return c->aux;
-  }
-  void forked() { if (c) { hipEventRecord(c->join[n], c->aux); ++n; } }
-  // main waits for every side kernel issued so far except the `keep` most recent ones
-  void join(int keep = 0) {
-    if (!c) return;
-    for (; waited < n - keep; ++waited) hipStreamWaitEvent(main, c->join[waited], 0);
-  }
-};
-
 // option "mlp_fused" = 0 selects the layer-by-layer kernels (A/B measurements, generic shapes always use them)
 static bool mlp_fused_enabled() { return pp_opt(PP_OPT_MLP_FUSED) == 1; }
 
@@ -333,7 +278,7 @@ extern "C" int pp_warp_lean_begin(const float* acts, const float* scratch, const
 
 // Ordered flushes (pp_ordered_attach): with a workspace recorded in the call's context the parameter gradients of the backward
 // chains are added up in a fixed order instead of by float atomics.  Only the split-precision layer-fused kernels have that
-// path, and only on the caller's stream: everything else is refused while a workspace is attached rather than left on atomics.
+// path: everything else is refused while a workspace is attached rather than left on atomics.
 // `bits`: the mlp_split bits of the kernels the call runs.  Returns the reason for a refusal, or nullptr.
 static const char* ordered_refusal(const void* ctx, int capacity, int bits, bool fused_shape = true) {
   const PPContext* c = static_cast<const PPContext*>(ctx);
@@ -341,7 +286,6 @@ static const char* ordered_refusal(const void* ctx, int capacity, int bits, bool
   if (!fused_shape || !mlp_fused_enabled() || (pp_opt(PP_OPT_MLP_SPLIT) & bits) != bits)
     return "an ordered-flush workspace is attached to the context: only the split-precision layer-fused kernels have ordered "
            "flushes (options mlp_fused = 1, mlp_split bits 2, 8 and 16; the Voxurf network shapes)";
-  if (pp_opt(PP_OPT_SIDE_STREAM) != 0) return "an ordered-flush workspace is attached to the context: option side_stream must be 0";
   if (capacity > c->ord_cap || pp_fused_wgs() > c->ord_wgs)
     return "the attached ordered-flush workspace is too small for this capacity / work-group count";
   return nullptr;
@@ -391,10 +335,9 @@ extern "C" int pp_mlp_pack(const float* warp_params, const float* rgbnet_params,
 }
 
 static const int GEMM_MAX_WG = 256 * 5;     // 5 resident work-groups per CU at BM=64 (25 KB LDS, 90 regs)
-static const int GEMM_MAX_WG_SHARED = 256 * 3;   // when a weight-gradient GEMM runs beside it (register file: 2 x 96 + 2 x 144)
-static inline int gemm_grid(int rows, int bm, bool shared = false) {
-  int t = pp_div_up(rows, bm), cap = shared ? GEMM_MAX_WG_SHARED : GEMM_MAX_WG;
-  return t < cap ? t : cap;
+static inline int gemm_grid(int rows, int bm) {
+  int t = pp_div_up(rows, bm);
+  return t < GEMM_MAX_WG ? t : GEMM_MAX_WG;
 }
 #define PP_GEMM_BM 64
 
@@ -439,7 +382,7 @@ extern "C" int pp_mlp_fwd(const float* params, const float* feat, int32_t in_ld,
 // Stage 1 of a layer-fused backward chain: the data-gradient kernel (split-precision or fp32 instructions), which also produces
 // the thin layers' gradients and leaves Ybar of the hidden layers in `scratch`.  Returns whether the hidden layers' bias
 // gradients are stage 2's to produce (the split-precision kernel leaves them to the weight-gradient kernel).
-// Stage 2: the three weight-gradient GEMMs on that Ybar, on stream `ws` with `side_wgs` work-groups (0: one per CU).
+// Stage 2: the three weight-gradient GEMMs on that Ybar, on the same stream.
 static bool warp_bwd_stage1(const float* params, const float* pts, const float* acts, const float* out_grad, const int32_t* count,
                             int capacity, float out_range, float* scratch, float* params_grad, float* pts_grad, void* ctx,
                             hipStream_t st) {
@@ -450,16 +393,16 @@ static bool warp_bwd_stage1(const float* params, const float* pts, const float* 
   return sb;
 }
 static void warp_bwd_stage2(const float* acts, const float* scratch, const int32_t* count, int capacity, float* params_grad, bool sb,
-                            hipStream_t ws, int side_wgs, const void* ctx) {
+                            hipStream_t st, const void* ctx) {
   const int rcap = capacity * 4;
   const size_t LS = (size_t)rcap * 128;
   // inside a lean scope slot 0 of `scratch` holds the output gradients and X0 only its primal rows: the kernel rebuilds the rest
   const float* lp = warp_lean_for(ctx, acts, scratch);
   const WgradLean lean{acts + 3 * LS, lp ? lp + WPF_W4 : nullptr, lp ? lp + WPF_W0 : nullptr};
   pp_launch_wgrad_chain(scratch, acts + 2 * LS, params_grad + WPF_W3, scratch + LS, acts + LS, params_grad + WPF_W2,
-                        scratch + 2 * LS, acts, params_grad + WPF_W1, 128, count, 4, rcap, ws,
+                        scratch + 2 * LS, acts, params_grad + WPF_W1, 128, count, 4, rcap, st,
                         sb ? params_grad + WPF_B3 : nullptr, sb ? params_grad + WPF_B2 : nullptr, sb ? params_grad + WPF_B1 : nullptr,
-                        side_wgs, ordered_part(ctx, 0), lp ? &lean : nullptr);
+                        ordered_part(ctx, 0), lp ? &lean : nullptr);
 }
 static bool rgb_bwd_stage1(const float* params, const float* acts, const float* rgb, const float* rgb_grad, const int32_t* count,
                            int capacity, float* scratch, float* params_grad, float* feat_grad, float* logit_grad, int lg_ld,
@@ -471,12 +414,12 @@ static bool rgb_bwd_stage1(const float* params, const float* acts, const float* 
   return sb;
 }
 static void rgb_bwd_stage2(const float* feat, const float* acts, const float* scratch, const int32_t* count, int capacity,
-                           float* params_grad, bool sb, hipStream_t ws, int side_wgs, const void* ctx) {
+                           float* params_grad, bool sb, hipStream_t st, const void* ctx) {
   const size_t FLS = (size_t)capacity * 128;
   pp_launch_wgrad_chain(scratch, acts + FLS, params_grad + RGF_W2, scratch + FLS, acts, params_grad + RGF_W1,
-                        scratch + 2 * FLS, feat, params_grad + RGF_W0, 64, count, 1, capacity, ws,
+                        scratch + 2 * FLS, feat, params_grad + RGF_W0, 64, count, 1, capacity, st,
                         sb ? params_grad + RGF_B2 : nullptr, sb ? params_grad + RGF_B1 : nullptr, sb ? params_grad + RGF_B0 : nullptr,
-                        side_wgs, ordered_part(ctx, 1));
+                        ordered_part(ctx, 1));
 }
 
 extern "C" int pp_mlp_bwd(const float* params, const float* feat, int32_t in_ld, int32_t n_gemm, const float* acts,
@@ -491,44 +434,35 @@ extern "C" int pp_mlp_bwd(const float* params, const float* feat, int32_t in_ld,
   if (in_ld == 64 && n_gemm == 3 && feat_grad && mlp_fused_enabled()) {
     const bool sb = rgb_bwd_stage1(params, acts, out, out_grad, count, capacity, scratch, params_grad, feat_grad, logit_add_grad,
                                    logit_add_ld, ctx, st);
-    hipStream_t ws = deferred_fork(ctx, st);
-    rgb_bwd_stage2(feat, acts, scratch, count, capacity, params_grad, sb, ws, ws != st ? pp_opt(PP_OPT_WGRAD_SIDE_WGS) : 0, ctx);
-    deferred_forked(ctx, ws, st);
+    rgb_bwd_stage2(feat, acts, scratch, count, capacity, params_grad, sb, st, ctx);
     PP_CHECK_LAUNCH();
     return PP_OK;
   }
-  SideLane side(ctx, st);
   const size_t LS = (size_t)capacity * 128;
   float* cur = scratch;
   float* nxt = scratch + LS;
   float* wt = scratch + 2 * LS;      // one transposed weight matrix at a time (128*128 floats)
-  dim3 g(gemm_grid(capacity, PP_GEMM_BM, side.c != nullptr)), gt(TN_WGS), b(256);
+  dim3 g(gemm_grid(capacity, PP_GEMM_BM)), gt(TN_WGS), b(256);
   const size_t oo = mlp_off_out(in_ld, n_gemm);
   hipLaunchKernelGGL(k_rgb_out_bwd, dim3(pp_div_up(capacity, STRIP)), b, 0, st, params + oo, acts + (n_gemm - 1) * LS, out,
                      out_grad, count, capacity, cur, params_grad + oo, params_grad + oo + 3 * 128, logit_add_grad,
                      logit_add_ld);
   for (int l = n_gemm - 1; l >= 1; --l) {
     const size_t ow = mlp_off_hidden(in_ld, l);
-    hipStream_t ss = side.fork();                      // weight gradient of layer l beside its data gradient
-    hipLaunchKernelGGL((k_gemm_tn<1>), gt, b, 0, ss, cur, 128, acts + (l - 1) * LS, 128, 128, params_grad + ow, 128,
+    hipLaunchKernelGGL((k_gemm_tn<1>), gt, b, 0, st, cur, 128, acts + (l - 1) * LS, 128, 128, params_grad + ow, 128,
                        params_grad + ow + 128 * 128, count, 1, capacity);
-    side.forked();
-    side.join(1);                                      // the previous layer's side GEMM still reads `nxt`
     hipLaunchKernelGGL(k_transpose, dim3(64), b, 0, st, params + ow, wt, 128, 128);
     hipLaunchKernelGGL((k_gemm128<MODE_NT, EPI_MASK, 1, PP_GEMM_BM>), g, b, 0, st, cur, 128, wt, 128, 128, 128, nullptr,
                        acts + (l - 1) * LS, 128, nxt, 128, count, 1, capacity);
     float* tmp = cur; cur = nxt; nxt = tmp;
   }
-  hipStream_t ss = side.fork();
-  hipLaunchKernelGGL((k_gemm_tn<1>), gt, b, 0, ss, cur, 128, feat, in_ld, in_ld, params_grad, in_ld,
+  hipLaunchKernelGGL((k_gemm_tn<1>), gt, b, 0, st, cur, 128, feat, in_ld, in_ld, params_grad, in_ld,
                      params_grad + (size_t)128 * in_ld, count, 1, capacity);
-  side.forked();
   if (feat_grad) {
     hipLaunchKernelGGL(k_transpose, dim3(pp_div_up(128 * in_ld, 256)), b, 0, st, params, wt, 128, in_ld);
     hipLaunchKernelGGL((k_gemm128<MODE_NT, EPI_PLAIN, 1, PP_GEMM_BM>), g, b, 0, st, cur, 128, wt, 128, 128, in_ld, nullptr,
                        nullptr, 0, feat_grad, in_ld, count, 1, capacity);
   }
-  side.join(0);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }
@@ -593,17 +527,14 @@ extern "C" int pp_warp_bwd(const float* params, const float* pts, const float* a
   if (mlp_fused_enabled()) {
     // one fused data-gradient kernel (+ thin layers), then the three weight-gradient GEMMs on the Ybar it left behind
     const bool sb = warp_bwd_stage1(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, ctx, st);
-    hipStream_t ws = deferred_fork(ctx, st);
-    warp_bwd_stage2(acts, scratch, count, capacity, params_grad, sb, ws, ws != st ? pp_opt(PP_OPT_WGRAD_SIDE_WGS) : 0, ctx);
-    deferred_forked(ctx, ws, st);
+    warp_bwd_stage2(acts, scratch, count, capacity, params_grad, sb, st, ctx);
     PP_CHECK_LAUNCH();
     return PP_OK;
   }
-  SideLane side(ctx, st);
   float* cur = scratch;
   float* nxt = scratch + LS;
   float* wt = scratch + 2 * LS;          // transposed weights W3^T, W2^T, W1^T
-  dim3 g(gemm_grid(rcap, PP_GEMM_BM, side.c != nullptr)), gt(TN_WGS), b(256);
+  dim3 g(gemm_grid(rcap, PP_GEMM_BM)), gt(TN_WGS), b(256);
   hipLaunchKernelGGL(k_transpose, dim3(64), b, 0, st, params + WPF_W3, wt, 128, 128);
   hipLaunchKernelGGL(k_transpose, dim3(64), b, 0, st, params + WPF_W2, wt + 16384, 128, 128);
   hipLaunchKernelGGL(k_transpose, dim3(64), b, 0, st, params + WPF_W1, wt + 32768, 128, 128);
@@ -612,11 +543,8 @@ extern "C" int pp_warp_bwd(const float* params, const float* pts, const float* a
   const int w_off[4] = {0, WPF_W1, WPF_W2, WPF_W3};
   const int b_off[4] = {0, WPF_B1, WPF_B2, WPF_B3};
   for (int l = 3; l >= 1; --l) {
-    hipStream_t ss = side.fork();                      // weight gradient of layer l beside its data gradient
-    hipLaunchKernelGGL((k_gemm_tn<4>), gt, b, 0, ss, cur, 128, acts + (l - 1) * LS, 128, 128, params_grad + w_off[l], 128,
+    hipLaunchKernelGGL((k_gemm_tn<4>), gt, b, 0, st, cur, 128, acts + (l - 1) * LS, 128, 128, params_grad + w_off[l], 128,
                        params_grad + b_off[l], count, 4, rcap);
-    side.forked();
-    side.join(1);                                      // the previous layer's side GEMM still reads `nxt`
     hipLaunchKernelGGL((k_gemm128<MODE_NT, EPI_MASK, 4, PP_GEMM_BM>), g, b, 0, st, cur, 128, wt + (3 - l) * 16384, 128, 128,
                        128, nullptr, acts + (l - 1) * LS, 128, nxt, 128, count, 4, rcap);
     float* tmp = cur; cur = nxt; nxt = tmp;
@@ -626,7 +554,6 @@ extern "C" int pp_warp_bwd(const float* params, const float* pts, const float* a
                      pts_grad);
   hipLaunchKernelGGL(k_warp_l0_bwd_w, dim3(pp_div_up(capacity, STRIP0)), b, 0, st, pts, cur, count, capacity,
                      params_grad + WPF_W0, params_grad + WPF_B0);
-  side.join(0);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }
@@ -660,7 +587,7 @@ extern "C" int pp_warp_bwd_weights(const float* acts, const float* scratch, cons
   if (!mlp_fused_enabled()) { pp_set_error("pp_warp_bwd_weights: option mlp_fused = 0 has no two-stage form"); return PP_ERR_UNSUPPORTED; }
   PP_REQUIRE_ORDERED(ctx, capacity, 16);
   // who owns b1..b3 was decided by stage 1 and is handed over explicitly (never re-read from the options)
-  warp_bwd_stage2(acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream), 0, ctx);
+  warp_bwd_stage2(acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream), ctx);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }
@@ -686,7 +613,7 @@ extern "C" int pp_rgbnet_bwd_weights(const float* feat, const float* acts, const
   PP_REQUIRE(capacity > 0 && (stage2 == 0 || stage2 == 1), "capacity<=0 or stage2 is not what pp_rgbnet_bwd_data returned");
   if (!mlp_fused_enabled()) { pp_set_error("pp_rgbnet_bwd_weights: option mlp_fused = 0 has no two-stage form"); return PP_ERR_UNSUPPORTED; }
   PP_REQUIRE_ORDERED(ctx, capacity, 16);
-  rgb_bwd_stage2(feat, acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream), 0, ctx);   // see pp_warp_bwd_weights
+  rgb_bwd_stage2(feat, acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream), ctx);   // see pp_warp_bwd_weights
   PP_CHECK_LAUNCH();
   return PP_OK;
 }

@@ -41,7 +41,7 @@ struct WgradLean {
 };
 int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                             const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                            hipStream_t st, float* bA, float* bB, float* bC, int wgs = 0, float* part = nullptr,
+                            hipStream_t st, float* bA, float* bB, float* bC, float* part = nullptr,
                             const WgradLean* lean = nullptr);
 // split-precision variants (pp_mlp_split.hip, option "mlp_split"): same contracts.  pack: the weight pack written by
 // pp_launch_mlp_pack FOR THESE params (pp_mlp_pack.h), or nullptr = the kernel derives the same quantities in its prologue.
@@ -60,7 +60,7 @@ int pp_launch_mlp_pack(const float* warp_params, const float* rgbnet_params, flo
 // form, every fourth row) or over all rows (kxc == 64: rgbnet)
 int pp_launch_wgrad_chain(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                           const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                          hipStream_t st, float* bA = nullptr, float* bB = nullptr, float* bC = nullptr, int wgs = 0 /* 0: one per CU */,
+                          hipStream_t st, float* bA = nullptr, float* bB = nullptr, float* bC = nullptr,
                           float* part = nullptr /* split-precision kernel only */, const WgradLean* lean = nullptr /* likewise */);
 
 // parameter block of rgbnet (64-wide padded input): W0[128x64] b0 | W1[128x128] b1 | W2[128x128] b2 | W3[3x128] b3

@@ -764,13 +764,12 @@ __global__ __launch_bounds__(256) void k_wgrad_chain(WgradLayer LA, WgradLayer L
 
 int pp_launch_wgrad_chain(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                           const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                          hipStream_t st, float* bA, float* bB, float* bC, int wgs, float* part, const WgradLean* lean) {
+                          hipStream_t st, float* bA, float* bB, float* bC, float* part, const WgradLean* lean) {
   if (pp_opt(PP_OPT_MLP_SPLIT) & 16)            // split-precision chain kernel (pp_mlp_split.hip): bias sums included when asked for
-    return pp_launch_wgrad_chain_s(YA, XA, WA, YB, XB, WB, YC, XC, WC, kxc, count, rmul, rcap, st, bA, bB, bC, wgs, part, lean);
+    return pp_launch_wgrad_chain_s(YA, XA, WA, YB, XB, WB, YC, XC, WC, kxc, count, rmul, rcap, st, bA, bB, bC, part, lean);
   WgradLayer LA{YA, XA, WA, bA}, LB{YB, XB, WB, bB}, LC{YC, XC, WC, bC};
   const int npairs = pp_div_up(rcap, 2 * TILE_ROWS);
-  const int cap_wgs = wgs > 0 ? (wgs < 16 ? 16 : wgs) : PP_FUSED_WGS;
-  const int grid = npairs < cap_wgs ? npairs : cap_wgs;
+  const int grid = npairs < PP_FUSED_WGS ? npairs : PP_FUSED_WGS;
   if (kxc == 128)
     hipLaunchKernelGGL((k_wgrad_chain<128>), dim3(grid), dim3(256), 0, st, LA, LB, LC, count, rmul, rcap);
   else

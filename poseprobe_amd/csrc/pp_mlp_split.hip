@@ -1864,14 +1864,13 @@ __global__ __launch_bounds__(ORD_RED_THREADS) void k_wgrad_reduce_s(WgradOperand
 
 int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                             const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                            hipStream_t st, float* bA, float* bB, float* bC, int wgs_, float* part, const WgradLean* lean) {
+                            hipStream_t st, float* bA, float* bB, float* bC, float* part, const WgradLean* lean) {
   WgradOperands LA{YA, XA, WA, bA}, LB{YB, XB, WB, bB}, LC{YC, XC, WC, bC};
   const WgradLean Z = lean ? *lean : WgradLean{nullptr, nullptr, nullptr};
   const int ntiles = pp_div_up(rcap, TILE_ROWS);
-  // persistent work-groups, two per CU over the three layers, shared out in proportion to the layers' work (wgs_ > 0: the caller's
-  // number of CUs - a launch on an auxiliary stream that leaves CUs to the kernels running beside it); the kernel idles half of
-  // them when the row count is small
-  const int wgs = 2 * (wgs_ > 0 ? (wgs_ < 16 ? 16 : wgs_) : PP_FUSED_WGS);
+  // persistent work-groups, two per CU over the three layers, shared out in proportion to the layers' work; the kernel idles half
+  // of them when the row count is small
+  const int wgs = 2 * PP_FUSED_WGS;
   // (a 64-wide layer costs about 3/4 of a 128-wide one: 3/4 of the bytes and of the values to convert, half the MFMAs)
   int nab = kxc == 128 ? wgs / 3 : (wgs * 4) / 11, nc = kxc == 128 ? wgs / 3 : wgs - 2 * ((wgs * 4) / 11);
   if (nab > ntiles) nab = ntiles;

@@ -126,8 +126,8 @@ class Workspace:
         # Ybar of the warp chain (+ transposed weights, layered path).  Zeroed once, here: inside a lean scope (ops.warp_lean_begin)
         # most of slot 0 is never written, and two engines that went through the same steps must hold the same bytes there
         self.scratch = torch.zeros(wsz['warp'][1], **f)
-        self.scratch_rgb = e(wsz['rgbnet'][1], **f)   # Ybar of rgbnet: its weight-gradient kernel may still be
-        #                                                         reading it on the side stream while the warp chain runs
+        self.scratch_rgb = e(wsz['rgbnet'][1], **f)   # Ybar of rgbnet: a buffer of its own, so that a lean scope's bytes in
+        #                                                         `scratch` depend on the warp chain alone
         self.g_rays_o, self.g_rays_d, self.g_viewdirs = e(N, 3, **f), e(N, 3, **f), e(N, 3, **f)
 
 
@@ -213,11 +213,7 @@ class RenderCore:
         """ordered: `ctx` (required then) has an ordered-flush workspace attached (ops.ordered_attach) - the fused step's backward
         uses the ordered form of the geometry backward as well (the MLP calls pick the workspace up from the context).
         ctx: the pp_context (ops.Context) every option-dependent kernel of this core is called with; None = the host's
-        default context.  Its option `side_stream` = 1 runs the weight-gradient kernel of each MLP chain on the context's
-        auxiliary stream beside the small, latency-bound kernels that follow the chain's data-gradient kernel and joins it before
-        the next register-hungry MLP kernel.  Measured on MI355X (kernel trace): the overlap happens, but the small kernels only
-        get the leftover wave slots (15 -> 45 us each) and the fork / join edges cost ~10 us per chain, so the step is 1 % SLOWER:
-        off by default (PP_SIDE_STREAM=1 in the host's environment turns it on in the default context)."""
+        default context."""
         self.cfg = cfg
         self.ctx = ctx
         self.ordered = bool(ordered)
@@ -245,7 +241,7 @@ class RenderCore:
     # -- backward ------------------------------------------------------------------------------------------
     def backward(self, ws, k0_cl, sdf, sdf_ab, rgbnet_p, warp_p, inv_s, pe_w, k0_grad_cl, sdf_ab_grad, rgbnet_grad,
                  warp_grad, g_depth=None, g_weights=None, g_gradient_ext=None, g_sdf_deform=None, g_grad_deform=None,
-                 g_correction=None, g_alpha_ext=None, g_rgb_ext=None, after_k0_grad=None, defer_join=False, priors=None):
+                 g_correction=None, g_alpha_ext=None, g_rgb_ext=None, after_k0_grad=None, priors=None):
         """Consumes ws.g_rgbm / ws.g_last / ws.g_cw (+ optional per-sample upstream grads), accumulates parameter
         grads (atomic +=) and leaves d/d ray_pts in ws.g_pts and the per-sample viewdir grads in ws.g_view_s."""
         cfg, sc = self.cfg, self.cfg.pp
@@ -282,12 +278,8 @@ class RenderCore:
             ops.geometry_bwd(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
                              ws.g_alpha, ws.g_gradient, None, g_sdf_deform, g_grad_deform, g_correction, 1, ws.g_warp_out,
                              ws.g_pts, ws.g_view_s, sdf_ab_grad)
-        ops.context_join(ctx)           # rgbnet's weight-gradient kernel is done before the next register-hungry kernel
         ops.warp_bwd(warp_p, ws.pts, ws.warp_acts, ws.g_warp_out, ws.count, ws.cap, cfg.out_range, ws.scratch, warp_grad,
                      ws.g_pts, ctx)
-        if not defer_join:
-            ops.context_join(ctx)
-        return ctx
 
 
 class TrainEngine:
@@ -312,8 +304,7 @@ class TrainEngine:
         they feed no update and may differ in the last bits between runs.
         The engine then always owns a private context (the host's default context's values + `options`).  Only the default,
         split-precision layer-fused MLP kernels have ordered flushes: options mlp_fused = 0, mlp_split without bits 2, 8 and 16
-        (e.g. mlp_split = 0), side_stream = 1 and wgrad_side_wgs != 0 are refused with ValueError.  Off (default): nothing
-        changes - same kernels, same launches.
+        (e.g. mlp_split = 0) are refused with ValueError.  Off (default): nothing changes - same kernels, same launches.
         deterministic_scatter: the k0 gradient is accumulated per voxel in sample order (sorted scatter, ~0.2 ms instead of
         0.04 ms per step) instead of by float atomics - bit-identical gradient grids for identical inputs, and bit-identical
         replicas in the multi-GPU "samples" mode without the periodic re-broadcast.
@@ -326,9 +317,7 @@ class TrainEngine:
             opts = dict(_lib.default_context().options(), **(options or {}))
             refused = [('mlp_fused = 0: the layer-by-layer kernels', opts['mlp_fused'] != 1),
                        (f"mlp_split = {opts['mlp_split']} (bits 2, 8 and 16 are needed): the fp32-instruction kernels",
-                        opts['mlp_split'] & 26 != 26),
-                       ('side_stream = 1: the deferred weight-gradient launches', opts['side_stream'] != 0),
-                       ('wgrad_side_wgs != 0: the side-stream launches it sizes', opts['wgrad_side_wgs'] != 0)]
+                        opts['mlp_split'] & 26 != 26)]
             for what, bad in refused:
                 if bad:
                     raise ValueError(f'deterministic=True with {what} have no ordered gradient flush (they keep float atomics)')
@@ -502,7 +491,7 @@ class TrainEngine:
         self.core.backward(ws, self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w,
                            k0_grad, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
                            priors=(1.0, w_dyn, ls, ws.loss_out, batch_norm),
-                           after_k0_grad=after_k0, defer_join=True)
+                           after_k0_grad=after_k0)
         ctx = self.ctx
         if self.deterministic:
             ops.raygen_select_bwd_ordered(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, ws.rays_o, ws.rays_d,
@@ -513,7 +502,6 @@ class TrainEngine:
                                   ws.t_min, ws.ray_start, ws.g_pts, ws.step, ws.g_view_s, None, None, None, None, None, None,
                                   None, self.c2w_grad)
         ops.pose_bwd(self.jac, self.c2w_grad, self.se3_grad)
-        ops.context_join(ctx)           # the warp net's weight gradients (side stream) before anything reads flat.grad
         ops.mlp_pack_invalidate(ctx)
         ops.warp_lean_end(ctx)
         return s_val, w_dyn

@@ -278,11 +278,6 @@ def rgbnet_fwd(params, feat, count, capacity, acts, rgb, ctx=None):
     _lib.call('pp_rgbnet_fwd', _f(params), _f(feat), _i(count), capacity, _f(acts), _f(rgb), _h(ctx), _stream())
 
 
-def context_join(ctx=None):
-    """Current stream waits for every weight-gradient kernel deferred onto the context's auxiliary stream (option side_stream)."""
-    _lib.call('pp_context_join', _h(ctx), _stream())
-
-
 def rgbnet_bwd(params, feat, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, ctx=None):
     _lib.call('pp_rgbnet_bwd', _f(params), _f(feat), _f(acts), _f(rgb), _f(rgb_grad), _i(count), capacity,
               _f(scratch), _f(params_grad), _f(feat_grad), _h(ctx), _stream())

@@ -20,8 +20,9 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(L, name), f'{name} declared in the header but not exported'
     assert hasattr(L, 'pp_last_error')
     L2 = _lib.lib()
-    assert L2.pp_abi_version() == _lib.header_abi_version() == 3
+    assert L2.pp_abi_version() == _lib.header_abi_version() == 4
     assert not hasattr(L, 'pp_set_option') and not hasattr(L, 'pp_get_option')     # no process-wide switches left in the ABI
+    assert not hasattr(L, 'pp_context_join')                                       # nor the join of the retired side-stream placement
 
 
 def test_pp_scene_struct_matches_header_layout():
@@ -39,10 +40,10 @@ def test_a_stale_library_is_refused(tmp_path, monkeypatch):
     built against another ABI would pass its stream where a pointer is read)."""
     from poseprobe_amd import _lib
     hdr = tmp_path / 'poseprobe_hip.h'
-    hdr.write_text(open(_lib.HEADER).read().replace('#define PP_ABI_VERSION 3', '#define PP_ABI_VERSION 4'))
+    hdr.write_text(open(_lib.HEADER).read().replace('#define PP_ABI_VERSION 4', '#define PP_ABI_VERSION 5'))
     monkeypatch.setattr(_lib, 'HEADER', str(hdr))
     monkeypatch.setattr(_lib, '_lib', None)
-    monkeypatch.setattr(_lib, 'header_abi_version', lambda path=None: 4)
+    monkeypatch.setattr(_lib, 'header_abi_version', lambda path=None: 5)
     with pytest.raises(_lib.PoseProbeError, match='ABI'):
         _lib.lib()
 
@@ -63,7 +64,7 @@ def test_options_live_in_caller_owned_contexts():
     with pytest.raises(_lib.PoseProbeError):
         a.set('nerf_tn256', 1)              # retired option
     with pytest.raises(_lib.PoseProbeError):
-        a.set('side_stream', 2)
+        a.set('side_stream', 2)             # retired option
     with pytest.raises(_lib.PoseProbeError):
         a.set('mlp_split', 64)
     assert set(a.options()) == set(_lib.OPTION_NAMES)

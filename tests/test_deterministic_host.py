@@ -20,7 +20,7 @@ def test_new_entry_points_are_declared_and_the_abi_version_stays():
     for name in NEW:
         assert name in protos, f'{name} is not declared in the header'
         assert hasattr(_lib.lib(), name)
-    assert _lib.header_abi_version() == 3
+    assert _lib.header_abi_version() == 4
     # the ordered variants take the arguments of the calls they stand in for, then the context in front of the stream
     for name in ('pp_geometry_bwd_priors', 'pp_raygen_select_bwd'):
         base, ordered = protos[name], protos[name + '_ordered']
@@ -62,6 +62,6 @@ def test_engine_refuses_options_without_an_ordered_flush_before_touching_the_dev
     from poseprobe_amd import synthetic as syn
     from poseprobe_amd.engine import SceneConfig, TrainEngine
     cfg = SceneConfig(syn.XYZ_MIN, syn.XYZ_MAX, 8 ** 3)
-    for options in ({'mlp_split': 0}, {'mlp_fused': 0}, {'side_stream': 1}, {'wgrad_side_wgs': 32}):
+    for options in ({'mlp_split': 0}, {'mlp_fused': 0}):
         with pytest.raises(ValueError, match='deterministic=True'):
             TrainEngine(cfg, 3, 8, 8, 16, device='cpu', deterministic=True, options=options)

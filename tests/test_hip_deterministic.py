@@ -234,7 +234,7 @@ def test_deterministic_step_stays_inside_its_buffers():
 
 def test_options_without_an_ordered_flush_are_refused():
     d = load('forward_g24_s10.npz')
-    for options in ({'mlp_split': 0}, {'mlp_fused': 0}, {'mlp_split': 15}, {'side_stream': 1}, {'wgrad_side_wgs': 96}):
+    for options in ({'mlp_split': 0}, {'mlp_fused': 0}, {'mlp_split': 15}):
         with pytest.raises(ValueError, match='deterministic=True'):
             build_engine(d, deterministic=True, options=options)
 
