@@ -565,6 +565,37 @@ int pp_nerf_pair_pose_bwd(const float* g_center, const float* g_ray, const float
                           const float* g_w2c, int32_t n_views, int32_t view_self, int32_t view_other, float* g_c2w,
                           void* stream);
 
+/* ---------------------------------------------------------------- scene branch: ordered weight-gradient flush
+ * The nine weight-gradient products of pp_nerf_bwd end in float atomics: up to 512 work-groups (row splits x 128 x 128 output
+ * blocks) add their block to params_grad, in the order the hardware retires them.  With a workspace ATTACHED to the context
+ * handed to pp_nerf_bwd, every work-group instead stores its scaled block and its 128 bias sums with plain stores into its own
+ * slot, and a reduction launched behind each product on the same stream adds the slots of an output block in a fixed order (a
+ * function of the row count alone) and adds the total to params_grad, one writer per address.  The row splits that receive no
+ * rows return before the flush; the reduction derives the same active count from `count` on the device and never reads their
+ * slots.  Every other sum of pp_nerf_fwd / pp_nerf_bwd is order-free already, so for one build, equal option values, equal
+ * shapes and the same device model identical inputs then give bit-identical params_grad, g_center and g_ray.
+ * pp_nerf_ordered_workspace: bytes of the workspace, a pure host function: 512 slots x (64 KB + 512 B) whatever the shapes (one
+ * launch's worth serves all nine products of a pass and any number of networks whose calls share a stream).
+ * pp_nerf_ordered_attach records `work` (16-byte aligned, at least that many bytes, caller-owned, alive and untouched by
+ * others while calls with this context are in flight) in `ctx`; work = NULL detaches: back to atomics.  Only the split-precision
+ * kernel has this flush: while a workspace is attached, pp_nerf_bwd with nerf_split = 0 is refused (PP_ERR_INVALID_ARG) rather
+ * than run on atomics. */
+int pp_nerf_ordered_workspace(int64_t* bytes);
+int pp_nerf_ordered_attach(void* ctx, void* work, int64_t work_bytes);
+/* The two sums of a joint step that the host otherwise forms with library reductions of unspecified order.
+ * pp_nerf_c2w_fold: g_c2w[v] = [sum_n g_ray[v][n] (x) dir_cam[v][n] | sum_n g_center[v][n]] for v < n_views over g_ray, g_center,
+ * dir_cam [n_views, n_rays, 3]; rows n_views .. n_views_total - 1 of g_c2w [n_views_total, 3, 4] receive zeros (overwritten).
+ * One work-group per view: a thread adds its rays in ascending order, the threads fold by a tree with fixed pairs.
+ * pp_nerf_sample_pdf: inverse-transform samples of the coarse weights merged with the coarse depths (renderer.py:702-738 and
+ * the cat + sort of :596-600): weights, depth [n_rays, n_samples]; grid [n_fine + 1], or [n_rays, n_fine + 1] when grid_per_ray;
+ * u_j = (grid_j + grid_j+1) / 2; pdf = w / (sum w + 1e-6), cdf its prefix sum (fixed order), the search of searchsorted(right =
+ * True), t = (u - cdf_lo) / (cdf_hi - cdf_lo + 1e-8) between the bin edges linspace(depth_min, depth_max, n_samples + 1);
+ * depth_out [n_rays, n_samples + n_fine] ascending.  One wavefront per ray; n_samples, n_fine <= 256. */
+int pp_nerf_c2w_fold(const float* g_ray, const float* g_center, const float* dir_cam, int32_t n_views, int32_t n_rays,
+                     int32_t n_views_total, float* g_c2w, void* stream);
+int pp_nerf_sample_pdf(const float* weights, const float* depth, const float* grid, int32_t grid_per_ray, int32_t n_rays,
+                       int32_t n_samples, int32_t n_fine, float depth_min, float depth_max, float* depth_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

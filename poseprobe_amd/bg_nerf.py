@@ -511,10 +511,40 @@ class SceneEngine:
     lib/recon_scene.py:765).  With `net_fine` and `fine=True` the step is the reference's hierarchical one
     (renderer.py:586-611): the fine network runs on the union of the coarse samples and inverse-transform samples of the
     coarse weights, `loss = huber(rgb) + huber(rgb_fine)` (base_losses.py:304-307), both networks receive gradients.
-    Ray gradients (sum over the passes) are returned for the caller's pose chain."""
+    Ray gradients (sum over the passes) are returned for the caller's pose chain.
 
-    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, net_fine=None):
+    deterministic=True: bit-reproducible step.  The one order-dependent sum of the kernels - the float-atomic flush of the nine
+    weight-gradient products per pass - goes through per-work-group slots of a workspace and a reduction in a fixed order
+    (ops.nerf_ordered_attach; 34 MB, allocated here once, shared by both networks), and the fine phase draws its samples with
+    ops.nerf_sample_pdf (weight sum, cdf, search, interpolation and merge in one kernel with fixed orders) instead of torch's
+    sum / cumsum, whose order on the device is not promised.  Each network gets a private context (the host's default context's
+    values) if it has none; the workspace stays attached to the networks' contexts.  GUARANTEE: for a fixed build, fixed option
+    values, fixed shapes and the same device model, identical inputs (state, center, ray, depth, image, replayed fine_grid,
+    the same correspondence rows) give bit-identical flat, m, v of both networks and bit-identical returned gradients, in the
+    coarse phase, the hierarchical phase and both with the correspondence term.  Only the split-precision kernels have the
+    ordered flush: a network with nerf_split = 0 is refused with ValueError.  Not covered: SceneRenderer's autograd route, and
+    multi-rank runs.  Off (default): nothing changes - same kernels, same launches, no context, no workspace."""
+
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, net_fine=None, deterministic=False):
         self.net, self.net_fine = net, net_fine
+        self.deterministic = bool(deterministic)
+        self._ordered_work = None
+        if self.deterministic:
+            from . import _lib
+            nets = [net] + ([net_fine] if net_fine is not None else [])
+            for n in nets:
+                if (n.ctx.get('nerf_split') if n.ctx is not None else _lib.default_context().get('nerf_split')) != 1:
+                    raise ValueError('deterministic=True with nerf_split = 0: the fp32-instruction weight-gradient kernel has no '
+                                     'ordered gradient flush (it keeps float atomics)')
+            work = next((n._ordered_work for n in nets if getattr(n, '_ordered_work', None) is not None), None)
+            if work is None:
+                work = torch.empty(ops.nerf_ordered_workspace(), dtype=torch.uint8, device=net.flat.device)
+            self._ordered_work = work
+            for n in nets:
+                if n.ctx is None:
+                    n.ctx = ops.Context(**_lib.default_context().options())
+                ops.nerf_ordered_attach(n.ctx, work)
+                n._ordered_work = work            # the context holds the address: the network keeps the buffer alive with it
         self.lr, self.betas, self.eps = lr, betas, eps
         self.states = [_NetState(net)] + ([_NetState(net_fine)] if net_fine is not None else [])
         self.grad, self.m, self.v = self.states[0].grad, self.states[0].m, self.states[0].v
@@ -587,11 +617,29 @@ class SceneEngine:
             opt = self.net.opt
             S = depth.shape[1]
             det = not opt.nerf.sample_stratified
-            fine_t = sample_depth_from_pdf(w[None], S, opt.nerf.sample_intvs_fine, depth_range, det=det, grid=fine_grid)
-            depth_f = torch.cat([depth, fine_t[0, :, :, 0]], dim=1).sort(dim=1).values.contiguous()
+            if self.deterministic:
+                depth_f = self._fine_depths_ordered(w, depth, opt.nerf.sample_intvs_fine, depth_range, det, fine_grid)
+            else:
+                fine_t = sample_depth_from_pdf(w[None], S, opt.nerf.sample_intvs_fine, depth_range, det=det, grid=fine_grid)
+                depth_f = torch.cat([depth, fine_t[0, :, :, 0]], dim=1).sort(dim=1).values.contiguous()
             loss_f, gc_f, gr_f, _ = self._pass(self.states[1], center, ray, depth_f, image)
             loss, g_center, g_ray = loss + loss_f, g_center + gc_f, g_ray + gr_f
         return loss, g_center, g_ray
+
+    @staticmethod
+    def _fine_depths_ordered(w, depth, n_fine, depth_range, det, grid):
+        """The fine pass's sorted [R, S + Nf] depths by ops.nerf_sample_pdf: the same draws as sample_depth_from_pdf (a replayed
+        `grid` [Nf + 1] or [R, Nf + 1], the regular grid when `det`, else a fresh host-side draw shared by the rays)."""
+        dev = depth.device
+        if grid is not None:
+            grid = grid.to(dev)
+        elif det:
+            grid = torch.linspace(0, 1, n_fine + 1, device=dev)
+        else:
+            grid = torch.rand(n_fine + 1).to(dev)
+        out = torch.empty(depth.shape[0], depth.shape[1] + n_fine, dtype=torch.float32, device=dev)
+        ops.nerf_sample_pdf(w, depth, grid.float().contiguous(), n_fine, depth_range, out)
+        return out
 
     def _forward_backward_corres(self, center, ray, depth, image, fine, depth_range, fine_grid, corres):
         """Photometric rows and matched-pixel rows in the same launches (the reference renders them in two calls, renderer.py
@@ -617,8 +665,11 @@ class SceneEngine:
                 gp = fine_grid if fine_grid is not None else torch.rand(Nf + 1)
                 gc = corres.fine_grid if corres.fine_grid is not None else torch.rand(Nf + 1)
                 grid = torch.cat([gp.to(dev).expand(Rp, Nf + 1), gc.to(dev).expand(2 * M, Nf + 1)])
-            fine_t = sample_depth_from_pdf(passes[0][3]['w'][None], S, Nf, depth_range, det=det, grid=grid)
-            depth_f = torch.cat([depth, fine_t[0, :, :, 0]], dim=1).sort(dim=1).values.contiguous()
+            if self.deterministic:
+                depth_f = self._fine_depths_ordered(passes[0][3]['w'], depth, Nf, depth_range, det, grid)
+            else:
+                fine_t = sample_depth_from_pdf(passes[0][3]['w'][None], S, Nf, depth_range, det=det, grid=grid)
+                depth_f = torch.cat([depth, fine_t[0, :, :, 0]], dim=1).sort(dim=1).values.contiguous()
             passes.append((self.states[1], depth_f) + self._fwd(self.states[1], center, ray, depth_f))
         grads, loss_photo = [], None
         for st, dep, ws, b in passes:

@@ -31,7 +31,7 @@ enum PPOption {
   PP_OPT_COUNT
 };
 
-// Caller-owned context: the option values + three records (weight pack, lean scope, ordered-flush workspace).  It owns no HIP
+// Caller-owned context: the option values + four records (weight pack, lean scope, the two ordered-flush workspaces).  It owns no HIP
 // object: every kernel runs on the stream the call is given.
 struct PPContext {
   int opt[PP_OPT_COUNT];
@@ -47,6 +47,9 @@ struct PPContext {
   // ord == nullptr: none, every flush uses float atomics
   float* ord;
   int ord_wgs, ord_cap, ord_rays;
+  // workspace of the scene branch's ordered weight-gradient flush (pp_nerf_ordered_attach, pp_gemm_tn_tr.h);
+  // nerf_ord == nullptr: none, pp_nerf_bwd flushes with float atomics
+  float* nerf_ord;
 };
 
 // Every entry point that takes a `ctx` opens a scope over ITS options for the duration of the call on the calling thread;

@@ -59,6 +59,7 @@ extern "C" int pp_context_create(void** ctx) {
   c->lean_acts = c->lean_scratch = c->lean_params = nullptr;
   c->ord = nullptr;
   c->ord_wgs = c->ord_cap = c->ord_rays = 0;
+  c->nerf_ord = nullptr;
   *ctx = c;
   return PP_OK;
 }

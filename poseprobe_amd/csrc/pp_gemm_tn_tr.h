@@ -8,12 +8,18 @@
 // thread stores what it loaded - four consecutive columns of a row, hi and lo, as 8-byte conflict-free stores - and a
 // fragment is two transposed reads.
 #pragma once
+#include "pp_ordered.h"
 #include "pp_split_image.h"
+
+// slot of a work-group in the ordered-flush workspace (floats): the 128 x 128 block in accumulator order | 128 bias sums
+#define TN_ORD_SLOT ORD_WGRAD_SLOT
+#define TN_ORD_BIAS ORD_WGRAD_BIAS
 
 static __global__ __launch_bounds__(256, 2) void k_gemm_tn_tr(const float* __restrict__ Y_, int ldy, const float* __restrict__ X_, int ldx,
                                                           int Kx_, float* __restrict__ Wbar_, int ldwb, float* __restrict__ bbar_,
                                                           const int32_t* __restrict__ count, int rcap,
-                                                          const float* __restrict__ y_max, const float* __restrict__ x_max) {
+                                                          const float* __restrict__ y_max, const float* __restrict__ x_max,
+                                                          float* __restrict__ ord) {
   constexpr int CH = 64;
   __shared__ __attribute__((aligned(1024))) unsigned char img[4 * CH * 256];       // Yh | Yl | Xh | Xl
   unsigned char* const Yh = img;
@@ -115,7 +121,22 @@ static __global__ __launch_bounds__(256, 2) void k_gemm_tn_tr(const float* __res
     __syncthreads();
   }
   const float inv = 1.0f / (sY * sX);
-  if (wc * 64 < Kx) {
+  // ordered flush (ord != nullptr, uniform over the launch): the scaled block as it lies in the registers and the bias sums go
+  // into slot (blockIdx.y, blockIdx.x) with plain stores, k_gemm_tn_tr_reduce adds the slots of a block in a fixed order
+  float* __restrict__ slot = ord ? ord + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * TN_ORD_SLOT : nullptr;
+  if (slot) {
+    if (wc * 64 < Kx) {
+      float4* __restrict__ s4 = reinterpret_cast<float4*>(slot);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            s4[((t * 2 + u) * 4 + q) * 256 + tid] = make_float4(acc[t][u][4 * q] * inv, acc[t][u][4 * q + 1] * inv,
+                                                                acc[t][u][4 * q + 2] * inv, acc[t][u][4 * q + 3] * inv);
+    }
+  } else if (wc * 64 < Kx) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -138,7 +159,48 @@ static __global__ __launch_bounds__(256, 2) void k_gemm_tn_tr(const float* __res
       float sum = 0.f;
 #pragma unroll
       for (int q = 0; q < 8; ++q) sum += red[q * 128 + tid];
-      atomicAdd(&bbar[tid], sum);
+      if (slot) slot[TN_ORD_BIAS + tid] = sum;
+      else atomicAdd(&bbar[tid], sum);
     }
   }
+}
+
+// Behind k_gemm_tn_tr with `ord` on the same stream (grid: TN_ORD_SLOT / 256 x the product's output blocks, ORD_RED_THREADS):
+// Wbar / bbar += the sum over the ACTIVE row splits of an output block's slots, splits added in the order of pp_ordered_rows_sum,
+// one writer per address.  The active count is derived from `count` with the producer's own expression (its work-groups with
+// rb >= R return before the flush): an idle slot is never read, nor is an entry its producer did not write (columns past Kx,
+// bias sums of a block that carries none).
+static __global__ __launch_bounds__(ORD_RED_THREADS) void k_gemm_tn_tr_reduce(const float* __restrict__ ord, int splits, int Kx_,
+                                                                              float* __restrict__ Wbar_, int ldwb,
+                                                                              float* __restrict__ bbar_,
+                                                                              const int32_t* __restrict__ count, int rcap) {
+  __shared__ float4 lds[ORD_RED_GROUPS * 64];
+  constexpr int CH = 64;
+  const int nkb = (Kx_ + 127) >> 7;
+  const int nb = blockIdx.y / nkb, kb = blockIdx.y - nb * nkb;
+  const int Kx = min(128, Kx_ - kb * 128);
+  const int R = min(count[0], rcap);
+  if (R <= 0) return;
+  const int rows_per_wg = ((R + splits - 1) / splits + CH - 1) / CH * CH;
+  const int active = (R + rows_per_wg - 1) / rows_per_wg;          // the work-groups with blockIdx.x * rows_per_wg < R
+  const int e4 = blockIdx.x * 64 + (threadIdx.x & 63);
+  // entry e4 of a slot: (tile t, u | register group q | thread tid) of the accumulator block, then 32 float4s of bias sums
+  const int tid = e4 & 255, q = (e4 >> 8) & 3, u = (e4 >> 10) & 1, t = (e4 >> 11) & 1;
+  const int lane = tid & 63, wid = tid >> 6, wr = wid >> 1, wc = wid & 1;
+  const int k = wc * 64 + u * 32 + (lane & 31);
+  const bool is_bias = e4 >= TN_ORD_BIAS / 4;
+  const bool valid = is_bias ? (e4 < TN_ORD_SLOT / 4 && bbar_ && kb == 0) : (k < Kx);
+  float4 s;
+  if (!pp_ordered_rows_sum(reinterpret_cast<const float4*>(ord), TN_ORD_SLOT / 4, blockIdx.y * splits, active, e4, valid, lds, s)) return;
+  if (is_bias) {
+    float* __restrict__ b = bbar_ + nb * 128 + 4 * (e4 - TN_ORD_BIAS / 4);      // (a bias block need not be 16-byte aligned)
+    b[0] += s.x; b[1] += s.y; b[2] += s.z; b[3] += s.w;
+    return;
+  }
+  float* __restrict__ W = Wbar_ + (size_t)nb * 128 * ldwb + kb * 128 + k;
+  const int n = wr * 64 + t * 32 + 8 * q + 4 * (lane >> 5);
+  W[(size_t)n * ldwb] += s.x;
+  W[(size_t)(n + 1) * ldwb] += s.y;
+  W[(size_t)(n + 2) * ldwb] += s.z;
+  W[(size_t)(n + 3) * ldwb] += s.w;
 }

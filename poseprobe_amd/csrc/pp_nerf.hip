@@ -718,15 +718,20 @@ static void nerf_gemm(hipStream_t st, const float* A, int lda, const float* W, i
                        count, 1, rows);
 }
 
+// ord: workspace of the ordered flush (pp_nerf_ordered_attach; nullptr = float atomics): NERF_TN_WGS * 4 slots serve every product
 static void nerf_gemm_tn(hipStream_t st, const float* Y, int ldy, int N, const float* X, int ldx, int Kx, float* Wbar,
-                         float* bbar, const int32_t* count, int rows, const float* y_max = nullptr, const float* x_max = nullptr) {
+                         float* bbar, const int32_t* count, int rows, const float* y_max = nullptr, const float* x_max = nullptr,
+                         float* ord = nullptr) {
   const int blocks = (N / 128) * pp_div_up(Kx, 128);
   dim3 g(NERF_TN_WGS * 4 / blocks, blocks), b(256);       // ~ 4 x NERF_TN_WGS work-groups whatever the block count (2, 3, 4 or 6)
-  if (NERF_SPLIT && y_max && x_max)     // two work-groups per CU since the operand conversion is three instructions per pair: 2.90
+  if (NERF_SPLIT && y_max && x_max) {   // two work-groups per CU since the operand conversion is three instructions per pair: 2.90
                                         // vs 2.99 ms per scene step (round 1, with the compiler's conversion: one per CU was best,
                                         // 3.69 vs 3.85 ms)
-    hipLaunchKernelGGL(k_gemm_tn_tr, g, b, 0, st, Y, ldy, X, ldx, Kx, Wbar, ldx, bbar, count, rows, y_max, x_max);
-  else
+    hipLaunchKernelGGL(k_gemm_tn_tr, g, b, 0, st, Y, ldy, X, ldx, Kx, Wbar, ldx, bbar, count, rows, y_max, x_max, ord);
+    if (ord)
+      hipLaunchKernelGGL(k_gemm_tn_tr_reduce, dim3(pp_div_up(TN_ORD_SLOT / 4, 64), blocks), dim3(ORD_RED_THREADS), 0, st, ord, (int)g.x,
+                         Kx, Wbar, ldx, bbar, count, rows);
+  } else
     hipLaunchKernelGGL((k_gemm_tn<1, 64>), g, b, 0, st, Y, ldy, X, ldx, Kx, Wbar, ldx, bbar, count, 1, rows);
 }
 
@@ -817,6 +822,9 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
                  params_grad && g_center && g_ray, "null pointer");
   PP_REQUIRE(n_rays > 0 && n_samples > 0 && (int64_t)n_rays * n_samples < (1LL << 30), "bad sizes");
   hipStream_t st = pp_stream(stream);
+  float* ord = ctx ? static_cast<const PPContext*>(ctx)->nerf_ord : nullptr;
+  PP_REQUIRE(!ord || NERF_SPLIT, "an ordered-flush workspace is attached (pp_nerf_ordered_attach) and nerf_split = 0 selects the "
+                                 "fp32-instruction weight-gradient kernel, which has no ordered flush");
   const int R = n_rays, S = n_samples, M = R * S;
   const NerfLayout L = nerf_layout();
   NerfActs A = nerf_acts(const_cast<float*>(acts), M);
@@ -882,7 +890,7 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
     hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(388, 64)), dim3(1024), 0, st, part, wgs, params_grad + L.r1, 384, params_grad + L.br1, 3,
                        slot(MX_DH));
   }
-  nerf_gemm_tn(st, dH, 128, 128, A.a[7], 288, 288, params_grad + L.r0, params_grad + L.br0, count, M, slot(MX_DH), slot(MX_A0 + 7));
+  nerf_gemm_tn(st, dH, 128, 128, A.a[7], 288, 288, params_grad + L.r0, params_grad + L.br0, count, M, slot(MX_DH), slot(MX_A0 + 7), ord);
   hipLaunchKernelGGL(k_nerf_ray_sum, dim3(R < 512 ? R : 512), dim3(512), 0, st, dH, R, S, dHsum, slot(MX_DHSUM));
   nerf_gemm<EPI_PLAIN>(st, dHsum, 128, R0T + 256 * 128, 128, 128, 32, nullptr, nullptr, 0, dView, 32, count, R, slot(MX_DHSUM),
                        slot(MX_R0), nullptr);
@@ -913,14 +921,14 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
       const int tiles = pp_div_up(M, 128);
       hipLaunchKernelGGL((k_nerf_trunk<true, true, 8>), dim3(tiles < cus ? tiles : cus), dim3(512), 0, st, T, count, M);
     }
-    nerf_gemm_tn(st, P, 288, 256, A.a[6], 256, 256, params_grad + L.w[7], params_grad + L.b[7], count, M, slot(MX_P), slot(MX_A0 + 6));
+    nerf_gemm_tn(st, P, 288, 256, A.a[6], 256, 256, params_grad + L.w[7], params_grad + L.b[7], count, M, slot(MX_P), slot(MX_A0 + 6), ord);
     for (int l = 6; l >= 1; --l)
       nerf_gemm_tn(st, DY[l], 256, 256, A.a[l - 1], NERF_OUT_LD[l - 1], NERF_IN_LD[l], params_grad + L.w[l], params_grad + L.b[l], count, M,
-                   slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1));
+                   slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1), ord);
     nerf_gemm<EPI_PLAIN>(st, DY[4], 256, WT[4] + 256 * 256, 256, 256, 64, nullptr, nullptr, 0, dEncS, 64, count, M,
                          slot(MX_DY6 + 2), slot(MX_W0 + 4), nullptr);
     nerf_gemm_tn(st, DY[0], 256, 256, A.enc, 64, 64, params_grad + L.w[0], params_grad + L.b[0], count, M, slot(MX_DY6 + 6),
-                 slot(MX_ENC));
+                 slot(MX_ENC), ord);
     nerf_gemm<EPI_PLAIN>(st, DY[0], 256, WT[0], 256, 256, 64, nullptr, nullptr, 0, dEnc0, 64, count, M, slot(MX_DY6 + 6),
                          slot(MX_W0), nullptr);
   } else {
@@ -933,7 +941,7 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
       hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(258, 64)), dim3(1024), 0, st, part, wgs, params_grad + L.wd, 256, params_grad + L.bd, 1,
                          slot(MX_P));
     }
-    nerf_gemm_tn(st, P, 288, 256, A.a[6], 256, 256, params_grad + L.w[7], params_grad + L.b[7], count, M, slot(MX_P), slot(MX_A0 + 6));
+    nerf_gemm_tn(st, P, 288, 256, A.a[6], 256, 256, params_grad + L.w[7], params_grad + L.b[7], count, M, slot(MX_P), slot(MX_A0 + 6), ord);
     nerf_gemm<EPI_MASK>(st, P, 288, WT[7], 288, 288, 256, nullptr, A.a[6], 256, Q, 256, count, M, slot(MX_P), slot(MX_W0 + 7),
                         slot(MX_DY6), A.bits[6], wt7_img);
     float* cur = Q;
@@ -942,7 +950,7 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
       const float* x = A.a[l - 1];
       const int ldx = NERF_OUT_LD[l - 1];            // 320 for layer 4's input (features + skip columns)
       nerf_gemm_tn(st, cur, 256, 256, x, ldx, NERF_IN_LD[l], params_grad + L.w[l], params_grad + L.b[l], count, M,
-                   slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1));
+                   slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1), ord);
       nerf_gemm<EPI_MASK>(st, cur, 256, WT[l], 256, 256, 256, nullptr, x, ldx, nxt, 256, count, M, slot(MX_DY6 + 6 - l),
                           slot(MX_W0 + l), slot(MX_DY6 + 7 - l), A.bits[l - 1], wt_img[l]);
       if (l == 4)                                    // skip columns: gradient of the encoding, no activation in between
@@ -951,7 +959,7 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
       float* t = cur; cur = nxt; nxt = t;
     }
     nerf_gemm_tn(st, cur, 256, 256, A.enc, 64, 64, params_grad + L.w[0], params_grad + L.b[0], count, M, slot(MX_DY6 + 6),
-                 slot(MX_ENC));
+                 slot(MX_ENC), ord);
     nerf_gemm<EPI_PLAIN>(st, cur, 256, WT[0], 256, 256, 64, nullptr, nullptr, 0, dEnc0, 64, count, M, slot(MX_DY6 + 6),
                          slot(MX_W0), nullptr);
   }
@@ -1042,6 +1050,142 @@ extern "C" int pp_nerf_composite_bwd(const float* rgb_samples, const float* dens
   hipLaunchKernelGGL(k_nerf_composite_bwd, dim3(pp_div_up(n_rays, 4)), dim3(256), 0, pp_stream(stream), rgb_samples,
                      density_samples, depth, ray, weights, n_rays, n_samples, white_bg, g_rgb, g_depth, g_opacity, g_weights,
                      g_rgb_samples, g_density_samples, g_ray);
+  PP_CHECK_LAUNCH();
+  return PP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ ordered (bit-reproducible) step
+// The workspace of the weight-gradient kernel's ordered flush (pp_gemm_tn_tr.h) and the two sums of a joint step that the host
+// otherwise leaves to library reductions of unspecified order (joint.DualBranchEngine, bg_nerf.SceneEngine with deterministic=True).
+static const int64_t NERF_ORD_BYTES = (int64_t)NERF_TN_WGS * 4 * TN_ORD_SLOT * sizeof(float);     // a launch never has more work-groups
+
+extern "C" int pp_nerf_ordered_workspace(int64_t* bytes) {
+  PP_REQUIRE(bytes, "null pointer");
+  *bytes = NERF_ORD_BYTES;
+  return PP_OK;
+}
+
+extern "C" int pp_nerf_ordered_attach(void* ctx, void* work, int64_t work_bytes) {
+  PP_REQUIRE(ctx, "null context (the workspace is recorded in a context: create one)");
+  PPContext* c = static_cast<PPContext*>(ctx);
+  if (!work) {                      // detach: back to the atomic flush
+    c->nerf_ord = nullptr;
+    return PP_OK;
+  }
+  PP_REQUIRE((reinterpret_cast<uintptr_t>(work) & 15) == 0, "work must be 16-byte aligned");
+  PP_REQUIRE(work_bytes >= NERF_ORD_BYTES, "work is smaller than pp_nerf_ordered_workspace()");
+  c->nerf_ord = static_cast<float*>(work);
+  return PP_OK;
+}
+
+// g_c2w[v] = [sum_n g_ray[v][n] (x) dir_cam[v][n] | sum_n g_center[v][n]]: one work-group per view, thread i adds rays i, i + 256,
+// ... in ascending order, then the 256 partial sums fold by a tree with fixed pairs (the scheme of k_raygen_c2w_reduce, pp_rays.hip)
+#define C2W_FOLD_T 256
+__global__ __launch_bounds__(C2W_FOLD_T) void k_nerf_c2w_fold(const float* __restrict__ g_ray, const float* __restrict__ g_center,
+                                                              const float* __restrict__ dir_cam, int V, int N,
+                                                              float* __restrict__ g_c2w) {
+  __shared__ float red[12][C2W_FOLD_T];
+  const int v = blockIdx.x, tid = threadIdx.x;
+  if (v >= V) {                      // a view that is not in play
+    if (tid < 12) g_c2w[v * 12 + tid] = 0.f;
+    return;
+  }
+  float part[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) part[k] = 0.f;
+  for (int n = tid; n < N; n += C2W_FOLD_T) {
+    const size_t r = ((size_t)v * N + n) * 3;
+    const float d0 = dir_cam[r], d1 = dir_cam[r + 1], d2 = dir_cam[r + 2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float g = g_ray[r + a];
+      part[a * 4] += g * d0; part[a * 4 + 1] += g * d1; part[a * 4 + 2] += g * d2; part[a * 4 + 3] += g_center[r + a];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) red[k][tid] = part[k];
+  __syncthreads();
+  for (int o = C2W_FOLD_T / 2; o > 0; o >>= 1) {
+    if (tid < o) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) red[k][tid] += red[k][tid + o];
+    }
+    __syncthreads();
+  }
+  if (tid < 12) g_c2w[v * 12 + tid] = red[tid][0];
+}
+
+extern "C" int pp_nerf_c2w_fold(const float* g_ray, const float* g_center, const float* dir_cam, int32_t n_views, int32_t n_rays,
+                                int32_t n_views_total, float* g_c2w, void* stream) {
+  PP_REQUIRE(g_ray && g_center && dir_cam && g_c2w, "null pointer");
+  PP_REQUIRE(n_views > 0 && n_rays > 0 && n_views_total >= n_views && (int64_t)n_views * n_rays < (1LL << 29), "bad sizes");
+  hipLaunchKernelGGL(k_nerf_c2w_fold, dim3(n_views_total), dim3(C2W_FOLD_T), 0, pp_stream(stream), g_ray, g_center, dir_cam, n_views,
+                     n_rays, g_c2w);
+  PP_CHECK_LAUNCH();
+  return PP_OK;
+}
+
+// Inverse-transform samples of the coarse weights, merged with the coarse depths (bg_nerf.sample_depth_from_pdf + cat + sort):
+// one wavefront (= one work-group) per ray.  The weight sum is a strided sum per lane and a butterfly over the lanes, the cdf a
+// wave scan per 64 entries with a running carry: fixed orders.  The merge ranks every value among all N + Nf (ties by index), so
+// neither the fine samples (a replayed random grid is not monotonic) nor the coarse ones need to arrive sorted.
+#define PDF_MAX 256
+__global__ __launch_bounds__(64) void k_nerf_sample_pdf(const float* __restrict__ weights, const float* __restrict__ depth,
+                                                        const float* __restrict__ grid, int grid_ld, int N, int Nf, float dmin,
+                                                        float dmax, float* __restrict__ out) {
+  __shared__ float cdf[PDF_MAX + 1];
+  __shared__ float val[2 * PDF_MAX];
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const float* __restrict__ w = weights + (size_t)r * N;
+  float s = 0.f;
+  for (int i = lane; i < N; i += 64) s += w[i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  const float denom = s + 1e-6f;
+  float carry = 0.f;
+  if (lane == 0) cdf[0] = 0.f;
+  for (int i0 = 0; i0 < N; i0 += 64) {
+    const int i = i0 + lane;
+    const float incl = wave_incl_scan(i < N ? w[i] / denom : 0.f, lane);
+    if (i < N) cdf[i + 1] = carry + incl;
+    carry += __shfl(incl, 63, 64);
+  }
+  for (int i = lane; i < N; i += 64) val[i] = depth[(size_t)r * N + i];
+  __syncthreads();
+  const float* __restrict__ g = grid + (size_t)r * grid_ld;
+  const float step = (dmax - dmin) / (float)N;          // torch.linspace(dmin, dmax, N + 1): from the start below the middle, from the end above
+  auto edge = [&](int k) { return k < (N + 1) / 2 ? dmin + step * (float)k : dmax - step * (float)(N - k); };
+  for (int j = lane; j < Nf; j += 64) {
+    const float u = 0.5f * (g[j] + g[j + 1]);
+    int lo = 0, hi = N + 1;                             // searchsorted(right = True): the first index with cdf[idx] > u
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (cdf[mid] <= u) lo = mid + 1; else hi = mid;
+    }
+    const int a = max(lo - 1, 0), b = min(lo, N);
+    const float c_lo = cdf[a], c_hi = cdf[b], d_lo = edge(a), d_hi = edge(b);
+    const float t = (u - c_lo) / (c_hi - c_lo + 1e-8f);
+    val[N + j] = d_lo + t * (d_hi - d_lo);
+  }
+  __syncthreads();
+  const int T = N + Nf;
+  for (int i = lane; i < T; i += 64) {
+    const float x = val[i];
+    int rank = 0;
+    for (int k = 0; k < T; ++k) {
+      const float y = val[k];
+      rank += (y < x || (y == x && k < i)) ? 1 : 0;
+    }
+    out[(size_t)r * T + rank] = x;
+  }
+}
+
+extern "C" int pp_nerf_sample_pdf(const float* weights, const float* depth, const float* grid, int32_t grid_per_ray, int32_t n_rays,
+                                  int32_t n_samples, int32_t n_fine, float depth_min, float depth_max, float* depth_out, void* stream) {
+  PP_REQUIRE(weights && depth && grid && depth_out, "null pointer");
+  PP_REQUIRE(n_rays > 0 && n_samples > 0 && n_samples <= PDF_MAX && n_fine > 0 && n_fine <= PDF_MAX, "bad sizes (n_samples, n_fine <= 256)");
+  hipLaunchKernelGGL(k_nerf_sample_pdf, dim3(n_rays), dim3(64), 0, pp_stream(stream), weights, depth, grid,
+                     grid_per_ray ? n_fine + 1 : 0, n_samples, n_fine, depth_min, depth_max, depth_out);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }

@@ -299,8 +299,8 @@ class TrainEngine:
         GUARANTEE: for a fixed build, fixed option values, fixed shapes and the same device model, identical inputs (state,
         ray_idx, jitter, global_step sequence) give bit-identical k0, k0_m, k0_v, flat.data, flat.m, flat.v, se3, se3_m, se3_v
         after every step.  It is NOT a promise of equal bits across different mlp_wgs values, builds or chips, and it covers the
-        single-GPU object branch only: the scene branch (joint.DualBranchEngine) and multi-rank runs (dist) work with such an
-        engine but keep their own atomics and reductions.  The reported scalars (ws.loss_out, ws.tv_out) stay on float atomics:
+        single-GPU object branch only: multi-rank runs (dist) work with such an engine but keep their own reductions, and the
+        scene branch / joint step need joint.DualBranchEngine(deterministic=True) on top of it.  The reported scalars (ws.loss_out, ws.tv_out) stay on float atomics:
         they feed no update and may differ in the last bits between runs.
         The engine then always owns a private context (the host's default context's values + `options`).  Only the default,
         split-precision layer-fused MLP kernels have ordered flushes: options mlp_fused = 0, mlp_split without bits 2, 8 and 16

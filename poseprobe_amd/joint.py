@@ -14,9 +14,26 @@ from . import bg_nerf, ops
 
 
 class DualBranchEngine:
-    def __init__(self, obj_engine, scene_net, lr_scene=1e-3, depth_range=(0.5, 3.0), scene_net_fine=None):
+    def __init__(self, obj_engine, scene_net, lr_scene=1e-3, depth_range=(0.5, 3.0), scene_net_fine=None, deterministic=False):
+        """deterministic=True: bit-reproducible joint step.  Needs a deterministic single-GPU object engine
+        (TrainEngine(deterministic=True), no `dist`; ValueError otherwise), builds a deterministic bg_nerf.SceneEngine and folds
+        the scene branch's ray gradients into the pose gradient with ops.nerf_c2w_fold (fixed order) instead of torch's einsum /
+        sum.  GUARANTEE (the conditions of TrainEngine's): identical state, ray_idx, jitter, global_step, pixels, image, replayed
+        depth_rand / fine_grid / corres_rand / corres_fine_grid and the same corres rows give, after every train_step, bit-identical
+        k0, k0_m, k0_v, flat.data, flat.m, flat.v, se3, se3_m, se3_v of the object engine and flat, m, v of the coarse and the
+        fine scene network - coarse phase, hierarchical phase, and both with the correspondence term.  Not covered: extra pose
+        terms a caller mixes into se3_grad through torch autograd (trainer.ReprojectionTerm), multi-rank runs, and
+        bg_nerf.SceneRenderer's autograd route.  Off (default): nothing changes."""
+        self.deterministic = bool(deterministic)
+        if self.deterministic:
+            if not getattr(obj_engine, 'deterministic', False):
+                raise ValueError('DualBranchEngine: deterministic=True with an object engine built without deterministic=True '
+                                 '(its gradients keep float atomics, and both branches feed one pose update)')
+            if getattr(obj_engine, 'dist', None) is not None:
+                raise ValueError('DualBranchEngine: deterministic=True with a multi-rank object engine (dist) is not covered: '
+                                 'the exchange keeps its own reductions')
         self.obj = obj_engine
-        self.scene = bg_nerf.SceneEngine(scene_net, lr=lr_scene, net_fine=scene_net_fine)
+        self.scene = bg_nerf.SceneEngine(scene_net, lr=lr_scene, net_fine=scene_net_fine, deterministic=self.deterministic)
         self.depth_range = depth_range
         e = obj_engine
         self._se3_tmp = torch.zeros_like(e.se3_grad)
@@ -109,10 +126,14 @@ class DualBranchEngine:
                 depth_range=self.depth_range, fine_grid=fine_grid, corres=rows)
         # fold the ray gradients into d L_bg / d c2w and through the object engine's pose Jacobian
         g_ray_p, g_center_p = g_ray[:V * N].view(V, N, 3), g_center[:V * N].view(V, N, 3)
-        g_c2w = torch.cat([torch.einsum('vni,vnj->vij', g_ray_p, dir_cam), g_center_p.sum(1)[..., None]], dim=-1)
-        if V < e.V:                                     # views that are not in play yet receive no scene gradient
-            g_c2w = torch.cat([g_c2w, torch.zeros(e.V - V, 3, 4, device=g_c2w.device)], dim=0)
-        g_c2w = g_c2w.contiguous()
+        if self.deterministic:                          # fixed summation order; views that are not in play receive zeros
+            g_c2w = torch.empty(e.V, 3, 4, dtype=torch.float32, device=g_ray.device)
+            ops.nerf_c2w_fold(g_ray_p, g_center_p, dir_cam.contiguous(), g_c2w)
+        else:
+            g_c2w = torch.cat([torch.einsum('vni,vnj->vij', g_ray_p, dir_cam), g_center_p.sum(1)[..., None]], dim=-1)
+            if V < e.V:                                     # views that are not in play yet receive no scene gradient
+                g_c2w = torch.cat([g_c2w, torch.zeros(e.V - V, 3, 4, device=g_c2w.device)], dim=0)
+            g_c2w = g_c2w.contiguous()
         if corres is not None:
             # the matched rows' ray gradients and the loss's direct gradient on both w2c, accumulated into views i and j
             ops.nerf_pair_pose_bwd(g_center[V * N:], g_ray[V * N:], c_dir.reshape(2 * M, 3), e.w2c, sc.last_g_w2c, i, j, g_c2w)

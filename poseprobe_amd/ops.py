@@ -494,3 +494,43 @@ def nerf_pair_pose_bwd(g_center, g_ray, dir_cam, w2c, g_w2c, view_self, view_oth
         raise RuntimeError('nerf_pair_pose_bwd: inconsistent shapes')
     _lib.call('pp_nerf_pair_pose_bwd', _f(g_center), _f(g_ray), _f(dir_cam), int(M2 // 2), _f(w2c), _f(g_w2c), int(V),
               int(view_self), int(view_other), _f(g_c2w), _stream())
+
+
+# ------------------------------------------------------------------------------------------- scene branch: ordered step
+def nerf_ordered_workspace():
+    """Bytes of the workspace of the scene branch's ordered weight-gradient flush (pp_nerf_ordered_workspace): 512 slots of
+    64 KB + 512 B, whatever the shapes."""
+    b = ctypes.c_int64()
+    _lib.call('pp_nerf_ordered_workspace', ctypes.byref(b))
+    return b.value
+
+
+def nerf_ordered_attach(ctx, work):
+    """Record `work` (uint8 tensor of nerf_ordered_workspace() bytes; None = detach) in `ctx` (an _lib.Context, required):
+    nerf_bwd calls handed this context then add the weight gradients up in a fixed order instead of by float atomics.  The
+    caller keeps `work` alive while such calls are in flight; contexts whose calls share a stream may share one workspace."""
+    if ctx is None:
+        raise ValueError('nerf_ordered_attach needs a context of its own (the default context is shared by everybody)')
+    _lib.call('pp_nerf_ordered_attach', ctx.handle, _u8(work), 0 if work is None else int(work.numel()))
+
+
+def nerf_c2w_fold(g_ray, g_center, dir_cam, g_c2w):
+    """g_ray / g_center / dir_cam [V, N, 3] -> g_c2w [V_total, 3, 4] = [sum g_ray (x) dir_cam | sum g_center] in a fixed order
+    (rows V .. V_total - 1: zeros)."""
+    V, N = g_ray.shape[:2]
+    if tuple(g_ray.shape) != (V, N, 3) or g_center.shape != g_ray.shape or dir_cam.shape != g_ray.shape or \
+            g_c2w.dim() != 3 or tuple(g_c2w.shape[1:]) != (3, 4) or g_c2w.shape[0] < V:
+        raise RuntimeError('nerf_c2w_fold: inconsistent shapes')
+    _lib.call('pp_nerf_c2w_fold', _f(g_ray), _f(g_center), _f(dir_cam), int(V), int(N), int(g_c2w.shape[0]), _f(g_c2w), _stream())
+
+
+def nerf_sample_pdf(weights, depth, grid, n_fine, depth_range, depth_out):
+    """weights, depth [R, S]; grid [n_fine + 1] (shared) or [R, n_fine + 1] -> depth_out [R, S + n_fine]: the coarse depths and the
+    inverse-transform samples of the coarse weights, ascending (bg_nerf.sample_depth_from_pdf + cat + sort in one launch)."""
+    R, S = weights.shape
+    per_ray = grid.dim() == 2
+    if depth.shape != weights.shape or tuple(grid.shape) != ((R, n_fine + 1) if per_ray else (n_fine + 1,)) or \
+            tuple(depth_out.shape) != (R, S + n_fine):
+        raise RuntimeError('nerf_sample_pdf: inconsistent shapes')
+    _lib.call('pp_nerf_sample_pdf', _f(weights), _f(depth), _f(grid), int(per_ray), int(R), int(S), int(n_fine),
+              ctypes.c_float(depth_range[0]), ctypes.c_float(depth_range[1]), _f(depth_out), _stream())

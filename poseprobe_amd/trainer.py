@@ -185,7 +185,8 @@ class ReprojectionTerm:
 
 class DualBranchTrainer:
     def __init__(self, obj_engine, opt, max_iter=60000, lr=1e-3, lr_end=1e-4, ratio_start_fine=0.3, ratio_end_pose=0.3,
-                 depth_range=(0.5, 3.0), seed=0, incremental_step=0, pose_initialiser=None, pose_terms=(), scene_matches=None):
+                 depth_range=(0.5, 3.0), seed=0, incremental_step=0, pose_initialiser=None, pose_terms=(), scene_matches=None,
+                 deterministic=False):
         """incremental_step > 0: the incremental view schedule (`active_views`); a view that joins gets its initial pose from
         `pose_initialiser(view, w2c_of_previous_view [3,4]) -> w2c [3,4]` - the reference's PnP hand-off (cv2.solvePnPRansac on
         matcher output, lib/recon_scene.py:202-214, :276-310) plugs in here; the default is its `use_identical` variant (the
@@ -194,7 +195,9 @@ class DualBranchTrainer:
         -> (weight, scalar loss)`, differentiated by torch autograd through camera.current_pose_c2w.
         scene_matches: per view i, (pix_self [P,2], pix_other [P,2], conf [P][, partner]) - the reference's coord1_scene[i],
         coord0_scene[i], mconf_scene[i] (recon_scene.py:247-257), paired with view pair_partner(i) unless a partner is given;
-        read when opt.loss_type contains 'corres'."""
+        read when opt.loss_type contains 'corres'.
+        deterministic: passed to DualBranchEngine (needs a deterministic, single-GPU obj_engine): the joint step's own sums run
+        in fixed orders.  Out of its scope: `pose_terms` (differentiated by torch autograd) and multi-rank runs."""
         self.opt, self.max_iter = opt, max_iter
         self.terms = loss_terms(getattr(opt, 'loss_type', None))
         self.photo_weight = loss_weight(opt, 'photometric') if 'loss_type' in opt else 1.0
@@ -217,7 +220,8 @@ class DualBranchTrainer:
         dev = obj_engine.dev
         self.nerf = bg_nerf.NeRF(opt, device=dev)
         self.nerf_fine = bg_nerf.NeRF(opt, is_fine_network=True, device=dev) if opt.nerf.fine_sampling else None
-        self.joint = DualBranchEngine(obj_engine, self.nerf, lr_scene=lr, depth_range=depth_range, scene_net_fine=self.nerf_fine)
+        self.joint = DualBranchEngine(obj_engine, self.nerf, lr_scene=lr, depth_range=depth_range, scene_net_fine=self.nerf_fine,
+                                      deterministic=deterministic)
         self.iteration = 0            # == the reference's Graph.iteration_nerf
         self.gen = torch.Generator(device=dev).manual_seed(seed)
         self.dev = dev
