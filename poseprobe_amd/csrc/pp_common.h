@@ -13,7 +13,9 @@ void pp_set_error(const char* fmt, ...);
 
 // Options (include/poseprobe_hip.h: pp_context_set_option / pp_context_get_option).  They are fields of a caller-owned
 // pp_context that travels with every call whose behaviour they select; a NULL context means the compiled-in defaults.
-// The library holds NO process-wide mutable state and never reads the environment.
+// An entry point reads them once, from the context it was handed (pp_options), and passes what it resolved down to its launch
+// helpers as arguments.  The library holds NO process-wide mutable state, no per-thread state beside the error text, and never
+// reads the environment.
 enum PPOption {
   PP_OPT_MLP_FUSED = 0,        // 1: layer-fused object-branch MLP kernels, 0: layer-by-layer GEMMs (A/B runs)
   PP_OPT_GRID_CHUNKS,          // x-chunks of the fused TV + Adam pass (0 = heuristic)
@@ -52,19 +54,13 @@ struct PPContext {
   float* nerf_ord;
 };
 
-// Every entry point that takes a `ctx` opens a scope over ITS options for the duration of the call on the calling thread;
-// the launch helpers below it read them through pp_opt().  Nothing outlives the call: two contexts with different
-// arithmetic coexist in one process, also on different threads at the same time.
-struct PPOptScope {
-  const int* prev;
-  explicit PPOptScope(const void* ctx);
-  ~PPOptScope();
-};
-int pp_opt(int id);
-int pp_num_cus();
+// The option array of a context (indexed by PPOption), or the compiled-in defaults for ctx == nullptr.  Two contexts with
+// different arithmetic coexist in one process, also on different threads at the same time.
+const int* pp_options(const void* ctx);
+int pp_num_cus();                                           // compute units of the current device (queried once per process: a hardware constant)
 // X-marching total-variation value / gradient pass on a channels-last grid (pp_optim.hip); false: shape not covered
 bool pp_launch_tv_march(const float* p, int X, int Y, int Z, int C, float scale, const float* g_scalar, float* grad, float* tv_out,
-                        hipStream_t st);                    // compute units of the current device (queried once per process: a hardware constant)
+                        hipStream_t st);
 
 #define PP_REQUIRE(cond, msg)                                     \
   do {                                                            \

@@ -1,4 +1,4 @@
-// thread-local error text, ABI version, tuning options
+// per-thread error text, ABI version, options / context
 #include <stdarg.h>
 
 #include "pp_common.h"
@@ -29,10 +29,7 @@ static const struct PPDefaults {
   PPDefaults() { for (int i = 0; i < PP_OPT_COUNT; ++i) v[i] = g_opt_def[i].dflt; }
 } g_defaults;
 
-static thread_local const int* t_opts = nullptr;      // options of the entry point running on this thread (PPOptScope)
-PPOptScope::PPOptScope(const void* ctx) : prev(t_opts) { t_opts = ctx ? static_cast<const PPContext*>(ctx)->opt : g_defaults.v; }
-PPOptScope::~PPOptScope() { t_opts = prev; }
-int pp_opt(int id) { return (t_opts ? t_opts : g_defaults.v)[id]; }
+const int* pp_options(const void* ctx) { return ctx ? static_cast<const PPContext*>(ctx)->opt : g_defaults.v; }
 
 int pp_num_cus() {
   static const int n = [] {

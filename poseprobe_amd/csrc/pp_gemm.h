@@ -1,4 +1,4 @@
-// Layer-by-layer fp32 MFMA GEMM templates shared by the object-branch MLPs (pp_mlp.hip) and the scene-branch NeRF
+// Layer-by-layer fp32 MFMA GEMM templates shared by the object-branch MLPs (pp_mlp_layered.hip) and the scene-branch NeRF
 // (pp_nerf.hip).  gridDim.y selects a 128-column block of the output (k_gemm128) or a 128 x 128 block of the weight
 // gradient (k_gemm_tn), so layers wider than 128 run as several column blocks over the same row tiles.
 #pragma once

@@ -1,4 +1,5 @@
-// Internal interface between pp_mlp.hip (C-ABI entry points) and pp_mlp_fused.hip (layer-fused kernels).
+// Internal interface between pp_mlp.hip (C-ABI entry points, routing) and the kernels of the object-branch MLPs: pp_mlp_fused.hip,
+// pp_mlp_split.hip (layer-fused), pp_mlp_layered.hip.  A launcher reads no option: what the entry point resolved comes in as arguments.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,16 +16,15 @@
 #define WPF_W4 (WPF_B3 + 128)
 #define WPF_B4 (WPF_W4 + 4 * 128)
 
-// persistent grid of the fused kernels: one work-group per CU (weights stationary in ~200 registers per lane, LDS 70-156 KB);
-// the CU count of the current device is queried once (256 on an MI355X in SPX mode)
-int pp_fused_wgs();
-#define PP_FUSED_WGS pp_fused_wgs()
+// wgs (every launcher of a layer-fused kernel): the call's persistent work-group count (MlpRoute, pp_mlp.hip); a kernel whose
+// work has fewer units than that gets one work-group per unit
+static inline int pp_fused_grid(int units, int wgs) { return units < wgs ? units : wgs; }
 
 int pp_launch_warp_fused_fwd(const float* params, const float* pts, const int32_t* count, int capacity, float out_range,
-                             float* acts, float* out, hipStream_t st);
+                             float* acts, float* out, hipStream_t st, int wgs);
 int pp_launch_warp_fused_bwd(const float* params, const float* pts, const float* acts, const float* out_grad,
                              const int32_t* count, int capacity, float out_range, float* ybar, float* params_grad,
-                             float* pts_grad, hipStream_t st);
+                             float* pts_grad, hipStream_t st, int wgs);
 // operands of one layer of the weight-gradient chain (split-precision kernel, pp_mlp_split.hip)
 struct WgradOperands {
   const float* Y;      // [R][128]  gradient w.r.t. the layer's pre-activation (already gated)
@@ -41,8 +41,7 @@ struct WgradLean {
 };
 int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                             const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                            hipStream_t st, float* bA, float* bB, float* bC, float* part = nullptr,
-                            const WgradLean* lean = nullptr);
+                            hipStream_t st, int wgs, float* bA, float* bB, float* bC, float* part, const WgradLean* lean);
 // split-precision variants (pp_mlp_split.hip, option "mlp_split"): same contracts.  pack: the weight pack written by
 // pp_launch_mlp_pack FOR THESE params (pp_mlp_pack.h), or nullptr = the kernel derives the same quantities in its prologue.
 // part (backward kernels, weight-gradient chain): this launch's region of the ordered-flush workspace (pp_ordered.h) - the
@@ -50,18 +49,17 @@ int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const f
 // lean (warp net, pp_warp_lean_begin): the forward kernel leaves the tangent rows of X0 unwritten, the backward kernel writes the
 // scaled output gradients to the start of `ybar` instead of Ybar3
 int pp_launch_warp_fused_fwd_s(const float* params, const float* pts, const int32_t* count, int capacity, float out_range,
-                               float* acts, float* out, hipStream_t st, const float* pack, bool lean = false);
+                               float* acts, float* out, hipStream_t st, int wgs, const float* pack, bool lean);
 int pp_launch_warp_fused_bwd_s(const float* params, const float* pts, const float* acts, const float* out_grad,
                                const int32_t* count, int capacity, float out_range, float* ybar, float* params_grad,
-                               float* pts_grad, hipStream_t st, const float* pack, float* part = nullptr, bool lean = false);
+                               float* pts_grad, hipStream_t st, int wgs, const float* pack, float* part, bool lean);
 int pp_launch_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, hipStream_t st);
 // weight gradients of three layers (Y_l^T X_l accumulated into W_l) in one persistent kernel; kxc = width of X of layer C;
 // bA / bB / bC: also accumulate the bias gradients = column sums of Y over the primal rows (kxc == 128: the warp net's 4-row
 // form, every fourth row) or over all rows (kxc == 64: rgbnet)
 int pp_launch_wgrad_chain(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                           const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                          hipStream_t st, float* bA = nullptr, float* bB = nullptr, float* bC = nullptr,
-                          float* part = nullptr /* split-precision kernel only */, const WgradLean* lean = nullptr /* likewise */);
+                          hipStream_t st, int wgs, float* bA, float* bB, float* bC);
 
 // parameter block of rgbnet (64-wide padded input): W0[128x64] b0 | W1[128x128] b1 | W2[128x128] b2 | W3[3x128] b3
 #define RGF_W0 0
@@ -74,12 +72,24 @@ int pp_launch_wgrad_chain(const float* YA, const float* XA, float* WA, const flo
 #define RGF_B3 (RGF_W3 + 3 * 128)
 
 int pp_launch_rgb_fused_fwd(const float* params, const float* feat, const int32_t* count, int capacity,
-                            const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st);
+                            const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st, int wgs);
 int pp_launch_rgb_fused_fwd_s(const float* params, const float* feat, const int32_t* count, int capacity,
-                              const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st, const float* pack);
+                              const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st, int wgs, const float* pack);
 int pp_launch_rgb_fused_bwd_s(const float* params, const float* acts, const float* rgb, const float* rgb_grad,
                               const int32_t* count, int capacity, float* ybar, float* params_grad, float* feat_grad,
-                              float* logit_grad, int lg_ld, hipStream_t st, const float* pack, float* part = nullptr);
+                              float* logit_grad, int lg_ld, hipStream_t st, int wgs, const float* pack, float* part);
 int pp_launch_rgb_fused_bwd(const float* params, const float* acts, const float* rgb, const float* rgb_grad,
                             const int32_t* count, int capacity, float* ybar, float* params_grad, float* feat_grad,
-                            float* logit_grad, int lg_ld, hipStream_t st);
+                            float* logit_grad, int lg_ld, hipStream_t st, int wgs);
+
+// layer-by-layer launch sequences (pp_mlp_layered.hip): the generic ReLU MLP in_ld -> 128 x n_gemm -> 3 and the warp net in 4-row
+// form; same buffers and contracts as the entry points of pp_mlp.hip that forward to them
+void pp_launch_mlp_layered_fwd(const float* params, const float* feat, int in_ld, int n_gemm, const int32_t* count, int capacity,
+                               const float* logit_add, int logit_add_ld, float* acts, float* out, hipStream_t st);
+void pp_launch_mlp_layered_bwd(const float* params, const float* feat, int in_ld, int n_gemm, const float* acts, const float* out,
+                               const float* out_grad, const int32_t* count, int capacity, float* scratch, float* params_grad,
+                               float* feat_grad, float* logit_add_grad, int logit_add_ld, hipStream_t st);
+void pp_launch_warp_layered_fwd(const float* params, const float* pts, const int32_t* count, int capacity, float out_range,
+                                float* acts, float* out, hipStream_t st);
+void pp_launch_warp_layered_bwd(const float* params, const float* pts, const float* acts, const float* out_grad, const int32_t* count,
+                                int capacity, float out_range, float* scratch, float* params_grad, float* pts_grad, hipStream_t st);

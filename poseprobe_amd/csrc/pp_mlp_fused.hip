@@ -8,7 +8,7 @@
 // MFMA B-operand layout, loaded once per work-group.  The inner loop is then ds_read_b128 (A operand, shared by the
 // four wavefronts) + v_mfma_f32_32x32x2_f32 only.
 //
-// Operand layouts (v_mfma_f32_32x32x2_f32, see pp_mlp.hip): lane = (l31, lh).  A: row l31, B: feature l31, both
+// Operand layouts (v_mfma_f32_32x32x2_f32, see pp_mlp_layered.hip): lane = (l31, lh).  A: row l31, B: feature l31, both
 // supply k = 8g + 4lh + j to the j-th MFMA of group g ("K-slot permutation": one 16-byte read feeds 4 MFMAs).
 // D: feature l31, rows (reg&3) + 8(reg>>2) + 4lh -> the 4 rows of a warp sample sit in 4 registers of one lane.
 #include "pp_common.h"
@@ -25,12 +25,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define LDA 132                 // LDS row stride of an activation tile (floats): 16-B aligned, 4-bank skew per row
 #define TILE_ROWS 64
-
-int pp_fused_wgs() {
-  const int opt = pp_opt(PP_OPT_MLP_WGS);          // of the calling entry point's context
-  if (opt > 0) return opt < 16 ? 16 : opt;        // the weight-gradient chains share the work-groups out over three layers
-  return pp_num_cus();
-}
 
 namespace {
 
@@ -290,9 +284,8 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd(const float* __restrict_
 }
 
 int pp_launch_warp_fused_fwd(const float* params, const float* pts, const int32_t* count, int capacity, float out_range,
-                             float* acts, float* out, hipStream_t st) {
-  const int ntiles = pp_div_up(capacity, 16);
-  const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
+                             float* acts, float* out, hipStream_t st, int wgs) {
+  const int grid = pp_fused_grid(pp_div_up(capacity, 16), wgs);
   hipLaunchKernelGGL(k_warp_fused_fwd, dim3(grid), dim3(256), 0, st, params, pts, count, capacity, out_range, acts, out);
   return 0;
 }
@@ -547,9 +540,8 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd(const float* __restrict_
 
 int pp_launch_warp_fused_bwd(const float* params, const float* pts, const float* acts, const float* out_grad,
                              const int32_t* count, int capacity, float out_range, float* ybar, float* params_grad,
-                             float* pts_grad, hipStream_t st) {
-  const int ntiles = pp_div_up(capacity, 16);
-  const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
+                             float* pts_grad, hipStream_t st, int wgs) {
+  const int grid = pp_fused_grid(pp_div_up(capacity, 16), wgs);
   hipLaunchKernelGGL(k_warp_fused_bwd, dim3(grid), dim3(256), 0, st, params, pts, acts, out_grad, count, capacity, out_range,
                      ybar, params_grad, pts_grad);
   return 0;
@@ -764,12 +756,9 @@ __global__ __launch_bounds__(256) void k_wgrad_chain(WgradLayer LA, WgradLayer L
 
 int pp_launch_wgrad_chain(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                           const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                          hipStream_t st, float* bA, float* bB, float* bC, float* part, const WgradLean* lean) {
-  if (pp_opt(PP_OPT_MLP_SPLIT) & 16)            // split-precision chain kernel (pp_mlp_split.hip): bias sums included when asked for
-    return pp_launch_wgrad_chain_s(YA, XA, WA, YB, XB, WB, YC, XC, WC, kxc, count, rmul, rcap, st, bA, bB, bC, part, lean);
+                          hipStream_t st, int wgs, float* bA, float* bB, float* bC) {
   WgradLayer LA{YA, XA, WA, bA}, LB{YB, XB, WB, bB}, LC{YC, XC, WC, bC};
-  const int npairs = pp_div_up(rcap, 2 * TILE_ROWS);
-  const int grid = npairs < PP_FUSED_WGS ? npairs : PP_FUSED_WGS;
+  const int grid = pp_fused_grid(pp_div_up(rcap, 2 * TILE_ROWS), wgs);
   if (kxc == 128)
     hipLaunchKernelGGL((k_wgrad_chain<128>), dim3(grid), dim3(256), 0, st, LA, LB, LC, count, rmul, rcap);
   else
@@ -938,9 +927,8 @@ __global__ __launch_bounds__(256) void k_rgb_fused_fwd(const float* __restrict__
 }
 
 int pp_launch_rgb_fused_fwd(const float* params, const float* feat, const int32_t* count, int capacity,
-                            const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st) {
-  const int ntiles = pp_div_up(capacity, TILE_ROWS);
-  const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
+                            const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st, int wgs) {
+  const int grid = pp_fused_grid(pp_div_up(capacity, TILE_ROWS), wgs);
   hipLaunchKernelGGL(k_rgb_fused_fwd, dim3(grid), dim3(256), 0, st, params, feat, count, capacity, logit_add, add_ld, acts, rgb);
   return 0;
 }
@@ -1113,9 +1101,8 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd(const float* __restrict__
 
 int pp_launch_rgb_fused_bwd(const float* params, const float* acts, const float* rgb, const float* rgb_grad,
                             const int32_t* count, int capacity, float* ybar, float* params_grad, float* feat_grad,
-                            float* logit_grad, int lg_ld, hipStream_t st) {
-  const int ntiles = pp_div_up(capacity, TILE_ROWS);
-  const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
+                            float* logit_grad, int lg_ld, hipStream_t st, int wgs) {
+  const int grid = pp_fused_grid(pp_div_up(capacity, TILE_ROWS), wgs);
   hipLaunchKernelGGL(k_rgb_fused_bwd, dim3(grid), dim3(256), 0, st, params, acts, rgb, rgb_grad, count, capacity, ybar,
                      params_grad, feat_grad, logit_grad, lg_ld);
   return 0;

@@ -492,9 +492,8 @@ static void launch_pack_variant(void (*with_pack)(P...), void (*without)(P...), 
 }
 
 int pp_launch_warp_fused_fwd_s(const float* params, const float* pts, const int32_t* count, int capacity, float out_range,
-                               float* acts, float* out, hipStream_t st, const float* pack, bool lean) {
-  const int ntiles = pp_div_up(capacity, 16);
-  const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
+                               float* acts, float* out, hipStream_t st, int wgs, const float* pack, bool lean) {
+  const int grid = pp_fused_grid(pp_div_up(capacity, 16), wgs);
   if (lean)
     launch_pack_variant(k_warp_fused_fwd_s<true, true>, k_warp_fused_fwd_s<false, true>, grid, st, pack, params, pts, count, capacity, out_range, acts, out);
   else
@@ -924,9 +923,8 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
 
 int pp_launch_warp_fused_bwd_s(const float* params, const float* pts, const float* acts, const float* out_grad,
                                const int32_t* count, int capacity, float out_range, float* ybar, float* params_grad,
-                               float* pts_grad, hipStream_t st, const float* pack, float* part, bool lean) {
-  const int ntiles = pp_div_up(capacity, 16);
-  const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
+                               float* pts_grad, hipStream_t st, int wgs, const float* pack, float* part, bool lean) {
+  const int grid = pp_fused_grid(pp_div_up(capacity, 16), wgs);
   if (lean)
     launch_pack_variant(k_warp_fused_bwd_s<true, true>, k_warp_fused_bwd_s<false, true>, grid, st, pack, params, pts, acts, out_grad, count,
                         capacity, out_range, ybar, params_grad, pts_grad, part);
@@ -1168,9 +1166,8 @@ __global__ __launch_bounds__(256) void k_rgb_fused_fwd_s(const float* __restrict
 }
 
 int pp_launch_rgb_fused_fwd_s(const float* params, const float* feat, const int32_t* count, int capacity,
-                              const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st, const float* pack) {
-  const int ntiles = pp_div_up(capacity, TILE_ROWS);
-  const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
+                              const float* logit_add, int add_ld, float* acts, float* rgb, hipStream_t st, int wgs, const float* pack) {
+  const int grid = pp_fused_grid(pp_div_up(capacity, TILE_ROWS), wgs);
   launch_pack_variant(k_rgb_fused_fwd_s<true>, k_rgb_fused_fwd_s<false>, grid, st, pack, params, feat, count, capacity, logit_add, add_ld, acts, rgb);
   return 0;
 }
@@ -1417,9 +1414,8 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
 
 int pp_launch_rgb_fused_bwd_s(const float* params, const float* acts, const float* rgb, const float* rgb_grad,
                               const int32_t* count, int capacity, float* ybar, float* params_grad, float* feat_grad,
-                              float* logit_grad, int lg_ld, hipStream_t st, const float* pack, float* part) {
-  const int ntiles = pp_div_up(capacity, TILE_ROWS);
-  const int grid = ntiles < PP_FUSED_WGS ? ntiles : PP_FUSED_WGS;
+                              float* logit_grad, int lg_ld, hipStream_t st, int wgs, const float* pack, float* part) {
+  const int grid = pp_fused_grid(pp_div_up(capacity, TILE_ROWS), wgs);
   launch_pack_variant(k_rgb_fused_bwd_s<true>, k_rgb_fused_bwd_s<false>, grid, st, pack, params, acts, rgb, rgb_grad, count, capacity, ybar,
                       params_grad, feat_grad, logit_grad, lg_ld, part);
   if (part) {
@@ -1864,13 +1860,13 @@ __global__ __launch_bounds__(ORD_RED_THREADS) void k_wgrad_reduce_s(WgradOperand
 
 int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                             const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
-                            hipStream_t st, float* bA, float* bB, float* bC, float* part, const WgradLean* lean) {
+                            hipStream_t st, int wgs_cu, float* bA, float* bB, float* bC, float* part, const WgradLean* lean) {
   WgradOperands LA{YA, XA, WA, bA}, LB{YB, XB, WB, bB}, LC{YC, XC, WC, bC};
   const WgradLean Z = lean ? *lean : WgradLean{nullptr, nullptr, nullptr};
   const int ntiles = pp_div_up(rcap, TILE_ROWS);
   // persistent work-groups, two per CU over the three layers, shared out in proportion to the layers' work; the kernel idles half
   // of them when the row count is small
-  const int wgs = 2 * PP_FUSED_WGS;
+  const int wgs = 2 * wgs_cu;
   // (a 64-wide layer costs about 3/4 of a 128-wide one: 3/4 of the bytes and of the values to convert, half the MFMAs)
   int nab = kxc == 128 ? wgs / 3 : (wgs * 4) / 11, nc = kxc == 128 ? wgs / 3 : wgs - 2 * ((wgs * 4) / 11);
   if (nab > ntiles) nab = ntiles;

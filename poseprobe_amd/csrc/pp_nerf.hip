@@ -658,40 +658,46 @@ __global__ __launch_bounds__(256) void k_nerf_encode_bwd(const float* __restrict
 static const int NERF_BM = 128;
 static constexpr int NERF_GEMM_WGS = 256;   // persistent work-groups per column block of the NT GEMMs (measured 256 = 512 > 384 > 128)
 static constexpr int NERF_TN_WGS = 128;     // row splits of a weight-gradient block: 128 x 4 blocks = 2 work-groups per CU, one round
-// Options (pp_context_set_option; defaults = the measured best on MI355X):
-//   nerf_split         every matrix product (forward, data and weight gradients) as three fp16 products with fp32 accumulation
-//                      (pp_gemm_split.h: error against fp64 equal to the fp32 matrix instructions', a third of their matrix-pipe
-//                      time); the 256-wide layers on pp_gemm_planes.h (weights pre-split into LDS images once per pass, 128 x 256
-//                      tile on eight wavefronts).  0 puts all of them on the fp32 matrix instructions (A/B runs, bisecting)
-#define NERF_SPLIT (pp_opt(PP_OPT_NERF_SPLIT) == 1)
-//   nerf_chain         forward pass: the eight feature layers and the density head as ONE kernel that keeps a 128-sample tile in LDS
-//                      across the layers (pp_nerf_trunk.h); needs nerf_split (every use below is behind the operand maxima `mx`);
-//                      0 = one GEMM per layer
-//                      bit 2 (value 3): the data-gradient chain of the backward pass likewise; the ReLU masks then travel in the
-//                      fused kernels' own layout, so both passes of a step must see the same value
-#define NERF_CHAIN (pp_opt(PP_OPT_NERF_CHAIN) & 1)
-#define NERF_CHAIN_BWD (pp_opt(PP_OPT_NERF_CHAIN) == 3)
-//   nerf_chain_nw      wavefronts per work-group of the fused chains: 8 = one work-group on a 128-sample tile per CU, 4 = two work-groups on
-//                      64-sample tiles per CU (one's epilogue beside the other's matrix instructions; twice the weight traffic from L2)
-#define NERF_CHAIN_NW pp_opt(PP_OPT_NERF_CHAIN_NW)
-//   nerf_chain_head    1: the colour head's 288 -> 128 layer rides as a ninth stage of the fused forward chain
-#define NERF_CHAIN_HEAD (pp_opt(PP_OPT_NERF_CHAIN_HEAD) == 1)
+// The scene-branch options (pp_context_set_option; defaults = the measured best on MI355X) of one call, resolved once by pp_nerf_fwd /
+// pp_nerf_bwd from the context they are handed.  The fused chains work on the operand maxima that only the split-precision path
+// records, so chain_fwd, chain_bwd and head are false without `split`, whatever their options say.
+struct NerfRoute {
+  // nerf_split: every matrix product (forward, data and weight gradients) as three fp16 products with fp32 accumulation
+  // (pp_gemm_split.h: error against fp64 equal to the fp32 matrix instructions', a third of their matrix-pipe time); the 256-wide
+  // layers on pp_gemm_planes.h (weights pre-split into LDS images once per pass, 128 x 256 tile on eight wavefronts).  false puts
+  // all of them on the fp32 matrix instructions (A/B runs, bisecting)
+  bool split;
+  // nerf_chain bit 1: forward pass with the eight feature layers and the density head as ONE kernel that keeps a 128-sample tile
+  // in LDS across the layers (pp_nerf_trunk.h); false = one GEMM per layer
+  bool chain_fwd;
+  // nerf_chain = 3: the data-gradient chain of the backward pass likewise; the ReLU masks then travel in the fused kernels' own
+  // layout, so both passes of a step must see the same value
+  bool chain_bwd;
+  // nerf_chain_nw: wavefronts per work-group of the fused chains: 8 = one work-group on a 128-sample tile per CU, 4 = two
+  // work-groups on 64-sample tiles per CU (one's epilogue beside the other's matrix instructions; twice the weight traffic from L2)
+  int nw;
+  // nerf_chain_head: the colour head's 288 -> 128 layer rides as a ninth stage of the fused forward chain
+  bool head;
+  explicit NerfRoute(const int* o)
+      : split(o[PP_OPT_NERF_SPLIT] == 1), chain_fwd(split && (o[PP_OPT_NERF_CHAIN] & 1)), chain_bwd(split && o[PP_OPT_NERF_CHAIN] == 3),
+        nw(o[PP_OPT_NERF_CHAIN_NW] == 4 ? 4 : 8), head(chain_fwd && o[PP_OPT_NERF_CHAIN_HEAD] == 1) {}
+};
 
 template <int EPI>
-static void nerf_gemm(hipStream_t st, const float* A, int lda, const float* W, int ldw, int K, int Nout, const float* bias,
+static void nerf_gemm(hipStream_t st, bool split, const float* A, int lda, const float* W, int ldw, int K, int Nout, const float* bias,
                       const float* mask, int ldm, float* C, int ldc, const int32_t* count, int rows,
                       const float* a_max = nullptr, const float* w_max = nullptr, float* c_max = nullptr,
                       uint16_t* bits = nullptr, const _Float16* wimg = nullptr) {
   const int tiles = pp_div_up(rows, NERF_BM);
   dim3 b(256);
-  if (wimg && bits && EPI != EPI_PLAIN && Nout == 256 && (K & 31) == 0 && a_max && w_max && NERF_SPLIT) {
+  if (wimg && bits && EPI != EPI_PLAIN && Nout == 256 && (K & 31) == 0 && a_max && w_max && split) {
     const int cus = pp_num_cus();
     constexpr int E = (EPI == EPI_PLAIN) ? EPI_MASK : EPI;
     hipLaunchKernelGGL((k_gemm256p<E>), dim3(tiles < cus ? tiles : cus), dim3(512), 0, st, A, lda, wimg, K, bias, C, ldc, count, rows,
                        a_max, w_max, c_max, bits);
     return;
   }
-  if (NERF_SPLIT && a_max && w_max) {
+  if (split && a_max && w_max) {
     if (Nout <= 64) {
       dim3 g(tiles < 2 * NERF_GEMM_WGS ? tiles : 2 * NERF_GEMM_WGS, 1);
       hipLaunchKernelGGL((k_gemm128s<EPI, 64>), g, b, 0, st, A, lda, W, ldw, K, Nout, bias, mask, ldm, C, ldc, count, rows, a_max,
@@ -719,12 +725,12 @@ static void nerf_gemm(hipStream_t st, const float* A, int lda, const float* W, i
 }
 
 // ord: workspace of the ordered flush (pp_nerf_ordered_attach; nullptr = float atomics): NERF_TN_WGS * 4 slots serve every product
-static void nerf_gemm_tn(hipStream_t st, const float* Y, int ldy, int N, const float* X, int ldx, int Kx, float* Wbar,
+static void nerf_gemm_tn(hipStream_t st, bool split, const float* Y, int ldy, int N, const float* X, int ldx, int Kx, float* Wbar,
                          float* bbar, const int32_t* count, int rows, const float* y_max = nullptr, const float* x_max = nullptr,
                          float* ord = nullptr) {
   const int blocks = (N / 128) * pp_div_up(Kx, 128);
   dim3 g(NERF_TN_WGS * 4 / blocks, blocks), b(256);       // ~ 4 x NERF_TN_WGS work-groups whatever the block count (2, 3, 4 or 6)
-  if (NERF_SPLIT && y_max && x_max) {   // two work-groups per CU since the operand conversion is three instructions per pair: 2.90
+  if (split && y_max && x_max) {   // two work-groups per CU since the operand conversion is three instructions per pair: 2.90
                                         // vs 2.99 ms per scene step (round 1, with the compiler's conversion: one per CU was best,
                                         // 3.69 vs 3.85 ms)
     hipLaunchKernelGGL(k_gemm_tn_tr, g, b, 0, st, Y, ldy, X, ldx, Kx, Wbar, ldx, bbar, count, rows, y_max, x_max, ord);
@@ -738,14 +744,14 @@ static void nerf_gemm_tn(hipStream_t st, const float* Y, int ldy, int N, const f
 extern "C" int pp_nerf_fwd(const float* params, const float* center, const float* ray, const float* depth,
                            const float* bands, const int32_t* count, int32_t n_rays, int32_t n_samples, float* acts,
                            float* rgb_samples, float* density_samples, void* ctx, void* stream) {
-  PPOptScope scope(ctx);
+  const NerfRoute rt(pp_options(ctx));
   PP_REQUIRE(params && center && ray && depth && bands && count && acts && rgb_samples && density_samples, "null pointer");
   PP_REQUIRE(n_rays > 0 && n_samples > 0 && (int64_t)n_rays * n_samples < (1LL << 30), "bad sizes");
   hipStream_t st = pp_stream(stream);
   const int M = n_rays * n_samples;
   const NerfLayout L = nerf_layout();
   NerfActs A = nerf_acts(acts, M);
-  float* mx = NERF_SPLIT ? A.mx : nullptr;
+  float* mx = rt.split ? A.mx : nullptr;
   if (mx) {
     hipMemsetAsync(mx, 0, MX_SLOTS * sizeof(float), st);
     NerfWmaxJobs J;
@@ -754,11 +760,11 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
     J.src[8] = params + L.r0; J.n[8] = 128 * 288;
     hipLaunchKernelGGL(k_nerf_wmax, dim3(16, 9), dim3(256), 0, st, J, mx);
     hipLaunchKernelGGL(k_nerf_enc_bound, dim3(n_rays < 256 ? pp_div_up(n_rays, 4) : 64), dim3(256), 0, st, center, ray, depth, n_rays, n_samples, mx);
-    if (NERF_CHAIN) {
+    if (rt.chain_fwd) {
       TrunkPackJobs P;
       for (int l = 0; l < 8; ++l) { P.src[l] = params + L.w[l]; P.ld[l] = NERF_IN_LD[l]; P.mx_w[l] = MX_W0 + l; }
       P.src[8] = params + L.r0; P.ld[8] = 288; P.mx_w[8] = MX_R0;        // the colour head's hidden layer rides as a ninth stage
-      P.nsteps = NERF_CHAIN_HEAD ? TR_STEPS + 10 : TR_STEPS; P.nw = NERF_CHAIN_NW == 4 ? 4 : 8;
+      P.nsteps = rt.head ? TR_STEPS + 10 : TR_STEPS; P.nw = rt.nw;
       hipLaunchKernelGGL(k_pack_trunk<false>, dim3(P.nsteps * 4), dim3(256), 0, st, P, mx, reinterpret_cast<unsigned char*>(A.wimg[0]));
     } else {
       PlanePackJobs P;
@@ -771,7 +777,7 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
   }
   hipLaunchKernelGGL(k_nerf_encode, dim3(pp_div_up(M, 16)), dim3(256), 0, st, center, ray, depth, bands, M,
                      n_samples, A.enc, A.a[3], A.a[7]);
-  if (mx && NERF_CHAIN) {
+  if (rt.chain_fwd) {
     TrunkArgs T;
     memset(&T, 0, sizeof(T));
     T.in = A.enc; T.in_ld = 64;
@@ -782,21 +788,21 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
     T.wstream = reinterpret_cast<const unsigned char*>(A.wimg[0]);
     T.wd = params + L.wd; T.bd = params + L.bd; T.raw = A.raw; T.density = density_samples;
     T.mx = mx; T.mx_in = MX_ENC;
-    T.head = NERF_CHAIN_HEAD; T.out[8] = A.h; T.ld[8] = 128; T.bias[8] = params + L.br0; T.mx_w[8] = MX_R0; T.in2 = A.a[7] + 256; T.in2_ld = 288;
+    T.head = rt.head; T.out[8] = A.h; T.ld[8] = 128; T.bias[8] = params + L.br0; T.mx_w[8] = MX_R0; T.in2 = A.a[7] + 256; T.in2_ld = 288;
     const int cus = pp_num_cus();
-    if (NERF_CHAIN_NW == 4) {                       // 64-row tiles, two work-groups per CU
+    if (rt.nw == 4) {                       // 64-row tiles, two work-groups per CU
       const int tiles = pp_div_up(M, 64), grid = tiles < 2 * cus ? tiles : 2 * cus;
-      if (NERF_CHAIN_BWD) hipLaunchKernelGGL((k_nerf_trunk<false, true, 4>), dim3(grid), dim3(256), 0, st, T, count, M);
+      if (rt.chain_bwd) hipLaunchKernelGGL((k_nerf_trunk<false, true, 4>), dim3(grid), dim3(256), 0, st, T, count, M);
       else hipLaunchKernelGGL((k_nerf_trunk<false, false, 4>), dim3(grid), dim3(256), 0, st, T, count, M);
     } else {
       const int tiles = pp_div_up(M, 128), grid = tiles < cus ? tiles : cus;
-      if (NERF_CHAIN_BWD) hipLaunchKernelGGL((k_nerf_trunk<false, true, 8>), dim3(grid), dim3(512), 0, st, T, count, M);
+      if (rt.chain_bwd) hipLaunchKernelGGL((k_nerf_trunk<false, true, 8>), dim3(grid), dim3(512), 0, st, T, count, M);
       else hipLaunchKernelGGL((k_nerf_trunk<false, false, 8>), dim3(grid), dim3(512), 0, st, T, count, M);
     }
   } else {
     const float* in = A.enc;
     for (int l = 0; l < 8; ++l) {
-      nerf_gemm<EPI_RELU>(st, in, NERF_IN_LD[l], params + L.w[l], NERF_IN_LD[l], NERF_IN_LD[l], 256, params + L.b[l], nullptr, 0,
+      nerf_gemm<EPI_RELU>(st, rt.split, in, NERF_IN_LD[l], params + L.w[l], NERF_IN_LD[l], NERF_IN_LD[l], 256, params + L.b[l], nullptr, 0,
                           A.a[l], NERF_OUT_LD[l], count, M, mx ? mx + (l == 0 ? MX_ENC : MX_A0 + l - 1) : nullptr,
                           mx ? mx + MX_W0 + l : nullptr, mx ? mx + MX_A0 + l : nullptr, A.bits[l], A.wimg[l]);
       in = A.a[l];
@@ -804,8 +810,8 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
     hipLaunchKernelGGL(k_nerf_density_fwd, dim3(pp_div_up(M, 4)), dim3(256), 0, st, A.a[6], params + L.wd, params + L.bd, M,
                        A.raw, density_samples);
   }
-  if (!(mx && NERF_CHAIN && NERF_CHAIN_HEAD))         // (else the fused chain has produced the head's hidden layer as its ninth stage)
-    nerf_gemm<EPI_RELU>(st, A.a[7], 288, params + L.r0, 288, 288, 128, params + L.br0, nullptr, 0, A.h, 128, count, M,
+  if (!rt.head)         // (else the fused chain has produced the head's hidden layer as its ninth stage)
+    nerf_gemm<EPI_RELU>(st, rt.split, A.a[7], 288, params + L.r0, 288, 288, 128, params + L.br0, nullptr, 0, A.h, 128, count, M,
                         mx ? mx + MX_A0 + 7 : nullptr, mx ? mx + MX_R0 : nullptr, nullptr);
   hipLaunchKernelGGL(k_nerf_rgb_fwd, dim3(pp_div_up(M * 16, 256)), dim3(256), 0, st, params + L.r1, params + L.br1, A.h, M,
                      rgb_samples);
@@ -817,13 +823,13 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
                            int32_t n_rays, int32_t n_samples, const float* acts, const float* rgb_samples, const float* g_rgb_samples,
                            const float* g_density_samples, float* scratch, float* params_grad, float* g_center, float* g_ray,
                            void* ctx, void* stream) {
-  PPOptScope scope(ctx);
+  const NerfRoute rt(pp_options(ctx));
   PP_REQUIRE(params && ray && depth && count && acts && rgb_samples && g_rgb_samples && g_density_samples && scratch &&
                  params_grad && g_center && g_ray, "null pointer");
   PP_REQUIRE(n_rays > 0 && n_samples > 0 && (int64_t)n_rays * n_samples < (1LL << 30), "bad sizes");
   hipStream_t st = pp_stream(stream);
   float* ord = ctx ? static_cast<const PPContext*>(ctx)->nerf_ord : nullptr;
-  PP_REQUIRE(!ord || NERF_SPLIT, "an ordered-flush workspace is attached (pp_nerf_ordered_attach) and nerf_split = 0 selects the "
+  PP_REQUIRE(!ord || rt.split, "an ordered-flush workspace is attached (pp_nerf_ordered_attach) and nerf_split = 0 selects the "
                                  "fp32-instruction weight-gradient kernel, which has no ordered flush");
   const int R = n_rays, S = n_samples, M = R * S;
   const NerfLayout L = nerf_layout();
@@ -860,9 +866,9 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
   hipLaunchKernelGGL(k_nerf_wd_column, dim3(1), b, 0, st, params + L.wd, WT[7]);
 
   // split-precision path: operand maxima of the gradient tensors are recorded by their producers (slots MX_DH .. MX_DHSUM)
-  float* mx = NERF_SPLIT ? A.mx : nullptr;
+  float* mx = rt.split ? A.mx : nullptr;
   if (mx) hipMemsetAsync(mx + MX_DH, 0, (MX_DHSUM - MX_DH + 1) * sizeof(float), st);
-  const bool chain = mx && NERF_CHAIN_BWD;
+  const bool chain = rt.chain_bwd;
   float* DY[7];                                    // d(pre-activation of layer l), l = 0 .. 6, for the fused chain
   for (int l = 0; l < 7; ++l) DY[l] = part + NERF_PART_FLOATS + (size_t)l * M * 256;
   if (chain) {
@@ -890,9 +896,9 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
     hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(388, 64)), dim3(1024), 0, st, part, wgs, params_grad + L.r1, 384, params_grad + L.br1, 3,
                        slot(MX_DH));
   }
-  nerf_gemm_tn(st, dH, 128, 128, A.a[7], 288, 288, params_grad + L.r0, params_grad + L.br0, count, M, slot(MX_DH), slot(MX_A0 + 7), ord);
+  nerf_gemm_tn(st, rt.split, dH, 128, 128, A.a[7], 288, 288, params_grad + L.r0, params_grad + L.br0, count, M, slot(MX_DH), slot(MX_A0 + 7), ord);
   hipLaunchKernelGGL(k_nerf_ray_sum, dim3(R < 512 ? R : 512), dim3(512), 0, st, dH, R, S, dHsum, slot(MX_DHSUM));
-  nerf_gemm<EPI_PLAIN>(st, dHsum, 128, R0T + 256 * 128, 128, 128, 32, nullptr, nullptr, 0, dView, 32, count, R, slot(MX_DHSUM),
+  nerf_gemm<EPI_PLAIN>(st, rt.split, dHsum, 128, R0T + 256 * 128, 128, 128, 32, nullptr, nullptr, 0, dView, 32, count, R, slot(MX_DHSUM),
                        slot(MX_R0), nullptr);
   if (chain) {
     // d raw (column 256 of P) and the density head's own gradients first: the chain reads that column
@@ -914,26 +920,26 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
     T.wd = params + L.wd; T.draw = P + 256; T.draw_ld = 288;
     T.mx = mx; T.mx_in = MX_DH;
     const int cus = pp_num_cus();
-    if (NERF_CHAIN_NW == 4) {
+    if (rt.nw == 4) {
       const int tiles = pp_div_up(M, 64);
       hipLaunchKernelGGL((k_nerf_trunk<true, true, 4>), dim3(tiles < 2 * cus ? tiles : 2 * cus), dim3(256), 0, st, T, count, M);
     } else {
       const int tiles = pp_div_up(M, 128);
       hipLaunchKernelGGL((k_nerf_trunk<true, true, 8>), dim3(tiles < cus ? tiles : cus), dim3(512), 0, st, T, count, M);
     }
-    nerf_gemm_tn(st, P, 288, 256, A.a[6], 256, 256, params_grad + L.w[7], params_grad + L.b[7], count, M, slot(MX_P), slot(MX_A0 + 6), ord);
+    nerf_gemm_tn(st, rt.split, P, 288, 256, A.a[6], 256, 256, params_grad + L.w[7], params_grad + L.b[7], count, M, slot(MX_P), slot(MX_A0 + 6), ord);
     for (int l = 6; l >= 1; --l)
-      nerf_gemm_tn(st, DY[l], 256, 256, A.a[l - 1], NERF_OUT_LD[l - 1], NERF_IN_LD[l], params_grad + L.w[l], params_grad + L.b[l], count, M,
+      nerf_gemm_tn(st, rt.split, DY[l], 256, 256, A.a[l - 1], NERF_OUT_LD[l - 1], NERF_IN_LD[l], params_grad + L.w[l], params_grad + L.b[l], count, M,
                    slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1), ord);
-    nerf_gemm<EPI_PLAIN>(st, DY[4], 256, WT[4] + 256 * 256, 256, 256, 64, nullptr, nullptr, 0, dEncS, 64, count, M,
+    nerf_gemm<EPI_PLAIN>(st, rt.split, DY[4], 256, WT[4] + 256 * 256, 256, 256, 64, nullptr, nullptr, 0, dEncS, 64, count, M,
                          slot(MX_DY6 + 2), slot(MX_W0 + 4), nullptr);
-    nerf_gemm_tn(st, DY[0], 256, 256, A.enc, 64, 64, params_grad + L.w[0], params_grad + L.b[0], count, M, slot(MX_DY6 + 6),
+    nerf_gemm_tn(st, rt.split, DY[0], 256, 256, A.enc, 64, 64, params_grad + L.w[0], params_grad + L.b[0], count, M, slot(MX_DY6 + 6),
                  slot(MX_ENC), ord);
-    nerf_gemm<EPI_PLAIN>(st, DY[0], 256, WT[0], 256, 256, 64, nullptr, nullptr, 0, dEnc0, 64, count, M, slot(MX_DY6 + 6),
+    nerf_gemm<EPI_PLAIN>(st, rt.split, DY[0], 256, WT[0], 256, 256, 64, nullptr, nullptr, 0, dEnc0, 64, count, M, slot(MX_DY6 + 6),
                          slot(MX_W0), nullptr);
   } else {
     // last feature layer: columns 0..255 through the colour head, column 256 from the density
-    nerf_gemm<EPI_MASK>(st, dH, 128, R0T, 128, 128, 256, nullptr, A.a[7], 288, P, 288, count, M, slot(MX_DH), slot(MX_R0),
+    nerf_gemm<EPI_MASK>(st, rt.split, dH, 128, R0T, 128, 128, 256, nullptr, A.a[7], 288, P, 288, count, M, slot(MX_DH), slot(MX_R0),
                         slot(MX_P), A.bits[7], r0t_img);
     {
       const int wgs = min(pp_div_up(M, NERF_DSTRIP), NERF_PART_WGS);
@@ -941,26 +947,26 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
       hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(258, 64)), dim3(1024), 0, st, part, wgs, params_grad + L.wd, 256, params_grad + L.bd, 1,
                          slot(MX_P));
     }
-    nerf_gemm_tn(st, P, 288, 256, A.a[6], 256, 256, params_grad + L.w[7], params_grad + L.b[7], count, M, slot(MX_P), slot(MX_A0 + 6), ord);
-    nerf_gemm<EPI_MASK>(st, P, 288, WT[7], 288, 288, 256, nullptr, A.a[6], 256, Q, 256, count, M, slot(MX_P), slot(MX_W0 + 7),
+    nerf_gemm_tn(st, rt.split, P, 288, 256, A.a[6], 256, 256, params_grad + L.w[7], params_grad + L.b[7], count, M, slot(MX_P), slot(MX_A0 + 6), ord);
+    nerf_gemm<EPI_MASK>(st, rt.split, P, 288, WT[7], 288, 288, 256, nullptr, A.a[6], 256, Q, 256, count, M, slot(MX_P), slot(MX_W0 + 7),
                         slot(MX_DY6), A.bits[6], wt7_img);
     float* cur = Q;
     float* nxt = P;
     for (int l = 6; l >= 1; --l) {                   // cur = d(pre-activation of layer l), [M][256]
       const float* x = A.a[l - 1];
       const int ldx = NERF_OUT_LD[l - 1];            // 320 for layer 4's input (features + skip columns)
-      nerf_gemm_tn(st, cur, 256, 256, x, ldx, NERF_IN_LD[l], params_grad + L.w[l], params_grad + L.b[l], count, M,
+      nerf_gemm_tn(st, rt.split, cur, 256, 256, x, ldx, NERF_IN_LD[l], params_grad + L.w[l], params_grad + L.b[l], count, M,
                    slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1), ord);
-      nerf_gemm<EPI_MASK>(st, cur, 256, WT[l], 256, 256, 256, nullptr, x, ldx, nxt, 256, count, M, slot(MX_DY6 + 6 - l),
+      nerf_gemm<EPI_MASK>(st, rt.split, cur, 256, WT[l], 256, 256, 256, nullptr, x, ldx, nxt, 256, count, M, slot(MX_DY6 + 6 - l),
                           slot(MX_W0 + l), slot(MX_DY6 + 7 - l), A.bits[l - 1], wt_img[l]);
       if (l == 4)                                    // skip columns: gradient of the encoding, no activation in between
-        nerf_gemm<EPI_PLAIN>(st, cur, 256, WT[4] + 256 * 256, 256, 256, 64, nullptr, nullptr, 0, dEncS, 64, count, M,
+        nerf_gemm<EPI_PLAIN>(st, rt.split, cur, 256, WT[4] + 256 * 256, 256, 256, 64, nullptr, nullptr, 0, dEncS, 64, count, M,
                              slot(MX_DY6 + 2), slot(MX_W0 + 4), nullptr);
       float* t = cur; cur = nxt; nxt = t;
     }
-    nerf_gemm_tn(st, cur, 256, 256, A.enc, 64, 64, params_grad + L.w[0], params_grad + L.b[0], count, M, slot(MX_DY6 + 6),
+    nerf_gemm_tn(st, rt.split, cur, 256, 256, A.enc, 64, 64, params_grad + L.w[0], params_grad + L.b[0], count, M, slot(MX_DY6 + 6),
                  slot(MX_ENC), ord);
-    nerf_gemm<EPI_PLAIN>(st, cur, 256, WT[0], 256, 256, 64, nullptr, nullptr, 0, dEnc0, 64, count, M, slot(MX_DY6 + 6),
+    nerf_gemm<EPI_PLAIN>(st, rt.split, cur, 256, WT[0], 256, 256, 64, nullptr, nullptr, 0, dEnc0, 64, count, M, slot(MX_DY6 + 6),
                          slot(MX_W0), nullptr);
   }
   hipLaunchKernelGGL(k_nerf_encode_bwd, dim3(R), b, 0, st, A.enc, dEnc0, dEncS, dView, A.a[7], ray, depth, R, S, g_center,

@@ -249,7 +249,6 @@ extern "C" int pp_grid_tv_adam_step_sparse(const float* p_in, float* p_out, floa
                                     float tv_scale, float grad_scale, float lr, float beta1, float beta2, float eps,
                                     int32_t step, float* tv_out, const uint8_t* touched,
                                             uint8_t* touched_clear, void* ctx, void* stream) {
-  PPOptScope scope(ctx);
   PP_REQUIRE(p_in && p_out && grad && exp_avg && exp_avg_sq, "null pointer");
   const int32_t size[3] = {size_x, size_y, size_z};
   PP_REQUIRE(p_in != p_out, "p_in and p_out must be distinct (ping-pong) buffers");
@@ -265,7 +264,7 @@ extern "C" int pp_grid_tv_adam_step_sparse(const float* p_in, float* p_out, floa
   // chunks: a multiple of 8 when possible so that chunk <-> XCD (blocks are dealt round-robin over the 8 XCDs)
   // measured (tools/bench_grid.py, MI355X): 16 chunks win from 128 planes up (160^3: 272 -> 256 us dense), 8 below
   int n_chunks = nx >= 128 ? 16 : (nx >= 8 ? 8 : nx);
-  { const int c = pp_opt(PP_OPT_GRID_CHUNKS); if (c > 0 && c <= nx) n_chunks = c; }   // tuning hook (option "grid_chunks")
+  { const int c = pp_options(ctx)[PP_OPT_GRID_CHUNKS]; if (c > 0 && c <= nx) n_chunks = c; }   // tuning hook (option "grid_chunks")
   const int chunk_len = (nx + n_chunks - 1) / n_chunks;
   n_chunks = (nx + chunk_len - 1) / chunk_len;
   const int tiles = (int)((plane + 255) / 256);

@@ -278,3 +278,90 @@ def test_forward_only_mode_gives_the_same_outputs_without_keeping_activations():
         ops.warp_fwd(warp_p, pts, count, cap, 1.5, None, out_b, fp32)
     with pytest.raises(_lib.PoseProbeError):
         ops.rgbnet_fwd(rgb_p, feat, count, cap, None, rgb_b, fp32)
+
+
+def _thread_case_inputs(M, cap, dev='cuda'):
+    from poseprobe_amd.engine import pack_rgbnet
+    g = torch.Generator().manual_seed(41)
+    P, rp = _pack(_warp_params(3)), pack_rgbnet(_rgb_params(5))
+    warp_p = torch.zeros(P.numel() + 60, device=dev); warp_p[:P.numel()] = P.to(dev)
+    rgb_p = torch.zeros(rp.numel() + 60, device=dev); rgb_p[:rp.numel()] = rp.to(dev)
+    feat = torch.zeros(cap, 64); feat[:, :57] = torch.randn(cap, 57, generator=g)
+    return dict(warp_p=warp_p, rgb_p=rgb_p, pts=(torch.randn(cap, 3, generator=g) * 0.5).to(dev), og=torch.randn(cap, 16, generator=g).to(dev),
+                feat=feat.to(dev), gr=torch.randn(cap, 3, generator=g).to(dev), count=torch.tensor([M], dtype=torch.int32, device=dev))
+
+
+def _thread_case_round(inp, cap, cx, buf=None):
+    """warp_fwd, warp_bwd_data, rgbnet_fwd, rgbnet_bwd_data on the current stream with context cx -> (the tensors that do not pass
+    through float atomics, (stage2 of the warp net, stage2 of rgbnet))."""
+    from poseprobe_amd import ops
+    dev = 'cuda'
+    if buf is None:
+        buf = dict(w_acts=torch.empty(4 * cap * 4 * 128, device=dev), w_out=torch.empty(cap, 16, device=dev),
+                   w_scratch=torch.empty(3 * cap * 4 * 128 + 49152, device=dev), pts_grad=torch.empty(cap, 3, device=dev),
+                   r_acts=torch.empty(3 * cap * 128, device=dev), rgb=torch.empty(cap, 3, device=dev),
+                   r_scratch=torch.empty(3 * cap * 128 + 49152, device=dev), feat_grad=torch.empty(cap, 64, device=dev),
+                   w_pgrad=torch.empty_like(inp['warp_p']), r_pgrad=torch.empty_like(inp['rgb_p']))
+    for k, t in buf.items():                                  # pts_grad accumulates; rows past the count are never written
+        t.fill_(float('nan') if k.endswith('acts') else 0.25 if k == 'pts_grad' else 0.0)
+    ops.warp_fwd(inp['warp_p'], inp['pts'], inp['count'], cap, OUT_RANGE, buf['w_acts'], buf['w_out'], cx)
+    s_w = ops.warp_bwd_data(inp['warp_p'], inp['pts'], buf['w_acts'], inp['og'], inp['count'], cap, OUT_RANGE, buf['w_scratch'],
+                            buf['w_pgrad'], buf['pts_grad'], cx)
+    ops.rgbnet_fwd(inp['rgb_p'], inp['feat'], inp['count'], cap, buf['r_acts'], buf['rgb'], cx)
+    s_r = ops.rgbnet_bwd_data(inp['rgb_p'], buf['r_acts'], buf['rgb'], inp['gr'], inp['count'], cap, buf['r_scratch'], buf['r_pgrad'],
+                              buf['feat_grad'], cx)
+    return buf, (s_w, s_r)
+
+
+def test_two_contexts_on_two_threads_at_once_each_keep_their_own_options():
+    """Options travel with the context a call is handed and nowhere else, so two host threads may run two contexts with different
+    arithmetic (mlp_split = 0 against the default) and grid (mlp_wgs = 48) at the same time, each on its own stream.  Every
+    iteration of either thread must give, bit for bit, what the same calls give alone on the main thread with the same context -
+    for every tensor that does not pass through float atomics - and hand back its own context's stage2.  M = 100 at capacity
+    128: a ragged last 64-row tile; the warp net's 400 rows span seven tiles."""
+    import threading
+    from poseprobe_amd import ops
+    M, cap, iters = 100, 128, 20
+    compared = ('w_out', 'w_acts', 'w_scratch', 'pts_grad', 'rgb', 'r_acts', 'r_scratch', 'feat_grad')
+    inp = _thread_case_inputs(M, cap)
+    cases = {'A': (ops.Context(mlp_split=0), (0, 0)), 'B': (ops.Context(mlp_wgs=48), (1, 1))}
+    alone = {}
+    for name, (cx, want) in cases.items():
+        alone[name], stage2 = _thread_case_round(inp, cap, cx)
+        assert stage2 == want, f'context {name} alone: stage2 {stage2}'
+    torch.cuda.synchronize()
+    # the two contexts do compute different bits: a thread that ran with the other's options would be caught
+    assert not torch.equal(alone['A']['w_out'][:M], alone['B']['w_out'][:M]) and not torch.equal(alone['A']['rgb'][:M], alone['B']['rgb'][:M])
+    barrier = threading.Barrier(2)
+    result = {}
+
+    def work(name):
+        try:
+            cx, want = cases[name]
+            ref = alone[name]
+            with torch.cuda.stream(torch.cuda.Stream()):
+                differing = {k: torch.zeros((), dtype=torch.int64, device='cuda') for k in compared}
+                stages, buf = [], None
+                barrier.wait(timeout=60)
+                for _ in range(iters):
+                    buf, stage2 = _thread_case_round(inp, cap, cx, buf)
+                    stages.append(stage2)
+                    for k in compared:                                   # on this thread's stream, no host wait inside the loop
+                        differing[k] += (buf[k].view(torch.int32) != ref[k].view(torch.int32)).sum()
+                torch.cuda.current_stream().synchronize()
+            result[name] = (stages, {k: int(v) for k, v in differing.items()}, want)
+        except BaseException as e:                                       # reported by the main thread
+            barrier.abort()
+            result[name] = e
+
+    threads = [threading.Thread(target=work, args=(n,)) for n in cases]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    for name in cases:
+        if isinstance(result[name], BaseException):
+            raise result[name]
+        stages, differing, want = result[name]
+        assert stages == [want] * iters, f'thread {name}: stage2 per iteration {stages}, expected {want}'
+        assert not any(differing.values()), f'thread {name}: elements that differ from the run alone, summed over {iters} iterations: {differing}'

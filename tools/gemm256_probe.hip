@@ -10,8 +10,6 @@
 
 #include "pp_gemm_planes.h"
 
-int pp_fused_wgs() { return 256; }
-
 int main(int argc, char** argv) {
   const int M = argc > 1 ? atoi(argv[1]) : 130944, K = 256, N = 256;
   std::vector<float> hA((size_t)M * K), hW((size_t)N * K), hb(N);
