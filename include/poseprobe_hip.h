@@ -45,6 +45,7 @@ const char* pp_last_error(void);
  * ownership from stage 1 to stage 2 explicitly -, pp_nerf_fwd / pp_nerf_bwd, pp_grid_tv_adam_step{,_sparse});
  * pp_scene gained `sdf_index_exact`; new: pp_sdf_crossing_dense_bwd, pp_context_set_option / pp_context_get_option.  4 (this header): the
  * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
+ * Entry points added without a version change (no existing signature moved): the pp_reproj_* group.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
  * (poseprobe_amd/_lib.py does): the signatures changed, so a stale caller would pass a stream where a pointer is read. */
 #define PP_ABI_VERSION 4
@@ -564,6 +565,48 @@ int pp_nerf_corres_loss(const float* depth0, const float* depth1, int32_t n_pair
 int pp_nerf_pair_pose_bwd(const float* g_center, const float* g_ray, const float* dir_cam, int32_t n_pairs, const float* w2c,
                           const float* g_w2c, int32_t n_views, int32_t view_self, int32_t view_other, float* g_c2w,
                           void* stream);
+
+/* ---------------------------------------------------------------- object branch: reprojection + near-surface pose terms
+ * lib/recon_scene.py:321-369 (get_project_error) as a second small ray batch of the object branch.  Row r: own view own[r],
+ * other view other[r] (int32), pixel pix[r] (x, y) in the own view, matched pixel match[r] in the other view, confidence
+ * conf[r].  Every per-row array below holds `capacity` rows; rows at or beyond n_rows (and rows whose view index lies outside
+ * [0, n_views)) are never read from the row inputs and contribute nothing: their per-row outputs are written as zeros, their
+ * rays miss the box.  intr [n_views,4] (fx, fy, cx, cy), c2w / w2c [n_views,3,4].
+ * pp_reproj_rays: cam = [(x - cx) / fx, (y - cy) / fy, 1] (no half-pixel shift, inverse_y), rays_d = viewdirs =
+ * normalize(R_c2w cam), rays_o = t_c2w of the own view (recon_scene.py:93-113 with mode 'no_center'). */
+int pp_reproj_rays(const pp_scene* sc, const int32_t* own, const float* pix, int32_t n_rows, int32_t capacity, const float* intr,
+                   const float* c2w, int32_t n_views, float* rays_o, float* rays_d, float* viewdirs, void* stream);
+/* Dense sample positions of the zero-crossing query (Voxurf.sample_ray_ori, voxurf_coarse.py:697-719, without the in-box
+ * compaction): pts[r, k] = o + d (t_min + stepsize voxel_size (k + jitter[r]) / |d|), k < sc->n_samples; pts [n_rays, S, 3]. */
+int pp_reproj_dense_pts(const pp_scene* sc, const float* rays_o, const float* rays_d, const float* t_min, const float* jitter,
+                        int32_t n_rays, float* pts, void* stream);
+/* Loss and every gradient that does not need the renderer.  render = 0: the surface point p [capacity,3] and the hit flag hit
+ * [capacity] (uint8) are inputs (pp_sdf_first_crossing); render = 1 (p = hit = NULL): depth = t_min[r] + acc[r] with acc = the
+ * ray's sum of weight x step (pp_march_fwd's depth), hit = acc > 0, p = o + d depth.
+ *   near  = sum_r max(dist_r - half_diagonal, 0) [conf > 0], dist = distance of `centre` to the half-line o + t d, t >= 0
+ *   q = R_w2c p + t_w2c of the OTHER view; behind = q_z < nl, then q := (nl, nl, nl) without gradient; (u, v) = K q / q_z
+ *   e = |(u, v) - match|; valid = !behind && hit && (e <= pixel_thre, when pixel_check); err = sum valid conf huber_1(e) /
+ *   (sum valid + 1e-6)
+ * terms[3] = (err, near, sum valid), overwritten.  The gradients of scale (w_near near + w_proj err), all overwritten:
+ * g_p [capacity,3]; g_depth [capacity] = g_p . d (render; 0 otherwise); g_o / g_d [capacity,3] = the direct gradient on the ray
+ * (near term, and with render = 1 the ray's explicit share of p: g_o += g_p, g_d += depth g_p); g_w2c [n_views,3,4] = the direct
+ * gradient on the other views' w2c.  One work-group, fixed summation order (strided per-thread partials, then a tree), no
+ * atomics: identical inputs give identical bits. */
+int pp_reproj_loss(int32_t render, int32_t n_rows, int32_t capacity, const int32_t* other, const float* match, const float* conf,
+                   const float* rays_o, const float* rays_d, const float* p, const uint8_t* hit, const float* t_min,
+                   const float* acc, const float* intr, const float* w2c, int32_t n_views, float centre_x, float centre_y,
+                   float centre_z, float half_diagonal, float nl, int32_t pixel_check, float pixel_thre, float w_near,
+                   float w_proj, float scale, float* terms, float* g_p, float* g_depth, float* g_o, float* g_d, float* g_w2c,
+                   void* stream);
+/* Own-view pose gradient: per-row ray gradients g_o, g_d, g_viewdirs (may be NULL) [capacity,3] and g_t_min (may be NULL)
+ * [capacity] - chained through the slab test of the sampler (voxurf_coarse.py:701-705, differentiated w.r.t. rays_o / rays_d
+ * [capacity,3]) - go through the direction normalisation and c2w of the own view and are summed per view; g_w2c (may be NULL)
+ * [n_views,3,4] is moved onto c2w through w2c = [R^T | -R^T t] as pp_nerf_pair_pose_bwd does.  g_c2w [n_views,3,4] is
+ * OVERWRITTEN (feed it to pp_pose_bwd).  One work-group per view, fixed summation order, no atomics. */
+int pp_reproj_pose_fold(const pp_scene* sc, const int32_t* own, const float* pix, int32_t n_rows, const float* intr,
+                        const float* c2w, const float* w2c, int32_t n_views, const float* rays_o, const float* rays_d,
+                        const float* g_o, const float* g_d, const float* g_viewdirs, const float* g_t_min, const float* g_w2c,
+                        float* g_c2w, void* stream);
 
 /* ---------------------------------------------------------------- scene branch: ordered weight-gradient flush
  * The nine weight-gradient products of pp_nerf_bwd end in float atomics: up to 512 work-groups (row splits x 128 x 128 output

@@ -290,8 +290,10 @@ class TrainEngine:
     def __init__(self, cfg: SceneConfig, n_views, H, W, n_rand, device='cuda', lr_pose=1e-3, lr_pose_end=1e-4,
                  pose_iters=1, lrate_decay=10, loss_scale=0.1, weight_main=1.0, weight_tv_k0=0.01, weight_mask=0.1,
                  fix_first=True, capacity=None, x_slab=None, dist_ctx=None, deterministic_scatter=False, options=None,
-                 deterministic=False):
-        """deterministic: bit-reproducible train step.  Implies deterministic_scatter and additionally replaces every other
+                 deterministic=False, reproj_rows=0):
+        """reproj_rows: row capacity of the engine-native reprojection pass (`reprojection_grads`); each row is one ray of a second
+        Workspace(reproj_rows, reproj_rows * n_samples).  0 (default): no second workspace, nothing changes.
+        deterministic: bit-reproducible train step.  Implies deterministic_scatter and additionally replaces every other
         floating-point sum of the object-branch step that feeds a parameter update and depends on the order in which work-groups
         or lanes finish - the weight and bias gradients of both MLPs, their thin layers, the alpha / beta gradient of the geometry
         backward, the pose gradient of the ray backward - by per-work-group (per-ray) partial sums in a workspace and a reduction
@@ -381,6 +383,31 @@ class TrainEngine:
         self.pe_w = self.step_dev[:self.npe]
         self.seg_lr = self.step_dev[self.npe:self.npe + 3]
         self.pose_seg_lr = self.step_dev[self.npe + 3:self.npe + 4]
+        self.reproj_rows = int(reproj_rows)
+        self.ws_reproj = None
+        self.last_reproj_terms = None
+        if self.reproj_rows > 0:
+            self._alloc_reproj()
+
+    def _alloc_reproj(self):
+        """Buffers of reprojection_grads: a workspace of its own (the main pass's activations stay untouched) and the per-row
+        gradients.  The ray-level colour gradients of that workspace are zero for good: the pass has a depth-only loss."""
+        R, S, cfg = self.reproj_rows, self.cfg.n_samples, self.cfg
+        f = dict(dtype=torch.float32, device=self.dev)
+        ws = self.ws_reproj = Workspace(R, R * S, self.dev, ctx=self.ctx)
+        for t in (ws.g_rgbm, ws.g_last, ws.g_cw):
+            t.zero_()
+        z = lambda *shape: torch.zeros(*shape, **f)
+        self._rp = dict(g_p=z(R, 3), g_depth=z(R), g_o=z(R, 3), g_d=z(R, 3), go=z(R, 3), gd=z(R, 3), gv=z(R, 3), g_t=z(R),
+                        p=z(R, 3), hit=torch.zeros(R, dtype=torch.uint8, device=self.dev), terms=z(3),
+                        g_w2c=z(self.V, 3, 4), g_c2w=z(self.V, 3, 4), se3=z(self.V, 6))
+        # the reference's "centre" and diagonal (lib/recon_scene.py:344, lib/voxurf_coarse.py:102; both sic), in its fp32 arithmetic
+        lo, hi = (torch.tensor(np.asarray(a, dtype=np.float32)) for a in (cfg.xyz_min, cfg.xyz_max))
+        self._rp_centre = [float(x) for x in (lo + hi)]
+        self._rp_half_diag = float(torch.sqrt(torch.sum(hi - lo ** 2)) / 2.)        # = Voxurf.diagonal_length / 2 (voxurf_coarse.py)
+        if not math.isfinite(self._rp_half_diag):
+            # the (sic) formula has a negative radicand for such a box: torch.clamp then propagates NaN, the kernel's fmaxf would not
+            raise ValueError('reproj_rows > 0: Voxurf.diagonal_length is not finite for this box (sum(xyz_max - xyz_min ** 2) < 0)')
 
     # ---- data / parameter loading ---------------------------------------------------------------------------
     def set_views(self, images, masks, Ks, w2c_init):
@@ -505,6 +532,90 @@ class TrainEngine:
         ops.mlp_pack_invalidate(ctx)
         ops.warp_lean_end(ctx)
         return s_val, w_dyn
+
+    def reprojection_grads(self, rows, mode, global_step, jitter=None, weight_projection=1.0, weight_near_surface=1.0, nl=0.0,
+                           pixel_thre=None, scale=None):
+        """Reprojection + near-surface terms of matched pixels (recon_utils.get_project_error; lib/recon_scene.py:321-369, :621-637)
+        inside the engine's own launches: the rows become a second ray batch that goes through the object branch's kernels on a
+        workspace of its own, and the gradient of scale * (weight_near_surface * near + weight_projection * err) is ACCUMULATED
+        into flat.grad (warp network, sdf_alpha / sdf_beta; mode 'render' only) and se3_grad.  k0_grad / k0_touched are left
+        exactly as they are.  No autograd, no host synchronisation, no parameter copy.
+        Must run after render_and_grads and before optimizer_step: it uses that step's w2c / c2w / jac and BARF weights.
+        rows: dict(own, other [R] int32 view indices, pix [R,2] pixel (x, y) in the own view, match [R,2] matched pixel in the
+        other view, conf [R]; optional n_rows <= R: the rows in play), R <= reproj_rows.
+        mode: 'crossing' - surface point = first zero crossing of the raw template (query_sdf_point_wocuda_wodeform; the reference
+        while at most two views are active) - or 'render' - expected ray depth of the full render
+        (query_sdf_point_wocuda_render).  jitter [R] (training-mode per-ray jitter); None: drawn on the device.
+        scale: None = the engine's loss_scale.  Leaves last_reproj_terms = dict(err, near, n_valid) as device tensors."""
+        if self.ws_reproj is None:
+            raise ValueError('reprojection_grads needs an engine built with reproj_rows > 0')
+        if self.deterministic:
+            raise ValueError('the reprojection pass is out of the scope of deterministic=True: its render backward uses the separate '
+                             'geometry backward, which keeps float atomics')
+        if self.dist is not None:
+            raise NotImplementedError('the reprojection pass is not sharded across ranks')
+        if not self.cfg.inverse_y:
+            raise NotImplementedError('the reprojection pass implements inverse_y=True without flips (the DTU setting)')
+        if mode not in ('crossing', 'render'):
+            raise ValueError(f"mode must be 'crossing' or 'render', got {mode!r}")
+        cfg, ws, sc, rp, P = self.cfg, self.ws_reproj, self.cfg.pp, self._rp, self.flat
+        R = rows['own'].shape[0]
+        n = int(rows.get('n_rows', R))
+        if not 0 < n <= R <= self.reproj_rows:
+            raise ValueError(f'{n} of {R} rows with reproj_rows = {self.reproj_rows}')
+        cap = self.reproj_rows
+        if jitter is None:
+            jitter = torch.rand(cap, device=self.dev)
+        elif jitter.shape[0] < cap:                               # rows past R are rays that miss the box: any jitter will do
+            jitter = torch.cat([jitter, jitter.new_zeros(cap - jitter.shape[0])])
+        render = mode == 'render'
+        scale = self.loss_scale if scale is None else scale
+        ops.reproj_rays(sc, rows['own'], rows['pix'], n, self.intr, self.c2w, ws.rays_o, ws.rays_d, ws.viewdirs)
+        self.core.sample(ws, jitter)
+        loss_args = (self.intr, self.w2c, self._rp_centre, self._rp_half_diag, nl, pixel_thre, weight_near_surface,
+                     weight_projection, scale, rp['terms'], rp['g_p'], rp['g_depth'], rp['g_o'], rp['g_d'], rp['g_w2c'])
+        if render:
+            s_val = cfg.s_val(global_step)
+            inv_s = float(np.float32(1.0) / np.float32(s_val))
+            ctx = self.ctx
+            # a weight pack and a lean scope of this pass's own, on its own buffers (render_and_grads closed its ones)
+            ops.mlp_pack(P.view('warp'), P.view('rgbnet'), self.mlp_pack, ctx)
+            if ws.warp_acts is not None:
+                ops.warp_lean_begin(ws.warp_acts, ws.scratch, P.view('warp'), ctx)
+            par = (self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w)
+            self.core.forward(ws, *par)
+            ops.reproj_loss(True, n, rows['other'], rows['match'], rows['conf'], ws.rays_o, ws.rays_d, None, None, ws.t_min,
+                            ws.depth_acc, *loss_args)
+            # depth-only loss: ws.g_rgbm / g_last / g_cw stay zero; no colour-grid gradient is requested (k0_grad = None, no scatter)
+            self.core.backward(ws, *par, None, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
+                               g_depth=rp['g_depth'])
+            ops.raygen_select_bwd(sc, None, None, None, 0, 0, True, ws.rays_o, ws.rays_d, ws.t_min, ws.ray_start, ws.g_pts,
+                                  ws.step, ws.g_view_s, rp['g_o'], rp['g_d'], None, rp['g_depth'], rp['go'], rp['gd'], rp['gv'],
+                                  None)
+            ops.mlp_pack_invalidate(ctx)
+            ops.warp_lean_end(ctx)
+            g_o, g_d, g_v, g_t = rp['go'], rp['gd'], rp['gv'], None
+        else:
+            S = cfg.n_samples
+            dist = float(np.float32(cfg.stepsize) * np.float32(cfg.voxel_size))
+            dense, sdf_d = ws.alpha, ws.sdf_final                   # [cap * S] each: free in this mode
+            ops.reproj_dense_pts(sc, ws.rays_o, ws.rays_d, ws.t_min, jitter, ws.pts)
+            ops.grid_sample_fwd(sc, self.sdf, 1, ws.pts, 1, dense)
+            ops.sdf_first_crossing(dense, None, None, cap, S, dist, ws.t_min, ws.rays_o, ws.rays_d, sdf_d, rp['p'], rp['hit'], None)
+            ops.reproj_loss(False, n, rows['other'], rows['match'], rows['conf'], ws.rays_o, ws.rays_d, rp['p'], rp['hit'], None,
+                            None, *loss_args)
+            ops.sdf_crossing_dense_bwd(sc, self.sdf, ws.rays_o, ws.rays_d, ws.t_min, jitter, cap, S, dist, sdf_d, rp['g_p'], None,
+                                       rp['go'], rp['gd'], rp['g_t'])
+            rp['go'].add_(rp['g_o'])
+            rp['gd'].add_(rp['g_d'])
+            g_o, g_d, g_v, g_t = rp['go'], rp['gd'], None, rp['g_t']
+        ops.reproj_pose_fold(sc, rows['own'], rows['pix'], n, self.intr, self.c2w, self.w2c, ws.rays_o, ws.rays_d, g_o, g_d, g_v,
+                             g_t, rp['g_w2c'], rp['g_c2w'])
+        ops.pose_bwd(self.jac, rp['g_c2w'], rp['se3'])
+        self.se3_grad += rp['se3']
+        t = rp['terms']
+        self.last_reproj_terms = dict(err=t[0], near=t[1], n_valid=t[2])
+        return self.last_reproj_terms
 
     def _upload_step_scalars(self, progress):
         """BARF weights for this step and the learning rates the optimiser will use at the END of this step (the

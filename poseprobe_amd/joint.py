@@ -22,7 +22,8 @@ class DualBranchEngine:
         depth_rand / fine_grid / corres_rand / corres_fine_grid and the same corres rows give, after every train_step, bit-identical
         k0, k0_m, k0_v, flat.data, flat.m, flat.v, se3, se3_m, se3_v of the object engine and flat, m, v of the coarse and the
         fine scene network - coarse phase, hierarchical phase, and both with the correspondence term.  Not covered: extra pose
-        terms a caller mixes into se3_grad through torch autograd (trainer.ReprojectionTerm), multi-rank runs, and
+        terms a caller mixes into se3_grad through torch autograd (trainer.ReprojectionTerm), the engine-native reprojection pass
+        (forward_backward(reproj=...): refused with ValueError), multi-rank runs, and
         bg_nerf.SceneRenderer's autograd route.  Off (default): nothing changes."""
         self.deterministic = bool(deterministic)
         if self.deterministic:
@@ -78,7 +79,7 @@ class DualBranchEngine:
         return c2w[:, None, :, 3].expand_as(ray), ray, dir_cam
 
     def forward_backward(self, ray_idx, jitter, global_step, pixels, image, depth_rand=None, fine=False, fine_grid=None,
-                         n_views=None, corres=None, corres_rand=None, corres_fine_grid=None):
+                         n_views=None, corres=None, corres_rand=None, corres_fine_grid=None, reproj=None):
         """ray_idx / jitter: the object branch's batch (engine.TrainEngine.train_step); pixels [N, 2] + image [V, N, 3]: the
         scene branch's batch; depth_rand [V, N, S, 1] / fine_grid [Nf + 1] optionally replay the samplers' draws.  On return every gradient
         buffer (object engine's k0 / MLPs / se3 - the pose gradient of BOTH branches - and the scene engine's block) is
@@ -86,11 +87,26 @@ class DualBranchEngine:
         corres: dict(i, j, pix_self [M,2], pix_other [M,2], conf [M], weight, opt=None, photo_weight=1.0) adds SPARF's
         correspondence term of the view pair (i, j) (corres_loss.py:140-222, weight = 10^-2 / gamma in the reference's DTU
         setting): its rows render in the same scene launches as the photometric rays, L_bg = photometric + weight * corres
-        (last_scene_terms holds both parts); corres_rand [2, M, S, 1] / corres_fine_grid [Nf + 1] replay its draws."""
+        (last_scene_terms holds both parts); corres_rand [2, M, S, 1] / corres_fine_grid [Nf + 1] replay its draws.
+        reproj: dict(rows, mode, weight_projection, weight_near_surface, nl, pixel_thre, jitter=None) adds the object loss's
+        reprojection + near-surface terms (lib/recon_scene.py:621-637) through engine.TrainEngine.reprojection_grads (the object
+        engine needs reproj_rows > 0): loss_scale * (weight_near_surface * near + weight_projection * err) joins the object
+        branch's gradients - the pose, and in mode 'render' the warp network and sdf_alpha / sdf_beta; the object engine's
+        last_reproj_terms holds the scalars as device tensors."""
         e, sc = self.obj, self.scene
         if corres is not None and e.dist is not None:
             raise NotImplementedError('DualBranchEngine: the correspondence term is not sharded across ranks')
+        if reproj is not None:
+            if self.deterministic or getattr(e, 'deterministic', False):
+                raise ValueError('DualBranchEngine: reproj is out of the scope of deterministic=True (its render backward keeps float '
+                                 'atomics)')
+            if e.dist is not None:
+                raise NotImplementedError('DualBranchEngine: the reprojection term is not sharded across ranks')
         out = e.render_and_grads(ray_idx, jitter, global_step)            # also refreshes e.c2w / e.jac for this step
+        if reproj is not None:
+            e.reprojection_grads(reproj['rows'], reproj['mode'], global_step, jitter=reproj.get('jitter'),
+                                 weight_projection=reproj['weight_projection'], weight_near_surface=reproj['weight_near_surface'],
+                                 nl=reproj['nl'], pixel_thre=reproj.get('pixel_thre'))
         opt = sc.net.opt
         V, N, S = (e.V if n_views is None else n_views), pixels.shape[0], opt.nerf.sample_intvs
         center, ray, dir_cam = self.scene_rays(pixels, V)
@@ -146,15 +162,12 @@ class DualBranchEngine:
         return out, loss_bg
 
     def train_step(self, ray_idx, jitter, global_step, pixels, image, depth_rand=None, optimize_pose=True, fine=False,
-                   fine_grid=None, n_views=None, before_step=None, corres=None):
+                   fine_grid=None, n_views=None, before_step=None, corres=None, reproj=None):
         """fine=True: the scene branch also runs its fine network (after ratio_start_fine_sampling_at_x of the schedule).
         before_step: callable run after both branches' backward and before the optimiser step (the trainer mixes its extra
-        pose-only loss terms into se3_grad there).  corres: see forward_backward."""
-        if corres is None:
-            out = self.forward_backward(ray_idx, jitter, global_step, pixels, image, depth_rand, fine, fine_grid, n_views)
-        else:
-            out = self.forward_backward(ray_idx, jitter, global_step, pixels, image, depth_rand, fine, fine_grid, n_views,
-                                        corres=corres)
+        pose-only loss terms into se3_grad there).  corres, reproj: see forward_backward."""
+        extra = {k: v for k, v in (('corres', corres), ('reproj', reproj)) if v is not None}
+        out = self.forward_backward(ray_idx, jitter, global_step, pixels, image, depth_rand, fine, fine_grid, n_views, **extra)
         if before_step is not None:
             before_step()
         e = self.obj

@@ -496,6 +496,56 @@ def nerf_pair_pose_bwd(g_center, g_ray, dir_cam, w2c, g_w2c, view_self, view_oth
               int(view_self), int(view_other), _f(g_c2w), _stream())
 
 
+# ------------------------------------------------------------------------------------------- object branch: reprojection terms
+def _rows_at_least(n, *named):
+    for t, width, what in named:
+        if t is not None and t.numel() < n * width:
+            raise RuntimeError(f'{what} holds {t.numel()} elements, needs {n * width}')
+
+
+def reproj_rays(sc, own, pix, n_rows, intr, c2w, rays_o, rays_d, viewdirs):
+    """own [n_rows] int32, pix [n_rows,2] -> rays_o / rays_d / viewdirs [capacity,3]; rows from n_rows on miss the box."""
+    cap = rays_o.shape[0]
+    _rows_at_least(n_rows, (own, 1, 'own'), (pix, 2, 'pix'))
+    _rows_at_least(cap, (rays_d, 3, 'rays_d'), (viewdirs, 3, 'viewdirs'))
+    _lib.call('pp_reproj_rays', ctypes.byref(sc), _i(own), _f(pix), int(n_rows), int(cap), _f(intr), _f(c2w), c2w.shape[0],
+              _f(rays_o), _f(rays_d), _f(viewdirs), _stream())
+
+
+def reproj_dense_pts(sc, rays_o, rays_d, t_min, jitter, pts):
+    """pts [N * n_samples, 3]: the dense sample positions of the zero-crossing query."""
+    N = rays_o.shape[0]
+    _rows_at_least(N, (rays_d, 3, 'rays_d'), (t_min, 1, 't_min'), (jitter, 1, 'jitter'), (pts, 3 * sc.n_samples, 'pts'))
+    _lib.call('pp_reproj_dense_pts', ctypes.byref(sc), _f(rays_o), _f(rays_d), _f(t_min), _f(jitter), int(N), _f(pts), _stream())
+
+
+def reproj_loss(render, n_rows, other, match, conf, rays_o, rays_d, p, hit, t_min, acc, intr, w2c, centre, half_diagonal, nl,
+                pixel_thre, w_near, w_proj, scale, terms, g_p, g_depth, g_o, g_d, g_w2c):
+    """See pp_reproj_loss (include/poseprobe_hip.h).  centre: three Python floats; pixel_thre None = no pixel filter.  The per-row
+    outputs define the capacity (g_p [capacity,3])."""
+    cap, V = g_p.shape[0], w2c.shape[0]
+    _rows_at_least(n_rows, (other, 1, 'other'), (match, 2, 'match'), (conf, 1, 'conf'), (rays_o, 3, 'rays_o'),
+                   (rays_d, 3, 'rays_d'), (p, 3, 'p'), (hit, 1, 'hit'), (t_min, 1, 't_min'), (acc, 1, 'acc'))
+    _rows_at_least(cap, (g_depth, 1, 'g_depth'), (g_o, 3, 'g_o'), (g_d, 3, 'g_d'))
+    _rows_at_least(V, (intr, 4, 'intr'), (g_w2c, 12, 'g_w2c'))
+    _rows_at_least(3, (terms, 1, 'terms'))
+    _lib.call('pp_reproj_loss', int(bool(render)), int(n_rows), int(cap), _i(other), _f(match), _f(conf), _f(rays_o), _f(rays_d),
+              _f(p), _u8(hit), _f(t_min), _f(acc), _f(intr), _f(w2c), int(V), float(centre[0]), float(centre[1]),
+              float(centre[2]), float(half_diagonal), float(nl), int(pixel_thre is not None),
+              float(0.0 if pixel_thre is None else pixel_thre), float(w_near), float(w_proj), float(scale), _f(terms), _f(g_p),
+              _f(g_depth), _f(g_o), _f(g_d), _f(g_w2c), _stream())
+
+
+def reproj_pose_fold(sc, own, pix, n_rows, intr, c2w, w2c, rays_o, rays_d, g_o, g_d, g_viewdirs, g_t_min, g_w2c, g_c2w):
+    """Per-row ray gradients of the rows' own views (+ the direct w2c gradient, or None) -> g_c2w [V,3,4], overwritten."""
+    V = c2w.shape[0]
+    _rows_at_least(n_rows, (own, 1, 'own'), (pix, 2, 'pix'), (rays_o, 3, 'rays_o'), (rays_d, 3, 'rays_d'), (g_o, 3, 'g_o'),
+                   (g_d, 3, 'g_d'), (g_viewdirs, 3, 'g_viewdirs'), (g_t_min, 1, 'g_t_min'))
+    _rows_at_least(V, (intr, 4, 'intr'), (w2c, 12, 'w2c'), (g_w2c, 12, 'g_w2c'), (g_c2w, 12, 'g_c2w'))
+    _lib.call('pp_reproj_pose_fold', ctypes.byref(sc), _i(own), _f(pix), int(n_rows), _f(intr), _f(c2w), _f(w2c), int(V),
+              _f(rays_o), _f(rays_d), _f(g_o), _f(g_d), _f(g_viewdirs), _f(g_t_min), _f(g_w2c), _f(g_c2w), _stream())
+
+
 # ------------------------------------------------------------------------------------------- scene branch: ordered step
 def nerf_ordered_workspace():
     """Bytes of the workspace of the scene branch's ordered weight-gradient flush (pp_nerf_ordered_workspace): 512 slots of

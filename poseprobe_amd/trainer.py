@@ -136,6 +136,12 @@ def corres_sample_size(n_matches, rand_rays):
     return min(int(n_matches), int(rand_rays) // 2)
 
 
+def reproj_sample_size(n_matches, reproj_rows):
+    """Matches of the drawn pair that take part in a step of the engine-native reprojection pass: all of them up to
+    reproj_rows // 2 (each match is two rows, one per direction), a random subset of that many beyond."""
+    return min(int(n_matches), int(reproj_rows) // 2)
+
+
 class ReprojectionTerm:
     """The reprojection + near-surface pose terms of the live loop (lib/recon_scene.py:624-637) as a `pose_terms` entry of
     DualBranchTrainer: one matched view pair is drawn per step among the ACTIVE views, every matched pixel is lifted to the
@@ -186,7 +192,7 @@ class ReprojectionTerm:
 class DualBranchTrainer:
     def __init__(self, obj_engine, opt, max_iter=60000, lr=1e-3, lr_end=1e-4, ratio_start_fine=0.3, ratio_end_pose=0.3,
                  depth_range=(0.5, 3.0), seed=0, incremental_step=0, pose_initialiser=None, pose_terms=(), scene_matches=None,
-                 deterministic=False):
+                 deterministic=False, reprojection=None):
         """incremental_step > 0: the incremental view schedule (`active_views`); a view that joins gets its initial pose from
         `pose_initialiser(view, w2c_of_previous_view [3,4]) -> w2c [3,4]` - the reference's PnP hand-off (cv2.solvePnPRansac on
         matcher output, lib/recon_scene.py:202-214, :276-310) plugs in here; the default is its `use_identical` variant (the
@@ -197,7 +203,19 @@ class DualBranchTrainer:
         coord0_scene[i], mconf_scene[i] (recon_scene.py:247-257), paired with view pair_partner(i) unless a partner is given;
         read when opt.loss_type contains 'corres'.
         deterministic: passed to DualBranchEngine (needs a deterministic, single-GPU obj_engine): the joint step's own sums run
-        in fixed orders.  Out of its scope: `pose_terms` (differentiated by torch autograd) and multi-rank runs."""
+        in fixed orders.  Out of its scope: `pose_terms` (differentiated by torch autograd) and multi-rank runs.
+        reprojection: dict(pairs, nl, weight_projection, weight_near_surface, pixel_thre=200, seed=0) - the reprojection +
+        near-surface terms of the object loss (lib/recon_scene.py:621-637; configs/dtu_e2e/scan1.py:60-61: 1e-3 / 1e-1) inside
+        the engine's own launches (TrainEngine.reprojection_grads): complete gradients (pose, and from the third active view on
+        the warp network and sdf_alpha / sdf_beta), no autograd, no host synchronisation.  pairs as ReprojectionTerm's: (i, j,
+        coord_i [P,2], coord_j [P,2], conf [P]); one pair among the active views is drawn per step from RandomState(seed), both
+        directions of its matches are the step's rows; mode 'render' iff more than two views are active (:584); active in the
+        object phase only (`object_phase(global_step, n_iters_object, start_object)`; optional keys n_iters_object - default: the
+        engine's cfg.N_iters - and start_object = 0).  obj_engine must have been built with reproj_rows > 0, the row
+        capacity: matches beyond reproj_rows // 2 are subsampled on the device, a fresh subset every step - a DEVIATION from
+        the reference, which uses every match.  The capacity costs one second render workspace: about 18 KB per sample, i.e.
+        18 KB * n_samples per row (160^3 voxels, 186 samples: 3.4 MB per row, 1024 rows = 512 matches: 3.5 GB).  The same term
+        may not also be given as a ReprojectionTerm in pose_terms (ValueError: it would be counted twice)."""
         self.opt, self.max_iter = opt, max_iter
         self.terms = loss_terms(getattr(opt, 'loss_type', None))
         self.photo_weight = loss_weight(opt, 'photometric') if 'loss_type' in opt else 1.0
@@ -215,6 +233,22 @@ class DualBranchTrainer:
         self.last_scene_terms = None
         self.incremental_step, self.pose_initialiser, self.pose_terms = incremental_step, pose_initialiser, tuple(pose_terms)
         self.n_active = None
+        self.reprojection = None
+        if reprojection is not None:
+            if any(isinstance(t, ReprojectionTerm) for t in self.pose_terms):
+                raise ValueError('reprojection= together with a ReprojectionTerm in pose_terms: the term would be counted twice')
+            if getattr(obj_engine, 'reproj_rows', 0) < 2:
+                raise ValueError('reprojection= needs an object engine built with reproj_rows >= 2')
+            if deterministic or getattr(obj_engine, 'deterministic', False):
+                raise ValueError('reprojection= is out of the scope of deterministic=True (its render backward keeps float atomics)')
+            r = dict(pixel_thre=200, seed=0, n_iters_object=obj_engine.cfg.N_iters, start_object=0)
+            r.update(reprojection)
+            dev_ = obj_engine.dev
+            fl = lambda t: torch.as_tensor(t, dtype=torch.float32).to(dev_)
+            r['pairs'] = [(int(i), int(j), fl(ci), fl(cj), fl(cf)) for i, j, ci, cj, cf in r['pairs']]
+            r['rng'] = np.random.RandomState(r['seed'])
+            self.reprojection = r
+        self.last_reproj = None
         self.lr, self.lr_end = lr, lr_end
         self.ratio_start_fine, self.ratio_end_pose = ratio_start_fine, ratio_end_pose
         dev = obj_engine.dev
@@ -281,6 +315,33 @@ class DualBranchTrainer:
         return dict(i=i, j=j, pix_self=ps, pix_other=po, conf=conf, opt=self.opt,
                     weight=self.corres_weight / corres_gamma(global_step, self.opt, self.max_iter))
 
+    def _reproj_batch(self, global_step, k):
+        """The reprojection rows of this step, or None: one live pair drawn on the host (as ReprojectionTerm draws it), both
+        directions of its matches as rows - own view j first, as ReprojectionTerm orders them -, subsampled on the device to
+        reproj_rows // 2 matches.  Shapes depend on host values only."""
+        r = self.reprojection
+        if r is None:
+            return None
+        if not object_phase(global_step, r['n_iters_object'], r['start_object']):
+            return None
+        live = [p for p in r['pairs'] if p[0] < k and p[1] < k]
+        if not live:
+            return None
+        i, j, ci, cj, conf = live[r['rng'].randint(len(live))]           # the draw sequence of ReprojectionTerm, empty pairs included
+        if ci.shape[0] == 0:                                               # a drawn pair without matches: no term this step
+            return None
+        n = reproj_sample_size(ci.shape[0], self.joint.obj.reproj_rows)
+        if n < ci.shape[0]:
+            sel = torch.randperm(ci.shape[0], device=self.dev, generator=self.gen)[:n]
+            ci, cj, conf = ci[sel], cj[sel], conf[sel]
+        own = torch.cat([torch.full((n,), j, dtype=torch.int32, device=self.dev), torch.full((n,), i, dtype=torch.int32, device=self.dev)])
+        other = torch.cat([torch.full((n,), i, dtype=torch.int32, device=self.dev), torch.full((n,), j, dtype=torch.int32, device=self.dev)])
+        rows = dict(own=own, other=other, pix=torch.cat([cj, ci]).contiguous(), match=torch.cat([ci, cj]).contiguous(),
+                    conf=torch.cat([conf, conf]).contiguous())
+        self.last_reproj = dict(pair=(i, j), mode='render' if k > 2 else 'crossing', n_rows=2 * n)
+        return dict(rows=rows, mode=self.last_reproj['mode'], weight_projection=r['weight_projection'],
+                    weight_near_surface=r['weight_near_surface'], nl=r['nl'], pixel_thre=r['pixel_thre'])
+
     def _mix_pose_terms(self, k):
         """loss += w_i * L_i(poses) for the extra pose-only terms: their se3 gradient joins the object branch's (which the
         engine scales by loss_scale = 0.1, lib/recon_scene.py:648)."""
@@ -308,10 +369,13 @@ class DualBranchTrainer:
         ray_idx, jitter, pixels, image = self.sample_batch(k)
         self.last_pose_terms = {}
         corres = self._corres_batch(global_step, k)
+        self.last_reproj = None
+        reproj = self._reproj_batch(global_step, k)
+        extra = {} if reproj is None else {'reproj': reproj}
         out = self.joint.train_step(ray_idx, jitter, global_step, pixels, image, fine=fine,
                                     optimize_pose=pose_phase(global_step, self.max_iter, self.ratio_end_pose), n_views=k,
                                     before_step=(lambda: self.last_pose_terms.update(self._mix_pose_terms(k))) if self.pose_terms else None,
-                                    corres=corres)
+                                    corres=corres, **extra)
         self.last_scene_terms = self.joint.last_scene_terms
         self.joint.scene.set_lr(scene_lr(self.iteration, self.lr, self.lr_end, self.max_iter))
         p = c2f_progress(self.iteration, self.max_iter)                # takes effect from the next iteration (renderer.py:399)
