@@ -5,6 +5,7 @@ Mirrors one iteration of the object branch in recon_scene.optimize_increamental
 (lib/recon_scene.py:572-606, :648-649, :742-747, :765-771) and Voxurf.forward (lib/voxurf_coarse.py:922-1092).
 torch is used for device memory and streams only; every arithmetic step is a kernel of libposeprobe_hip.so.
 """
+import contextlib
 import math
 from dataclasses import dataclass
 
@@ -56,6 +57,15 @@ class SceneConfig:
     def s_val(self, global_step):
         return 1. / (global_step + self.s_ratio / self.s_start - self.step_start) * self.s_ratio
 
+    def inv_s(self, global_step):
+        """1 / s_val as the kernels take it: the fp32 quotient."""
+        return float(np.float32(1.0) / np.float32(self.s_val(global_step)))
+
+    @property
+    def step_dist(self):
+        """Distance between two samples of a ray: the fp32 product stepsize * voxel_size."""
+        return float(np.float32(self.stepsize) * np.float32(self.voxel_size))
+
     def pe_weights(self, progress):
         """BARF c2f weights for xyz (L=posbase_pe) then view (L=viewbase_pe); voxurf_coarse.py:721-732 (fp32 ops)."""
         out = []
@@ -78,22 +88,29 @@ def dynamic_weight(w0, w1, it, total):
 
 class Workspace:
     """All per-ray / per-sample device buffers for N rays and `capacity` samples (default N*S)."""
+    SAMPLER = ('t_min', 't_max', 'ray_start', 'count', 'pts', 'ray_id', 'step_k', 'step')
 
-    def __init__(self, N, capacity, device, sample_capacity=None, backward=True, keep_activations=True, ctx=None):
+    def __init__(self, N, capacity, device, sample_capacity=None, backward=True, keep_activations=True, ctx=None, samples=None):
+        """samples: {name: tensor} with the SAMPLER buffers of a sampler that has already run: adopted instead of allocated."""
         f = dict(dtype=torch.float32, device=device)
         i = dict(dtype=torch.int32, device=device)
-        self.N, self.cap = N, capacity
-        self.sample_cap = sc_ = sample_capacity or capacity
+        self.N, self.cap, self.device = N, capacity, device
         e = torch.empty
         # rays
         self.rays_o, self.rays_d, self.viewdirs = e(N, 3, **f), e(N, 3, **f), e(N, 3, **f)
         self.target, self.mask_px = e(N, 3, **f), e(N, **f)
-        self.t_min, self.t_max = e(N, **f), e(N, **f)
-        self.ray_start = torch.zeros(N + 1, **i)
-        self.count = torch.zeros(1, **i)
         # samples
-        self.pts, self.ray_id, self.step_k, self.step = e(sc_, 3, **f), e(sc_, **i), e(sc_, **i), e(sc_, **f)
-        wsz = ops.mlp_workspaces(capacity)                 # sizes come from the library (pp_rgbnet_workspace / pp_warp_workspace)
+        if samples is None:
+            self.sample_cap = sc_ = sample_capacity or capacity
+            self.t_min, self.t_max = e(N, **f), e(N, **f)
+            self.ray_start = torch.zeros(N + 1, **i)
+            self.count = torch.zeros(1, **i)
+            self.pts, self.ray_id, self.step_k, self.step = e(sc_, 3, **f), e(sc_, **i), e(sc_, **i), e(sc_, **f)
+        else:
+            for k in self.SAMPLER:
+                setattr(self, k, samples[k])
+            self.sample_cap = self.pts.shape[0]
+        self.wsz = wsz = ops.mlp_workspaces(capacity)      # sizes come from the library (pp_rgbnet_workspace / pp_warp_workspace)
         assert wsz['warp'][0] == 4 * capacity * 4 * 128 and wsz['rgbnet'][0] == 3 * capacity * 128
         # keep_activations=False (inference: nobody will differentiate this pass): the MLP activations are not kept when the forward kernels can run without them
         # (pp_warp_fwd / pp_rgbnet_fwd with acts = NULL: the split-precision kernels, the default): 2.5 KB per sample less to write
@@ -114,21 +131,27 @@ class Workspace:
         self.cum_weights, self.depth_acc = e(N, **f), e(N, **f)
         self.zero_block = torch.zeros(16, **f)          # loss_out[8] | tv_out[1] | mask_sum[1] : one memset per step
         self.loss_out, self.tv_out, self.mask_sum = self.zero_block[:8], self.zero_block[8:9], self.zero_block[9:10]
-        if not backward:
+        if backward:
+            self.alloc_backward(True)
+
+    def alloc_backward(self, zero_scratch):
+        """Backward buffers (no-op when they exist).  zero_scratch: Ybar of the warp chain (+ transposed weights, layered path) is
+        zeroed once, here: inside a lean scope (ops.warp_lean_begin) most of slot 0 is never written, and two engines that went
+        through the same steps must hold the same bytes there.  The autograd node's backward runs outside any scope: no memset."""
+        if hasattr(self, 'g_alpha'):
             return
-        # backward buffers
+        f = dict(dtype=torch.float32, device=self.device)
+        e, N, capacity = torch.empty, self.N, self.cap
         self.g_rgbm, self.g_last, self.g_cw = e(N, 3, **f), e(N, **f), e(N, **f)
         self.g_alpha, self.g_rgb = e(capacity, **f), e(capacity, 3, **f)
         self.g_feat = e(capacity, ops.FEAT_LD, **f)
         self.g_gradient, self.g_pts, self.g_view_s = e(capacity, 3, **f), e(capacity, 3, **f), e(capacity, 3, **f)
-        self.g_grad_deform, self.g_corr, self.g_sdf_deform = e(capacity, 9, **f), e(capacity, **f), e(capacity, **f)
         self.g_warp_out = e(capacity, 16, **f)
-        # Ybar of the warp chain (+ transposed weights, layered path).  Zeroed once, here: inside a lean scope (ops.warp_lean_begin)
-        # most of slot 0 is never written, and two engines that went through the same steps must hold the same bytes there
-        self.scratch = torch.zeros(wsz['warp'][1], **f)
-        self.scratch_rgb = e(wsz['rgbnet'][1], **f)   # Ybar of rgbnet: a buffer of its own, so that a lean scope's bytes in
-        #                                                         `scratch` depend on the warp chain alone
-        self.g_rays_o, self.g_rays_d, self.g_viewdirs = e(N, 3, **f), e(N, 3, **f), e(N, 3, **f)
+        # no kernel of the product is handed these three; tests/test_hip_step.py takes its shapes from them
+        self.g_grad_deform, self.g_corr, self.g_sdf_deform = e(capacity, 9, **f), e(capacity, **f), e(capacity, **f)
+        self.scratch = (torch.zeros if zero_scratch else e)(self.wsz['warp'][1], **f)
+        self.scratch_rgb = e(self.wsz['rgbnet'][1], **f)   # Ybar of rgbnet: a buffer of its own, so that a lean scope's bytes in
+        #                                                              `scratch` depend on the warp chain alone
 
 
 class FlatParams:
@@ -165,44 +188,51 @@ class FlatParams:
         return g
 
 
-def pack_rgbnet(layers, in_dim=57):
-    W0, b0 = layers[0]
-    W0p = torch.zeros(128, 64, dtype=torch.float32, device=W0.device)
-    W0p[:, :W0.shape[1]] = W0
-    parts = [W0p.reshape(-1), b0]
-    for W, b in layers[1:]:
+# The two MLPs inside the flat parameter block, layer by layer: logical (out, in), leading dimension of W as stored (rgbnet layer 0:
+# 57 input columns zero-padded to 64), the reference's state_dict prefix.  Each layer is W[out, ld] followed by b[out].
+_WARP_PREFIX = 'warp_network.deform_net.net.net.{}.0'
+MLP_LAYOUT = {
+    'rgbnet': ((128, 57, 64, 'rgbnet.0'), (128, 128, 128, 'rgbnet.2.0'), (128, 128, 128, 'rgbnet.3.0'), (3, 128, 128, 'rgbnet.4')),
+    'warp': tuple((o, i, i, _WARP_PREFIX.format(l)) for l, (o, i) in enumerate(((128, 3), (128, 128), (128, 128), (128, 128), (4, 128)))),
+}
+
+
+def _pack(net, layers):
+    parts = []
+    for (o, i, ld, _), (W, b) in zip(MLP_LAYOUT[net], layers):
+        if ld != i:
+            Wp = torch.zeros(o, ld, dtype=torch.float32, device=W.device)
+            Wp[:, :W.shape[1]] = W
+            W = Wp
         parts += [W.reshape(-1), b]
     return torch.cat([p.detach().float() for p in parts])
+
+
+def _unpack(net, flat):
+    at, out = 0, []
+    for o, i, ld, _ in MLP_LAYOUT[net]:
+        W = flat[at:at + o * ld].reshape(o, ld)[:, :i]; at += o * ld
+        b = flat[at:at + o]; at += o
+        out.append((W, b))
+    return out
+
+
+def pack_rgbnet(layers, in_dim=57):
+    assert in_dim == MLP_LAYOUT['rgbnet'][0][1]              # the table fixes the layout; the argument is kept for callers
+    return _pack('rgbnet', layers)
 
 
 def unpack_rgbnet(flat, in_dim=57):
-    o, out = 0, []
-    W0 = flat[o:o + 128 * 64].reshape(128, 64)[:, :in_dim]; o += 128 * 64
-    b0 = flat[o:o + 128]; o += 128
-    out.append((W0, b0))
-    for shp in ((128, 128), (128, 128), (3, 128)):
-        n = shp[0] * shp[1]
-        W = flat[o:o + n].reshape(shp); o += n
-        b = flat[o:o + shp[0]]; o += shp[0]
-        out.append((W, b))
-    return out
+    assert in_dim == MLP_LAYOUT['rgbnet'][0][1]
+    return _unpack('rgbnet', flat)
 
 
 def pack_warp(layers):
-    parts = []
-    for W, b in layers:
-        parts += [W.reshape(-1), b]
-    return torch.cat([p.detach().float() for p in parts])
+    return _pack('warp', layers)
 
 
 def unpack_warp(flat):
-    o, out = 0, []
-    for shp in ((128, 3), (128, 128), (128, 128), (128, 128), (4, 128)):
-        n = shp[0] * shp[1]
-        W = flat[o:o + n].reshape(shp); o += n
-        b = flat[o:o + shp[0]]; o += shp[0]
-        out.append((W, b))
-    return out
+    return _unpack('warp', flat)
 
 
 class RenderCore:
@@ -220,13 +250,34 @@ class RenderCore:
         if self.ordered and ctx is None:
             raise ValueError('an ordered RenderCore needs its own context (the workspace is attached to it)')
 
+    @contextlib.contextmanager
+    def pass_scope(self, flat, pack, lean_ws=None):
+        """One render pass: the MLP weights of `flat` are packed into `pack` HERE, on the pass's stream, and the record is dropped when
+        the pass's kernels are enqueued - also when the pass raises.  Every writer of the parameters (the optimiser, a checkpoint
+        load, an in-place copy from outside) runs between two scopes, so no kernel can read a pack older than its parameters.
+        lean_ws: the Workspace whose warp_acts / scratch the pass differentiates through - a lean scope of the warp net, closed with
+        the pack record: the forward kernel leaves out the tangent rows of X0, the data-gradient kernel Ybar3, and the
+        weight-gradient kernel rebuilds both (option warp_lean)."""
+        lean = lean_ws is not None and lean_ws.warp_acts is not None
+        try:
+            ops.mlp_pack(flat.view('warp'), flat.view('rgbnet'), pack, self.ctx)
+            if lean:
+                ops.warp_lean_begin(lean_ws.warp_acts, lean_ws.scratch, flat.view('warp'), self.ctx)
+            yield
+        finally:
+            ops.mlp_pack_invalidate(self.ctx)
+            if lean:
+                ops.warp_lean_end(self.ctx)
+
     # -- forward -------------------------------------------------------------------------------------------
     def sample(self, ws, jitter):
         ops.sample_dense(self.cfg.pp, ws.rays_o, ws.rays_d, jitter, ws.sample_cap, ws.t_min, ws.t_max, ws.ray_start, ws.count,
                          ws.pts, ws.ray_id, ws.step_k, ws.step)
 
-    def forward(self, ws, k0_cl, sdf, sdf_ab, rgbnet_p, warp_p, inv_s, pe_w, step_w=None, before_k0_use=None):
+    def forward(self, ws, k0_cl, sdf, sdf_ab, rgbnet_p, warp_p, inv_s, pe_w, step_w=None, before_k0_use=None, normals=None):
+        """normals: (nrm [cap,3], normal_marched [N,3]) - the marching kernel composites the unit SDF gradients as well."""
         cfg, sc = self.cfg, self.cfg.pp
+        nrm, normal_marched = (None, None) if normals is None else normals
         ops.warp_fwd(warp_p, ws.pts, ws.count, ws.cap, cfg.out_range, ws.warp_acts, ws.warp_out, self.ctx)
         ops.geometry_fwd(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
                          ws.alpha, ws.gradient, ws.sdf_final, ws.sdf_deform, ws.grad_deform)
@@ -234,9 +285,12 @@ class RenderCore:
             before_k0_use()             # multi-GPU: the all-gather of the updated grid overlaps everything above
         ops.color_feat_fwd(sc, k0_cl, ws.pts, ws.viewdirs, ws.ray_id, ws.gradient, pe_w, ws.count, ws.cap, ws.feat)
         ops.rgbnet_fwd(rgbnet_p, ws.feat, ws.count, ws.cap, ws.rgb_acts, ws.rgb, self.ctx)
-        ops.march_fwd(ws.alpha, ws.rgb, ws.step if step_w is None else step_w, None, ws.ray_start, ws.N, cfg.bg,
+        if nrm is not None:
+            # rows past the count hold stale values: harmless, the marching kernel walks ray_start ranges only
+            torch.div(ws.gradient, ws.gradient.norm(2, -1, keepdim=True) + 1e-6, out=nrm)
+        ops.march_fwd(ws.alpha, ws.rgb, ws.step if step_w is None else step_w, nrm, ws.ray_start, ws.N, cfg.bg,
                       ws.weights, ws.T, ws.alphainv_last, ws.i_end, ws.rgb_marched, ws.rgb_pre, ws.cum_weights,
-                      ws.depth_acc, None)
+                      ws.depth_acc, normal_marched)
 
     # -- backward ------------------------------------------------------------------------------------------
     def backward(self, ws, k0_cl, sdf, sdf_ab, rgbnet_p, warp_p, inv_s, pe_w, k0_grad_cl, sdf_ab_grad, rgbnet_grad,
@@ -345,7 +399,7 @@ class TrainEngine:
         self.touch_par = 0
         self._k0_marked = False
         self.flat = FlatParams(self.dev)
-        # weight pack of the two MLPs (ops.mlp_pack): written at the start of every render_and_grads, valid until its end
+        # weight pack of the two MLPs: written when a pass opens its scope (RenderCore.pass_scope), valid until the scope closes
         self.mlp_pack = torch.empty(ops.mlp_pack_workspace(), **f)
         self.se3 = torch.zeros(n_views, 6, **f)
         self.se3_grad, self.se3_m, self.se3_v = (torch.zeros(n_views, 6, **f) for _ in range(3))
@@ -479,58 +533,47 @@ class TrainEngine:
             self.dist.start_batch_stats(ws.count, ws.mask_px)
         progress = global_step / cfg.N_iters
         self._upload_step_scalars(progress)
-        s_val = cfg.s_val(global_step)
-        inv_s = float(np.float32(1.0) / np.float32(s_val))
+        s_val, inv_s = cfg.s_val(global_step), cfg.inv_s(global_step)
         P = self.flat
-        # The MLP weights are packed HERE, on the step's stream, and the record is dropped when the step's kernels are enqueued:
-        # every writer of flat.data (the optimiser, load_reference_params, a checkpoint load, an in-place copy from outside)
-        # runs between two calls of this function, so no kernel can read a pack older than its parameters.
-        ops.mlp_pack(P.view('warp'), P.view('rgbnet'), self.mlp_pack, self.ctx)
-        # Lean scope of the warp net, for this step's buffers and closed with the pack record: the forward kernel leaves out the
-        # tangent rows of X0, the data-gradient kernel Ybar3, and the weight-gradient kernel rebuilds both (option warp_lean)
-        if ws.warp_acts is not None:
-            ops.warp_lean_begin(ws.warp_acts, ws.scratch, P.view('warp'), self.ctx)
-        self.core.forward(ws, self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w,
-                          before_k0_use=None if self.dist is None else (lambda: self.dist.wait_parameters(self)))
-        ws.zero_block.zero_()
-        w_dyn = dynamic_weight(1e-1, 1e-3, global_step, cfg.N_iters)
-        ls = self.loss_scale
-        batch_norm = None if self.dist is None else self.dist.wait_batch_stats()
-        ops.loss_rays(ws.rgb_marched, ws.alphainv_last, ws.cum_weights, ws.target, ws.mask_px, ws.mask_sum, self.w_main,
-                      0.01, self.w_mask, ls, ws.g_rgbm, ws.g_last, ws.g_cw, ws.loss_out, batch_norm)
+        with self.core.pass_scope(P, self.mlp_pack, ws):
+            self.core.forward(ws, self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w,
+                              before_k0_use=None if self.dist is None else (lambda: self.dist.wait_parameters(self)))
+            ws.zero_block.zero_()
+            w_dyn = dynamic_weight(1e-1, 1e-3, global_step, cfg.N_iters)
+            ls = self.loss_scale
+            batch_norm = None if self.dist is None else self.dist.wait_batch_stats()
+            ops.loss_rays(ws.rgb_marched, ws.alphainv_last, ws.cum_weights, ws.target, ws.mask_px, ws.mask_sum, self.w_main,
+                          0.01, self.w_mask, ls, ws.g_rgbm, ws.g_last, ws.g_cw, ws.loss_out, batch_norm)
 
-        # The k0 scatter is issued from here (not inside colour-feature backward) so that it can mark the voxels it reaches:
-        # single GPU = right after the colour-feature backward; multi-GPU "samples" mode = replayed for all ranks' gathered
-        # samples at the end of the backward; "zero1" = dense reduce-scatter, no marking (every voxel may be non-zero).
-        dense_exchange = self.dist is not None and self.dist.local_scatter
-        k0_grad = self.k0_grad if dense_exchange else None
-        self._k0_marked = not dense_exchange
-        touched = self.k0_touched[self.touch_par]
+            # The k0 scatter is issued from here (not inside colour-feature backward) so that it can mark the voxels it reaches:
+            # single GPU = right after the colour-feature backward; multi-GPU "samples" mode = replayed for all ranks' gathered
+            # samples at the end of the backward; "zero1" = dense reduce-scatter, no marking (every voxel may be non-zero).
+            dense_exchange = self.dist is not None and self.dist.local_scatter
+            k0_grad = self.k0_grad if dense_exchange else None
+            self._k0_marked = not dense_exchange
+            touched = self.k0_touched[self.touch_par]
 
-        def after_k0():
-            if self.dist is None:
-                if self.deterministic_scatter:
-                    ops.k0_scatter_samples_sorted(sc, ws.pts, ws.count, ws.cap, ws.g_feat, self.k0_grad, self.scatter_work(ws.cap), touched)
+            def after_k0():
+                if self.dist is None:
+                    if self.deterministic_scatter:
+                        ops.k0_scatter_samples_sorted(sc, ws.pts, ws.count, ws.cap, ws.g_feat, self.k0_grad, self.scatter_work(ws.cap), touched)
+                    else:
+                        ops.k0_scatter_samples(sc, ws.pts, ws.count, ws.cap, ws.g_feat, self.k0_grad, touched)
                 else:
-                    ops.k0_scatter_samples(sc, ws.pts, ws.count, ws.cap, ws.g_feat, self.k0_grad, touched)
+                    self.dist.start_grid_reduce(self)
+            self.core.backward(ws, self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w,
+                               k0_grad, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
+                               priors=(1.0, w_dyn, ls, ws.loss_out, batch_norm),
+                               after_k0_grad=after_k0)
+            if self.deterministic:
+                ops.raygen_select_bwd_ordered(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, ws.rays_o, ws.rays_d,
+                                              ws.t_min, ws.ray_start, ws.g_pts, ws.step, ws.g_view_s, None, None, None, None, None,
+                                              None, None, self.c2w_grad, self.ctx)
             else:
-                self.dist.start_grid_reduce(self)
-        self.core.backward(ws, self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w,
-                           k0_grad, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
-                           priors=(1.0, w_dyn, ls, ws.loss_out, batch_norm),
-                           after_k0_grad=after_k0)
-        ctx = self.ctx
-        if self.deterministic:
-            ops.raygen_select_bwd_ordered(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, ws.rays_o, ws.rays_d,
-                                          ws.t_min, ws.ray_start, ws.g_pts, ws.step, ws.g_view_s, None, None, None, None, None,
-                                          None, None, self.c2w_grad, ctx)
-        else:
-            ops.raygen_select_bwd(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, ws.rays_o, ws.rays_d,
-                                  ws.t_min, ws.ray_start, ws.g_pts, ws.step, ws.g_view_s, None, None, None, None, None, None,
-                                  None, self.c2w_grad)
-        ops.pose_bwd(self.jac, self.c2w_grad, self.se3_grad)
-        ops.mlp_pack_invalidate(ctx)
-        ops.warp_lean_end(ctx)
+                ops.raygen_select_bwd(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, ws.rays_o, ws.rays_d,
+                                      ws.t_min, ws.ray_start, ws.g_pts, ws.step, ws.g_view_s, None, None, None, None, None, None,
+                                      None, self.c2w_grad)
+            ops.pose_bwd(self.jac, self.c2w_grad, self.se3_grad)
         return s_val, w_dyn
 
     def reprojection_grads(self, rows, mode, global_step, jitter=None, weight_projection=1.0, weight_near_surface=1.0, nl=0.0,
@@ -575,29 +618,22 @@ class TrainEngine:
         loss_args = (self.intr, self.w2c, self._rp_centre, self._rp_half_diag, nl, pixel_thre, weight_near_surface,
                      weight_projection, scale, rp['terms'], rp['g_p'], rp['g_depth'], rp['g_o'], rp['g_d'], rp['g_w2c'])
         if render:
-            s_val = cfg.s_val(global_step)
-            inv_s = float(np.float32(1.0) / np.float32(s_val))
-            ctx = self.ctx
+            par = (self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), cfg.inv_s(global_step), self.pe_w)
             # a weight pack and a lean scope of this pass's own, on its own buffers (render_and_grads closed its ones)
-            ops.mlp_pack(P.view('warp'), P.view('rgbnet'), self.mlp_pack, ctx)
-            if ws.warp_acts is not None:
-                ops.warp_lean_begin(ws.warp_acts, ws.scratch, P.view('warp'), ctx)
-            par = (self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w)
-            self.core.forward(ws, *par)
-            ops.reproj_loss(True, n, rows['other'], rows['match'], rows['conf'], ws.rays_o, ws.rays_d, None, None, ws.t_min,
-                            ws.depth_acc, *loss_args)
-            # depth-only loss: ws.g_rgbm / g_last / g_cw stay zero; no colour-grid gradient is requested (k0_grad = None, no scatter)
-            self.core.backward(ws, *par, None, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
-                               g_depth=rp['g_depth'])
-            ops.raygen_select_bwd(sc, None, None, None, 0, 0, True, ws.rays_o, ws.rays_d, ws.t_min, ws.ray_start, ws.g_pts,
-                                  ws.step, ws.g_view_s, rp['g_o'], rp['g_d'], None, rp['g_depth'], rp['go'], rp['gd'], rp['gv'],
-                                  None)
-            ops.mlp_pack_invalidate(ctx)
-            ops.warp_lean_end(ctx)
+            with self.core.pass_scope(P, self.mlp_pack, ws):
+                self.core.forward(ws, *par)
+                ops.reproj_loss(True, n, rows['other'], rows['match'], rows['conf'], ws.rays_o, ws.rays_d, None, None, ws.t_min,
+                                ws.depth_acc, *loss_args)
+                # depth-only loss: ws.g_rgbm / g_last / g_cw stay zero; no colour-grid gradient is requested (k0_grad = None, no scatter)
+                self.core.backward(ws, *par, None, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
+                                   g_depth=rp['g_depth'])
+                ops.raygen_select_bwd(sc, None, None, None, 0, 0, True, ws.rays_o, ws.rays_d, ws.t_min, ws.ray_start, ws.g_pts,
+                                      ws.step, ws.g_view_s, rp['g_o'], rp['g_d'], None, rp['g_depth'], rp['go'], rp['gd'], rp['gv'],
+                                      None)
             g_o, g_d, g_v, g_t = rp['go'], rp['gd'], rp['gv'], None
         else:
             S = cfg.n_samples
-            dist = float(np.float32(cfg.stepsize) * np.float32(cfg.voxel_size))
+            dist = cfg.step_dist
             dense, sdf_d = ws.alpha, ws.sdf_final                   # [cap * S] each: free in this mode
             ops.reproj_dense_pts(sc, ws.rays_o, ws.rays_d, ws.t_min, jitter, ws.pts)
             ops.grid_sample_fwd(sc, self.sdf, 1, ws.pts, 1, dense)
@@ -675,7 +711,11 @@ class TrainEngine:
         return out
 
     # ---- checkpoint / resume (wire format of recon_scene.save_checkpoints, lib/recon_scene.py:779-790) -------------
-    RGBNET_KEYS = ('rgbnet.0', 'rgbnet.2.0', 'rgbnet.3.0', 'rgbnet.4')
+    def _mlp_state(self, which='data'):
+        """(state_dict prefix, W, b) of every layer of both MLPs: views into flat.<which> in the reference's logical shapes."""
+        for net in ('rgbnet', 'warp'):
+            for (*_, key), (W, b) in zip(MLP_LAYOUT[net], _unpack(net, self.flat.view(net, which))):
+                yield key, W, b
 
     def model_state_dict(self):
         """The trainable state under the reference's state_dict names and logical shapes (lib/voxurf_coarse.py module tree,
@@ -688,11 +728,8 @@ class TrainEngine:
               'sdf.grid': c(self.sdf)[None, None], 'k0.grid': c(self.k0_reference_layout()).contiguous()}
         for name in ('sdf', 'k0'):
             sd[name + '.xyz_min'], sd[name + '.xyz_max'] = sd['xyz_min'].clone(), sd['xyz_max'].clone()
-        for key, (W, b) in zip(self.RGBNET_KEYS, unpack_rgbnet(P.view('rgbnet'))):
+        for key, W, b in self._mlp_state():
             sd[key + '.weight'], sd[key + '.bias'] = c(W).contiguous(), c(b)
-        for i, (W, b) in enumerate(unpack_warp(P.view('warp'))):
-            sd[f'warp_network.deform_net.net.net.{i}.0.weight'] = c(W)
-            sd[f'warp_network.deform_net.net.net.{i}.0.bias'] = c(b)
         return sd
 
     def voxurf_view(self, model=None):
@@ -710,18 +747,13 @@ class TrainEngine:
             model.sdf_alpha.data.copy_(P.view('sdf_ab')[0:1])
             model.sdf_beta.data.copy_(P.view('sdf_ab')[1:2])
             sd = dict(model.named_parameters())
-            for key, (W, b) in zip(self.RGBNET_KEYS, unpack_rgbnet(P.view('rgbnet'))):
+            for key, W, b in self._mlp_state():
                 sd[key + '.weight'].data.copy_(W)
                 sd[key + '.bias'].data.copy_(b)
-            for i, (W, b) in enumerate(unpack_warp(P.view('warp'))):
-                sd[f'warp_network.deform_net.net.net.{i}.0.weight'].data.copy_(W)
-                sd[f'warp_network.deform_net.net.net.{i}.0.bias'].data.copy_(b)
         return model
 
     def load_model_state_dict(self, sd):
-        rg = [(sd[k + '.weight'], sd[k + '.bias']) for k in self.RGBNET_KEYS]
-        wp = [(sd[f'warp_network.deform_net.net.net.{i}.0.weight'], sd[f'warp_network.deform_net.net.net.{i}.0.bias'])
-              for i in range(5)]
+        rg, wp = ([(sd[k + '.weight'], sd[k + '.bias']) for *_, k in MLP_LAYOUT[net]] for net in ('rgbnet', 'warp'))
         self.load_reference_params(sd['k0.grid'], sd['sdf.grid'], sd['sdf_alpha'], sd['sdf_beta'], rg, wp)
 
     # ---- optimiser state in the reference's layout ---------------------------------------------------------------------
@@ -828,10 +860,9 @@ class TrainEngine:
             for which, pick in (('data', 0), ('m', 1), ('v', 2)):
                 ab = F.view('sdf_ab', which)
                 ab[0:1].copy_(d(tensors['sdf_alpha'][pick]).reshape(1)); ab[1:2].copy_(d(tensors['sdf_beta'][pick]).reshape(1))
-                for li, (W, b) in enumerate(unpack_rgbnet(F.view('rgbnet', which))):
-                    W.copy_(d(tensors[f'rgbnet.{li}.weight'][pick])); b.copy_(d(tensors[f'rgbnet.{li}.bias'][pick]))
-                for li, (W, b) in enumerate(unpack_warp(F.view('warp', which))):
-                    W.copy_(d(tensors[f'warp.{li}.weight'][pick])); b.copy_(d(tensors[f'warp.{li}.bias'][pick]))
+                for net in ('rgbnet', 'warp'):
+                    for li, (W, b) in enumerate(_unpack(net, F.view(net, which))):
+                        W.copy_(d(tensors[f'{net}.{li}.weight'][pick])); b.copy_(d(tensors[f'{net}.{li}.bias'][pick]))
             self.se3.copy_(d(se3)); self.se3_m.copy_(d(se3_m)); self.se3_v.copy_(d(se3_v))
         self.n_step = int(n_step)
         for k in self.lr:

@@ -11,8 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import camera, grid, ops
-from .engine import (FlatParams, RenderCore, SceneConfig, Workspace, pack_rgbnet, pack_warp, unpack_rgbnet,
-                     unpack_warp)
+from .engine import FlatParams, RenderCore, SceneConfig, Workspace
 from .grid import channels_last_view
 
 
@@ -125,10 +124,8 @@ class _VoxurfRender(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, ws, inv_s, pe_w, rays_o, rays_d, viewdirs, k0, sdf_alpha, sdf_beta, *mlp):
         core = model._core
-        flat = FlatParams(rays_o.device, moments=False)
-        rg = [(mlp[2 * i], mlp[2 * i + 1]) for i in range(4)]
-        wp = [(mlp[8 + 2 * i], mlp[8 + 2 * i + 1]) for i in range(5)]
-        flat.load_reference(sdf_alpha, sdf_beta, rg, wp)
+        flat = FlatParams(rays_o.device, moments=False)        # this node's own: its `grad` half belongs to this node's backward
+        flat.load_reference(sdf_alpha, sdf_beta, list(zip(mlp[0:8:2], mlp[1:8:2])), list(zip(mlp[8::2], mlp[9::2])))
         k0_cl = channels_last_view(k0)
         sdf_g = model.sdf.grid.detach()[0, 0].contiguous()
         core.forward(ws, k0_cl, sdf_g, flat.view('sdf_ab'), flat.view('rgbnet'), flat.view('warp'), inv_s, pe_w)
@@ -153,7 +150,7 @@ class _VoxurfRender(torch.autograd.Function):
     def backward(ctx, g_rgbm, g_last, g_cw, g_w, g_alpha, g_rgb, g_depth, g_grad, g_sdfd, g_gdef, g_corr, g_nstep, g_tv):
         model, ws, flat = ctx.model, ctx.ws, ctx.flat
         core, M, cap = model._core, ws.M, ws.cap
-        ws.alloc_backward()
+        ws.alloc_backward(False)
         dev = ws.rays_o.device
 
         def padded(t, width=None):
@@ -210,23 +207,6 @@ class _VoxurfRender(torch.autograd.Function):
         for W, b in g['rgbnet'] + g['warp']:
             mlp_grads += [W.contiguous(), b.contiguous()]
         return (None, None, None, None, go, gd, gv, k0_grad, g['sdf_alpha'], g['sdf_beta'], *mlp_grads)
-
-
-def _ws_alloc_backward(self):
-    if hasattr(self, 'g_alpha'):
-        return
-    f = dict(dtype=torch.float32, device=self.rays_o.device)
-    e, N, cap = torch.empty, self.N, self.cap
-    self.g_rgbm, self.g_last, self.g_cw = e(N, 3, **f), e(N, **f), e(N, **f)
-    self.g_alpha, self.g_rgb = e(cap, **f), e(cap, 3, **f)
-    self.g_feat = e(cap, ops.FEAT_LD, **f)
-    self.g_gradient, self.g_pts, self.g_view_s = e(cap, 3, **f), e(cap, 3, **f), e(cap, 3, **f)
-    self.g_warp_out = e(cap, 16, **f)
-    self.scratch = e(3 * cap * 4 * 128 + 49152, **f)
-    self.scratch_rgb = e(3 * cap * 128 + 49152, **f)
-
-
-Workspace.alloc_backward = _ws_alloc_backward
 
 
 class _WarpNet(nn.Module):
@@ -359,6 +339,7 @@ class Voxurf(torch.nn.Module):
             p.requires_grad = False
         self.grad_mode = grad_mode
         self._core = None
+        self._flat = {}
 
     # ---- construction helpers -----------------------------------------------------------------------------
     def _set_grid_resolution(self, num_voxels):
@@ -424,12 +405,22 @@ class Voxurf(torch.nn.Module):
         return total_variation(self.k0.grid) if k0_tv > 0 else 0
 
     # ---- parameter gathering ----------------------------------------------------------------------------------
-    def _mlp_tensors(self):
+    def _mlp_layers(self):
+        """-> [(W, b)] of rgbnet, [(W, b)] of the warp net, in layer order."""
         rg = [self.rgbnet[0], self.rgbnet[2][0], self.rgbnet[3][0], self.rgbnet[4]]
-        out = []
-        for lin in rg + self.warp_network.linears():
-            out += [lin.weight, lin.bias]
-        return out
+        return [[(lin.weight, lin.bias) for lin in net] for net in (rg, self.warp_network.linears())]
+
+    def _mlp_tensors(self):
+        return [t for net in self._mlp_layers() for Wb in net for t in Wb]
+
+    def _flat_params(self, dev):
+        """The module's small parameters (alpha / beta, both MLPs) as the forward-only callers' kernels read them: one FlatParams
+        without optimiser moments per device, refilled from the current values on every call."""
+        flat = self._flat.get(str(dev))
+        if flat is None:
+            flat = self._flat[str(dev)] = FlatParams(dev, moments=False)
+        flat.load_reference(self.sdf_alpha, self.sdf_beta, *self._mlp_layers())
+        return flat
 
     def _set_progress(self, global_step):
         v = 1. if global_step is None else global_step / self.N_iters
@@ -502,7 +493,7 @@ class Voxurf(torch.nn.Module):
         if is_train:
             jitter = render_kwargs.get('jitter')
             jitter = torch.rand(N, device=dev) if jitter is None else jitter.to(dev).float().contiguous()
-        dist = float(np.float32(cfg.stepsize) * np.float32(cfg.voxel_size))
+        dist = cfg.step_dist
         if not mapped:
             needs_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
             # t_min enters the surface point explicitly; its dependence on the ray (slab test) is plain torch algebra
@@ -526,10 +517,7 @@ class Voxurf(torch.nn.Module):
             cap = max(M, 1)
             vd = rd / rd.norm(dim=-1, keepdim=True)
             warp_out = torch.zeros(cap, 16, device=dev)
-            flat = FlatParams(dev)
-            mlp = self._mlp_tensors()
-            flat.load_reference(self.sdf_alpha, self.sdf_beta, [(mlp[2 * k], mlp[2 * k + 1]) for k in range(4)],
-                                [(mlp[8 + 2 * k], mlp[8 + 2 * k + 1]) for k in range(5)])
+            flat = self._flat_params(dev)
             if use_deform and M > 0:
                 acts = torch.empty(4, cap * 4, 128, device=dev)
                 ops.warp_fwd(flat.view('warp'), sb['pts'], sb['count'], cap, cfg.out_range, acts, warp_out, core.ctx)
@@ -618,11 +606,9 @@ class Voxurf(torch.nn.Module):
         sb = self._sample_dense(core, ro.detach(), rd.detach(), jitter)
         M = sb['M']
         cap = max((M + 4095) // 4096 * 4096, 4096)
-        ws = Workspace(N, cap, ro.device, sample_capacity=sb['pts'].shape[0], backward=False, ctx=core.ctx)
+        ws = Workspace(N, cap, ro.device, backward=False, ctx=core.ctx, samples=sb)
         ws.M = M
         ws.rays_o, ws.rays_d, ws.viewdirs = ro.detach(), rd.detach(), vd.detach()
-        for k in ('t_min', 't_max', 'ray_start', 'count', 'pts', 'ray_id', 'step_k', 'step'):
-            setattr(ws, k, sb[k])
         s_val, inv_s = self._inv_s(global_step, is_train)
         pe_w = self._pe_weights(cfg, progress, ro.device)
         self.k0.ensure_layout()
@@ -647,50 +633,68 @@ class Voxurf(torch.nn.Module):
             '_t_min': ws.t_min, '_n_step': n_step,   # extras (not in the reference dict) for query_sdf_point_wocuda_render
         }
 
-    @torch.no_grad()
-    def inference(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
-        """voxurf_coarse.py:1094-1222: variable-length sampler (sample_pts_on_rays semantics), forward chain only."""
+    def _inference_pass(self, rays_o, rays_d, viewdirs, global_step, render_kwargs, per_ray):
+        """What inference and inference_rays share: checks, variable-length sampler (sample_pts_on_rays semantics), step distances,
+        s_val, PE weights, parameters, and the forward chain inside one pass scope -> (ws, s_val).
+        per_ray=False: buffers of this call; ONE host round trip for the sample count M (ws.M) sizes the workspace.
+        per_ray=True: the buffers are sized for the sampler's worst case (N (S + 2) samples) and kept on the module, every kernel
+        stops at the device-side count, and the marching kernel composites the normals (ws.normal_marched)."""
         self._check_inputs(rays_o, rays_d, viewdirs)
         core = self._scene(render_kwargs)
         cfg = core.cfg
-        is_train = global_step is not None
         progress = self._set_progress(global_step)
-        N = len(rays_o)
-        dev = rays_o.device
+        N, dev = len(rays_o), rays_o.device
         ro, rd, vd = rays_o.contiguous().float(), rays_d.contiguous().float(), viewdirs.contiguous().float()
         f, i = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
         sc = N * (cfg.n_samples + 2)
-        t_min, t_max, n_steps = torch.empty(N, **f), torch.empty(N, **f), torch.empty(N, **i)
-        ray_start, count = torch.zeros(N + 1, **i), torch.zeros(1, **i)
-        pts, ray_id, step_id = torch.empty(sc, 3, **f), torch.empty(sc, **i), torch.empty(sc, **i)
-        ops.sample_var(cfg.pp, ro, rd, sc, t_min, t_max, n_steps, ray_start, count, pts, ray_id, step_id)
-        M = int(count.item())
-        cap = max((M + 4095) // 4096 * 4096, 4096)
-        ws = Workspace(N, cap, dev, sample_capacity=sc, backward=False, keep_activations=False, ctx=core.ctx)
-        ws.M = M
+        if per_ray:
+            cap = (sc + 4095) // 4096 * 4096
+            key = (N, cap, str(dev), id(core))
+            cache = getattr(self, '_ray_cache', None)
+            if cache is None or cache['key'] != key:
+                ws = Workspace(N, cap, dev, sample_capacity=cap, backward=False, keep_activations=False, ctx=core.ctx)
+                ws.n_steps = torch.empty(N, **i)
+                ws.nrm = torch.empty(cap, 3, **f)
+                ws.normal_marched = torch.empty(N, 3, **f)
+                self._ray_cache = cache = dict(key=key, ws=ws, pack=torch.empty(ops.mlp_pack_workspace(), **f))
+            ws, pack = cache['ws'], cache['pack']
+            sm, n_steps = {k: getattr(ws, k) for k in Workspace.SAMPLER}, ws.n_steps
+        else:
+            sm = dict(t_min=torch.empty(N, **f), t_max=torch.empty(N, **f), ray_start=torch.zeros(N + 1, **i),
+                      count=torch.zeros(1, **i), pts=torch.empty(sc, 3, **f), ray_id=torch.empty(sc, **i),
+                      step_k=torch.empty(sc, **i))
+            n_steps = torch.empty(N, **i)
+        ops.sample_var(cfg.pp, ro, rd, sm['pts'].shape[0], sm['t_min'], sm['t_max'], n_steps, sm['ray_start'], sm['count'], sm['pts'],
+                       sm['ray_id'], sm['step_k'])
+        if per_ray:
+            torch.mul(ws.step_k, cfg.step_dist, out=ws.step)        # step_id * dist (fp32 product of an exact integer)
+        else:
+            M = int(sm['count'].item())
+            sm['step'] = sm['step_k'].float() * cfg.step_dist
+            ws = Workspace(N, max((M + 4095) // 4096 * 4096, 4096), dev, backward=False, keep_activations=False, ctx=core.ctx,
+                           samples=sm)
+            ws.M = M
+            pack = torch.empty(ops.mlp_pack_workspace(), **f)
         ws.rays_o, ws.rays_d, ws.viewdirs = ro, rd, vd
-        ws.t_min, ws.t_max, ws.ray_start, ws.count, ws.pts, ws.ray_id, ws.step_k = t_min, t_max, ray_start, count, pts, ray_id, step_id
-        dist = float(np.float32(cfg.stepsize) * np.float32(cfg.voxel_size))
-        ws.step = step_id[:].float() * dist
-        s_val, inv_s = self._inv_s(global_step, is_train)
+        s_val, inv_s = self._inv_s(global_step, global_step is not None)
         pe_w = self._pe_weights(cfg, progress, dev)
         self.k0.ensure_layout()
-        flat = FlatParams(dev)
-        mlp = self._mlp_tensors()
-        flat.load_reference(self.sdf_alpha, self.sdf_beta, [(mlp[2 * k], mlp[2 * k + 1]) for k in range(4)],
-                            [(mlp[8 + 2 * k], mlp[8 + 2 * k + 1]) for k in range(5)])
-        # the weights are packed once per call (ops.mlp_pack) and the record is dropped before returning
-        pack = torch.empty(ops.mlp_pack_workspace(), **f)
-        ops.mlp_pack(flat.view('warp'), flat.view('rgbnet'), pack, core.ctx)
-        try:
+        flat = self._flat_params(dev)
+        with core.pass_scope(flat, pack):       # the weights are packed once per call and the record is dropped before returning
             core.forward(ws, channels_last_view(self.k0.grid), self.sdf.grid[0, 0].contiguous(), flat.view('sdf_ab'),
-                         flat.view('rgbnet'), flat.view('warp'), inv_s, pe_w)
-        finally:
-            ops.mlp_pack_invalidate(core.ctx)
+                         flat.view('rgbnet'), flat.view('warp'), inv_s, pe_w,
+                         normals=(ws.nrm, ws.normal_marched) if per_ray else None)
+        return ws, s_val
+
+    @torch.no_grad()
+    def inference(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
+        """voxurf_coarse.py:1094-1222: variable-length sampler (sample_pts_on_rays semantics), forward chain only."""
+        ws, s_val = self._inference_pass(rays_o, rays_d, viewdirs, global_step, render_kwargs, per_ray=False)
+        M, ray_id, step_id = ws.M, ws.ray_id, ws.step_k
         gradient = ws.gradient[:M]
         normal = gradient / (gradient.norm(2, -1, keepdim=True) + 1e-6)
         weights = ws.weights[:M]
-        normal_marched = torch.zeros(N, 3, device=dev).index_add_(0, ray_id[:M].long(), weights.unsqueeze(-1) * normal)
+        normal_marched = torch.zeros(ws.N, 3, device=rays_o.device).index_add_(0, ray_id[:M].long(), weights.unsqueeze(-1) * normal)
         depth = ws.depth_acc.clone()
         return {
             'alphainv_cum': ws.alphainv_last, 'weights': weights, 'cum_weights': ws.cum_weights.unsqueeze(-1),
@@ -701,57 +705,13 @@ class Voxurf(torch.nn.Module):
             'ray_id': ray_id[:M].long(), 'step_id': step_id[:M].long(),
         }
 
-
     @torch.no_grad()
     def inference_rays(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
         """The per-RAY outputs of `inference` (rgb_marched, alphainv_cum, cum_weights, depth, disp, normal_marched) WITHOUT the
         host round trip for the sample count: what a whole-view driver keeps of a chunk (lib/nvs_fun.py:74-85 discards every
-        per-sample entry).  Same kernels on the same samples as `inference` - the chunk's buffers are sized for the sampler's
-        worst case (N (S + 2) samples) and kept on the module, every kernel stops at the device-side count, the normals are
-        composited by the marching kernel itself - so a view is 40 chunks enqueued back to back instead of 40 syncs."""
-        self._check_inputs(rays_o, rays_d, viewdirs)
-        core = self._scene(render_kwargs)
-        cfg = core.cfg
-        is_train = global_step is not None
-        progress = self._set_progress(global_step)
-        N, dev = len(rays_o), rays_o.device
-        ro, rd, vd = rays_o.contiguous().float(), rays_d.contiguous().float(), viewdirs.contiguous().float()
-        sc = N * (cfg.n_samples + 2)
-        cap = (sc + 4095) // 4096 * 4096
-        key = (N, cap, str(dev), id(core))
-        cache = getattr(self, '_ray_cache', None)
-        if cache is None or cache['key'] != key:
-            f, i = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
-            ws = Workspace(N, cap, dev, sample_capacity=cap, backward=False, keep_activations=False, ctx=core.ctx)
-            ws.n_steps = torch.empty(N, **i)
-            ws.nrm = torch.empty(cap, 3, **f)
-            ws.normal_marched = torch.empty(N, 3, **f)
-            self._ray_cache = cache = dict(key=key, ws=ws, flat=FlatParams(dev, moments=False),
-                                           pack=torch.empty(ops.mlp_pack_workspace(), **f))
-        ws, flat = cache['ws'], cache['flat']
-        ws.rays_o, ws.rays_d, ws.viewdirs = ro, rd, vd
-        ops.sample_var(cfg.pp, ro, rd, cap, ws.t_min, ws.t_max, ws.n_steps, ws.ray_start, ws.count, ws.pts, ws.ray_id, ws.step_k)
-        dist = float(np.float32(cfg.stepsize) * np.float32(cfg.voxel_size))
-        torch.mul(ws.step_k, dist, out=ws.step)                     # step_id * dist (fp32 product of an exact integer)
-        s_val, inv_s = self._inv_s(global_step, is_train)
-        pe_w = self._pe_weights(cfg, progress, dev)
-        self.k0.ensure_layout()
-        mlp = self._mlp_tensors()
-        flat.load_reference(self.sdf_alpha, self.sdf_beta, [(mlp[2 * k], mlp[2 * k + 1]) for k in range(4)],
-                            [(mlp[8 + 2 * k], mlp[8 + 2 * k + 1]) for k in range(5)])
-        sdf_g = self.sdf.grid[0, 0].contiguous()
-        ops.mlp_pack(flat.view('warp'), flat.view('rgbnet'), cache['pack'], core.ctx)     # after load_reference: once per call
-        ops.warp_fwd(flat.view('warp'), ws.pts, ws.count, ws.cap, cfg.out_range, ws.warp_acts, ws.warp_out, core.ctx)
-        ops.geometry_fwd(cfg.pp, sdf_g, flat.view('sdf_ab'), ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
-                         ws.alpha, ws.gradient, ws.sdf_final, ws.sdf_deform, ws.grad_deform)
-        ops.color_feat_fwd(cfg.pp, channels_last_view(self.k0.grid), ws.pts, ws.viewdirs, ws.ray_id, ws.gradient, pe_w, ws.count,
-                           ws.cap, ws.feat)
-        ops.rgbnet_fwd(flat.view('rgbnet'), ws.feat, ws.count, ws.cap, ws.rgb_acts, ws.rgb, core.ctx)
-        ops.mlp_pack_invalidate(core.ctx)
-        # rows past the count hold stale values: harmless, the marching kernel walks ray_start ranges only
-        torch.div(ws.gradient, ws.gradient.norm(2, -1, keepdim=True) + 1e-6, out=ws.nrm)
-        ops.march_fwd(ws.alpha, ws.rgb, ws.step, ws.nrm, ws.ray_start, N, cfg.bg, ws.weights, ws.T, ws.alphainv_last, ws.i_end,
-                      ws.rgb_marched, ws.rgb_pre, ws.cum_weights, ws.depth_acc, ws.normal_marched)
+        per-sample entry).  Same kernels on the same samples as `inference`, so a view is 40 chunks enqueued back to back instead
+        of 40 syncs.  The buffers are reused by the next call: every output is a clone."""
+        ws, s_val = self._inference_pass(rays_o, rays_d, viewdirs, global_step, render_kwargs, per_ray=True)
         depth = ws.depth_acc.clone()
         return {'alphainv_cum': ws.alphainv_last.clone(), 'cum_weights': ws.cum_weights.clone().unsqueeze(-1),
                 'rgb_marched': ws.rgb_marched.clone(), 'normal_marched': ws.normal_marched.clone(), 'depth': depth, 'disp': 1 / depth,

@@ -44,6 +44,41 @@ def test_parameter_packing_roundtrip():
         assert torch.equal(W, W2) and torch.equal(b, b2)
 
 
+def test_layout_table_sums_to_the_library_parameter_counts():
+    from poseprobe_amd import ops
+    from poseprobe_amd.engine import MLP_LAYOUT
+    size = lambda net: sum(o * ld + o for o, i, ld, key in MLP_LAYOUT[net])
+    assert size('rgbnet') == ops.RGBNET_PARAMS and size('warp') == ops.WARP_PARAMS
+    assert all(ld >= i and key for net in MLP_LAYOUT.values() for o, i, ld, key in net)
+    assert [len(MLP_LAYOUT[net]) for net in ('rgbnet', 'warp')] == [4, 5] and MLP_LAYOUT['rgbnet'][0][1:3] == (57, 64)
+
+
+def test_scene_scalars_are_the_fp32_expressions():
+    from poseprobe_amd import synthetic as syn
+    from poseprobe_amd.engine import SceneConfig
+    cfg = SceneConfig(syn.XYZ_MIN, syn.XYZ_MAX, 24 ** 3)
+    assert cfg.step_dist == float(np.float32(cfg.stepsize) * np.float32(cfg.voxel_size))
+    for gs in (0, 10, 7000):
+        assert cfg.inv_s(gs) == float(np.float32(1.0) / np.float32(cfg.s_val(gs)))
+
+
+def test_alloc_backward_gives_the_buffers_of_a_backward_workspace():
+    """Workspace(backward=False) + alloc_backward(False) holds what Workspace(backward=True) holds: names, shapes, dtypes."""
+    from poseprobe_amd.engine import Workspace
+    N, cap = 5, 70
+    full, late = Workspace(N, cap, 'cpu'), Workspace(N, cap, 'cpu', backward=False)
+    assert not hasattr(late, 'g_alpha')
+    late.alloc_backward(False)
+    sig = lambda ws: {k: (tuple(v.shape), v.dtype) if torch.is_tensor(v) else v for k, v in vars(ws).items()}
+    assert sig(full) == sig(late)
+    assert {'g_rgbm', 'g_last', 'g_cw', 'g_alpha', 'g_rgb', 'g_feat', 'g_gradient', 'g_pts', 'g_view_s', 'g_warp_out', 'scratch',
+            'scratch_rgb'} <= set(vars(full))
+    assert full.scratch.numel() == 3 * cap * 4 * 128 + 49152 and full.scratch_rgb.numel() == 3 * cap * 128 + 49152
+    assert float(full.scratch.abs().sum()) == 0                    # zeroed for the lean scope
+    late.alloc_backward(True)                                       # no-op once the buffers exist
+    assert sig(full) == sig(late)
+
+
 def test_schedules_match_the_oracle():
     from oracle import voxurf_oracle as O
     from poseprobe_amd import synthetic as syn
