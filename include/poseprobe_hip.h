@@ -45,7 +45,7 @@ const char* pp_last_error(void);
  * ownership from stage 1 to stage 2 explicitly -, pp_nerf_fwd / pp_nerf_bwd, pp_grid_tv_adam_step{,_sparse});
  * pp_scene gained `sdf_index_exact`; new: pp_sdf_crossing_dense_bwd, pp_context_set_option / pp_context_get_option.  4 (this header): the
  * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
- * Entry points added without a version change (no existing signature moved): the pp_reproj_* group.
+ * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_mc_* group.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
  * (poseprobe_amd/_lib.py does): the signatures changed, so a stale caller would pass a stream where a pointer is read. */
 #define PP_ABI_VERSION 4
@@ -638,6 +638,39 @@ int pp_nerf_c2w_fold(const float* g_ray, const float* g_center, const float* dir
                      int32_t n_views_total, float* g_c2w, void* stream);
 int pp_nerf_sample_pdf(const float* weights, const float* depth, const float* grid, int32_t grid_per_ray, int32_t n_rays,
                        int32_t n_samples, int32_t n_fine, float depth_min, float depth_max, float* depth_out, void* stream);
+
+/* ---------------------------------------------------------------- mesh extraction: marching cubes
+ * lib/dvgo_ori.py:695-703 calls mcubes.marching_cubes(u, threshold) on a host lattice; here u [X,Y,Z] (fp32, C order, the
+ * layout extract_fields fills) stays on the device and the result is an indexed mesh with shared vertices in lattice (index)
+ * coordinates: vertices [n_vertices,3] fp32, triangles [n_triangles,3] int32 vertex ids.
+ *   - a corner is BELOW iff u < threshold (fp32 compare); a lattice edge is ACTIVE iff exactly one endpoint is below; it is
+ *     owned by its lower endpoint p0 and its axis a (0 x, 1 y, 2 z);
+ *   - every active edge carries one vertex: t = (threshold - u[p0]) / (u[p1] - u[p0]) in fp32 (0 <= t <= 1), coordinate a is
+ *     float(p0[a]) + t, the other two are the integers of p0;
+ *   - canonical order, no atomics: the vertex id is the rank of its edge among the active edges in the order
+ *     3 (x Y Z + y Z + z) + a; triangles are ordered by cell in C order over (X-1, Y-1, Z-1), then by table row order: the
+ *     output is bit-reproducible;
+ *   - winding: the geometric normal (v1 - v0) x (v2 - v0) points toward DECREASING u (for u = -sdf: outward);
+ *   - non-finite field values are the caller's problem (a NaN corner counts as not below; its edges interpolate to NaN).
+ * Case table (pp_mc_table, a pure host function: table [256*16] int32 on the HOST): corner c of a cell sits at offset
+ * (c & 1, (c >> 1) & 1, (c >> 2) & 1) from the cell's low corner and bit c of the case index is set iff that corner is below;
+ * edge e in 0..11 runs along axis a = e >> 2, and with j = e & 3 its lower endpoint sits at the offset whose two OTHER
+ * coordinates, in ascending axis order, are (j & 1, j >> 1) (edge 0..3: x edges at (y,z) = (0,0) (1,0) (0,1) (1,1); 4..7: y
+ * edges at (x,z) likewise; 8..11: z edges at (x,y) likewise).  Row `case` holds at most 5 triangles as triples of edge ids,
+ * terminated by -1 (tools/gen_mc_table.py generates it; tests/test_mesh_host.py checks its properties exhaustively).
+ * pp_mc_workspace (pure host function): bytes of `work` for a lattice - one flag byte and one int32 vertex base per point
+ * (padded to whole 1024-point tiles) plus 8 bytes per tile, about 5 X Y Z.
+ * pp_mc_count classifies the lattice into `work` and writes counts[2] (DEVICE) = (vertices, triangles); a triangle total
+ * above 2^31 - 1 is reported as -1.  pp_mc_emit, given the SAME u, sizes, threshold and work, ordered behind pp_mc_count,
+ * writes rows [0, n_vertices) and [0, n_triangles) - the counted rows when handed the counts - and nothing past them.
+ * `work` is 16-byte aligned.  All four refuse, before any GPU call: null pointers, a dimension below 2, 3 X Y Z >= 2^31
+ * (PP_ERR_UNSUPPORTED: vertex ids are 32-bit), a workspace that is too small. */
+int pp_mc_table(int32_t* table_host);
+int pp_mc_workspace(int32_t X, int32_t Y, int32_t Z, int64_t* bytes);
+int pp_mc_count(const float* u, int32_t X, int32_t Y, int32_t Z, float threshold, void* work, int64_t work_bytes,
+                int32_t* counts, void* stream);
+int pp_mc_emit(const float* u, int32_t X, int32_t Y, int32_t Z, float threshold, void* work, int64_t work_bytes,
+               float* vertices, int32_t n_vertices, int32_t* triangles, int32_t n_triangles, void* stream);
 
 #ifdef __cplusplus
 }

@@ -291,7 +291,8 @@ class DirectVoxGO(torch.nn.Module):
                 'depth': depth, 'disp': 1 / depth, 'mask': mask_d, 'mask_outbbox': ~keep.bool().reshape(N, S)}
 
     def extract_geometry(self, *a, **k):
-        raise NotImplementedError('mesh extraction needs `mcubes`, which is out of scope of the hot path (DESIGN.md 8)')
+        raise NotImplementedError('mesh extraction needs `mcubes`, which is not available offline; use '
+                                  'poseprobe_amd.mesh.dvgo_extract_geometry(model, ...) (marching cubes as HIP kernels)')
 
 
 # ---- remaining names of lib/dvgo_ori.py's module surface ---------------------------------------------------------
@@ -358,7 +359,7 @@ def extract_fields(bound_min, bound_max, resolution, query_func, N=64):
 
 
 def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, N=64):
-    """lib/dvgo_ori.py:695-703 needs `mcubes.marching_cubes`, which is not available offline: the sampled field is what
-    this package can deliver (extract_fields); triangulate it with any marching-cubes implementation."""
+    """lib/dvgo_ori.py:695-703 needs `mcubes.marching_cubes`, which is not available offline.  This name keeps refusing;
+    poseprobe_amd.mesh.extract_geometry has the same signature and triangulates on the GPU (in a canonical order of its own)."""
     raise NotImplementedError('extract_geometry (lib/dvgo_ori.py:695-703): marching cubes (`mcubes`) is not available '
-                              'offline; use extract_fields(...) and triangulate the returned lattice elsewhere')
+                              'offline; use poseprobe_amd.mesh.extract_geometry(...), which triangulates on the GPU')

@@ -584,3 +584,44 @@ def nerf_sample_pdf(weights, depth, grid, n_fine, depth_range, depth_out):
         raise RuntimeError('nerf_sample_pdf: inconsistent shapes')
     _lib.call('pp_nerf_sample_pdf', _f(weights), _f(depth), _f(grid), int(per_ray), int(R), int(S), int(n_fine),
               ctypes.c_float(depth_range[0]), ctypes.c_float(depth_range[1]), _f(depth_out), _stream())
+
+
+# ------------------------------------------------------------------------------------------- mesh extraction
+def mc_table():
+    """The 256-case triangle table of the marching-cubes kernels as an int32 [256, 16] numpy array (rows of edge ids in triples,
+    -1 terminated; numbering in include/poseprobe_hip.h).  A pure host call: needs no GPU."""
+    t = np.empty((256, 16), dtype=np.int32)
+    _lib.call('pp_mc_table', t.ctypes.data_as(ctypes.c_void_p))
+    return t
+
+
+def mc_workspace(X, Y, Z):
+    """Bytes of device workspace pp_mc_count / pp_mc_emit need for an [X, Y, Z] lattice."""
+    b = ctypes.c_int64()
+    _lib.call('pp_mc_workspace', int(X), int(Y), int(Z), ctypes.byref(b))
+    return b.value
+
+
+def _mc_lattice(u):
+    if u is not None and u.dim() != 3:
+        raise RuntimeError('u must be a [X, Y, Z] lattice')
+    return (0, 0, 0) if u is None else tuple(int(s) for s in u.shape)
+
+
+def mc_count(u, threshold, work, counts):
+    """Classify the lattice u [X,Y,Z] into `work` (uint8, mc_workspace bytes); counts [2] int32 <- (vertices, triangles)."""
+    X, Y, Z = _mc_lattice(u)
+    _lib.call('pp_mc_count', _f(u, 'u'), X, Y, Z, ctypes.c_float(threshold), _u8(work, 'work'),
+              0 if work is None else int(work.numel()), _i(counts, 'counts'), _stream())
+
+
+def mc_emit(u, threshold, work, vertices, n_vertices, triangles, n_triangles):
+    """After mc_count with the same u, threshold and work: rows [0, n_vertices) of vertices [.,3] fp32 and [0, n_triangles) of
+    triangles [.,3] int32."""
+    X, Y, Z = _mc_lattice(u)
+    for t, n, name in ((vertices, n_vertices, 'vertices'), (triangles, n_triangles, 'triangles')):
+        if t is not None and t.numel() < 3 * int(n):
+            raise RuntimeError(f'{name}: {t.numel() // 3} rows, {int(n)} to be written')
+    _lib.call('pp_mc_emit', _f(u, 'u'), X, Y, Z, ctypes.c_float(threshold), _u8(work, 'work'),
+              0 if work is None else int(work.numel()), _f(vertices, 'vertices'), int(n_vertices), _i(triangles, 'triangles'),
+              int(n_triangles), _stream())

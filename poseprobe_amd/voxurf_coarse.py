@@ -932,9 +932,9 @@ def get_training_rays_in_maskcache_sampling(rgb_tr_ori, train_poses, HW, Ks, ndc
 
 def _no_mesh(name, where):
     def method(self, *a, **k):
-        raise NotImplementedError(f'{name} ({where}): marching cubes (`mcubes`) is not available offline and mesh '
-                                  'extraction is outside the hot path (DESIGN.md 8); query the SDF with '
-                                  'Voxurf.query_sdf_point_wocuda* or sample `sdf.grid` directly')
+        raise NotImplementedError(f'{name} ({where}): marching cubes (`mcubes`) is not available offline; use '
+                                  f'poseprobe_amd.mesh.voxurf_{name}(model, ...), which samples the field and triangulates '
+                                  'it on the GPU')
     method.__name__ = name
     return method
 

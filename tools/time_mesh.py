@@ -1,0 +1,122 @@
+"""Times of mesh extraction (poseprobe_amd.mesh) on a 160^3 Voxurf model with the synthetic scene's box and a perturbed warp net,
+at lattice resolutions 128, 256 and 512: the device field fill (plain and deform), marching cubes (pp_mc_count, pp_mc_emit) and
+the device-to-host copy of the mesh.  Everything runs in ONE process; each stage is warmed up, then timed `--runs` times with
+device events (the copy with a host clock around a synchronising copy); medians are reported.
+
+Beside each marching-cubes time: the bytes the stage has to move, from the shapes alone -
+  count: the field once (4 N) + one flag byte per point (N)
+  emit:  flags twice (2 N) + one vertex base per point written (4 N) + the output (12 Nv + 12 Nt)
+(the field and the bases are read again near the surface only; that traffic is not counted) - and that figure over the time
+as a fraction of the achievable HBM rate of MI355X_MICROARCH.md (6.3 TB/s).  It is a whole-stage rate (launch gaps and the
+single-work-group tile scan included), not a kernel's share of peak.
+
+    python tools/time_mesh.py [--resolutions 128 256 512] [--runs 5] [--out FILE]
+
+Needs a GPU: there is no CPU timing path.
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+G = 160
+HBM_ACHIEVABLE = 6.3e12
+
+
+def build_model():
+    from poseprobe_amd import synthetic as syn
+    from poseprobe_amd import voxurf_coarse as Model
+    from poseprobe_amd.engine import SceneConfig
+    from poseprobe_amd.params_init import reference_like_params
+    rs = syn.range_shape()
+    m = Model.Voxurf(syn.XYZ_MIN, syn.XYZ_MAX, num_voxels=G ** 3, num_voxels_base=G ** 3, alpha_init=1e-2, rgbnet_dim=12,
+                     rgbnet_direct=True, rgbnet_depth=4, rgbnet_width=128, posbase_pe=5, viewbase_pe=1, geo_rgb_dim=3, s_ratio=50,
+                     s_start=0.2, barf_c2f=[0.6, 1], i_train=np.arange(3), N_iters=10000, HW=np.array([[400, 400]] * 3),
+                     range_shape=rs, rect_size=rs.tolist(), camera_noise=0.)
+    P = reference_like_params(SceneConfig(syn.XYZ_MIN, syn.XYZ_MAX, G ** 3, out_range=float(rs.max())), 3)
+    with torch.no_grad():
+        for lin, (Wt, b) in zip(m.warp_network.linears(), P['warp']):      # a non-trivial deformation, as after training
+            lin.weight.copy_(Wt)
+            lin.bias.copy_(b)
+    return m.cuda()
+
+
+def device_ms(fn, runs, warmup=1):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(runs):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        t1.synchronize()
+        out.append(t0.elapsed_time(t1))
+    return out
+
+
+def fmt(ms):
+    return f'{statistics.median(ms):10.3f} ms  (min {min(ms):.3f}, max {max(ms):.3f}, {len(ms)} runs)'
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--resolutions', type=int, nargs='+', default=[128, 256, 512])
+    ap.add_argument('--runs', type=int, default=5)
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'needs a GPU'
+    from poseprobe_amd import mesh, ops
+    m = build_model()
+    lo, hi = m.xyz_min, m.xyz_max
+    lines = [f'mesh extraction, Voxurf {G}^3, box {lo.tolist()} .. {hi.tolist()}, {torch.cuda.get_device_name(0)}',
+             f'medians of {a.runs} runs in one process after one warm-up run per stage; fractions against {HBM_ACHIEVABLE / 1e12} TB/s']
+    for res in a.resolutions:
+        n = res ** 3
+        lines.append(f'\n== resolution {res} ({n} lattice points, field {4 * n / 2 ** 20:.0f} MiB, workspace '
+                     f'{ops.mc_workspace(res, res, res) / 2 ** 20:.0f} MiB) ==')
+        fields = {}
+        for name, query in (('plain', mesh.voxurf_field(m)), ('deform', mesh.voxurf_deform_field(m))):
+            ms = device_ms(lambda: fields.__setitem__(name, mesh.extract_fields_device(lo, hi, res, query, device='cuda')), a.runs)
+            lines.append(f'field fill, {name:6s}            {fmt(ms)}')
+        u = fields['deform']
+        del fields
+        work = torch.empty(ops.mc_workspace(res, res, res), dtype=torch.uint8, device='cuda')
+        counts = torch.empty(2, dtype=torch.int32, device='cuda')
+        ms_count = device_ms(lambda: ops.mc_count(u, 0.0, work, counts), a.runs)
+        nv, nt = counts.tolist()
+        vertices, triangles = torch.empty(nv, 3, device='cuda'), torch.empty(nt, 3, dtype=torch.int32, device='cuda')
+        ms_emit = device_ms(lambda: ops.mc_emit(u, 0.0, work, vertices, nv, triangles, nt), a.runs)
+        b_count, b_emit = 5 * n, 6 * n + 12 * (nv + nt)
+        lines.append(f'deform field: {nv} vertices, {nt} triangles')
+        for name, ms, b in (('pp_mc_count', ms_count, b_count), ('pp_mc_emit', ms_emit, b_emit)):
+            rate = b / (statistics.median(ms) * 1e-3)
+            lines.append(f'{name:28s}  {fmt(ms)}  {b / 2 ** 20:9.1f} MiB to move, {rate / 1e12:.3f} TB/s = '
+                         f'{rate / HBM_ACHIEVABLE:.1%} of achievable HBM')
+        ms_both = device_ms(lambda: mesh.marching_cubes(u, 0.0), a.runs)
+        lines.append(f'mesh.marching_cubes (both + the host read of the counts + allocation)  {fmt(ms_both)}')
+        host = []
+        for _ in range(a.runs + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            vertices.cpu(), triangles.cpu()
+            host.append((time.perf_counter() - t0) * 1e3)
+        lines.append(f'device-to-host copy of the mesh ({12 * (nv + nt) / 2 ** 20:.1f} MiB, pageable)  {fmt(host[1:])}')
+        del u, work, vertices, triangles
+        torch.cuda.empty_cache()
+    text = '\n'.join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(text + '\n')
+
+
+if __name__ == '__main__':
+    main()
