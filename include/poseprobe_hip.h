@@ -45,7 +45,7 @@ const char* pp_last_error(void);
  * ownership from stage 1 to stage 2 explicitly -, pp_nerf_fwd / pp_nerf_bwd, pp_grid_tv_adam_step{,_sparse});
  * pp_scene gained `sdf_index_exact`; new: pp_sdf_crossing_dense_bwd, pp_context_set_option / pp_context_get_option.  4 (this header): the
  * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
- * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_mc_* group.
+ * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_mc_* group, the pp_pnp_* group.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
  * (poseprobe_amd/_lib.py does): the signatures changed, so a stale caller would pass a stream where a pointer is read. */
 #define PP_ABI_VERSION 4
@@ -671,6 +671,34 @@ int pp_mc_count(const float* u, int32_t X, int32_t Y, int32_t Z, float threshold
                 int32_t* counts, void* stream);
 int pp_mc_emit(const float* u, int32_t X, int32_t Y, int32_t Z, float threshold, void* work, int64_t work_bytes,
                float* vertices, int32_t n_vertices, int32_t* triangles, int32_t n_triangles, void* stream);
+
+/* ---------------------------------------------------------------- pose initialisation: PnP-RANSAC
+ * lib/recon_scene.py:276-310 hands surface points and matched pixels to cv2.solvePnPRansac on the host; here they stay on the
+ * device.  cv2's random draws and internal solver are not reproduced: the caller draws the samples, which makes the result a
+ * pure, bit-reproducible function of its inputs.
+ *   inputs: world [P,3], pix [P,2] (u = fx Xc / Zc + cx, v = fy Yc / Zc + cy, camera looking along +z: inverse_y), valid [P]
+ *     uint8 (NULL = every row valid), intr [4] = (fx, fy, cx, cy) on the DEVICE, samples [H,4] int32, fallback [3,4];
+ *   hypothesis h is VALID iff its four indices are in range, pairwise distinct and point at valid rows, and a P3P solve on the
+ *     first three rows has a solution under which all four rows have positive depth (exactly collinear triples and zero side
+ *     lengths have none); among those solutions the one with the smallest reprojection error at the fourth row is kept;
+ *   score = rows with valid, depth > 0 and reprojection error < reproj_error (strict; compared as squares);
+ *   winner = the largest score, ties to the lowest h; success needs score >= min_inliers;
+ *   success: inliers [P] uint8 = the winner's mask (not recomputed after refinement), w2c [3,4] = its pose after refine_iters
+ *     Gauss-Newton steps on the summed squared reprojection error of the inliers (left-multiplied SE(3) increment, 6 x 6
+ *     normal equations by Cholesky; a non-positive pivot ends the refinement with the pose reached so far),
+ *     info [2] int32 = (score, h);
+ *   failure: w2c = fallback bit for bit, inliers all zero, info = (0, -1) - written by the kernel, no host decision.
+ * fp32 in and out; the minimal solve, the scoring and the refinement run in fp64 with every sum in a fixed order.  Three
+ * launches on `stream`, no atomics, no allocation, no host read.
+ * Limits: 4 <= P <= 2^22, 1 <= H <= 2^16 (beyond the upper limits: PP_ERR_UNSUPPORTED), reproj_error > 0,
+ * 0 <= refine_iters <= 1000, min_inliers >= 1.  pp_pnp_workspace (pure host function): bytes of `work`, 16-byte aligned, laid
+ * out as poses double [H,12] at 0, validity flags int32 [H] at r(96 H), scores int32 [H] (-1 = invalid hypothesis) at
+ * r(96 H) + r(4 H), with r(x) = x rounded up to a multiple of 256; all three are left behind for inspection.  Both entry points
+ * refuse, before any GPU call: null pointers (except valid), sizes outside the limits, a workspace that is too small. */
+int pp_pnp_workspace(int32_t P, int32_t H, int64_t* bytes);
+int pp_pnp_ransac(const float* world, const float* pix, const uint8_t* valid, int32_t P, const float* intr, const int32_t* samples,
+                  int32_t H, float reproj_error, int32_t refine_iters, int32_t min_inliers, const float* fallback, void* work,
+                  int64_t work_bytes, float* w2c, uint8_t* inliers, int32_t* info, void* stream);
 
 #ifdef __cplusplus
 }

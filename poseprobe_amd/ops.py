@@ -625,3 +625,37 @@ def mc_emit(u, threshold, work, vertices, n_vertices, triangles, n_triangles):
     _lib.call('pp_mc_emit', _f(u, 'u'), X, Y, Z, ctypes.c_float(threshold), _u8(work, 'work'),
               0 if work is None else int(work.numel()), _f(vertices, 'vertices'), int(n_vertices), _i(triangles, 'triangles'),
               int(n_triangles), _stream())
+
+
+# ------------------------------------------------------------------------------------------- pose initialisation (PnP-RANSAC)
+def pnp_workspace(P, H):
+    """Bytes of device workspace pp_pnp_ransac needs for P rows and H hypotheses (a pure host call)."""
+    b = ctypes.c_int64()
+    _lib.call('pp_pnp_workspace', int(P), int(H), ctypes.byref(b))
+    return b.value
+
+
+def pnp_workspace_views(work, H):
+    """(poses [H,3,4] float64, flags [H] int32, counts [H] int32) as views of a workspace pnp_ransac has filled: what every
+    hypothesis came to (layout in include/poseprobe_hip.h); counts is -1 where the hypothesis is invalid."""
+    r = lambda n: (n + 255) // 256 * 256
+    H = int(H)
+    o1 = r(96 * H)
+    o2 = o1 + r(4 * H)
+    return (work[:96 * H].view(torch.float64).view(H, 3, 4), work[o1:o1 + 4 * H].view(torch.int32),
+            work[o2:o2 + 4 * H].view(torch.int32))
+
+
+def pnp_ransac(world, pix, valid, intr, samples, reproj_error, refine_iters, min_inliers, fallback, work, w2c, inliers, info):
+    """world [P,3], pix [P,2], valid [P] uint8 or None, intr [4] (fx, fy, cx, cy), samples [H,4] int32, fallback [3,4] ->
+    w2c [3,4], inliers [P] uint8, info [2] int32 = (inlier count, winning hypothesis) or the fallback pose, zeros and (0, -1).
+    Three launches on the current stream; nothing is read back."""
+    P = 0 if world is None else int(world.shape[0])
+    H = 0 if samples is None else int(samples.shape[0])
+    for t, n, name in ((world, 3 * P, 'world'), (pix, 2 * P, 'pix'), (valid, P, 'valid'), (intr, 4, 'intr'), (samples, 4 * H, 'samples'),
+                       (fallback, 12, 'fallback'), (w2c, 12, 'w2c'), (inliers, P, 'inliers'), (info, 2, 'info')):
+        if t is not None and t.numel() != n:
+            raise RuntimeError(f'{name}: {t.numel()} elements, {n} expected')
+    _lib.call('pp_pnp_ransac', _f(world, 'world'), _f(pix, 'pix'), _u8(valid, 'valid'), P, _f(intr, 'intr'), _i(samples, 'samples'), H,
+              ctypes.c_float(reproj_error), int(refine_iters), int(min_inliers), _f(fallback, 'fallback'), _u8(work, 'work'),
+              0 if work is None else int(work.numel()), _f(w2c, 'w2c'), _u8(inliers, 'inliers'), _i(info, 'info'), _stream())

@@ -195,7 +195,8 @@ class DualBranchTrainer:
                  deterministic=False, reprojection=None):
         """incremental_step > 0: the incremental view schedule (`active_views`); a view that joins gets its initial pose from
         `pose_initialiser(view, w2c_of_previous_view [3,4]) -> w2c [3,4]` - the reference's PnP hand-off (cv2.solvePnPRansac on
-        matcher output, lib/recon_scene.py:202-214, :276-310) plugs in here; the default is its `use_identical` variant (the
+        matcher output, lib/recon_scene.py:202-214, :276-310) plugs in here: `pnp.PnPInitialiser` is its counterpart on the HIP
+        path (PnP-RANSAC kernels, the previous pose as the fallback); the default is its `use_identical` variant (the
         previous view's current pose).  pose_terms: extra pose-only loss terms mixed into the object loss as the reference
         mixes its reprojection / near-surface terms (:616-637): callables `f(se3 [V,6] requiring grad, w2c_init, n_active)
         -> (weight, scalar loss)`, differentiated by torch autograd through camera.current_pose_c2w.
