@@ -344,6 +344,14 @@ int pp_warp_lean_end(void* ctx);
  * refused.  work = NULL detaches: back to atomics.  Order of magnitude: 2 x 2 x 256 x 64.5 KB = 66 MB on an MI355X. */
 int pp_ordered_workspace(int32_t work_groups, int32_t capacity, int32_t n_rays, int64_t* bytes);
 int pp_ordered_attach(void* ctx, void* work, int64_t work_bytes, int32_t work_groups, int32_t capacity, int32_t n_rays);
+/* pp_geometry_fwd + pp_color_feat_fwd as work-group roles of ONE launch, for k0_dim = 12, pos_pe = 5, view_pe = 1: the geometry role
+ * writes the normal columns and the zero padding of feat[M,64], the colour role the columns before them.  Every role runs the
+ * stand-alone kernel's code: all outputs are bit-identical to the separate launches. */
+int pp_geometry_color_feat_fwd(const pp_scene* sc, const float* sdf_grid, const float* sdf_ab, const float* pts,
+                               const float* warp_out, const float* viewdirs, const int32_t* ray_id, const int32_t* count,
+                               int32_t capacity, float inv_s, float* alpha, float* gradient, float* sdf_final,
+                               float* sdf_deform, float* grad_deform, const float* k0_cl, const float* pe_w, float* feat,
+                               void* stream);
 /* pp_geometry_bwd_priors / pp_raygen_select_bwd (same arguments, same kernels, same results up to summation order) with
  * sdf_ab_grad (+=, required) / c2w_grad (overwritten, required) added up in work-group / ray order through the workspace attached
  * to `ctx` (required). */
@@ -402,6 +410,27 @@ int pp_grid_tv_adam_step_sparse(const float* p_in, float* p_out, float* grad, fl
                                 int32_t x_end, float tv_scale, float grad_scale, float lr, float beta1, float beta2,
                                 float eps, int32_t step, float* tv_out, const uint8_t* touched, uint8_t* touched_clear,
                                 void* ctx, void* stream);
+/* pp_grid_tv_adam_step_sparse (touched / touched_clear may be NULL: the dense pass) that carries the end of the step as
+ * work-group roles of the SAME launch - they read nothing the grid pass writes and run beside it instead of after it.
+ * Always: pp_adam_flat(flat_*, grad_scale, step, zero_grad = 1).  se3 != NULL && se3_update: pp_adam_flat over the se3 block
+ * [n_views*6], one segment with the learning rate pose_lr[0] (device).  sc != NULL (needs se3): ahead of the se3 update the
+ * launch runs pp_raygen_select_bwd (c2w_grad and viewdir_grad_s only, no ray-level inputs or outputs) and pp_pose_bwd; the
+ * last ray work-group to arrive does the pose part.  c2w_grad[n_views*12] and arrive[1] must be ZERO on entry and are zero
+ * again when the launch ends (no per-step memset); with se3_update = 0 the launch stops at se3_grad = jac^T c2w_grad.
+ * Every role runs the stand-alone kernel's code: outputs without float atomics are bit-identical to the separate launches. */
+int pp_grid_tv_adam_step_tail(const float* p_in, float* p_out, float* grad, float* exp_avg, float* exp_avg_sq,
+                              int32_t size_x, int32_t size_y, int32_t size_z, int32_t channels, int32_t x_begin,
+                              int32_t x_end, float tv_scale, float grad_scale, float lr, float beta1, float beta2,
+                              float eps, int32_t step, float* tv_out, const uint8_t* touched, uint8_t* touched_clear,
+                              float* flat_p, float* flat_grad, float* flat_m, float* flat_v, int32_t flat_n,
+                              const int32_t* flat_seg_end, const float* flat_seg_lr, int32_t flat_n_seg, float flat_beta1,
+                              float flat_beta2, float flat_eps, float* se3, float* se3_grad, float* se3_m, float* se3_v,
+                              int32_t n_views, const float* pose_lr, float pose_beta1, float pose_beta2, float pose_eps,
+                              int32_t se3_update, const pp_scene* sc, const int32_t* ray_idx, int32_t n_rays,
+                              const float* c2w, const float* intr, int32_t H, int32_t W, int32_t inverse_y,
+                              const float* rays_o, const float* rays_d, const float* t_min, const int32_t* ray_start,
+                              const float* pts_grad, const float* step_len, const float* viewdir_grad_s, const float* jac,
+                              float* c2w_grad, int32_t* arrive, void* ctx, void* stream);
 /* Flat Adam over a packed parameter buffer with per-segment learning rates: seg_end[n_seg], seg_lr[n_seg]. */
 int pp_adam_flat(float* p, float* grad, float* exp_avg, float* exp_avg_sq, int32_t n, const int32_t* seg_end,
                  const float* seg_lr, int32_t n_seg, float grad_scale, float beta1, float beta2, float eps,

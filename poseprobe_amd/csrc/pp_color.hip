@@ -4,8 +4,7 @@
 // C*4-byte read (3 x 16 B for C=12) instead of C strided 4-byte reads of the reference's [1,C,X,Y,Z] layout.
 #include "pp_common.h"
 #include "pp_k0_tri.h"
-
-__device__ __forceinline__ float pp_norm3c(float x, float y, float z) { return sqrtf(fmaf(z, z, fmaf(y, y, x * x))); }
+#include "pp_color_body.h"
 
 template <int TC, int TLP, int TLV>
 __global__ __launch_bounds__(256) void k_color_feat_fwd(SceneDev sc, const float* __restrict__ k0,
@@ -14,68 +13,8 @@ __global__ __launch_bounds__(256) void k_color_feat_fwd(SceneDev sc, const float
                                                         const float* __restrict__ gradient, const float* __restrict__ pe_w,
                                                         const int32_t* __restrict__ count, int capacity,
                                                         float* __restrict__ feat) {
-  int m = blockIdx.x * blockDim.x + threadIdx.x;
-  int M = min(count[0], capacity);
-  if (m >= M) return;
-  float f[PP_FEAT_LD];
-#pragma unroll
-  for (int i = 0; i < PP_FEAT_LD; ++i) f[i] = 0.f;
-  float p[3] = {pts[m * 3], pts[m * 3 + 1], pts[m * 3 + 2]};
-  K0Tri t;
-  k0_setup(sc, p, t);
-  const int C = TC ? TC : sc.C;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    size_t off; float w;
-    if (k0_corner(sc, t, c, off, w)) {
-      const float4* src = reinterpret_cast<const float4*>(k0 + off);
-#pragma unroll
-      for (int q = 0; q < C / 4; ++q) {
-        float4 v = src[q];
-        f[q * 4 + 0] += v.x * w; f[q * 4 + 1] += v.y * w; f[q * 4 + 2] += v.z * w; f[q * 4 + 3] += v.w * w;
-      }
-    }
-  }
-  int o = C;
-  const int Lp = TLP ? TLP : sc.Lp, Lv = TLV ? TLV : sc.Lv;
-  // xyz embedding: [t(3) | w_k sin(2^k t_a) (a major, k minor) | w_k cos(...)]
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    float ta = pp_div(pp_sub(p[a], sc.mn[a]), pp_sub(sc.mx[a], sc.mn[a]));
-    f[o + a] = ta;
-    float fr = 1.f;
-#pragma unroll
-    for (int k = 0; k < Lp; ++k) {
-      float ang = ta * fr, s, c;
-      sincosf(ang, &s, &c);
-      f[o + 3 + a * Lp + k] = s * pe_w[k];
-      f[o + 3 + 3 * Lp + a * Lp + k] = c * pe_w[k];
-      fr *= 2.f;
-    }
-  }
-  o += 3 + 6 * Lp;
-  int r = ray_id[m];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    float va = viewdirs[r * 3 + a];
-    f[o + a] = va;
-    float fr = 1.f;
-#pragma unroll
-    for (int k = 0; k < Lv; ++k) {
-      float ang = va * fr, s, c;
-      sincosf(ang, &s, &c);
-      f[o + 3 + a * Lv + k] = s * pe_w[Lp + k];
-      f[o + 3 + 3 * Lv + a * Lv + k] = c * pe_w[Lp + k];
-      fr *= 2.f;
-    }
-  }
-  o += 3 + 6 * Lv;
-  float g[3] = {gradient[m * 3], gradient[m * 3 + 1], gradient[m * 3 + 2]};
-  float gn = pp_norm3c(g[0], g[1], g[2]) + 1e-5f;
-  for (int a = 0; a < 3; ++a) f[o + a] = g[a] / gn;
-  float4* dst = reinterpret_cast<float4*>(feat + (size_t)m * PP_FEAT_LD);
-#pragma unroll
-  for (int q = 0; q < PP_FEAT_LD / 4; ++q) dst[q] = make_float4(f[q * 4], f[q * 4 + 1], f[q * 4 + 2], f[q * 4 + 3]);
+  color_feat_fwd_body<TC, TLP, TLV, true>(blockIdx.x * blockDim.x + threadIdx.x, sc, k0, pts, viewdirs, ray_id, gradient, pe_w, count,
+                                          capacity, feat);
 }
 
 // backward, part 1 (thread per sample): everything except the k0 scatter

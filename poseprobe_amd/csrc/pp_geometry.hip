@@ -5,6 +5,7 @@
 // 3.5 MB at 96^3, 16 MB at 160^3).
 #include "pp_common.h"
 #include "pp_ordered.h"
+#include "pp_color_body.h"
 
 struct Tri {
   float w0[3], w1[3];
@@ -132,16 +133,17 @@ __device__ __forceinline__ void geo_forward(const SceneDev& sc, const float* __r
   o.a_un = o.num / o.den;
 }
 
-__global__ __launch_bounds__(256) void k_geometry_fwd(SceneDev sc, const float* __restrict__ grid,
-                                                      const float* __restrict__ sdf_ab, const float* __restrict__ pts,
-                                                      const float* __restrict__ warp_out,
-                                                      const float* __restrict__ viewdirs,
-                                                      const int32_t* __restrict__ ray_id,
-                                                      const int32_t* __restrict__ count, int capacity, float inv_s,
-                                                      float* __restrict__ alpha, float* __restrict__ gradient,
-                                                      float* __restrict__ sdf_final, float* __restrict__ sdf_deform,
-                                                      float* __restrict__ grad_deform) {
-  int m = blockIdx.x * blockDim.x + threadIdx.x;
+// sample m of the geometry forward.  feat != nullptr (k_geometry_color_fwd): the normal columns 54 - 56 and the zero padding
+// 57 - 63 of the rgbnet's input row are written here, with the colour kernel's own expression, beside the colour role that
+// writes columns 0 - 53; columns 52 - 55 share one float4: that piece goes out as scalar stores from each side.
+__device__ __forceinline__ void geometry_fwd_body(int m, const SceneDev& sc, const float* __restrict__ grid,
+                                                  const float* __restrict__ sdf_ab, const float* __restrict__ pts,
+                                                  const float* __restrict__ warp_out, const float* __restrict__ viewdirs,
+                                                  const int32_t* __restrict__ ray_id, const int32_t* __restrict__ count,
+                                                  int capacity, float inv_s, float* __restrict__ alpha,
+                                                  float* __restrict__ gradient, float* __restrict__ sdf_final,
+                                                  float* __restrict__ sdf_deform, float* __restrict__ grad_deform,
+                                                  float* __restrict__ feat) {
   int M = min(count[0], capacity);
   if (m >= M) return;
   MapAB mp = map_ab(sdf_ab);
@@ -164,6 +166,50 @@ __global__ __launch_bounds__(256) void k_geometry_fwd(SceneDev sc, const float* 
   if (sdf_deform) sdf_deform[m] = o.sdf - o.vp;
   if (grad_deform)
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) grad_deform[m * 9 + i * 3 + j] = o.A[i][j];
+  if (feat) {
+    const float gn = pp_norm3c(o.grad[0], o.grad[1], o.grad[2]) + 1e-5f;
+    float* row = feat + (size_t)m * PP_FEAT_LD;
+    row[54] = o.grad[0] / gn;
+    row[55] = o.grad[1] / gn;
+    float4* r4 = reinterpret_cast<float4*>(row);
+    r4[14] = make_float4(o.grad[2] / gn, 0.f, 0.f, 0.f);
+    r4[15] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_geometry_fwd(SceneDev sc, const float* __restrict__ grid,
+                                                      const float* __restrict__ sdf_ab, const float* __restrict__ pts,
+                                                      const float* __restrict__ warp_out,
+                                                      const float* __restrict__ viewdirs,
+                                                      const int32_t* __restrict__ ray_id,
+                                                      const int32_t* __restrict__ count, int capacity, float inv_s,
+                                                      float* __restrict__ alpha, float* __restrict__ gradient,
+                                                      float* __restrict__ sdf_final, float* __restrict__ sdf_deform,
+                                                      float* __restrict__ grad_deform) {
+  geometry_fwd_body(blockIdx.x * blockDim.x + threadIdx.x, sc, grid, sdf_ab, pts, warp_out, viewdirs, ray_id, count, capacity, inv_s,
+                    alpha, gradient, sdf_final, sdf_deform, grad_deform, nullptr);
+}
+
+// Geometry forward and colour lookup in ONE launch: only the three normal columns of the rgbnet's input need the
+// geometry; the k0 gather, both encodings and their stores need pts / viewdirs / ray_id alone.  Work-groups alternate:
+// even = geometry role, odd = colour role, each over samples [256 (blockIdx / 2), ...) - the live work-groups of both roles sit
+// at the front of the grid and run side by side.
+__global__ __launch_bounds__(256) void k_geometry_color_fwd(SceneDev sc, const float* __restrict__ grid,
+                                                            const float* __restrict__ sdf_ab, const float* __restrict__ pts,
+                                                            const float* __restrict__ warp_out,
+                                                            const float* __restrict__ viewdirs,
+                                                            const int32_t* __restrict__ ray_id,
+                                                            const int32_t* __restrict__ count, int capacity, float inv_s,
+                                                            float* __restrict__ alpha, float* __restrict__ gradient,
+                                                            float* __restrict__ sdf_final, float* __restrict__ sdf_deform,
+                                                            float* __restrict__ grad_deform, const float* __restrict__ k0,
+                                                            const float* __restrict__ pe_w, float* feat) {
+  const int m = (blockIdx.x >> 1) * 256 + threadIdx.x;
+  if (blockIdx.x & 1)
+    color_feat_fwd_body<12, 5, 1, false>(m, sc, k0, pts, viewdirs, ray_id, nullptr, pe_w, count, capacity, feat);
+  else
+    geometry_fwd_body(m, sc, grid, sdf_ab, pts, warp_out, viewdirs, ray_id, count, capacity, inv_s, alpha, gradient, sdf_final,
+                      sdf_deform, grad_deform, feat);
 }
 
 // PRIORS: the sample-level regularisers of object_losses (lib/losses.py:6-23: eikonal, deformation-Jacobian norm,
@@ -390,6 +436,23 @@ extern "C" int pp_geometry_bwd_priors_ordered(const pp_scene* sc, const float* s
                      w_eikonal, w_deform, loss_scale, loss_out, batch_norm, part);
   const OrdSegs segs{1, {2, 0, 0, 0}, {0, 0, 0, 0}};
   pp_launch_ordered_flush(part, ORD_GEO_ROW, grid, nullptr, 0, 1, segs, sdf_ab_grad, st);
+  PP_CHECK_LAUNCH();
+  return PP_OK;
+}
+
+// pp_geometry_fwd and pp_color_feat_fwd (k0_dim = 12, pos_pe = 5, view_pe = 1 only) in one launch: k_geometry_color_fwd
+extern "C" int pp_geometry_color_feat_fwd(const pp_scene* sc, const float* sdf_grid, const float* sdf_ab, const float* pts,
+                                          const float* warp_out, const float* viewdirs, const int32_t* ray_id,
+                                          const int32_t* count, int32_t capacity, float inv_s, float* alpha, float* gradient,
+                                          float* sdf_final, float* sdf_deform, float* grad_deform, const float* k0_cl,
+                                          const float* pe_w, float* feat, void* stream) {
+  PP_REQUIRE(sc && sdf_grid && sdf_ab && pts && warp_out && viewdirs && ray_id && count && alpha && gradient && k0_cl && pe_w && feat,
+             "null pointer");
+  PP_REQUIRE(capacity > 0, "capacity<=0");
+  PP_REQUIRE(sc->k0_dim == 12 && sc->pos_pe == 5 && sc->view_pe == 1, "the split feature row needs k0_dim = 12, pos_pe = 5, view_pe = 1");
+  hipLaunchKernelGGL(k_geometry_color_fwd, dim3(2 * pp_div_up(capacity, 256)), dim3(256), 0, pp_stream(stream), pp_scene_dev(sc),
+                     sdf_grid, sdf_ab, pts, warp_out, viewdirs, ray_id, count, capacity, inv_s, alpha, gradient, sdf_final,
+                     sdf_deform, grad_deform, k0_cl, pe_w, feat);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "pp_common.h"
+#include "pp_ray_bwd.h"
 
 __device__ __forceinline__ float sgnf(float x) { return (x > 0.f) ? 1.f : (x < 0.f ? -1.f : 0.f); }
 __device__ __forceinline__ float4 sgn4(float4 a, float4 b) {
@@ -42,18 +43,17 @@ __device__ __forceinline__ void acc_sgn(float4& tv, float4 p, float4 n) {
   tv.x += sgnf(p.x - n.x); tv.y += sgnf(p.y - n.y); tv.z += sgnf(p.z - n.z); tv.w += sgnf(p.w - n.w);
 }
 
-__global__ __launch_bounds__(256) void k_grid_tv_adam(const float4* __restrict__ p_in, float4* __restrict__ p_out,
-                                                      float4* __restrict__ grad, float4* __restrict__ m_,
-                                                      float4* __restrict__ v_, int X, int Y, int Z, int q4,
-                                                      int x_begin, int x_end, int n_chunks, int chunk_len,
-                                                      float tv_scale, float grad_scale, float b1, float b2, float eps,
-                                                      float step_size, float inv_sqrt_bc2, float* __restrict__ tv_out,
-                                                      const uint8_t* __restrict__ touched,
-                                                      uint8_t* __restrict__ touched_clear) {
-  __shared__ float sm[4];
+// bid: the work-group's index within the pass (blockIdx.x of the stand-alone kernel); sm: 4 floats of LDS
+__device__ __forceinline__ void grid_tv_adam_body(const int bid, float* sm, const float4* __restrict__ p_in,
+                                                  float4* __restrict__ p_out, float4* __restrict__ grad,
+                                                  float4* __restrict__ m_, float4* __restrict__ v_, int X, int Y, int Z, int q4,
+                                                  int x_begin, int x_end, int n_chunks, int chunk_len, float tv_scale,
+                                                  float grad_scale, float b1, float b2, float eps, float step_size,
+                                                  float inv_sqrt_bc2, float* __restrict__ tv_out,
+                                                  const uint8_t* __restrict__ touched, uint8_t* __restrict__ touched_clear) {
   const int plane = Y * Z * q4;                      // float4 per x-plane
-  const int chunk = blockIdx.x % n_chunks;
-  const int tile = blockIdx.x / n_chunks;
+  const int chunk = bid % n_chunks;
+  const int tile = bid / n_chunks;
   const int i = tile * 256 + threadIdx.x;            // position inside the plane
   const int xs = x_begin + chunk * chunk_len;
   const int xe = min(xs + chunk_len, x_end);
@@ -115,6 +115,19 @@ __global__ __launch_bounds__(256) void k_grid_tv_adam(const float4* __restrict__
       if (s != 0.f) atomicAdd(tv_out, s);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void k_grid_tv_adam(const float4* __restrict__ p_in, float4* __restrict__ p_out,
+                                                      float4* __restrict__ grad, float4* __restrict__ m_,
+                                                      float4* __restrict__ v_, int X, int Y, int Z, int q4,
+                                                      int x_begin, int x_end, int n_chunks, int chunk_len,
+                                                      float tv_scale, float grad_scale, float b1, float b2, float eps,
+                                                      float step_size, float inv_sqrt_bc2, float* __restrict__ tv_out,
+                                                      const uint8_t* __restrict__ touched,
+                                                      uint8_t* __restrict__ touched_clear) {
+  __shared__ float sm[4];
+  grid_tv_adam_body(blockIdx.x, sm, p_in, p_out, grad, m_, v_, X, Y, Z, q4, x_begin, x_end, n_chunks, chunk_len, tv_scale,
+                    grad_scale, b1, b2, eps, step_size, inv_sqrt_bc2, tv_out, touched, touched_clear);
 }
 
 // The total-variation term ON ITS OWN for the drop-in autograd path (lib/voxurf_coarse.py:443-456, :1298-1313: k0_tv is an
@@ -226,17 +239,15 @@ __global__ __launch_bounds__(256) void k_grid_tv_value(const float4* __restrict_
   if (threadIdx.x == 0) atomicAdd(tv_out, sm[0] + sm[1] + sm[2] + sm[3]);
 }
 
-__global__ __launch_bounds__(256) void k_adam_flat(float* __restrict__ p, float* __restrict__ grad, float* __restrict__ m_,
-                                                   float* __restrict__ v_, int n, const int32_t* __restrict__ seg_end,
-                                                   const float* __restrict__ seg_lr, int n_seg, float grad_scale,
-                                                   float b1, float b2, float eps, float inv_bc1, float inv_sqrt_bc2,
-                                                   int zero_grad) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+// element i of a flat block; g_raw: its gradient before grad_scale (adam_flat_body reads it from grad[i])
+__device__ __forceinline__ void adam_flat_elem(int i, float g_raw, float* __restrict__ p, float* __restrict__ grad,
+                                               float* __restrict__ m_, float* __restrict__ v_, const int32_t* __restrict__ seg_end,
+                                               const float* __restrict__ seg_lr, int n_seg, float grad_scale, float b1, float b2,
+                                               float eps, float inv_bc1, float inv_sqrt_bc2, int zero_grad) {
   int s = 0;
   while (s < n_seg - 1 && i >= seg_end[s]) ++s;
   float lr = seg_lr[s];
-  float g = grad[i] * grad_scale, m = m_[i], v = v_[i];
+  float g = g_raw * grad_scale, m = m_[i], v = v_[i];
   float o = adam1(p[i], g, m, v, b1, b2, eps, lr * inv_bc1, inv_sqrt_bc2);
   if (lr != 0.f) p[i] = o;
   m_[i] = m;
@@ -244,23 +255,130 @@ __global__ __launch_bounds__(256) void k_adam_flat(float* __restrict__ p, float*
   if (zero_grad) grad[i] = 0.f;
 }
 
-extern "C" int pp_grid_tv_adam_step_sparse(const float* p_in, float* p_out, float* grad, float* exp_avg, float* exp_avg_sq,
-                                    int32_t size_x, int32_t size_y, int32_t size_z, int32_t channels, int32_t x_begin, int32_t x_end,
-                                    float tv_scale, float grad_scale, float lr, float beta1, float beta2, float eps,
-                                    int32_t step, float* tv_out, const uint8_t* touched,
-                                            uint8_t* touched_clear, void* ctx, void* stream) {
-  PP_REQUIRE(p_in && p_out && grad && exp_avg && exp_avg_sq, "null pointer");
+__device__ __forceinline__ void adam_flat_body(int i, float* __restrict__ p, float* __restrict__ grad, float* __restrict__ m_,
+                                               float* __restrict__ v_, int n, const int32_t* __restrict__ seg_end,
+                                               const float* __restrict__ seg_lr, int n_seg, float grad_scale, float b1, float b2,
+                                               float eps, float inv_bc1, float inv_sqrt_bc2, int zero_grad) {
+  if (i >= n) return;
+  adam_flat_elem(i, grad[i], p, grad, m_, v_, seg_end, seg_lr, n_seg, grad_scale, b1, b2, eps, inv_bc1, inv_sqrt_bc2, zero_grad);
+}
+
+__global__ __launch_bounds__(256) void k_adam_flat(float* __restrict__ p, float* __restrict__ grad, float* __restrict__ m_,
+                                                   float* __restrict__ v_, int n, const int32_t* __restrict__ seg_end,
+                                                   const float* __restrict__ seg_lr, int n_seg, float grad_scale,
+                                                   float b1, float b2, float eps, float inv_bc1, float inv_sqrt_bc2,
+                                                   int zero_grad) {
+  adam_flat_body(blockIdx.x * blockDim.x + threadIdx.x, p, grad, m_, v_, n, seg_end, seg_lr, n_seg, grad_scale, b1, b2, eps,
+                 inv_bc1, inv_sqrt_bc2, zero_grad);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The grid pass with the step's small kernels as work-group roles of the SAME launch.  The grid pass reads only
+// k0_grad / touched, complete since the k0 scatter; the tail reads nothing the grid pass writes - so the flat-block Adam, the
+// pose Adam and (train step only) the ray / pose backward run beside it instead of after it.  Roles by blockIdx:
+//   [0, n_ray)                 ray backward, 4 rays per work-group (k_raygen_bwd's body); the LAST of them to arrive then runs the
+//                              pose backward, the se3 Adam update and leaves c2w_grad and the arrival counter zero
+//   [n_ray, n_ray + n_flat)    Adam over the flat MLP / alpha-beta block (k_adam_flat's body)
+//   n_ray + n_flat             se3 Adam alone (k_adam_flat's body, one work-group), when there is no ray role
+//   ... n_tail                 padding to a multiple of 16 work-groups, which return at once: (blockIdx - n_tail) % n_chunks and
+//                              the work-group <-> XCD dealing of the grid role are those of the stand-alone pass
+//   [n_tail, ...)              the grid pass (k_grid_tv_adam's body)
+// Arrival: every ray work-group adds its sums to c2w_grad with RETURNING device-scope atomics and waits for them, then one lane
+// draws a ticket from the counter (returning atomic as well); the work-group that draws n_ray - 1 reads c2w_grad by agent-scope
+// atomic loads.  No fence: nothing but atomics writes or reads the words that are handed over.
+// The grid role's arguments stay plain kernel parameters: handed over in a struct they cost 74 registers per lane instead of 71,
+// one occupancy step (7 -> 6 wavefronts per SIMD) below the stand-alone pass.
+struct FlatArgs {
+  float *p, *grad, *m, *v; int n; const int32_t* seg_end; const float* seg_lr; int n_seg;
+  float b1, b2, eps, inv_bc1, inv_sqrt_bc2;
+};
+struct RayArgs {
+  SceneDev sc; const int32_t* ray_idx; int n_rays; const float *c2w, *intr; int n_views, H, W, inverse_y;
+  const float *rays_o, *rays_d, *t_min; const int32_t* ray_start; const float *pts_grad, *step, *vgrad_s, *jac;
+  float* c2w_grad; unsigned* arrive;
+};
+struct TailArgs {
+  int n_ray, n_flat, n_tail, optimize_pose;     // optimize_pose: the se3 block is updated (else the ray role leaves se3_grad)
+  FlatArgs flat, pose;
+  RayArgs ray;
+};
+
+__global__ __launch_bounds__(256) void k_grid_tv_adam_tail(const float4* __restrict__ p_in, float4* __restrict__ p_out,
+   float4* __restrict__ grad, float4* __restrict__ m_, float4* __restrict__ v_, int X, int Y, int Z, int q4,
+   int x_begin, int x_end, int n_chunks, int chunk_len, float tv_scale, float grad_scale, float b1, float b2, float eps,
+   float step_size, float inv_sqrt_bc2, float* __restrict__ tv_out, const uint8_t* __restrict__ touched,
+   uint8_t* __restrict__ touched_clear, const TailArgs t) {
+  extern __shared__ __align__(16) float s_dyn[];  // ray role: [n_views*12]
+  __shared__ float sm[4];
+  __shared__ int s_last;
+  const int b = blockIdx.x;
+  if (b >= t.n_tail) {
+    grid_tv_adam_body(b - t.n_tail, sm, p_in, p_out, grad, m_, v_, X, Y, Z, q4, x_begin, x_end, n_chunks, chunk_len, tv_scale,
+                      grad_scale, b1, b2, eps, step_size, inv_sqrt_bc2, tv_out, touched, touched_clear);
+    return;
+  }
+  const FlatArgs& f = t.flat;
+  const FlatArgs& q = t.pose;
+  if (b < t.n_ray) {
+    const RayArgs& r = t.ray;
+    raygen_bwd_body<true>(b, s_dyn, r.sc, r.ray_idx, r.n_rays, r.c2w, r.intr, r.n_views, r.H, r.W, r.inverse_y, r.rays_o, r.rays_d,
+                          r.t_min, r.ray_start, r.pts_grad, r.step, r.vgrad_s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, r.c2w_grad, nullptr);
+    __syncthreads();                             // every wavefront's additions have been performed
+    if (threadIdx.x == 0)
+      s_last = __hip_atomic_fetch_add(r.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(t.n_ray - 1);
+    __syncthreads();
+    if (!s_last) return;
+    for (int i = threadIdx.x; i < q.n; i += 256) {
+      const float s = pose_bwd_elem<true>(r.jac, r.c2w_grad, i);
+      if (t.optimize_pose)
+        adam_flat_elem(i, s, q.p, q.grad, q.m, q.v, q.seg_end, q.seg_lr, q.n_seg, grad_scale, q.b1, q.b2, q.eps, q.inv_bc1,
+                       q.inv_sqrt_bc2, 1);
+      else
+        q.grad[i] = s;
+    }
+    __syncthreads();                             // c2w_grad has been read: leave it and the counter zero for the next step
+    for (int i = threadIdx.x; i < r.n_views * 12; i += 256)
+      __hip_atomic_store(r.c2w_grad + i, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) __hip_atomic_store(r.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  if (b < t.n_ray + t.n_flat) {
+    adam_flat_body((b - t.n_ray) * 256 + threadIdx.x, f.p, f.grad, f.m, f.v, f.n, f.seg_end, f.seg_lr, f.n_seg, grad_scale, f.b1,
+                   f.b2, f.eps, f.inv_bc1, f.inv_sqrt_bc2, 1);
+    return;
+  }
+  if (b == t.n_ray + t.n_flat && t.n_ray == 0 && t.optimize_pose)
+    for (int i = threadIdx.x; i < q.n; i += 256)
+      adam_flat_body(i, q.p, q.grad, q.m, q.v, q.n, q.seg_end, q.seg_lr, q.n_seg, grad_scale, q.b1, q.b2, q.eps, q.inv_bc1,
+                     q.inv_sqrt_bc2, 1);
+}
+
+// errors carry the name of the entry point that was called (`who`)
+#define GRID_REQUIRE(cond, msg)                \
+  do {                                         \
+    if (!(cond)) {                             \
+      pp_set_error("%s: %s", who, msg);        \
+      return PP_ERR_INVALID_ARG;               \
+    }                                          \
+  } while (0)
+static int grid_tv_adam_step(const char* who, const float* p_in, float* p_out, float* grad, float* exp_avg, float* exp_avg_sq,
+                             int32_t size_x, int32_t size_y, int32_t size_z, int32_t channels, int32_t x_begin, int32_t x_end,
+                             float tv_scale, float grad_scale, float lr, float beta1, float beta2, float eps, int32_t step,
+                             float* tv_out, const uint8_t* touched, uint8_t* touched_clear, TailArgs* tail, void* ctx,
+                             void* stream) {
+  GRID_REQUIRE(p_in && p_out && grad && exp_avg && exp_avg_sq, "null pointer");
   const int32_t size[3] = {size_x, size_y, size_z};
-  PP_REQUIRE(p_in != p_out, "p_in and p_out must be distinct (ping-pong) buffers");
-  PP_REQUIRE(channels > 0 && channels % 4 == 0, "channels must be a positive multiple of 4");
-  PP_REQUIRE(0 <= x_begin && x_begin < x_end && x_end <= size[0], "bad x slab");
-  PP_REQUIRE(step >= 1, "step must be >= 1");
+  GRID_REQUIRE(p_in != p_out, "p_in and p_out must be distinct (ping-pong) buffers");
+  GRID_REQUIRE(channels > 0 && channels % 4 == 0, "channels must be a positive multiple of 4");
+  GRID_REQUIRE(0 <= x_begin && x_begin < x_end && x_end <= size[0], "bad x slab");
+  GRID_REQUIRE(step >= 1, "step must be >= 1");
   const int q4 = channels / 4;
   const long long n = (long long)(x_end - x_begin) * size[1] * size[2] * q4;
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   const int nx = x_end - x_begin;
   const long long plane = (long long)size[1] * size[2] * q4;
-  PP_REQUIRE(plane < (1ll << 31) && n < (1ll << 40), "grid too large for 32-bit plane indexing");
+  GRID_REQUIRE(plane < (1ll << 31) && n < (1ll << 40), "grid too large for 32-bit plane indexing");
   // chunks: a multiple of 8 when possible so that chunk <-> XCD (blocks are dealt round-robin over the 8 XCDs)
   // measured (tools/bench_grid.py, MI355X): 16 chunks win from 128 planes up (160^3: 272 -> 256 us dense), 8 below
   int n_chunks = nx >= 128 ? 16 : (nx >= 8 ? 8 : nx);
@@ -268,14 +386,84 @@ extern "C" int pp_grid_tv_adam_step_sparse(const float* p_in, float* p_out, floa
   const int chunk_len = (nx + n_chunks - 1) / n_chunks;
   n_chunks = (nx + chunk_len - 1) / chunk_len;
   const int tiles = (int)((plane + 255) / 256);
-  hipLaunchKernelGGL(k_grid_tv_adam, dim3(tiles * n_chunks), dim3(256), 0, pp_stream(stream),
-                     reinterpret_cast<const float4*>(p_in), reinterpret_cast<float4*>(p_out),
-                     reinterpret_cast<float4*>(grad), reinterpret_cast<float4*>(exp_avg),
-                     reinterpret_cast<float4*>(exp_avg_sq), size[0], size[1], size[2], q4, x_begin, x_end, n_chunks,
-                     chunk_len, tv_scale, grad_scale, beta1, beta2, eps, (float)((double)lr / bc1),
-                     (float)(1.0 / sqrt(bc2)), tv_out, touched, touched_clear);
-  PP_CHECK_LAUNCH();
+  const float step_size = (float)((double)lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  if (!tail) {
+    hipLaunchKernelGGL(k_grid_tv_adam, dim3(tiles * n_chunks), dim3(256), 0, pp_stream(stream),
+                       reinterpret_cast<const float4*>(p_in), reinterpret_cast<float4*>(p_out),
+                       reinterpret_cast<float4*>(grad), reinterpret_cast<float4*>(exp_avg),
+                       reinterpret_cast<float4*>(exp_avg_sq), size[0], size[1], size[2], q4, x_begin, x_end, n_chunks,
+                       chunk_len, tv_scale, grad_scale, beta1, beta2, eps, step_size, inv_sqrt_bc2, tv_out, touched,
+                       touched_clear);
+  } else {
+    GRID_REQUIRE((long long)tail->n_tail + (long long)tiles * n_chunks < (1ll << 31), "too many work-groups");
+    const size_t lds = tail->n_ray ? sizeof(float) * 12 * tail->ray.n_views : 0;
+    hipLaunchKernelGGL(k_grid_tv_adam_tail, dim3(tail->n_tail + tiles * n_chunks), dim3(256), lds, pp_stream(stream),
+                       reinterpret_cast<const float4*>(p_in), reinterpret_cast<float4*>(p_out),
+                       reinterpret_cast<float4*>(grad), reinterpret_cast<float4*>(exp_avg),
+                       reinterpret_cast<float4*>(exp_avg_sq), size[0], size[1], size[2], q4, x_begin, x_end, n_chunks,
+                       chunk_len, tv_scale, grad_scale, beta1, beta2, eps, step_size, inv_sqrt_bc2, tv_out, touched,
+                       touched_clear, *tail);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    pp_set_error("%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    return PP_ERR_LAUNCH;
+  }
   return PP_OK;
+}
+
+extern "C" int pp_grid_tv_adam_step_sparse(const float* p_in, float* p_out, float* grad, float* exp_avg, float* exp_avg_sq,
+                                    int32_t size_x, int32_t size_y, int32_t size_z, int32_t channels, int32_t x_begin, int32_t x_end,
+                                    float tv_scale, float grad_scale, float lr, float beta1, float beta2, float eps,
+                                    int32_t step, float* tv_out, const uint8_t* touched,
+                                            uint8_t* touched_clear, void* ctx, void* stream) {
+  return grid_tv_adam_step("pp_grid_tv_adam_step_sparse", p_in, p_out, grad, exp_avg, exp_avg_sq, size_x, size_y, size_z, channels,
+                           x_begin, x_end, tv_scale, grad_scale, lr, beta1, beta2, eps, step, tv_out, touched, touched_clear, nullptr,
+                           ctx, stream);
+}
+
+// pp_grid_tv_adam_step_sparse (touched / touched_clear may be NULL: the dense pass) carrying the end of the step in the same
+// launch: Adam (grad_scale, step as the grid's; gradients zeroed) over the flat block and, if se3 != NULL, over the se3 block
+// [n_views*6] with the learning rate pose_lr[0].  sc != NULL: the launch also runs the ray backward (pp_raygen_select_bwd with
+// c2w_grad and viewdir_grad_s only) and the pose backward (pp_pose_bwd) ahead of the se3 update - c2w_grad [n_views*12] and
+// arrive[1] must be ZERO on entry and are zero again afterwards; with se3_update = 0 the launch stops at se3_grad = jac^T c2w_grad.
+extern "C" int pp_grid_tv_adam_step_tail(
+    const float* p_in, float* p_out, float* grad, float* exp_avg, float* exp_avg_sq, int32_t size_x, int32_t size_y, int32_t size_z,
+    int32_t channels, int32_t x_begin, int32_t x_end, float tv_scale, float grad_scale, float lr, float beta1, float beta2, float eps,
+    int32_t step, float* tv_out, const uint8_t* touched, uint8_t* touched_clear,
+    float* flat_p, float* flat_grad, float* flat_m, float* flat_v, int32_t flat_n, const int32_t* flat_seg_end,
+    const float* flat_seg_lr, int32_t flat_n_seg, float flat_beta1, float flat_beta2, float flat_eps,
+    float* se3, float* se3_grad, float* se3_m, float* se3_v, int32_t n_views, const float* pose_lr, float pose_beta1,
+    float pose_beta2, float pose_eps, int32_t se3_update,
+    const pp_scene* sc, const int32_t* ray_idx, int32_t n_rays, const float* c2w, const float* intr, int32_t H, int32_t W,
+    int32_t inverse_y, const float* rays_o, const float* rays_d, const float* t_min, const int32_t* ray_start,
+    const float* pts_grad, const float* step_len, const float* viewdir_grad_s, const float* jac, float* c2w_grad, int32_t* arrive,
+    void* ctx, void* stream) {
+  PP_REQUIRE(flat_p && flat_grad && flat_m && flat_v && flat_seg_end && flat_seg_lr, "null pointer (flat block)");
+  PP_REQUIRE(flat_n > 0 && flat_n_seg > 0 && step >= 1, "bad sizes (flat block)");
+  PP_REQUIRE(!se3 || (se3_grad && se3_m && se3_v && pose_lr && n_views > 0), "null pointer or n_views<=0 (se3 block)");
+  PP_REQUIRE(!sc || (se3 && ray_idx && c2w && intr && rays_o && rays_d && t_min && ray_start && pts_grad && step_len && jac &&
+                     c2w_grad && arrive && n_rays > 0),
+             "null pointer or n_rays<=0 (ray backward)");
+  PP_REQUIRE(!sc || n_views * 12 * sizeof(float) <= 32768, "too many views for the ray role's LDS");
+  TailArgs t{};
+  const auto bc = [&](float beta) { return 1.0 - pow((double)beta, (double)step); };
+  t.flat = FlatArgs{flat_p, flat_grad, flat_m, flat_v, flat_n, flat_seg_end, flat_seg_lr, flat_n_seg, flat_beta1, flat_beta2,
+                    flat_eps, (float)(1.0 / bc(flat_beta1)), (float)(1.0 / sqrt(bc(flat_beta2)))};
+  if (se3)
+    t.pose = FlatArgs{se3, se3_grad, se3_m, se3_v, n_views * 6, nullptr, pose_lr, 1, pose_beta1, pose_beta2, pose_eps,
+                      (float)(1.0 / bc(pose_beta1)), (float)(1.0 / sqrt(bc(pose_beta2)))};
+  t.optimize_pose = se3 && se3_update;
+  if (sc) {
+    t.ray = RayArgs{pp_scene_dev(sc), ray_idx, n_rays, c2w, intr, n_views, H, W, inverse_y, rays_o, rays_d, t_min, ray_start,
+                    pts_grad, step_len, viewdir_grad_s, jac, c2w_grad, reinterpret_cast<unsigned*>(arrive)};
+    t.n_ray = pp_div_up(n_rays, 4);
+  }
+  t.n_flat = pp_div_up(flat_n, 256);
+  t.n_tail = pp_div_up(t.n_ray + t.n_flat + 1, 16) * 16;
+  return grid_tv_adam_step("pp_grid_tv_adam_step_tail", p_in, p_out, grad, exp_avg, exp_avg_sq, size_x, size_y, size_z, channels,
+                           x_begin, x_end, tv_scale, grad_scale, lr, beta1, beta2, eps, step, tv_out, touched, touched_clear, &t, ctx,
+                           stream);
 }
 
 extern "C" int pp_grid_tv_adam_step(const float* p_in, float* p_out, float* grad, float* exp_avg, float* exp_avg_sq,

@@ -274,16 +274,24 @@ class RenderCore:
         ops.sample_dense(self.cfg.pp, ws.rays_o, ws.rays_d, jitter, ws.sample_cap, ws.t_min, ws.t_max, ws.ray_start, ws.count,
                          ws.pts, ws.ray_id, ws.step_k, ws.step)
 
-    def forward(self, ws, k0_cl, sdf, sdf_ab, rgbnet_p, warp_p, inv_s, pe_w, step_w=None, before_k0_use=None, normals=None):
-        """normals: (nrm [cap,3], normal_marched [N,3]) - the marching kernel composites the unit SDF gradients as well."""
+    def forward(self, ws, k0_cl, sdf, sdf_ab, rgbnet_p, warp_p, inv_s, pe_w, step_w=None, before_k0_use=None, normals=None,
+                side_by_side=False):
+        """normals: (nrm [cap,3], normal_marched [N,3]) - the marching kernel composites the unit SDF gradients as well.
+        side_by_side (the train step's default path): geometry forward and colour lookup share one launch unless a
+        before_k0_use hook has to run between them."""
         cfg, sc = self.cfg, self.cfg.pp
         nrm, normal_marched = (None, None) if normals is None else normals
         ops.warp_fwd(warp_p, ws.pts, ws.count, ws.cap, cfg.out_range, ws.warp_acts, ws.warp_out, self.ctx)
-        ops.geometry_fwd(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
-                         ws.alpha, ws.gradient, ws.sdf_final, ws.sdf_deform, ws.grad_deform)
-        if before_k0_use is not None:
-            before_k0_use()             # multi-GPU: the all-gather of the updated grid overlaps everything above
-        ops.color_feat_fwd(sc, k0_cl, ws.pts, ws.viewdirs, ws.ray_id, ws.gradient, pe_w, ws.count, ws.cap, ws.feat)
+        if side_by_side and before_k0_use is None and (sc.k0_dim, sc.pos_pe, sc.view_pe) == (12, 5, 1):
+            # only the normal columns of feat need the geometry: the colour lookup runs beside it, in the same launch
+            ops.geometry_color_feat_fwd(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
+                                        ws.alpha, ws.gradient, ws.sdf_final, ws.sdf_deform, ws.grad_deform, k0_cl, pe_w, ws.feat)
+        else:
+            ops.geometry_fwd(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
+                             ws.alpha, ws.gradient, ws.sdf_final, ws.sdf_deform, ws.grad_deform)
+            if before_k0_use is not None:
+                before_k0_use()             # multi-GPU: the all-gather of the updated grid overlaps everything above
+            ops.color_feat_fwd(sc, k0_cl, ws.pts, ws.viewdirs, ws.ray_id, ws.gradient, pe_w, ws.count, ws.cap, ws.feat)
         ops.rgbnet_fwd(rgbnet_p, ws.feat, ws.count, ws.cap, ws.rgb_acts, ws.rgb, self.ctx)
         if nrm is not None:
             # rows past the count hold stale values: harmless, the marching kernel walks ray_start ranges only
@@ -407,6 +415,11 @@ class TrainEngine:
         self.w2c, self.c2w = torch.zeros(n_views, 3, 4, **f), torch.zeros(n_views, 3, 4, **f)
         self.jac = torch.zeros(n_views, 12, 6, **f)
         self.c2w_grad = torch.zeros(n_views, 3, 4, **f)
+        # train step on the default path: the optimiser launch carries the ray / pose backward (ops._tail_args).  Its last ray
+        # work-group leaves c2w_grad and this arrival counter zero again; _c2w_clean = both are zero now
+        self.tail_arrive = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self._c2w_clean = True
+        self._deferred_rays = None
         mask = torch.ones(n_views, dtype=torch.int32)
         if fix_first:
             mask[0] = 0                     # get_current_pose_pnp never refines view 0 (recon_scene.py:68)
@@ -516,10 +529,23 @@ class TrainEngine:
         self._k0_marked = False
         self.flat.grad.zero_()
         self.se3_grad.zero_()
+        self.c2w_grad.zero_()
+        self.tail_arrive.zero_()
+        self._c2w_clean = True
+        self._deferred_rays = None
 
-    def render_and_grads(self, ray_idx, jitter, global_step):
+    @property
+    def side_by_side(self):
+        """The default path (single GPU, no ordered flush): independent small kernels ride in a neighbour's launch."""
+        return self.dist is None and not self.deterministic
+
+    def render_and_grads(self, ray_idx, jitter, global_step, defer_pose_bwd=False):
         """pose -> rays -> forward -> losses -> full backward.  Gradients are accumulated into k0_grad / flat.grad /
-        se3_grad (which must be zero on entry)."""
+        se3_grad (which must be zero on entry).
+        defer_pose_bwd (train_step only; default path only): the ray / pose backward is left to the optimiser launch of THIS step -
+        se3_grad is not complete when this returns, optimizer_step must follow before anything reads it."""
+        defer_pose_bwd = defer_pose_bwd and self.side_by_side
+        self._deferred_rays = None
         cfg, ws, sc = self.cfg, self.ws, self.cfg.pp
         if self.deterministic:
             self.ordered_work()
@@ -537,7 +563,8 @@ class TrainEngine:
         P = self.flat
         with self.core.pass_scope(P, self.mlp_pack, ws):
             self.core.forward(ws, self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w,
-                              before_k0_use=None if self.dist is None else (lambda: self.dist.wait_parameters(self)))
+                              before_k0_use=None if self.dist is None else (lambda: self.dist.wait_parameters(self)),
+                              side_by_side=self.side_by_side)
             ws.zero_block.zero_()
             w_dyn = dynamic_weight(1e-1, 1e-3, global_step, cfg.N_iters)
             ls = self.loss_scale
@@ -565,7 +592,9 @@ class TrainEngine:
                                k0_grad, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
                                priors=(1.0, w_dyn, ls, ws.loss_out, batch_norm),
                                after_k0_grad=after_k0)
-            if self.deterministic:
+            if defer_pose_bwd:
+                self._deferred_rays = ray_idx
+            elif self.deterministic:
                 ops.raygen_select_bwd_ordered(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, ws.rays_o, ws.rays_d,
                                               ws.t_min, ws.ray_start, ws.g_pts, ws.step, ws.g_view_s, None, None, None, None, None,
                                               None, None, self.c2w_grad, self.ctx)
@@ -573,7 +602,9 @@ class TrainEngine:
                 ops.raygen_select_bwd(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, ws.rays_o, ws.rays_d,
                                       ws.t_min, ws.ray_start, ws.g_pts, ws.step, ws.g_view_s, None, None, None, None, None, None,
                                       None, self.c2w_grad)
-            ops.pose_bwd(self.jac, self.c2w_grad, self.se3_grad)
+            if not defer_pose_bwd:
+                self._c2w_clean = False
+                ops.pose_bwd(self.jac, self.c2w_grad, self.se3_grad)
         return s_val, w_dyn
 
     def reprojection_grads(self, rows, mode, global_step, jitter=None, weight_projection=1.0, weight_near_surface=1.0, nl=0.0,
@@ -669,6 +700,11 @@ class TrainEngine:
         self.n_step += 1
         for k in self.lr:                       # per-step exponential decay precedes the step (recon_scene.py:742-768)
             self.lr[k] *= self.decay
+        if self.side_by_side:
+            self._k0_step(self.lr['k0'], self.n_step, grad_scale, tail=self._optimizer_tail(optimize_pose))
+            if optimize_pose:
+                self.lr_pose *= self.pose_gamma
+            return
         self._k0_step(self.lr['k0'], self.n_step, grad_scale)
         if self.dist is not None:
             self.dist.wait_small()          # the small all-reduce (MLP / alpha-beta / pose gradients) ran beside the grid pass
@@ -679,8 +715,28 @@ class TrainEngine:
                           self.pose_seg_end, self.pose_seg_lr, grad_scale, 0.9, 0.999, 1e-8, self.n_step, 1)
             self.lr_pose *= self.pose_gamma
 
-    def _k0_step(self, lr_k0, n_step, grad_scale):
-        """Fused TV + Adam pass over the colour grid (ping-pong buffers flip)."""
+    def _optimizer_tail(self, optimize_pose):
+        """What the grid pass's launch carries beside it (ops._tail_args): both flat Adam updates and, when render_and_grads left
+        it to this launch, the ray / pose backward."""
+        ws, cfg, rays = self.ws, self.cfg, None
+        if self._deferred_rays is not None:
+            if not self._c2w_clean:         # a separate ray backward ran since: its sums are still in c2w_grad
+                self.c2w_grad.zero_()
+                self.tail_arrive.zero_()
+                self._c2w_clean = True
+            rays = (cfg.pp, self._deferred_rays, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, ws.rays_o, ws.rays_d, ws.t_min,
+                    ws.ray_start, ws.g_pts, ws.step, ws.g_view_s, self.jac, self.c2w_grad, self.tail_arrive)
+            self._deferred_rays = None
+        pose = None
+        if optimize_pose or rays is not None:
+            pose = (self.se3.view(-1), self.se3_grad.view(-1), self.se3_m.view(-1), self.se3_v.view(-1), self.pose_seg_lr, 0.9, 0.999,
+                    1e-8, optimize_pose)
+        return dict(flat=(self.flat.data, self.flat.grad, self.flat.m, self.flat.v, self.seg_end, self.seg_lr, 0.9, 0.99, 1e-8),
+                    pose=pose, rays=rays)
+
+    def _k0_step(self, lr_k0, n_step, grad_scale, tail=None):
+        """Fused TV + Adam pass over the colour grid (ping-pong buffers flip).  tail: see _optimizer_tail."""
+        kw = {} if tail is None else dict(tail=tail)
         cfg = self.cfg
         X, Y, Z = cfg.world_size
         tv_scale = self.loss_scale * self.w_tv / (3.0 * X * Y * Z * cfg.k0_dim)
@@ -690,18 +746,18 @@ class TrainEngine:
             cur = self.touch_par
             ops.grid_tv_adam_step_sparse(src, dst, self.k0_grad, self.k0_m, self.k0_v, cfg.world_size, cfg.k0_dim, xb, xe,
                                          tv_scale, grad_scale, lr_k0, 0.9, 0.99, 1e-8, n_step, self.ws.tv_out,
-                                         self.k0_touched[cur], self.k0_touched[1 - cur], self.ctx)
+                                         self.k0_touched[cur], self.k0_touched[1 - cur], self.ctx, **kw)
             self.touch_par = 1 - cur
             self._k0_marked = False
         else:
             ops.grid_tv_adam_step(src, dst, self.k0_grad, self.k0_m, self.k0_v, cfg.world_size, cfg.k0_dim, xb, xe, tv_scale,
-                                  grad_scale, lr_k0, 0.9, 0.99, 1e-8, n_step, self.ws.tv_out, self.ctx)
+                                  grad_scale, lr_k0, 0.9, 0.99, 1e-8, n_step, self.ws.tv_out, self.ctx, **kw)
         self.k0_cur = 1 - self.k0_cur
 
     def train_step(self, ray_idx, jitter, global_step, optimize_pose=True):
         """Gradients are zeroed by the optimiser kernels themselves after use; call zero_grads() once before the
         first step."""
-        out = self.render_and_grads(ray_idx, jitter, global_step)
+        out = self.render_and_grads(ray_idx, jitter, global_step, defer_pose_bwd=True)
         self.grad_scale = 1.0
         if self.dist is not None:
             self.dist.reduce_gradients(self)          # sets x_slab and grad_scale = 1/world

@@ -172,6 +172,14 @@ def geometry_bwd_priors(sc, sdf_grid, sdf_ab, pts, warp_out, viewdirs, ray_id, c
               _f(loss_out), _f(batch_norm), _stream())
 
 
+def geometry_color_feat_fwd(sc, sdf_grid, sdf_ab, pts, warp_out, viewdirs, ray_id, count, capacity, inv_s, alpha, gradient,
+                           sdf_final, sdf_deform, grad_deform, k0_cl, pe_w, feat):
+    """geometry_fwd and color_feat_fwd as two roles of one launch (k0_dim = 12, pos_pe = 5, view_pe = 1 only)."""
+    _lib.call('pp_geometry_color_feat_fwd', ctypes.byref(sc), _f(sdf_grid), _f(sdf_ab), _f(pts), _f(warp_out), _f(viewdirs),
+              _i(ray_id), _i(count), capacity, float(inv_s), _f(alpha), _f(gradient), _f(sdf_final), _f(sdf_deform),
+              _f(grad_deform), _f(k0_cl), _f(pe_w), _f(feat), _stream())
+
+
 # ------------------------------------------------------------------------------------------- ordered gradient flushes
 def ordered_workspace(work_groups, capacity, n_rays):
     """Bytes of the ordered-flush workspace (pp_ordered_workspace): work_groups = the largest persistent grid the MLP kernels
@@ -341,19 +349,54 @@ def loss_samples(gradient, grad_deform, warp_out, sdf_deform, count, capacity, w
               _f(g_sdf_deform), _f(loss_out), _f(batch_norm), _stream())
 
 
+def _tail_args(tail):
+    """Arguments of pp_grid_tv_adam_step_tail after the grid pass's own ones.  tail: dict(
+    flat=(p, grad, m, v, seg_end, seg_lr, beta1, beta2, eps)            Adam over the flat block (grad zeroed),
+    pose=(se3, grad, m, v, lr[1], beta1, beta2, eps, update) or None    Adam over the se3 block when `update`,
+    rays=(sc, ray_idx, c2w, intr, H, W, inverse_y, rays_o, rays_d, t_min, ray_start, pts_grad, step, vgrad_s, jac, c2w_grad,
+          arrive) or None                                               ray + pose backward ahead of it (needs pose; c2w_grad and
+                                                                        arrive [1] int32 are zero on entry and on exit))."""
+    fp, fg, fm, fv, seg_end, seg_lr, b1, b2, eps = tail['flat']
+    out = [_f(fp), _f(fg), _f(fm), _f(fv), fp.numel(), _i(seg_end), _f(seg_lr), seg_end.numel(), float(b1), float(b2), float(eps)]
+    pose, rays = tail.get('pose'), tail.get('rays')
+    if pose is None:
+        out += [None, None, None, None, 0, None, 0., 0., 0., 0]
+    else:
+        se3, g, m, v, lr, b1, b2, eps, update = pose
+        out += [_f(se3), _f(g), _f(m), _f(v), se3.numel() // 6, _f(lr), float(b1), float(b2), float(eps), int(bool(update))]
+    if rays is None:
+        out += [None, None, 0, None, None, 0, 0, 0] + [None] * 10
+    else:
+        sc, ray_idx, c2w, intr, H, W, inverse_y, rays_o, rays_d, t_min, ray_start, pts_grad, step, vgrad_s, jac, c2w_grad, arrive = rays
+        out += [ctypes.byref(sc), _i(ray_idx), rays_o.shape[0], _f(c2w), _f(intr), H, W, int(inverse_y), _f(rays_o), _f(rays_d),
+                _f(t_min), _i(ray_start), _f(pts_grad), _f(step), _f(vgrad_s), _f(jac), _f(c2w_grad), _i(arrive)]
+    return out
+
+
 def grid_tv_adam_step(p_in, p_out, grad, exp_avg, exp_avg_sq, size, channels, x_begin, x_end, tv_scale, grad_scale, lr,
-                      beta1, beta2, eps, step, tv_out, ctx=None):
+                      beta1, beta2, eps, step, tv_out, ctx=None, tail=None):
+    """tail (see _tail_args): the launch also carries the end of the step (pp_grid_tv_adam_step_tail)."""
+    if tail is not None:            # the dense pass of the tail-carrying entry point: no touched-voxel maps
+        _lib.call('pp_grid_tv_adam_step_tail', _f(p_in), _f(p_out), _f(grad), _f(exp_avg), _f(exp_avg_sq),
+                  int(size[0]), int(size[1]), int(size[2]), channels, x_begin, x_end, float(tv_scale), float(grad_scale),
+                  float(lr), float(beta1), float(beta2), float(eps), int(step), _f(tv_out), None, None, *_tail_args(tail),
+                  _h(ctx), _stream())
+        return
     _lib.call('pp_grid_tv_adam_step', _f(p_in), _f(p_out), _f(grad), _f(exp_avg), _f(exp_avg_sq),
               int(size[0]), int(size[1]), int(size[2]), channels, x_begin, x_end, float(tv_scale), float(grad_scale),
               float(lr), float(beta1), float(beta2), float(eps), int(step), _f(tv_out), _h(ctx), _stream())
 
 
 def grid_tv_adam_step_sparse(p_in, p_out, grad, exp_avg, exp_avg_sq, size, channels, x_begin, x_end, tv_scale, grad_scale,
-                             lr, beta1, beta2, eps, step, tv_out, touched, touched_clear, ctx=None):
-    _lib.call('pp_grid_tv_adam_step_sparse', _f(p_in), _f(p_out), _f(grad), _f(exp_avg), _f(exp_avg_sq),
-              int(size[0]), int(size[1]), int(size[2]), channels, x_begin, x_end, float(tv_scale), float(grad_scale),
-              float(lr), float(beta1), float(beta2), float(eps), int(step), _f(tv_out), _u8(touched), _u8(touched_clear),
-              _h(ctx), _stream())
+                             lr, beta1, beta2, eps, step, tv_out, touched, touched_clear, ctx=None, tail=None):
+    """tail (see _tail_args): the launch also carries the end of the step (pp_grid_tv_adam_step_tail)."""
+    grid = (_f(p_in), _f(p_out), _f(grad), _f(exp_avg), _f(exp_avg_sq),
+            int(size[0]), int(size[1]), int(size[2]), channels, x_begin, x_end, float(tv_scale), float(grad_scale),
+            float(lr), float(beta1), float(beta2), float(eps), int(step), _f(tv_out), _u8(touched), _u8(touched_clear))
+    if tail is None:
+        _lib.call('pp_grid_tv_adam_step_sparse', *grid, _h(ctx), _stream())
+    else:
+        _lib.call('pp_grid_tv_adam_step_tail', *grid, *_tail_args(tail), _h(ctx), _stream())
 
 
 def grid_tv_value(p, size, channels, out):
