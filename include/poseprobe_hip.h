@@ -45,7 +45,8 @@ const char* pp_last_error(void);
  * ownership from stage 1 to stage 2 explicitly -, pp_nerf_fwd / pp_nerf_bwd, pp_grid_tv_adam_step{,_sparse});
  * pp_scene gained `sdf_index_exact`; new: pp_sdf_crossing_dense_bwd, pp_context_set_option / pp_context_get_option.  4 (this header): the
  * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
- * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_mc_* group, the pp_pnp_* group.
+ * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_mc_* group, the pp_pnp_* group,
+ * the pp_dtu_* group.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
  * (poseprobe_amd/_lib.py does): the signatures changed, so a stale caller would pass a stream where a pointer is read. */
 #define PP_ABI_VERSION 4
@@ -728,6 +729,48 @@ int pp_pnp_workspace(int32_t P, int32_t H, int64_t* bytes);
 int pp_pnp_ransac(const float* world, const float* pix, const uint8_t* valid, int32_t P, const float* intr, const int32_t* samples,
                   int32_t H, float reproj_error, int32_t refine_iters, int32_t min_inliers, const float* fallback, void* work,
                   int64_t work_bytes, float* w2c, uint8_t* inliers, int32_t* info, void* stream);
+
+/* ---------------------------------------------------------------- mesh evaluation: DTU Chamfer distance
+ * lib/dtu_eval.py::eval samples points from the triangles, thins them by radius and runs two nearest-neighbour passes on the
+ * host; here the three stages run on device-resident points.  Sorting, scans and compaction are the caller's.
+ * Sampling (lib/dtu_eval.py:70-89, decided in fp64 in the reference's operation order): vertices [V,3] fp64, triangles [T,3]
+ *   int32.  v1 = p1 - p0, v2 = p2 - p0, l = sqrt((x x + y y) + z z), area2 = |v1 x v2|; a triangle with area2 > 0 has
+ *   thr = thresh sqrt(l1 l2 / area2), n1 = floor(l1 / thr), n2 = floor(l2 / thr) and, when both are at least 1, the points
+ *   (v1 a + v2 b) + p0 for 0 <= i <= n1, 0 <= j <= n2 with a = (i + 0.5) / n1, b = (j + 0.5) / n2, a + b < 1, i-major, rounded
+ *   once to fp32.  pp_dtu_sample_count writes counts [T] int64 (DEVICE); a triangle with an index outside [0, V) counts 0, one
+ *   whose n1 or n2 reaches 2^31 counts 2^31.  pp_dtu_sample_emit, given the same inputs and offsets [T] = the exclusive scan of
+ *   counts, writes rows [0, n_points) of points [.,3] fp32 and nothing past them; n_points above 2^31 - 1 is PP_ERR_UNSUPPORTED.
+ * Cell grid: origin (ox, oy, oz), cubic cells of `edge`, nx x ny x nz cells (each at most 2^20: PP_ERR_UNSUPPORTED beyond); a
+ *   point's cell along an axis is floor((p - o) / edge) in fp32, clamped into the grid; pp_dtu_cell_keys writes the int64 keys
+ *   (x ny + y) nz + z.  The two searches below take the points SORTED by key: points [N,3], keys [N], and order [N] int32 = the
+ *   index each sorted point had before sorting.
+ * Distance: d2 = (dx dx + dy dy) + dz dz in fp32.
+ * pp_dtu_thin_rounds (lib/dtu_eval.py:98-106): the keep mask of walking the points in `order` order, a point still marked
+ *   keeping itself and unmarking every point with d2 <= radius radius - computed in rounds on a state byte per sorted point
+ *   (0 undecided, 1 kept, 2 removed): an undecided point is removed if a neighbour of lower order is kept, kept if every such
+ *   neighbour is removed.  `work` (pp_dtu_thin_workspace: two state arrays of N bytes, each rounded up to 256) holds the
+ *   state: round r reads the array at (r & 1) r256(N) and writes the other.  A call runs rounds first_round ..
+ *   first_round + n_rounds - 1 (first_round = 0 clears the state first; 1 <= n_rounds <= 1024) and sets undecided[k]
+ *   (DEVICE int32 [n_rounds]) to 1 iff a point is still undecided after its k-th round.  edge >= radius is required, and the
+ *   caller leaves a margin for the rounding of the cell coordinate (poseprobe_amd/dtu_eval.py: 1 %, below 2^13 cells per axis).
+ * pp_dtu_nearest (lib/dtu_eval.py:145-146, :158-159): d2 [Q] fp32 and idx [Q] int32 (in `order` numbering) of the exact nearest
+ *   point of every query, ties to the lowest index; (inf, -1) where no point has d2 < max_dist max_dist.  The result does not
+ *   depend on the grid (same margin rule as above).
+ * All refuse, before any GPU call: null pointers, sizes below 1, a non-finite or non-positive thresh / edge / max_dist, a
+ * negative radius, a workspace that is too small.  No allocation, no atomics, no host read. */
+int pp_dtu_sample_count(const double* vertices, int32_t V, const int32_t* triangles, int32_t T, double thresh, int64_t* counts,
+                        void* stream);
+int pp_dtu_sample_emit(const double* vertices, int32_t V, const int32_t* triangles, int32_t T, double thresh, const int64_t* offsets,
+                       float* points, int64_t n_points, void* stream);
+int pp_dtu_cell_keys(const float* points, int32_t N, float ox, float oy, float oz, float edge, int32_t nx, int32_t ny, int32_t nz,
+                     int64_t* keys, void* stream);
+int pp_dtu_thin_workspace(int32_t N, int64_t* bytes);
+int pp_dtu_thin_rounds(const float* points, const int64_t* keys, const int32_t* order, int32_t N, float ox, float oy, float oz,
+                       float edge, int32_t nx, int32_t ny, int32_t nz, float radius, int32_t first_round, int32_t n_rounds, void* work,
+                       int64_t work_bytes, int32_t* undecided, void* stream);
+int pp_dtu_nearest(const float* queries, int32_t Q, const float* points, const int64_t* keys, const int32_t* order, int32_t P, float ox,
+                   float oy, float oz, float edge, int32_t nx, int32_t ny, int32_t nz, float max_dist, float* d2, int32_t* idx,
+                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,8 @@ def parse_header(path=HEADER):
                 ct = ctypes.c_int32
             elif 'float' in a:
                 ct = ctypes.c_float
+            elif 'double' in a:
+                ct = ctypes.c_double
             else:
                 raise ValueError(f'unhandled argument "{a}" in {name}')
             parsed.append((ct, argname))

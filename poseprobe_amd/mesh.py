@@ -199,3 +199,71 @@ def write_ply(path, vertices, triangles, vertex_colors=None):
         f.write(('\n'.join(header) + '\n').encode('ascii'))
         f.write(vert.tobytes())
         f.write(face.tobytes())
+
+
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+
+
+def read_ply(path):
+    """A minimal PLY reader: ascii and binary little-endian, scalar properties of the usual types, faces as lists of 3 vertex
+    indices -> (vertices [Nv,3] in the stored float type, triangles [Nt,3] int32 - empty for a point cloud).  Other vertex
+    properties (normals, colours) and other scalar-only elements are skipped.  It reads what `write_ply` writes."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    end = data.find(b'end_header')
+    if not data.startswith(b'ply') or end < 0:
+        raise ValueError(f'{path}: not a PLY file')
+    body = data.find(b'\n', end) + 1
+    fmt, elements = None, []                    # elements: [name, count, [(property name, dtype or ('list', count type, item type))]]
+    for line in data[:end].decode('ascii').splitlines()[1:]:
+        w = line.split()
+        if not w or w[0] in ('comment', 'obj_info'):
+            continue
+        if w[0] == 'format':
+            fmt = w[1]
+        elif w[0] == 'element':
+            elements.append([w[1], int(w[2]), []])
+        elif w[0] == 'property':
+            if w[1] == 'list':
+                elements[-1][2].append((w[4], ('list', _PLY_TYPES[w[2]], _PLY_TYPES[w[3]])))
+            else:
+                elements[-1][2].append((w[2], _PLY_TYPES[w[1]]))
+    if fmt not in ('ascii', 'binary_little_endian'):
+        raise ValueError(f'{path}: format {fmt} is not supported (ascii and binary_little_endian are)')
+    vertices, triangles = None, np.empty((0, 3), np.int32)
+    tokens = data[body:].split() if fmt == 'ascii' else None
+    pos = 0 if fmt == 'ascii' else body
+    for name, count, props in elements:
+        lists = [p for p in props if isinstance(p[1], tuple)]
+        if lists and (name != 'face' or len(props) != 1):
+            raise ValueError(f'{path}: element {name}: list properties are only read as the single property of `face`')
+        if lists:
+            ct, it = lists[0][1][1:]
+            if fmt == 'ascii':
+                rows = np.array(tokens[pos:pos + 4 * count], dtype=np.float64).reshape(count, 4)
+                pos += 4 * count
+                n, tri = rows[:, 0], rows[:, 1:]
+            else:
+                dt = np.dtype([('n', '<' + ct), ('v', '<' + it, (3,))])
+                rows = np.frombuffer(data, dt, count, pos)
+                pos += count * dt.itemsize
+                n, tri = rows['n'], rows['v']
+            if count and not (n == 3).all():
+                raise ValueError(f'{path}: only triangle faces are read')
+            triangles = np.ascontiguousarray(tri).astype(np.int32)
+            continue
+        dt = np.dtype([(p, '<' + t) for p, t in props])
+        if fmt == 'ascii':
+            rows = np.array(tokens[pos:pos + len(props) * count], dtype=np.float64).reshape(count, len(props))
+            pos += len(props) * count
+            col = {p: rows[:, k].astype(t) for k, (p, t) in enumerate(props)}
+        else:
+            rows = np.frombuffer(data, dt, count, pos)
+            pos += count * dt.itemsize
+            col = rows
+        if name == 'vertex':
+            vertices = np.stack([col['x'], col['y'], col['z']], -1)
+    if vertices is None:
+        raise ValueError(f'{path}: no vertex element')
+    return vertices, triangles

@@ -702,3 +702,95 @@ def pnp_ransac(world, pix, valid, intr, samples, reproj_error, refine_iters, min
     _lib.call('pp_pnp_ransac', _f(world, 'world'), _f(pix, 'pix'), _u8(valid, 'valid'), P, _f(intr, 'intr'), _i(samples, 'samples'), H,
               ctypes.c_float(reproj_error), int(refine_iters), int(min_inliers), _f(fallback, 'fallback'), _u8(work, 'work'),
               0 if work is None else int(work.numel()), _f(w2c, 'w2c'), _u8(inliers, 'inliers'), _i(info, 'info'), _stream())
+
+
+# ------------------------------------------------------------------------------------------- mesh evaluation (DTU Chamfer distance)
+def _dtu_mesh(vertices, triangles):
+    for t, name in ((vertices, 'vertices'), (triangles, 'triangles')):
+        if t is not None and (t.dim() != 2 or t.shape[1] != 3):
+            raise RuntimeError(f'{name} must be [.,3]')
+    return (0 if vertices is None else int(vertices.shape[0])), (0 if triangles is None else int(triangles.shape[0]))
+
+
+def dtu_sample_count(vertices, triangles, thresh, counts):
+    """vertices [V,3] float64, triangles [T,3] int32 -> counts [T] int64: the sampled points of every triangle."""
+    V, T = _dtu_mesh(vertices, triangles)
+    if counts is not None and counts.numel() != T:
+        raise RuntimeError(f'counts: {counts.numel()} elements, {T} expected')
+    _lib.call('pp_dtu_sample_count', _ptr(vertices, torch.float64, 'vertices'), V, _i(triangles, 'triangles'), T, ctypes.c_double(thresh),
+              _ptr(counts, torch.int64, 'counts'), _stream())
+
+
+def dtu_sample_emit(vertices, triangles, thresh, offsets, points, n_points):
+    """After dtu_sample_count: offsets [T] int64 = the exclusive scan of the counts -> rows [0, n_points) of points [.,3] fp32."""
+    V, T = _dtu_mesh(vertices, triangles)
+    if offsets is not None and offsets.numel() != T:
+        raise RuntimeError(f'offsets: {offsets.numel()} elements, {T} expected')
+    if points is not None and points.numel() < 3 * int(n_points):
+        raise RuntimeError(f'points: {points.numel() // 3} rows, {int(n_points)} to be written')
+    _lib.call('pp_dtu_sample_emit', _ptr(vertices, torch.float64, 'vertices'), V, _i(triangles, 'triangles'), T, ctypes.c_double(thresh),
+              _ptr(offsets, torch.int64, 'offsets'), _f(points, 'points'), int(n_points), _stream())
+
+
+def _dtu_grid(grid):
+    """grid = (origin [3], edge, cells [3]) -> the seven scalars of the C ABI."""
+    o, edge, n = grid
+    return (ctypes.c_float(o[0]), ctypes.c_float(o[1]), ctypes.c_float(o[2]), ctypes.c_float(edge), int(n[0]), int(n[1]), int(n[2]))
+
+
+def _dtu_rows(t, name):
+    if t is not None and (t.dim() != 2 or t.shape[1] != 3):
+        raise RuntimeError(f'{name} must be [.,3]')
+    return 0 if t is None else int(t.shape[0])
+
+
+def dtu_cell_keys(points, grid, keys):
+    """points [N,3] fp32 -> keys [N] int64: (x ny + y) nz + z of the point's cell in grid = (origin, edge, cells)."""
+    N = _dtu_rows(points, 'points')
+    if keys is not None and keys.numel() != N:
+        raise RuntimeError(f'keys: {keys.numel()} elements, {N} expected')
+    _lib.call('pp_dtu_cell_keys', _f(points, 'points'), N, *_dtu_grid(grid), _ptr(keys, torch.int64, 'keys'), _stream())
+
+
+def dtu_thin_workspace(N):
+    """Bytes of device workspace pp_dtu_thin_rounds needs for N points (a pure host call)."""
+    b = ctypes.c_int64()
+    _lib.call('pp_dtu_thin_workspace', int(N), ctypes.byref(b))
+    return b.value
+
+
+def dtu_thin_state(work, N, rounds_done):
+    """The state bytes [N] (0 undecided, 1 kept, 2 removed; in key order) that `rounds_done` rounds have left in the workspace."""
+    off = (rounds_done & 1) * ((int(N) + 255) // 256 * 256)
+    return work[off:off + int(N)]
+
+
+def _dtu_sorted(points, keys, order):
+    N = _dtu_rows(points, 'points')
+    for t, name in ((keys, 'keys'), (order, 'order')):
+        if t is not None and t.numel() != N:
+            raise RuntimeError(f'{name}: {t.numel()} elements, {N} expected')
+    return N
+
+
+def dtu_thin_rounds(points, keys, order, grid, radius, first_round, n_rounds, work, undecided):
+    """Rounds first_round .. first_round + n_rounds - 1 of the radius thinning on points sorted by key (order [N] int32 = their
+    indices before sorting); undecided [n_rounds] int32 <- 1 where a point is still undecided after that round."""
+    N = _dtu_sorted(points, keys, order)
+    if undecided is not None and undecided.numel() < int(n_rounds):
+        raise RuntimeError(f'undecided: {undecided.numel()} elements, {int(n_rounds)} expected')
+    _lib.call('pp_dtu_thin_rounds', _f(points, 'points'), _ptr(keys, torch.int64, 'keys'), _i(order, 'order'), N, *_dtu_grid(grid),
+              ctypes.c_float(radius), int(first_round), int(n_rounds), _u8(work, 'work'), 0 if work is None else int(work.numel()),
+              _i(undecided, 'undecided'), _stream())
+
+
+def dtu_nearest(queries, points, keys, order, grid, max_dist, d2, idx):
+    """queries [Q,3]; points sorted by key with keys and order -> d2 [Q] fp32, idx [Q] int32 (in `order` numbering) of the exact
+    nearest point, ties to the lowest index; (inf, -1) beyond max_dist."""
+    Q = _dtu_rows(queries, 'queries')
+    P = _dtu_sorted(points, keys, order)
+    for t, name in ((d2, 'd2'), (idx, 'idx')):
+        if t is not None and t.numel() != Q:
+            raise RuntimeError(f'{name}: {t.numel()} elements, {Q} expected')
+    _lib.call('pp_dtu_nearest', _f(queries, 'queries'), Q, _f(points, 'points'), _ptr(keys, torch.int64, 'keys'), _i(order, 'order'), P,
+              *_dtu_grid(grid), ctypes.c_float(max_dist), _f(d2, 'd2'), _i(idx, 'idx'), _stream())
