@@ -46,7 +46,7 @@ const char* pp_last_error(void);
  * pp_scene gained `sdf_index_exact`; new: pp_sdf_crossing_dense_bwd, pp_context_set_option / pp_context_get_option.  4 (this header): the
  * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
  * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_mc_* group, the pp_pnp_* group,
- * the pp_dtu_* group.
+ * the pp_dtu_* group, pp_step_begin, pp_march_loss_bwd / pp_march_loss_workspace.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
  * (poseprobe_amd/_lib.py does): the signatures changed, so a stale caller would pass a stream where a pointer is read. */
 #define PP_ABI_VERSION 4
@@ -301,6 +301,15 @@ int pp_rgbnet_bwd_weights(const float* feat, const float* acts, const float* scr
 int pp_mlp_pack_workspace(int64_t* pack_floats);
 int pp_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, void* ctx, void* stream);
 int pp_mlp_pack_invalidate(void* ctx);
+/* Head of a train step in ONE launch of independent work-group roles: pp_pose_fwd (same arguments, bit-identical w2c / c2w /
+ * jac); step_dev[0..n_scalars) = step_scalars[0..n_scalars) - a HOST array of at most 32 floats, read during the call and handed
+ * to the kernel by value, so that no copy sits in the stream (more than 32 are refused with PP_ERR_INVALID_ARG: upload them); zero_block[0..n_zero) = 0; and, with pack != NULL, pp_mlp_pack
+ * (same pack, same record in `ctx`, which is then required; with option mlp_pack = 0 nothing is packed or recorded).  An earlier
+ * record of `ctx` is dropped in every case. */
+int pp_step_begin(const float* se3, const float* w2c_init, const int32_t* refine_mask, int32_t n_views, float* w2c,
+                  float* c2w, float* jac, const float* step_scalars, int32_t n_scalars, float* step_dev,
+                  float* zero_block, int32_t n_zero, const float* warp_params, const float* rgbnet_params, float* pack,
+                  void* ctx, void* stream);
 
 /* Lean scope of the warp net (option warp_lean, default 1).  Two of the per-sample blocks that the warp net's three kernels
  * exchange through `acts` and `scratch` can be rebuilt by their only reader, the weight-gradient kernel, from a few bytes:
@@ -387,6 +396,25 @@ int pp_loss_rays(const float* rgb_marched, const float* alphainv_last, const flo
                  const float* target, const float* mask_px, float* mask_sum, int32_t n_rays, float w_main,
                  float w_entropy, float w_mask, float loss_scale, float* g_rgb_marched, float* g_alphainv_last,
                  float* g_cum_weights, float* loss_out, const float* batch_norm, void* stream);
+/* pp_march_fwd -> pp_loss_rays -> pp_march_bwd in ONE launch, one wavefront per ray: the ray's composite, its loss terms and its
+ * compositing backward in sequence, with the samples' values kept in registers (no nrm_in / normal_marched, no batch_norm: callers
+ * that need them keep the separate calls).  sample_cap = an upper bound of the samples of one ray (ray_start[r + 1] - ray_start[r]);
+ * the kernel holds 192: a larger sample_cap is refused with PP_ERR_INVALID_ARG before anything is launched - take the separate
+ * calls then.  The bound is the CALLER'S promise: the kernel does not compare it with ray_start, and a ray that is longer all the
+ * same is composited from its first 192 samples only (never indexed past them) - wrong outputs for that ray, no error.
+ * Every output of the three calls is written; all are bit-identical to them except loss_out[0], [1], [6], [7] (+=),
+ * whose sums are formed per work-group and added up in a fixed order by the last work-group to arrive: they differ from
+ * pp_loss_rays' by summation order only, and are the same bits from call to call.
+ * work: pp_march_loss_workspace bytes, 16-byte aligned, ZERO before the first call; every call leaves its first word zero again.
+ * step_w, depth_acc, loss_out, g_depth_acc, g_weights, grad_rgb may be NULL (as in the separate calls). */
+int pp_march_loss_workspace(int32_t n_rays, int32_t sample_cap, int64_t* bytes);
+int pp_march_loss_bwd(const float* alpha, const float* rgb, const float* step_w, const int32_t* ray_start,
+                      int32_t n_rays, int32_t sample_cap, float bg, float* weights, float* T, float* alphainv_last,
+                      int32_t* i_end, float* rgb_marched, float* rgb_pre, float* cum_weights, float* depth_acc,
+                      const float* target, const float* mask_px, float* mask_sum, float w_main, float w_entropy,
+                      float w_mask, float loss_scale, float* g_rgb_marched, float* g_alphainv_last,
+                      float* g_cum_weights, float* loss_out, const float* g_depth_acc, const float* g_weights,
+                      float* grad_alpha, float* grad_rgb, void* work, int64_t work_bytes, void* stream);
 /* g_gradient[M,3] is ACCUMULATED (+=); g_grad_deform[M,9], g_correction[M], g_sdf_deform[M] are written. */
 int pp_loss_samples(const float* gradient, const float* grad_deform, const float* warp_out,
                     const float* sdf_deform, const int32_t* count, int32_t capacity, float w_eikonal,

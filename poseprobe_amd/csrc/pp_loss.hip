@@ -2,15 +2,7 @@
 // Ray-level terms (masked MSE :26-29, entropy on alphainv_cum :42-45, BCE mask :66) and sample-level terms
 // (eikonal :6-10, deformation priors :11-23) are reduced per block and accumulated with one atomic per block.
 #include "pp_common.h"
-
-__device__ __forceinline__ float block_sum256(float v, float* sm) {
-  v = pp_wave_sum(v);
-  int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sm[wid] = v;
-  __syncthreads();
-  return sm[0] + sm[1] + sm[2] + sm[3];
-}
+#include "pp_loss_body.h"
 
 __global__ __launch_bounds__(256) void k_loss_rays(const float* __restrict__ rgbm, const float* __restrict__ alast,
                                                    const float* __restrict__ cw, const float* __restrict__ target,
@@ -22,42 +14,24 @@ __global__ __launch_bounds__(256) void k_loss_rays(const float* __restrict__ rgb
   __shared__ float sm[4];
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   float l_mse = 0.f, l_ent = 0.f, l_bce = 0.f;
-  // number of masked-in pixels of the batch: every block sums the (few KB of) masks itself, in k_sum's order, instead of
-  // waiting for a separate single-block kernel
-  float part = 0.f;
-  for (int i = threadIdx.x; i < n_rays; i += 256) part += mask_px[i];
-  const float msum_local = block_sum256(part, sm);
+  const float msum_local = loss_mask_sum(mask_px, n_rays, sm);
   if (blockIdx.x == 0 && threadIdx.x == 0) mask_sum[0] = msum_local;
   // ray-sharded data parallelism: the masked MSE is normalised by the UNION batch's masked-pixel count / world size
   const float msum = batch_norm ? batch_norm[0] : msum_local;
   const float invN = 1.f / (float)n_rays;
   if (r < n_rays) {
-    float y = mask_px[r];
-    for (int k = 0; k < 3; ++k) {
-      float d = rgbm[r * 3 + k] * y - target[r * 3 + k] * y;
-      l_mse += d * d;
-      g_rgbm[r * 3 + k] = ls * w_main * 2.f * d * y / (msum * 3.f);
-    }
-    float a = alast[r];
-    float p = fminf(fmaxf(a, 1e-6f), 1.f - 1e-6f);
-    float lp = logf(p), lq = logf(1.f - p);
-    l_ent = -(p * lp + (1.f - p) * lq);
-    g_alast[r] = (a >= 1e-6f && a <= 1.f - 1e-6f) ? ls * w_ent * (-(lp - lq)) * invN : 0.f;
-    float c0 = cw[r];
-    float c = fminf(fmaxf(c0, 1e-3f), 1.f - 1e-3f);
-    l_bce = -(y * logf(c) + (1.f - y) * logf(1.f - c));
-    g_cw[r] = (c0 >= 1e-3f && c0 <= 1.f - 1e-3f) ? ls * w_mask * (-(y / c) + (1.f - y) / (1.f - c)) * invN : 0.f;
+    const float pix[3] = {rgbm[r * 3], rgbm[r * 3 + 1], rgbm[r * 3 + 2]};
+    const float tgt[3] = {target[r * 3], target[r * 3 + 1], target[r * 3 + 2]};
+    const RayLoss L = loss_ray_terms(pix, alast[r], cw[r], tgt, mask_px[r], msum, invN, w_main, w_ent, w_mask, ls);
+    for (int k = 0; k < 3; ++k) g_rgbm[r * 3 + k] = L.g_rgbm[k];
+    g_alast[r] = L.g_last;
+    g_cw[r] = L.g_cw;
+    l_mse = L.l_mse; l_ent = L.l_ent; l_bce = L.l_bce;
   }
   l_mse = block_sum256(l_mse, sm);
   l_ent = block_sum256(l_ent, sm);
   l_bce = block_sum256(l_bce, sm);
-  if (threadIdx.x == 0 && loss_out) {
-    atomicAdd(&loss_out[0], l_mse / (msum * 3.f));
-    atomicAdd(&loss_out[1], l_ent * invN);
-    atomicAdd(&loss_out[6], l_bce * invN);
-    // [7]: the WEIGHTED sum of all terms (both kernels add their share): object_losses' `loss` without the TV term
-    atomicAdd(&loss_out[7], w_main * (l_mse / (msum * 3.f)) + w_ent * (l_ent * invN) + w_mask * (l_bce * invN));
-  }
+  if (threadIdx.x == 0 && loss_out) loss_rays_add(loss_out, l_mse, l_ent, l_bce, msum, invN, w_main, w_ent, w_mask);
 }
 
 __global__ __launch_bounds__(256) void k_loss_samples(const float* __restrict__ gradient, const float* __restrict__ gdef,

@@ -132,6 +132,38 @@ extern "C" int pp_mlp_pack(const float* warp_params, const float* rgbnet_params,
   return PP_OK;
 }
 
+// pp_pose_fwd, the upload of the step's scalars, the memset of the zero block and pp_mlp_pack in one launch (k_step_begin)
+extern "C" int pp_step_begin(const float* se3, const float* w2c_init, const int32_t* refine_mask, int32_t n_views, float* w2c,
+                             float* c2w, float* jac, const float* step_scalars, int32_t n_scalars, float* step_dev,
+                             float* zero_block, int32_t n_zero, const float* warp_params, const float* rgbnet_params, float* pack,
+                             void* ctx, void* stream) {
+  PP_REQUIRE(se3 && w2c_init && w2c && c2w && jac && n_views > 0, "null pointer or n_views<=0");
+  PP_REQUIRE(n_scalars >= 0 && n_scalars <= PP_STEP_SCALARS_MAX && (n_scalars == 0 || (step_scalars && step_dev)),
+             "0 <= n_scalars <= 32, with step_scalars (host) and step_dev");
+  PP_REQUIRE(n_zero >= 0 && (n_zero == 0 || zero_block), "n_zero<0 or null zero_block");
+  PP_REQUIRE(pack == nullptr || (ctx && (warp_params || rgbnet_params)), "a pack needs a context and parameters");
+  PP_REQUIRE((reinterpret_cast<uintptr_t>(pack) & 15) == 0, "pack must be 16-byte aligned");
+  PPStepScalars sv;
+  sv.n = n_scalars;
+  for (int i = 0; i < PP_STEP_SCALARS_MAX; ++i) sv.v[i] = i < n_scalars ? step_scalars[i] : 0.f;
+  bool packs = false;
+  if (ctx) {
+    pp_mlp_pack_invalidate(ctx);
+    const MlpRoute rt(ctx);
+    packs = pack && rt.pack && rt.fused && (rt.split & 15) != 0;      // as pp_mlp_pack: otherwise nothing would read it
+  }
+  pp_launch_step_begin(se3, w2c_init, refine_mask, n_views, w2c, c2w, jac, sv, step_dev, zero_block, n_zero, warp_params,
+                       rgbnet_params, packs ? pack : nullptr, pp_stream(stream));
+  PP_CHECK_LAUNCH();
+  if (packs) {
+    PPContext* c = static_cast<PPContext*>(ctx);
+    c->pack = pack;
+    c->pack_params[0] = warp_params;
+    c->pack_params[1] = rgbnet_params;
+  }
+  return PP_OK;
+}
+
 // Generic ReLU MLP  in_ld -> 128 -> ... -> 128 -> 3 (+ optional sigmoid), n_gemm = number of 128-wide hidden layers.
 // Parameter block: W0[128*in_ld] b0[128] | (W[128*128] b[128]) x (n_gemm-1) | Wout[3*128] bout[3].
 extern "C" int pp_mlp_fwd(const float* params, const float* feat, int32_t in_ld, int32_t n_gemm, const int32_t* count,

@@ -54,6 +54,13 @@ int pp_launch_warp_fused_bwd_s(const float* params, const float* pts, const floa
                                const int32_t* count, int capacity, float out_range, float* ybar, float* params_grad,
                                float* pts_grad, hipStream_t st, int wgs, const float* pack, float* part, bool lean);
 int pp_launch_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, hipStream_t st);
+// the step's scalars as a kernel argument of k_step_begin (pp_step_begin): n <= PP_STEP_SCALARS_MAX floats
+#define PP_STEP_SCALARS_MAX 32
+struct PPStepScalars { float v[PP_STEP_SCALARS_MAX]; int n; };
+// pose forward + step scalars + zero block in work-group 0, the PK_TASKS tasks of the weight pack beside it (pack == nullptr: none)
+int pp_launch_step_begin(const float* se3, const float* w2c_init, const int32_t* refine_mask, int n_views, float* w2c, float* c2w,
+                         float* jac, const PPStepScalars& sv, float* step_dev, float* zero_block, int n_zero,
+                         const float* warp_params, const float* rgbnet_params, float* pack, hipStream_t st);
 // weight gradients of three layers (Y_l^T X_l accumulated into W_l) in one persistent kernel; kxc = width of X of layer C;
 // bA / bB / bC: also accumulate the bias gradients = column sums of Y over the primal rows (kxc == 128: the warp net's 4-row
 // form, every fourth row) or over all rows (kxc == 64: rgbnet)

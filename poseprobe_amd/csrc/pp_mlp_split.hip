@@ -37,6 +37,7 @@
 #include "pp_gemm_split.h"
 #include "pp_split_image.h"
 #include "pp_mlp_pack.h"
+#include "pp_pose_body.h"
 #include "pp_ordered.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -1429,9 +1430,9 @@ int pp_launch_rgb_fused_bwd_s(const float* params, const float* acts, const floa
 // One work-group per image (PK_TASKS, pp_mlp_pack.h): it runs the SAME prologue code as the kernels above - same loads, same
 // summation order, same reductions - and stores what that code leaves in registers, so a kernel that reads the pack starts from
 // bit-identical weights, exponents and norms.  `warp` / `rgb` == nullptr: that net's part of the pack is left alone.
-__global__ __launch_bounds__(256) void k_mlp_pack(const float* __restrict__ warp, const float* __restrict__ rgb, float* __restrict__ pack) {
-  __shared__ __attribute__((aligned(16))) float red4[32];
-  const int task = blockIdx.x;
+// the work of ONE task (work-group): the body of k_mlp_pack and of the pack roles of k_step_begin
+__device__ __forceinline__ void mlp_pack_task(const int task, const float* __restrict__ warp, const float* __restrict__ rgb,
+                                              float* __restrict__ pack, float* red4) {
   const float* __restrict__ params = task < PK_TASKS_WARP ? warp : rgb;
   if (params == nullptr) return;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -1490,6 +1491,39 @@ __global__ __launch_bounds__(256) void k_mlp_pack(const float* __restrict__ warp
     if (tid == 0) { S[PKR_B0MX] = b0mx; S[PKR_B1MX] = b1mx; }
     put(PKR_EW3, ew3, PKR_W3L1, w3l1);
   }
+}
+
+__global__ __launch_bounds__(256) void k_mlp_pack(const float* __restrict__ warp, const float* __restrict__ rgb, float* __restrict__ pack) {
+  __shared__ __attribute__((aligned(16))) float red4[32];
+  mlp_pack_task(blockIdx.x, warp, rgb, pack, red4);
+}
+
+// What a train step needs before its first ray, in ONE launch of independent work-group roles.  Work-group 0: the pose
+// forward (body of k_pose_fwd, pp_pose_body.h), the step's scalars - handed over by value as a kernel argument, so that no copy
+// sits in the stream - stored to step_dev, and zeros over zero_block.  Work-groups 1 .. PK_TASKS (only launched with a pack): the
+// tasks of k_mlp_pack.  No role reads what another writes; no work-group waits for another.
+__global__ __launch_bounds__(256) void k_step_begin(const float* __restrict__ se3, const float* __restrict__ w2c_init,
+                                                    const int32_t* __restrict__ refine_mask, int n_views, float* __restrict__ w2c,
+                                                    float* __restrict__ c2w, float* __restrict__ jac, const PPStepScalars sv,
+                                                    float* __restrict__ step_dev, float* __restrict__ zero_block, int n_zero,
+                                                    const float* __restrict__ warp, const float* __restrict__ rgb,
+                                                    float* __restrict__ pack) {
+  __shared__ __attribute__((aligned(16))) float red4[32];
+  if (blockIdx.x == 0) {
+    for (int t = threadIdx.x; t < n_views * 6; t += 256) pose_fwd_elem(t, se3, w2c_init, refine_mask, n_views, w2c, c2w, jac);
+    if ((int)threadIdx.x < sv.n) step_dev[threadIdx.x] = sv.v[threadIdx.x];
+    for (int i = threadIdx.x; i < n_zero; i += 256) zero_block[i] = 0.f;
+    return;
+  }
+  mlp_pack_task(blockIdx.x - 1, warp, rgb, pack, red4);
+}
+
+int pp_launch_step_begin(const float* se3, const float* w2c_init, const int32_t* refine_mask, int n_views, float* w2c, float* c2w,
+                         float* jac, const PPStepScalars& sv, float* step_dev, float* zero_block, int n_zero,
+                         const float* warp_params, const float* rgbnet_params, float* pack, hipStream_t st) {
+  hipLaunchKernelGGL(k_step_begin, dim3(pack ? 1 + PK_TASKS : 1), dim3(256), 0, st, se3, w2c_init, refine_mask, n_views, w2c, c2w,
+                     jac, sv, step_dev, zero_block, n_zero, warp_params, rgbnet_params, pack);
+  return 0;
 }
 
 int pp_launch_mlp_pack(const float* warp_params, const float* rgbnet_params, float* pack, hipStream_t st) {

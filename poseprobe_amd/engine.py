@@ -7,6 +7,7 @@ torch is used for device memory and streams only; every arithmetic step is a ker
 """
 import contextlib
 import math
+import warnings
 from dataclasses import dataclass
 
 import numpy as np
@@ -251,16 +252,21 @@ class RenderCore:
             raise ValueError('an ordered RenderCore needs its own context (the workspace is attached to it)')
 
     @contextlib.contextmanager
-    def pass_scope(self, flat, pack, lean_ws=None):
+    def pass_scope(self, flat, pack, lean_ws=None, pack_with=None):
         """One render pass: the MLP weights of `flat` are packed into `pack` HERE, on the pass's stream, and the record is dropped when
         the pass's kernels are enqueued - also when the pass raises.  Every writer of the parameters (the optimiser, a checkpoint
         load, an in-place copy from outside) runs between two scopes, so no kernel can read a pack older than its parameters.
+        pack_with: a callable that packs exactly these into `pack` for this context in a launch it shares with other work (the train
+        step's ops.step_begin) - called in place of ops.mlp_pack.
         lean_ws: the Workspace whose warp_acts / scratch the pass differentiates through - a lean scope of the warp net, closed with
         the pack record: the forward kernel leaves out the tangent rows of X0, the data-gradient kernel Ybar3, and the
         weight-gradient kernel rebuilds both (option warp_lean)."""
         lean = lean_ws is not None and lean_ws.warp_acts is not None
         try:
-            ops.mlp_pack(flat.view('warp'), flat.view('rgbnet'), pack, self.ctx)
+            if pack_with is not None:
+                pack_with()
+            else:
+                ops.mlp_pack(flat.view('warp'), flat.view('rgbnet'), pack, self.ctx)
             if lean:
                 ops.warp_lean_begin(lean_ws.warp_acts, lean_ws.scratch, flat.view('warp'), self.ctx)
             yield
@@ -275,10 +281,12 @@ class RenderCore:
                          ws.pts, ws.ray_id, ws.step_k, ws.step)
 
     def forward(self, ws, k0_cl, sdf, sdf_ab, rgbnet_p, warp_p, inv_s, pe_w, step_w=None, before_k0_use=None, normals=None,
-                side_by_side=False):
+                side_by_side=False, composite=True):
         """normals: (nrm [cap,3], normal_marched [N,3]) - the marching kernel composites the unit SDF gradients as well.
         side_by_side (the train step's default path): geometry forward and colour lookup share one launch unless a
-        before_k0_use hook has to run between them."""
+        before_k0_use hook has to run between them.
+        composite=False (the train step's default path): the pass stops in front of the compositing - the caller composites, takes
+        the ray losses and differentiates the composite in one launch (ops.loss_rays(march=...)) and calls backward(march_done=True)."""
         cfg, sc = self.cfg, self.cfg.pp
         nrm, normal_marched = (None, None) if normals is None else normals
         ops.warp_fwd(warp_p, ws.pts, ws.count, ws.cap, cfg.out_range, ws.warp_acts, ws.warp_out, self.ctx)
@@ -296,6 +304,10 @@ class RenderCore:
         if nrm is not None:
             # rows past the count hold stale values: harmless, the marching kernel walks ray_start ranges only
             torch.div(ws.gradient, ws.gradient.norm(2, -1, keepdim=True) + 1e-6, out=nrm)
+        if not composite:
+            if normals is not None or step_w is not None:
+                raise ValueError('composite=False: the fused ray launch composites neither normals nor a step_w of the caller')
+            return
         ops.march_fwd(ws.alpha, ws.rgb, ws.step if step_w is None else step_w, nrm, ws.ray_start, ws.N, cfg.bg,
                       ws.weights, ws.T, ws.alphainv_last, ws.i_end, ws.rgb_marched, ws.rgb_pre, ws.cum_weights,
                       ws.depth_acc, normal_marched)
@@ -303,12 +315,17 @@ class RenderCore:
     # -- backward ------------------------------------------------------------------------------------------
     def backward(self, ws, k0_cl, sdf, sdf_ab, rgbnet_p, warp_p, inv_s, pe_w, k0_grad_cl, sdf_ab_grad, rgbnet_grad,
                  warp_grad, g_depth=None, g_weights=None, g_gradient_ext=None, g_sdf_deform=None, g_grad_deform=None,
-                 g_correction=None, g_alpha_ext=None, g_rgb_ext=None, after_k0_grad=None, priors=None):
+                 g_correction=None, g_alpha_ext=None, g_rgb_ext=None, after_k0_grad=None, priors=None, march_done=False):
         """Consumes ws.g_rgbm / ws.g_last / ws.g_cw (+ optional per-sample upstream grads), accumulates parameter
-        grads (atomic +=) and leaves d/d ray_pts in ws.g_pts and the per-sample viewdir grads in ws.g_view_s."""
+        grads (atomic +=) and leaves d/d ray_pts in ws.g_pts and the per-sample viewdir grads in ws.g_view_s.
+        march_done: the caller ran ops.loss_rays(march=...) after forward(composite=False) - ws.g_alpha / ws.g_rgb are in place."""
         cfg, sc = self.cfg, self.cfg.pp
-        ops.march_bwd(ws.alpha, ws.rgb, ws.step, ws.weights, ws.T, ws.alphainv_last, ws.ray_start, ws.i_end, ws.N, cfg.bg,
-                      ws.rgb_pre, ws.g_rgbm, ws.g_cw, ws.g_last, g_depth, g_weights, ws.g_alpha, ws.g_rgb)
+        if march_done:
+            if not (g_depth is None and g_weights is None and g_alpha_ext is None and g_rgb_ext is None):
+                raise ValueError('march_done: the fused ray launch takes no upstream gradients beside the ray losses')
+        else:
+            ops.march_bwd(ws.alpha, ws.rgb, ws.step, ws.weights, ws.T, ws.alphainv_last, ws.ray_start, ws.i_end, ws.N, cfg.bg,
+                          ws.rgb_pre, ws.g_rgbm, ws.g_cw, ws.g_last, g_depth, g_weights, ws.g_alpha, ws.g_rgb)
         if g_alpha_ext is not None:
             ws.g_alpha.add_(g_alpha_ext)
         if g_rgb_ext is not None:
@@ -352,8 +369,11 @@ class TrainEngine:
     def __init__(self, cfg: SceneConfig, n_views, H, W, n_rand, device='cuda', lr_pose=1e-3, lr_pose_end=1e-4,
                  pose_iters=1, lrate_decay=10, loss_scale=0.1, weight_main=1.0, weight_tv_k0=0.01, weight_mask=0.1,
                  fix_first=True, capacity=None, x_slab=None, dist_ctx=None, deterministic_scatter=False, options=None,
-                 deterministic=False, reproj_rows=0):
-        """reproj_rows: row capacity of the engine-native reprojection pass (`reprojection_grads`); each row is one ray of a second
+                 deterministic=False, reproj_rows=0, fuse_head=True, fuse_rays=True):
+        """fuse_head / fuse_rays (default path only, see `side_by_side`): the step starts with ONE launch (ops.step_begin: pose forward,
+        step scalars, zero block, weight pack) / composites, evaluates the ray losses and differentiates the composite in ONE launch
+        (ops.march_loss_bwd) - DESIGN 17.  False: the separate launches (A/B runs, tests); also plain attributes of the engine.
+        reproj_rows: row capacity of the engine-native reprojection pass (`reprojection_grads`); each row is one ray of a second
         Workspace(reproj_rows, reproj_rows * n_samples).  0 (default): no second workspace, nothing changes.
         deterministic: bit-reproducible train step.  Implies deterministic_scatter and additionally replaces every other
         floating-point sum of the object-branch step that feeds a parameter update and depends on the order in which work-groups
@@ -418,6 +438,15 @@ class TrainEngine:
         # train step on the default path: the optimiser launch carries the ray / pose backward (ops._tail_args).  Its last ray
         # work-group leaves c2w_grad and this arrival counter zero again; _c2w_clean = both are zero now
         self.tail_arrive = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.fuse_head, self.fuse_rays = bool(fuse_head), bool(fuse_rays)
+        # partial loss rows + arrival ticket of the fused ray launch; None: a ray may have more samples than that kernel holds -
+        # the step then keeps march_fwd / loss_rays / march_bwd
+        self.ray_work = None
+        if cfg.n_samples <= ops.MARCH_LOSS_MAX_SAMPLES:
+            self.ray_work = torch.zeros(ops.march_loss_workspace(n_rand, cfg.n_samples), dtype=torch.uint8, device=self.dev)
+        elif self.fuse_rays:
+            warnings.warn(f'{cfg.n_samples} samples per ray: more than the fused ray launch holds ({ops.MARCH_LOSS_MAX_SAMPLES}); '
+                          'the step composites, takes the ray losses and differentiates in separate launches')
         self._c2w_clean = True
         self._deferred_rays = None
         mask = torch.ones(n_views, dtype=torch.int32)
@@ -447,6 +476,10 @@ class TrainEngine:
             self.step_host = self.step_host.pin_memory()
         self._slot = 0
         self.step_dev = torch.zeros(self.npe + 4, **f)
+        if self.npe + 4 > ops.STEP_SCALARS_MAX and self.fuse_head:
+            # more step scalars than ops.step_begin hands over by value: pose_fwd, the pinned upload and mlp_pack stay separate
+            warnings.warn(f'{self.npe} position-encoding bands: the step keeps its separate head launches')
+            self.fuse_head = False
         self.pe_w = self.step_dev[:self.npe]
         self.seg_lr = self.step_dev[self.npe:self.npe + 3]
         self.pose_seg_lr = self.step_dev[self.npe + 3:self.npe + 4]
@@ -549,28 +582,47 @@ class TrainEngine:
         cfg, ws, sc = self.cfg, self.ws, self.cfg.pp
         if self.deterministic:
             self.ordered_work()
-        ops.pose_fwd(self.se3, self.w2c_init, self.refine_mask, self.w2c, self.c2w, self.jac)
-        ops.raygen_select_fwd(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, True, self.images, self.masks,
-                              ws.rays_o, ws.rays_d, ws.viewdirs, ws.target, ws.mask_px)
-        self.core.sample(ws, jitter)
-        if self.dist is not None:
-            # (sample count, masked-pixel count) of every rank: sizes the sample exchange exactly and normalises the losses
-            # over the union batch; the 8-byte all-gather completes under the forward pass
-            self.dist.start_batch_stats(ws.count, ws.mask_px)
         progress = global_step / cfg.N_iters
-        self._upload_step_scalars(progress)
-        s_val, inv_s = cfg.s_val(global_step), cfg.inv_s(global_step)
         P = self.flat
-        with self.core.pass_scope(P, self.mlp_pack, ws):
+        head = None
+        if self.side_by_side and self.fuse_head:
+            # one launch for everything the step needs before its first ray.  The pack is made HERE, at the start of the
+            # step that uses it, so a parameter write between two steps (checkpoint load, in-place copy) is seen
+            head = lambda: ops.step_begin(self.se3, self.w2c_init, self.refine_mask, self.w2c, self.c2w, self.jac,
+                                          self._step_scalars(progress), self.step_dev, ws.zero_block, P.view('warp'),
+                                          P.view('rgbnet'), self.mlp_pack, self.ctx)
+        fused_rays = self.side_by_side and self.fuse_rays and self.ray_work is not None
+        s_val, inv_s = cfg.s_val(global_step), cfg.inv_s(global_step)
+        w_dyn = dynamic_weight(1e-1, 1e-3, global_step, cfg.N_iters)
+        ls = self.loss_scale
+
+        def rays_and_samples():
+            ops.raygen_select_fwd(sc, ray_idx, self.c2w, self.intr, self.H, self.W, cfg.inverse_y, True, self.images, self.masks,
+                                  ws.rays_o, ws.rays_d, ws.viewdirs, ws.target, ws.mask_px)
+            self.core.sample(ws, jitter)
+            if self.dist is not None:
+                # (sample count, masked-pixel count) of every rank: sizes the sample exchange exactly and normalises the losses
+                # over the union batch; the 8-byte all-gather completes under the forward pass
+                self.dist.start_batch_stats(ws.count, ws.mask_px)
+        if head is None:
+            # separate launches, in the order they always had: pose, rays, samples, scalars; the scope then packs
+            ops.pose_fwd(self.se3, self.w2c_init, self.refine_mask, self.w2c, self.c2w, self.jac)
+            rays_and_samples()
+            self._upload_step_scalars(progress)
+        with self.core.pass_scope(P, self.mlp_pack, ws, pack_with=head):
+            if head is not None:
+                rays_and_samples()          # behind the head launch, which the scope has just issued
             self.core.forward(ws, self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w,
                               before_k0_use=None if self.dist is None else (lambda: self.dist.wait_parameters(self)),
-                              side_by_side=self.side_by_side)
-            ws.zero_block.zero_()
-            w_dyn = dynamic_weight(1e-1, 1e-3, global_step, cfg.N_iters)
-            ls = self.loss_scale
+                              side_by_side=self.side_by_side, composite=not fused_rays)
+            if head is None:
+                ws.zero_block.zero_()
             batch_norm = None if self.dist is None else self.dist.wait_batch_stats()
+            # fused_rays: the composite, the ray losses and the compositing backward of a ray by one wavefront, in this launch
+            march = (ws.alpha, ws.rgb, ws.step, ws.ray_start, cfg.n_samples, cfg.bg, ws.weights, ws.T, ws.i_end, ws.rgb_pre,
+                     ws.depth_acc, ws.g_alpha, ws.g_rgb, self.ray_work) if fused_rays else None
             ops.loss_rays(ws.rgb_marched, ws.alphainv_last, ws.cum_weights, ws.target, ws.mask_px, ws.mask_sum, self.w_main,
-                          0.01, self.w_mask, ls, ws.g_rgbm, ws.g_last, ws.g_cw, ws.loss_out, batch_norm)
+                          0.01, self.w_mask, ls, ws.g_rgbm, ws.g_last, ws.g_cw, ws.loss_out, batch_norm, march=march)
 
             # The k0 scatter is issued from here (not inside colour-feature backward) so that it can mark the voxels it reaches:
             # single GPU = right after the colour-feature backward; multi-GPU "samples" mode = replayed for all ranks' gathered
@@ -591,7 +643,7 @@ class TrainEngine:
             self.core.backward(ws, self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w,
                                k0_grad, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
                                priors=(1.0, w_dyn, ls, ws.loss_out, batch_norm),
-                               after_k0_grad=after_k0)
+                               after_k0_grad=after_k0, march_done=fused_rays)
             if defer_pose_bwd:
                 self._deferred_rays = ray_idx
             elif self.deterministic:
@@ -689,11 +741,14 @@ class TrainEngine:
         per-step exponential decay precedes the optimiser step, recon_scene.py:742-768)."""
         h = self.step_host[self._slot]
         self._slot = (self._slot + 1) % self.step_host.shape[0]
-        h[:self.npe] = torch.from_numpy(self.cfg.pe_weights(progress))
-        d = self.decay
-        h[self.npe + 0], h[self.npe + 1], h[self.npe + 2] = self.lr['sdf_ab'] * d, self.lr['rgbnet'] * d, self.lr['warp'] * d
-        h[self.npe + 3] = self.lr_pose
+        h.copy_(torch.from_numpy(self._step_scalars(progress)))
         self.step_dev.copy_(h, non_blocking=True)
+
+    def _step_scalars(self, progress):
+        """The npe + 4 floats of step_dev for this step (layout: see step_host), as float32 on the host."""
+        d = self.decay
+        lrs = np.array([self.lr['sdf_ab'] * d, self.lr['rgbnet'] * d, self.lr['warp'] * d, self.lr_pose], dtype=np.float32)
+        return np.concatenate([self.cfg.pe_weights(progress), lrs])
 
     def optimizer_step(self, optimize_pose=True, grad_scale=1.0):
         cfg = self.cfg

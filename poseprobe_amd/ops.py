@@ -77,6 +77,19 @@ def pose_fwd(se3, w2c_init, refine_mask, w2c, c2w, jac):
     _lib.call('pp_pose_fwd', _f(se3), _f(w2c_init), _i(refine_mask), V, _f(w2c), _f(c2w), _f(jac), _stream())
 
 
+def step_begin(se3, w2c_init, refine_mask, w2c, c2w, jac, scalars, step_dev, zero_block, warp_params=None, rgbnet_params=None,
+               pack=None, ctx=None):
+    """Head of a train step in one launch (pp_step_begin): pose_fwd; step_dev[:len(scalars)] = scalars (a host sequence of at most
+    32 floats, handed to the kernel by value: no copy in the stream); zero_block = 0; with `pack`, mlp_pack of the two parameter
+    blocks, recorded in `ctx` as mlp_pack records it."""
+    vals = np.ascontiguousarray(scalars, dtype=np.float32)
+    n = vals.shape[0]
+    host = (ctypes.c_float * max(n, 1)).from_buffer_copy(vals.tobytes() if n else bytes(4))
+    _lib.call('pp_step_begin', _f(se3), _f(w2c_init), _i(refine_mask), se3.shape[0], _f(w2c), _f(c2w), _f(jac),
+              ctypes.cast(host, ctypes.c_void_p), n, _f(step_dev), _f(zero_block), 0 if zero_block is None else zero_block.numel(),
+              _f(warp_params), _f(rgbnet_params), _f(pack), _h(ctx), _stream())
+
+
 def pose_bwd(jac, c2w_grad, se3_grad):
     _lib.call('pp_pose_bwd', _f(jac), _f(c2w_grad), se3_grad.shape[0], _f(se3_grad), _stream())
 
@@ -132,6 +145,28 @@ def march_bwd(alpha, rgb, step_w, weights, T, alphainv_last, ray_start, i_end, n
     _lib.call('pp_march_bwd', _f(alpha), _f(rgb), _f(step_w), _f(weights), _f(T), _f(alphainv_last), _i(ray_start),
               _i(i_end), n_rays, float(bg), _f(rgb_pre), _f(g_rgbm), _f(g_cw), _f(g_last), _f(g_depth),
               _f(g_weights), _f(grad_alpha), _f(grad_rgb), _stream())
+
+
+MARCH_LOSS_MAX_SAMPLES = 192       # samples of one ray that march_loss_bwd's kernel holds (pp_march_loss_workspace refuses more)
+STEP_SCALARS_MAX = 32              # floats that step_begin hands to its kernel by value
+
+
+def march_loss_workspace(n_rays, sample_cap):
+    """Bytes of the workspace of march_loss_bwd (zero before the first call); raises PoseProbeError when the kernel cannot hold
+    `sample_cap` samples of a ray - the caller then takes march_fwd / loss_rays / march_bwd."""
+    b = ctypes.c_int64()
+    _lib.call('pp_march_loss_workspace', int(n_rays), int(sample_cap), ctypes.byref(b))
+    return b.value
+
+
+def march_loss_bwd(alpha, rgb, step_w, ray_start, n_rays, sample_cap, bg, weights, T, alphainv_last, i_end, rgb_marched, rgb_pre,
+                   cum_weights, depth_acc, target, mask_px, mask_sum, w_main, w_entropy, w_mask, loss_scale, g_rgbm, g_last, g_cw,
+                   loss_out, g_depth, g_weights, grad_alpha, grad_rgb, work):
+    """march_fwd -> loss_rays -> march_bwd of every ray by one wavefront, in one launch (pp_march_loss_bwd)."""
+    _lib.call('pp_march_loss_bwd', _f(alpha), _f(rgb), _f(step_w), _i(ray_start), n_rays, int(sample_cap), float(bg), _f(weights),
+              _f(T), _f(alphainv_last), _i(i_end), _f(rgb_marched), _f(rgb_pre), _f(cum_weights), _f(depth_acc), _f(target),
+              _f(mask_px), _f(mask_sum), float(w_main), float(w_entropy), float(w_mask), float(loss_scale), _f(g_rgbm), _f(g_last),
+              _f(g_cw), _f(loss_out), _f(g_depth), _f(g_weights), _f(grad_alpha), _f(grad_rgb), _u8(work), work.numel(), _stream())
 
 
 # ------------------------------------------------------------------------------------------- geometry / colour
@@ -336,7 +371,18 @@ def rgbnet_bwd_weights(feat, acts, scratch, count, capacity, params_grad, stage2
 
 # ------------------------------------------------------------------------------------------- losses / optimiser
 def loss_rays(rgb_marched, alphainv_last, cum_weights, target, mask_px, mask_sum, w_main, w_entropy, w_mask,
-              loss_scale, g_rgbm, g_last, g_cw, loss_out, batch_norm=None):
+              loss_scale, g_rgbm, g_last, g_cw, loss_out, batch_norm=None, march=None):
+    """march: (alpha, rgb, step_w, ray_start, sample_cap, bg, weights, T, i_end, rgb_pre, depth_acc, grad_alpha, grad_rgb, work) - the
+    rays have not been composited yet: march_fwd before the losses and march_bwd behind them run in the same launch, a wavefront
+    per ray (march_loss_bwd); rgb_marched / alphainv_last / cum_weights are then outputs as well.  Not with batch_norm."""
+    if march is not None:
+        if batch_norm is not None:
+            raise ValueError('loss_rays(march=...) has no batch_norm: composite and differentiate with the separate calls')
+        alpha, rgb, step_w, ray_start, sample_cap, bg, weights, T, i_end, rgb_pre, depth_acc, grad_alpha, grad_rgb, work = march
+        march_loss_bwd(alpha, rgb, step_w, ray_start, rgb_marched.shape[0], sample_cap, bg, weights, T, alphainv_last, i_end,
+                       rgb_marched, rgb_pre, cum_weights, depth_acc, target, mask_px, mask_sum, w_main, w_entropy, w_mask,
+                       loss_scale, g_rgbm, g_last, g_cw, loss_out, None, None, grad_alpha, grad_rgb, work)
+        return
     _lib.call('pp_loss_rays', _f(rgb_marched), _f(alphainv_last), _f(cum_weights), _f(target), _f(mask_px),
               _f(mask_sum), rgb_marched.shape[0], float(w_main), float(w_entropy), float(w_mask), float(loss_scale),
               _f(g_rgbm), _f(g_last), _f(g_cw), _f(loss_out), _f(batch_norm), _stream())
