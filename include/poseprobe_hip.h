@@ -331,6 +331,26 @@ int pp_step_begin(const float* se3, const float* w2c_init, const int32_t* refine
 int pp_warp_lean_begin(const float* acts, const float* scratch, const float* params, void* ctx);
 int pp_warp_lean_end(void* ctx);
 
+/* Join scope of the weight gradients: the hidden layers' weight and bias gradients of BOTH nets in one launch.  Nothing but the
+ * optimiser reads rgbnet's, and the warp net's chain - the same layer code - comes later on the same stream, so inside the scope
+ *   - pp_rgbnet_bwd called with `ctx` runs its data-gradient kernel as always and, instead of launching its weight-gradient
+ *     chain, RECORDS it in `ctx` (feat, acts, scratch, count, capacity, params_grad, stream) - if that chain would be the
+ *     split-precision one (options mlp_fused = 1, mlp_split bits 8 and 16) and no ordered-flush workspace is attached; otherwise
+ *     it launches it as always.  pp_rgbnet_bwd_weights and pp_mlp_bwd never defer.
+ *   - the next pp_warp_bwd / pp_warp_bwd_weights with `ctx` launches ONE kernel for its own three products and the recorded
+ *     three, if it runs the lean form of the split-precision chain (inside a pp_warp_lean_begin scope, for its buffers) with
+ *     float atomics and is handed the SAME count pointer and stream as the record; otherwise it first launches the recorded
+ *     chain on its own (on the recorded stream), exactly as pp_rgbnet_bwd would have.  Either way the record is cleared.
+ * Between the two calls the recorded buffers must stay as they are and rgbnet's params_grad is incomplete.  The sums are the
+ * same terms as in the two launches, shared out differently among the work-groups: results agree to fp32 rounding.
+ * Work-groups (two per CU, or 2 x option mlp_wgs) are shared out 10 : 10 : 10 : 4 : 4 : 3 over the warp net's three layers,
+ * rgbnet's two 128-wide layers and its input layer, rounded to nearest, the input layer taking the rest.
+ * pp_wgrad_join_end closes the scope: a record nobody took is launched on its own (launch_pending = 1) or dropped
+ * (launch_pending = 0: the pass failed, its gradients will not be used).  pp_wgrad_join_begin on an open scope ends it first,
+ * with launch.  Neither is an option: outside a scope nothing changes. */
+int pp_wgrad_join_begin(void* ctx);
+int pp_wgrad_join_end(void* ctx, int32_t launch_pending);
+
 /* ---------------------------------------------------------------- ordered gradient flushes: a bit-reproducible train step.
  * By default the parameter gradients of the object branch are accumulated with float atomics wherever several work-groups (or
  * lanes) contribute to one address: the hidden layers' weight and bias gradients of both MLPs (pp_warp_bwd, pp_rgbnet_bwd /

@@ -33,7 +33,7 @@ enum PPOption {
   PP_OPT_COUNT
 };
 
-// Caller-owned context: the option values + four records (weight pack, lean scope, the two ordered-flush workspaces).  It owns no HIP
+// Caller-owned context: the option values + five records (weight pack, lean scope, the two ordered-flush workspaces, join scope).  It owns no HIP
 // object: every kernel runs on the stream the call is given.
 struct PPContext {
   int opt[PP_OPT_COUNT];
@@ -52,6 +52,16 @@ struct PPContext {
   // workspace of the scene branch's ordered weight-gradient flush (pp_nerf_ordered_attach, pp_gemm_tn_tr.h);
   // nerf_ord == nullptr: none, pp_nerf_bwd flushes with float atomics
   float* nerf_ord;
+  // join scope of the weight gradients (pp_wgrad_join_begin): open or not, and the rgbnet chain that a pp_rgbnet_bwd inside it
+  // left to the next warp chain on this context (the arguments of its launch); join_pending == false: none
+  bool join_open, join_pending;
+  struct {
+    const float *feat, *acts, *scratch;
+    const int32_t* count;
+    int capacity;
+    float* params_grad;
+    hipStream_t stream;
+  } join;
 };
 
 // The option array of a context (indexed by PPOption), or the compiled-in defaults for ctx == nullptr.  Two contexts with

@@ -57,6 +57,7 @@ extern "C" int pp_context_create(void** ctx) {
   c->ord = nullptr;
   c->ord_wgs = c->ord_cap = c->ord_rays = 0;
   c->nerf_ord = nullptr;
+  c->join_open = c->join_pending = false;
   *ctx = c;
   return PP_OK;
 }

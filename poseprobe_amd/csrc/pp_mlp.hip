@@ -10,7 +10,7 @@
 // passes and their double backward (lib/voxurf_coarse.py:968-984) by plain matrix products.
 //
 // This file holds the C-ABI entry points of both MLPs: argument checks, the records a context carries for them (weight pack, lean
-// scope, ordered-flush workspace) and the routing of a call to its kernels, decided once per call (MlpRoute).  The kernels are
+// scope, ordered-flush workspace, join scope of the weight gradients) and the routing of a call to its kernels, decided once per call (MlpRoute).  The kernels are
 // elsewhere: layer-fused on the fp32 matrix instructions in pp_mlp_fused.hip, layer-fused split-precision in pp_mlp_split.hip,
 // layer by layer (generic MLP shapes, option mlp_fused = 0) in pp_mlp_layered.hip.
 #include "pp_common.h"
@@ -199,14 +199,90 @@ static bool warp_bwd_stage1(const MlpRoute& rt, const float* params, const float
   else pp_launch_warp_fused_bwd(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st, rt.wgs);
   return sb;
 }
+// the split-precision weight-gradient chain of rgbnet (part: its region of an ordered workspace, or nullptr)
+static void rgb_wgrad_chain_s(const float* feat, const float* acts, const float* scratch, const int32_t* count, int capacity,
+                              float* pg, bool sb, hipStream_t st, int wgs, float* part) {
+  const size_t FLS = (size_t)capacity * 128;
+  float *b2 = sb ? pg + RGF_B2 : nullptr, *b1 = sb ? pg + RGF_B1 : nullptr, *b0 = sb ? pg + RGF_B0 : nullptr;
+  pp_launch_wgrad_chain_s(scratch, acts + FLS, pg + RGF_W2, scratch + FLS, acts, pg + RGF_W1, scratch + 2 * FLS, feat, pg + RGF_W0,
+                          64, count, 1, capacity, st, wgs, b2, b1, b0, part, nullptr);
+}
+
+// Join scope of the weight gradients (pp_wgrad_join_begin).  Inside it pp_rgbnet_bwd leaves its weight-gradient chain
+// as a record in the context - nothing but the optimiser reads those gradients - and the next warp chain on that context carries
+// the three products in its own launch (k_wgrad_join_s).  Whatever cannot be joined is launched exactly as outside the scope.
+// the pending chain of `c` in a launch of its own, as pp_rgbnet_bwd would have made it
+static void wgrad_join_flush(PPContext* c, int wgs) {
+  if (!c->join_pending) return;
+  c->join_pending = false;
+  rgb_wgrad_chain_s(c->join.feat, c->join.acts, c->join.scratch, c->join.count, c->join.capacity, c->join.params_grad, true,
+                    c->join.stream, wgs, nullptr);
+}
+// pp_rgbnet_bwd behind its data-gradient kernel: is the chain left to the next warp chain?  Only the split-precision chain with
+// float atomics whose bias sums are stage 2's (sb) can ride; a record nobody took is launched first
+static bool wgrad_join_defer(void* ctx, const MlpRoute& rt, bool sb, const float* feat, const float* acts, const float* scratch,
+                             const int32_t* count, int capacity, float* params_grad, hipStream_t st) {
+  PPContext* c = static_cast<PPContext*>(ctx);
+  if (!c || !c->join_open || !sb || !rt.runs_split(16) || c->ord) return false;
+  wgrad_join_flush(c, rt.wgs);
+  c->join.feat = feat; c->join.acts = acts; c->join.scratch = scratch;
+  c->join.count = count; c->join.capacity = capacity; c->join.params_grad = params_grad; c->join.stream = st;
+  c->join_pending = true;
+  return true;
+}
+// a warp chain about to be launched: does the pending record ride in it?  Only in the lean form of the split-precision chain with
+// float atomics and bias sums (sb), for the same `count` and stream; otherwise the pending chain is launched on its own, now
+static bool wgrad_join_rides(void* ctx, const MlpRoute& rt, const float* acts, const float* scratch, const int32_t* count, bool sb,
+                             hipStream_t st) {
+  PPContext* c = static_cast<PPContext*>(ctx);
+  if (!c || !c->join_pending) return false;
+  if (sb && !c->ord && rt.runs_split(16) && warp_lean_for(rt, acts, scratch) && c->join.count == count && c->join.stream == st)
+    return true;
+  wgrad_join_flush(c, rt.wgs);
+  return false;
+}
+
+extern "C" int pp_wgrad_join_end(void* ctx, int32_t launch_pending) {
+  PP_REQUIRE(ctx, "null context");
+  PPContext* c = static_cast<PPContext*>(ctx);
+  c->join_open = false;
+  if (launch_pending) {
+    wgrad_join_flush(c, MlpRoute(ctx).wgs);
+    PP_CHECK_LAUNCH();
+  }
+  c->join_pending = false;
+  return PP_OK;
+}
+
+extern "C" int pp_wgrad_join_begin(void* ctx) {
+  PP_REQUIRE(ctx, "null context (the scope is recorded in a context: create one)");
+  const int status = pp_wgrad_join_end(ctx, 1);
+  if (status != PP_OK) return status;
+  static_cast<PPContext*>(ctx)->join_open = true;
+  return PP_OK;
+}
+
+// join (wgrad_join_rides said so): the pending rgbnet chain of context `jc` rides in this launch
 static void warp_bwd_stage2(const MlpRoute& rt, const float* acts, const float* scratch, const int32_t* count, int capacity,
-                            float* params_grad, bool sb, hipStream_t st) {
+                            float* params_grad, bool sb, hipStream_t st, PPContext* jc = nullptr) {
   const int rcap = capacity * 4;
   const size_t LS = (size_t)rcap * 128;
   float *pg = params_grad, *b3 = sb ? pg + WPF_B3 : nullptr, *b2 = sb ? pg + WPF_B2 : nullptr, *b1 = sb ? pg + WPF_B1 : nullptr;
   // inside a lean scope slot 0 of `scratch` holds the output gradients and X0 only its primal rows: the kernel rebuilds the rest
   const float* lp = warp_lean_for(rt, acts, scratch);
   const WgradLean lean{acts + 3 * LS, lp ? lp + WPF_W4 : nullptr, lp ? lp + WPF_W0 : nullptr};
+  if (jc) {
+    jc->join_pending = false;
+    const size_t FLS = (size_t)jc->join.capacity * 128;
+    const float *ra = jc->join.acts, *rs = jc->join.scratch;
+    float* rg = jc->join.params_grad;
+    const WgradOperands warp3[3] = {{scratch, acts + 2 * LS, pg + WPF_W3, b3}, {scratch + LS, acts + LS, pg + WPF_W2, b2},
+                                    {scratch + 2 * LS, acts, pg + WPF_W1, b1}};
+    const WgradOperands rgb3[3] = {{rs, ra + FLS, rg + RGF_W2, rg + RGF_B2}, {rs + FLS, ra, rg + RGF_W1, rg + RGF_B1},
+                                   {rs + 2 * FLS, jc->join.feat, rg + RGF_W0, rg + RGF_B0}};
+    pp_launch_wgrad_join_s(warp3, rgb3, count, rcap, jc->join.capacity, st, rt.wgs, lean);
+    return;
+  }
   if (rt.runs_split(16))
     pp_launch_wgrad_chain_s(scratch, acts + 2 * LS, pg + WPF_W3, scratch + LS, acts + LS, pg + WPF_W2, scratch + 2 * LS, acts, pg + WPF_W1,
                             128, count, 4, rcap, st, rt.wgs, b3, b2, b1, ordered_part(rt, 0), lp ? &lean : nullptr);
@@ -228,17 +304,16 @@ static void rgb_bwd_stage2(const MlpRoute& rt, const float* feat, const float* a
   const size_t FLS = (size_t)capacity * 128;
   float *pg = params_grad, *b2 = sb ? pg + RGF_B2 : nullptr, *b1 = sb ? pg + RGF_B1 : nullptr, *b0 = sb ? pg + RGF_B0 : nullptr;
   if (rt.runs_split(16))
-    pp_launch_wgrad_chain_s(scratch, acts + FLS, pg + RGF_W2, scratch + FLS, acts, pg + RGF_W1, scratch + 2 * FLS, feat, pg + RGF_W0,
-                            64, count, 1, capacity, st, rt.wgs, b2, b1, b0, ordered_part(rt, 1), nullptr);
+    rgb_wgrad_chain_s(feat, acts, scratch, count, capacity, pg, sb, st, rt.wgs, ordered_part(rt, 1));
   else
     pp_launch_wgrad_chain(scratch, acts + FLS, pg + RGF_W2, scratch + FLS, acts, pg + RGF_W1, scratch + 2 * FLS, feat, pg + RGF_W0,
                           64, count, 1, capacity, st, rt.wgs, b2, b1, b0);
 }
 
-extern "C" int pp_mlp_bwd(const float* params, const float* feat, int32_t in_ld, int32_t n_gemm, const float* acts,
-                          const float* out, const float* out_grad, const int32_t* count, int32_t capacity,
-                          float* scratch, float* params_grad, float* feat_grad, float* logit_add_grad,
-                          int32_t logit_add_ld, void* ctx, void* stream) {
+// may_defer (pp_rgbnet_bwd): inside a join scope the weight-gradient chain may be left to the next warp chain (wgrad_join_defer)
+static int pp_mlp_bwd_impl(const float* params, const float* feat, int32_t in_ld, int32_t n_gemm, const float* acts, const float* out,
+                           const float* out_grad, const int32_t* count, int32_t capacity, float* scratch, float* params_grad,
+                           float* feat_grad, float* logit_add_grad, int32_t logit_add_ld, void* ctx, void* stream, bool may_defer) {
   const MlpRoute rt(ctx);
   PP_REQUIRE(params && feat && acts && out && out_grad && count && scratch && params_grad, "null pointer");
   PP_REQUIRE(capacity > 0 && in_ld % 32 == 0 && in_ld <= 128 && n_gemm >= 1 && n_gemm <= 8, "bad sizes");
@@ -247,12 +322,21 @@ extern "C" int pp_mlp_bwd(const float* params, const float* feat, int32_t in_ld,
   if (in_ld == 64 && n_gemm == 3 && feat_grad && rt.fused) {
     const bool sb = rgb_bwd_stage1(rt, params, acts, out, out_grad, count, capacity, scratch, params_grad, feat_grad, logit_add_grad,
                                    logit_add_ld, st);
-    rgb_bwd_stage2(rt, feat, acts, scratch, count, capacity, params_grad, sb, st);
+    if (!(may_defer && wgrad_join_defer(ctx, rt, sb, feat, acts, scratch, count, capacity, params_grad, st)))
+      rgb_bwd_stage2(rt, feat, acts, scratch, count, capacity, params_grad, sb, st);
   } else
     pp_launch_mlp_layered_bwd(params, feat, in_ld, n_gemm, acts, out, out_grad, count, capacity, scratch, params_grad, feat_grad,
                               logit_add_grad, logit_add_ld, st);
   PP_CHECK_LAUNCH();
   return PP_OK;
+}
+
+extern "C" int pp_mlp_bwd(const float* params, const float* feat, int32_t in_ld, int32_t n_gemm, const float* acts,
+                          const float* out, const float* out_grad, const int32_t* count, int32_t capacity,
+                          float* scratch, float* params_grad, float* feat_grad, float* logit_add_grad,
+                          int32_t logit_add_ld, void* ctx, void* stream) {
+  return pp_mlp_bwd_impl(params, feat, in_ld, n_gemm, acts, out, out_grad, count, capacity, scratch, params_grad, feat_grad,
+                         logit_add_grad, logit_add_ld, ctx, stream, false);
 }
 
 // rgbnet of the Voxurf configuration = generic MLP with a 64-wide (57 used) input and three 128-wide layers.
@@ -265,8 +349,8 @@ extern "C" int pp_rgbnet_bwd(const float* params, const float* feat, const float
                              const float* rgb_grad, const int32_t* count, int32_t capacity, float* scratch,
                              float* params_grad, float* feat_grad, void* ctx, void* stream) {
   PP_REQUIRE(feat_grad, "null pointer");
-  return pp_mlp_bwd(params, feat, 64, 3, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, nullptr, 0,
-                    ctx, stream);
+  return pp_mlp_bwd_impl(params, feat, 64, 3, acts, rgb, rgb_grad, count, capacity, scratch, params_grad, feat_grad, nullptr, 0,
+                         ctx, stream, true);
 }
 
 extern "C" int pp_warp_fwd(const float* params, const float* pts, const int32_t* count, int32_t capacity,
@@ -294,10 +378,12 @@ extern "C" int pp_warp_bwd(const float* params, const float* pts, const float* a
   PP_REQUIRE(capacity > 0, "capacity<=0");
   PP_REQUIRE_ORDERED(rt, capacity, 2 | 16);
   hipStream_t st = pp_stream(stream);
+  // a pending rgbnet chain of this context (pp_wgrad_join_begin) rides in stage 2, or is launched on its own first
+  const bool ride = wgrad_join_rides(ctx, rt, acts, scratch, count, rt.runs_split(2), st);
   if (rt.fused) {
     // one fused data-gradient kernel (+ thin layers), then the three weight-gradient GEMMs on the Ybar it left behind
     const bool sb = warp_bwd_stage1(rt, params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st);
-    warp_bwd_stage2(rt, acts, scratch, count, capacity, params_grad, sb, st);
+    warp_bwd_stage2(rt, acts, scratch, count, capacity, params_grad, sb, st, ride ? static_cast<PPContext*>(ctx) : nullptr);
   } else
     pp_launch_warp_layered_bwd(params, pts, acts, out_grad, count, capacity, out_range, scratch, params_grad, pts_grad, st);
   PP_CHECK_LAUNCH();
@@ -333,7 +419,10 @@ extern "C" int pp_warp_bwd_weights(const float* acts, const float* scratch, cons
   if (!rt.fused) { pp_set_error("pp_warp_bwd_weights: option mlp_fused = 0 has no two-stage form"); return PP_ERR_UNSUPPORTED; }
   PP_REQUIRE_ORDERED(rt, capacity, 16);
   // who owns b1..b3 was decided by stage 1 and is handed over explicitly (never re-read from the options)
-  warp_bwd_stage2(rt, acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream));
+  // (a pending rgbnet chain of this context rides, or is launched on its own first: pp_wgrad_join_begin)
+  const bool ride = wgrad_join_rides(ctx, rt, acts, scratch, count, stage2 != 0, pp_stream(stream));
+  warp_bwd_stage2(rt, acts, scratch, count, capacity, params_grad, stage2 != 0, pp_stream(stream),
+                  ride ? static_cast<PPContext*>(ctx) : nullptr);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }

@@ -42,6 +42,11 @@ struct WgradLean {
 int pp_launch_wgrad_chain_s(const float* YA, const float* XA, float* WA, const float* YB, const float* XB, float* WB,
                             const float* YC, const float* XC, float* WC, int kxc, const int32_t* count, int rmul, int rcap,
                             hipStream_t st, int wgs, float* bA, float* bB, float* bC, float* part, const WgradLean* lean);
+// the weight gradients of both nets in one launch (k_wgrad_join_s; pp_wgrad_join_begin): warp3 = the warp net's three layers in
+// lean form (4 count rows, capacity rcap_w), rgb3 = rgbnet's (count rows, capacity rcap_r; rgb3[2] is the 64-wide input layer),
+// all with bias sums; float atomics only
+int pp_launch_wgrad_join_s(const WgradOperands* warp3, const WgradOperands* rgb3, const int32_t* count, int rcap_w, int rcap_r,
+                           hipStream_t st, int wgs_cu, const WgradLean& lean);
 // split-precision variants (pp_mlp_split.hip, option "mlp_split"): same contracts.  pack: the weight pack written by
 // pp_launch_mlp_pack FOR THESE params (pp_mlp_pack.h), or nullptr = the kernel derives the same quantities in its prologue.
 // part (backward kernels, weight-gradient chain): this launch's region of the ordered-flush workspace (pp_ordered.h) - the

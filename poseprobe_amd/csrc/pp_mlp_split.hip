@@ -1856,6 +1856,71 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_chain_s(WgradOperands LA, Wgra
   else wgs_layer<KXC, CSTEP, false>(L, Z.gate3, wls, layer, R, ntiles, wg, nwg, img, flags, slot);
 }
 
+// The weight gradients of BOTH object-branch MLPs in one launch (pp_wgrad_join_begin): six independent layers in one
+// grid of persistent work-groups, every work-group on ONE layer with the layer code of k_wgrad_chain_s unchanged - A, B, C: the
+// warp net's in lean form (R = 4 count rows), D, E: rgbnet's 128-wide layers, F: its 64-wide input layer (R = count rows).
+// nw / nd / nf: work-groups per warp layer / per 128-wide rgbnet layer / of the input layer, shared out by the host in proportion
+// to the layers' work.  rgbnet's work-groups come first in the grid (RGB_FIRST) or last.  No role reads what another writes; no
+// work-group waits for another.  Atomic flush only: a call with an ordered workspace keeps the two launches.
+constexpr bool WGJ_RGB_FIRST = true;                 // measured in one job: first 161.4 us, last 165.4 us
+struct WgradJoinLayers { WgradOperands L[6]; };      // A .. F; a work-group reads its own layer's only (one indexed kernarg load)
+template <bool RGB_FIRST>
+__global__ __launch_bounds__(256, 2) void k_wgrad_join_s(WgradJoinLayers A, const int32_t* __restrict__ count, int rcap_w, int rcap_r,
+                                                         int nw, int nd, int nf, WgradLean Z) {
+  __shared__ __attribute__((aligned(1024))) unsigned char img[4 * TILE_ROWS * 256];      // Yh | Yl | Xh | Xl
+  __shared__ __attribute__((aligned(16))) float2 flags[8];                                // [2 sets][4 wavefronts]
+  __shared__ __attribute__((aligned(16))) float wls[512];                                 // warp roles: W4 (layer A) or W0 (layer C)
+  const int cnt = count[0];
+  const int Rw = min(cnt * 4, rcap_w), Rr = min(cnt, rcap_r);
+  const int ntw = (Rw + TILE_ROWS - 1) / TILE_ROWS, ntr = (Rr + TILE_ROWS - 1) / TILE_ROWS;
+  // the half-grid rule of k_wgrad_chain_s, decided on the warp layers (their work-groups have the most tiles) for all six
+  if (ntw < 8 * nw) {
+    nw = max(nw / 2, 1);
+    nd = max(nd / 2, 1);
+    nf = max(nf / 2, 1);
+  }
+  const int n_warp = 3 * nw, n_rgb = 2 * nd + nf;
+  const int bx = blockIdx.x;
+  if (bx >= n_warp + n_rgb) return;
+  const bool rgb = RGB_FIRST ? bx < n_rgb : bx >= n_warp;
+  const int b = RGB_FIRST ? (rgb ? bx : bx - n_rgb) : (rgb ? bx - n_warp : bx);
+  if (!rgb) {
+    const int layer = b / nw, wg = b - layer * nw;
+    const WgradOperands L = A.L[layer];
+    if (layer == 0) { wls[threadIdx.x] = Z.w4[threadIdx.x]; wls[256 + threadIdx.x] = Z.w4[256 + threadIdx.x]; }
+    else if (layer == 2) { wls[threadIdx.x] = Z.w0[threadIdx.x]; if (threadIdx.x < 128) wls[256 + threadIdx.x] = Z.w0[256 + threadIdx.x]; }
+    __syncthreads();
+    wgs_layer<128, 4, true>(L, Z.gate3, wls, layer, Rw, ntw, wg, nw, img, flags, nullptr);
+  } else if (b < 2 * nd) {
+    const int layer = b / nd, wg = b - layer * nd;
+    const WgradOperands L = A.L[3 + layer];
+    wgs_layer<128, 1, false>(L, nullptr, wls, 1, Rr, ntr, wg, nd, img, flags, nullptr);
+  } else {
+    const WgradOperands L = A.L[5];
+    wgs_layer<64, 1, false>(L, nullptr, wls, 2, Rr, ntr, b - 2 * nd, nf, img, flags, nullptr);
+  }
+}
+
+int pp_launch_wgrad_join_s(const WgradOperands* warp3, const WgradOperands* rgb3, const int32_t* count, int rcap_w, int rcap_r,
+                           hipStream_t st, int wgs_cu, const WgradLean& lean) {
+  // work-groups per warp layer / 128-wide rgbnet layer / input layer, two per CU in all, in proportion to the layers' measured
+  // work: 10 : 10 : 10 : 4 : 4 : 3 of 41, rounded to nearest, the input layer taking what is left.  (By rows alone a warp layer
+  // would weigh 4 rgbnet layers; the lean layers read less per row, and every work-group pays one ramp and one flush - with
+  // 16 : 16 : 16 : 4 : 4 : 3 rgbnet's work-groups finished last and their sums were long enough to miss the accuracy bound of
+  // tests/test_hip_wgrad_join.py)
+  const int wgs = 2 * wgs_cu;
+  int nw = (wgs * 10 + 20) / 41, nd = (wgs * 4 + 20) / 41, nf = wgs - 3 * nw - 2 * nd;
+  if (nf < 1) nf = 1;
+  const int ntw = pp_div_up(rcap_w, TILE_ROWS), ntr = pp_div_up(rcap_r, TILE_ROWS);
+  if (nw > ntw) nw = ntw;
+  if (nd > ntr) nd = ntr;
+  if (nf > ntr) nf = ntr;
+  const WgradJoinLayers A{{warp3[0], warp3[1], warp3[2], rgb3[0], rgb3[1], rgb3[2]}};
+  hipLaunchKernelGGL((k_wgrad_join_s<WGJ_RGB_FIRST>), dim3(3 * nw + 2 * nd + nf), dim3(256), 0, st, A, count, rcap_w, rcap_r, nw, nd,
+                     nf, lean);
+  return 0;
+}
+
 // Ordered flush of k_wgrad_chain_s: grid (65, 3) - blockIdx.y = layer, blockIdx.x = 64 consecutive float4s of the layer's block
 // (64 of them at KX = 128, 32 at KX = 64), block 64 = the 128 bias sums.  The rows of a layer are the slots of its work-groups in
 // ascending order; how many took part is derived from `count` exactly as the chain kernel does, on the device.

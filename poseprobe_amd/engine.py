@@ -252,7 +252,7 @@ class RenderCore:
             raise ValueError('an ordered RenderCore needs its own context (the workspace is attached to it)')
 
     @contextlib.contextmanager
-    def pass_scope(self, flat, pack, lean_ws=None, pack_with=None):
+    def pass_scope(self, flat, pack, lean_ws=None, pack_with=None, join_wgrad=False):
         """One render pass: the MLP weights of `flat` are packed into `pack` HERE, on the pass's stream, and the record is dropped when
         the pass's kernels are enqueued - also when the pass raises.  Every writer of the parameters (the optimiser, a checkpoint
         load, an in-place copy from outside) runs between two scopes, so no kernel can read a pack older than its parameters.
@@ -260,8 +260,14 @@ class RenderCore:
         step's ops.step_begin) - called in place of ops.mlp_pack.
         lean_ws: the Workspace whose warp_acts / scratch the pass differentiates through - a lean scope of the warp net, closed with
         the pack record: the forward kernel leaves out the tangent rows of X0, the data-gradient kernel Ybar3, and the
-        weight-gradient kernel rebuilds both (option warp_lean)."""
+        weight-gradient kernel rebuilds both (option warp_lean).
+        join_wgrad (the train step's default path): a join scope of the weight gradients (ops.wgrad_join_begin) inside the lean scope -
+        rgbnet_bwd leaves its weight-gradient chain to the launch of warp_bwd / warp_bwd_weights.  Nothing between the
+        two may write ws.feat, ws.rgb_acts or ws.scratch_rgb.  A chain nobody took is launched when the scope closes, or dropped
+        when the pass raised."""
         lean = lean_ws is not None and lean_ws.warp_acts is not None
+        join = bool(join_wgrad) and lean
+        raised = True
         try:
             if pack_with is not None:
                 pack_with()
@@ -269,9 +275,14 @@ class RenderCore:
                 ops.mlp_pack(flat.view('warp'), flat.view('rgbnet'), pack, self.ctx)
             if lean:
                 ops.warp_lean_begin(lean_ws.warp_acts, lean_ws.scratch, flat.view('warp'), self.ctx)
+            if join:
+                ops.wgrad_join_begin(self.ctx)
             yield
+            raised = False
         finally:
             ops.mlp_pack_invalidate(self.ctx)
+            if join:
+                ops.wgrad_join_end(self.ctx, launch_pending=not raised)
             if lean:
                 ops.warp_lean_end(self.ctx)
 
@@ -369,10 +380,12 @@ class TrainEngine:
     def __init__(self, cfg: SceneConfig, n_views, H, W, n_rand, device='cuda', lr_pose=1e-3, lr_pose_end=1e-4,
                  pose_iters=1, lrate_decay=10, loss_scale=0.1, weight_main=1.0, weight_tv_k0=0.01, weight_mask=0.1,
                  fix_first=True, capacity=None, x_slab=None, dist_ctx=None, deterministic_scatter=False, options=None,
-                 deterministic=False, reproj_rows=0, fuse_head=True, fuse_rays=True):
+                 deterministic=False, reproj_rows=0, fuse_head=True, fuse_rays=True, fuse_wgrad=True):
         """fuse_head / fuse_rays (default path only, see `side_by_side`): the step starts with ONE launch (ops.step_begin: pose forward,
         step scalars, zero block, weight pack) / composites, evaluates the ray losses and differentiates the composite in ONE launch
         (ops.march_loss_bwd) - DESIGN 17.  False: the separate launches (A/B runs, tests); also plain attributes of the engine.
+        fuse_wgrad (default path only, as the two above): the hidden layers' weight gradients of rgbnet ride in the launch of the warp
+        net's (pass_scope(join_wgrad=True)).  False: the two launches.
         reproj_rows: row capacity of the engine-native reprojection pass (`reprojection_grads`); each row is one ray of a second
         Workspace(reproj_rows, reproj_rows * n_samples).  0 (default): no second workspace, nothing changes.
         deterministic: bit-reproducible train step.  Implies deterministic_scatter and additionally replaces every other
@@ -438,7 +451,7 @@ class TrainEngine:
         # train step on the default path: the optimiser launch carries the ray / pose backward (ops._tail_args).  Its last ray
         # work-group leaves c2w_grad and this arrival counter zero again; _c2w_clean = both are zero now
         self.tail_arrive = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        self.fuse_head, self.fuse_rays = bool(fuse_head), bool(fuse_rays)
+        self.fuse_head, self.fuse_rays, self.fuse_wgrad = bool(fuse_head), bool(fuse_rays), bool(fuse_wgrad)
         # partial loss rows + arrival ticket of the fused ray launch; None: a ray may have more samples than that kernel holds -
         # the step then keeps march_fwd / loss_rays / march_bwd
         self.ray_work = None
@@ -609,7 +622,7 @@ class TrainEngine:
             ops.pose_fwd(self.se3, self.w2c_init, self.refine_mask, self.w2c, self.c2w, self.jac)
             rays_and_samples()
             self._upload_step_scalars(progress)
-        with self.core.pass_scope(P, self.mlp_pack, ws, pack_with=head):
+        with self.core.pass_scope(P, self.mlp_pack, ws, pack_with=head, join_wgrad=self.side_by_side and self.fuse_wgrad):
             if head is not None:
                 rays_and_samples()          # behind the head launch, which the scope has just issued
             self.core.forward(ws, self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), inv_s, self.pe_w,

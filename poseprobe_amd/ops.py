@@ -317,6 +317,18 @@ def warp_lean_end(ctx=None):
     _lib.call('pp_warp_lean_end', _h(ctx))
 
 
+def wgrad_join_begin(ctx=None):
+    """Open a join scope of the weight gradients (pp_wgrad_join_begin): until wgrad_join_end, rgbnet_bwd called with `ctx` leaves
+    its weight-gradient chain as a record in the context, and the next warp_bwd / warp_bwd_weights with `ctx`, the same `count`
+    tensor and the same stream carries it in its own launch; whatever cannot be joined is launched as outside the scope."""
+    _lib.call('pp_wgrad_join_begin', _h(ctx))
+
+
+def wgrad_join_end(ctx=None, launch_pending=True):
+    """Close the scope; a record nobody took is launched on its own, or dropped with launch_pending=False (the pass raised)."""
+    _lib.call('pp_wgrad_join_end', _h(ctx), int(bool(launch_pending)))
+
+
 def rgbnet_fwd(params, feat, count, capacity, acts, rgb, ctx=None):
     _lib.call('pp_rgbnet_fwd', _f(params), _f(feat), _i(count), capacity, _f(acts), _f(rgb), _h(ctx), _stream())
 
