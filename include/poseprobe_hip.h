@@ -46,7 +46,7 @@ const char* pp_last_error(void);
  * pp_scene gained `sdf_index_exact`; new: pp_sdf_crossing_dense_bwd, pp_context_set_option / pp_context_get_option.  4 (this header): the
  * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
  * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_mc_* group, the pp_pnp_* group,
- * the pp_dtu_* group, pp_step_begin, pp_march_loss_bwd / pp_march_loss_workspace.
+ * the pp_dtu_* group, the pp_ssim_* group, pp_step_begin, pp_march_loss_bwd / pp_march_loss_workspace.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
  * (poseprobe_amd/_lib.py does): the signatures changed, so a stale caller would pass a stream where a pointer is read. */
 #define PP_ABI_VERSION 4
@@ -819,6 +819,29 @@ int pp_dtu_thin_rounds(const float* points, const int64_t* keys, const int32_t* 
 int pp_dtu_nearest(const float* queries, int32_t Q, const float* points, const int64_t* keys, const int32_t* order, int32_t P, float ox,
                    float oy, float oz, float edge, int32_t nx, int32_t ny, int32_t nz, float max_dist, float* d2, int32_t* idx,
                    void* stream);
+
+/* ---------------------------------------------------------------- image score: SSIM
+ * lib/utils.py:792-838 (rgb_ssim) on device-resident image pairs: img0, img1 [V,H,W,C] fp32, contiguous, channels
+ * last, 1 <= C <= 4.  The 1-D filter f_k = exp(-0.5 ((k - hw + shift) / filter_sigma)^2) / sum, hw = filter_size / 2 (integer),
+ * shift = (2 hw - filter_size + 1) / 2, is computed on the host in fp64 and handed to the kernel by value (no upload, no copy in the stream).
+ * Per channel the five images x, y, x x, y y, x y are blurred separably in `valid` mode, which leaves a map of
+ * (H - filter_size + 1) x (W - filter_size + 1) x C values
+ *   mu0 = B x, mu1 = B y, s00 = max(0, B xx - mu0^2), s11 = max(0, B yy - mu1^2), s01 = B xy - mu0 mu1 limited to
+ *   sign(s01) min(sqrt(s00 s11), |s01|), c1 = (k1 max_val)^2, c2 = (k2 max_val)^2,
+ *   ((2 mu0 mu1 + c1) (2 s01 + c2)) / ((mu0^2 + mu1^2 + c1) (s00 + s11 + c2)),
+ * computed in fp64 from the fp32 inputs.  ssim [V] (DEVICE) receives the mean of each view's map; map (optional,
+ * [V, H - fs + 1, W - fs + 1, C] fp32) the map, rounded once.  One work-group per tile of pp_ssim_tile x pp_ssim_tile map pixels
+ * writes its fp64 sum to its own slot of `work` (pp_ssim_workspace, a pure host function: 8 bytes per tile and view, 8-byte
+ * aligned) and a second kernel adds a view's slots in a fixed order: no atomics, no allocation, no host read, and a view's value
+ * does not depend on the batch it is in, bit for bit.  Indexing is 64-bit; V times the tiles of a view must stay below 2^31
+ * (PP_ERR_UNSUPPORTED beyond).  Both refuse, before any GPU call: null pointers (except map), V < 1, C outside 1..4, filter_size
+ * outside 1..33, H or W below filter_size, a non-finite or non-positive filter_sigma / max_val, non-finite k1 / k2, a workspace
+ * that is too small or misaligned. */
+int pp_ssim_tile(int32_t* tile);
+int pp_ssim_workspace(int32_t V, int32_t H, int32_t W, int32_t filter_size, int64_t* bytes);
+int pp_ssim(const float* img0, const float* img1, int32_t V, int32_t H, int32_t W, int32_t C, int32_t filter_size,
+            double filter_sigma, double max_val, double k1, double k2, void* work, int64_t work_bytes, float* ssim, float* map,
+            void* stream);
 
 #ifdef __cplusplus
 }

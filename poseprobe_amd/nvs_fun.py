@@ -4,8 +4,9 @@ per-ray outputs assembled into images (`rgb_marched`, `disp`, `alphainv_cum`, `n
 (full image, foreground, background, as the reference logs them), optional files.
 
 Same call signature and return value (`rgbs [V,H,W,3]`, `disps [V,H,W,1]` as numpy) so that `run.py`-style callers work
-unchanged; the metrics of the last call are kept in `render_viewpoints.last` (the reference only prints them).  SSIM / LPIPS
-need networks that cannot exist offline (lib/utils.py rgb_lpips fetches AlexNet / VGG weights): requesting them raises.
+unchanged; the metrics of the last call are kept in `render_viewpoints.last` (the reference only prints them).  Requesting
+SSIM / LPIPS here raises: SSIM (and the PSNRs, on the device) come from `evaluation.evaluate_viewpoints` / `evaluation.rgb_ssim`;
+LPIPS needs network weights that are not part of this repository (lib/utils.py rgb_lpips fetches AlexNet / VGG).
 Images are written as PNG by a 20-line encoder (zlib) - imageio is not a dependency.
 """
 import os
@@ -79,8 +80,9 @@ def render_viewpoints(model, render_poses, cfg, HW, Ks, ndc, render_kwargs, gt_i
                       step=0, rgb_only=False):
     """render_poses [V,3|4,4] world-to-camera (inverted here, as at lib/nvs_fun.py:47)."""
     if eval_ssim or eval_lpips_alex or eval_lpips_vgg:
-        raise NotImplementedError('render_viewpoints: SSIM / LPIPS (lib/utils.py rgb_ssim, rgb_lpips) need network weights '
-                                  'that are fetched online; compute them outside with the returned images')
+        raise NotImplementedError('render_viewpoints: for SSIM use evaluation.evaluate_viewpoints (same views, scored on the device) '
+                                  'or evaluation.rgb_ssim on the returned images; LPIPS (lib/utils.py rgb_lpips) needs network '
+                                  'weights that are not part of this repository')
     dev = next(model.parameters()).device
     poses = torch.as_tensor(np.asarray(render_poses.cpu() if isinstance(render_poses, torch.Tensor) else render_poses),
                             dtype=torch.float32)

@@ -852,3 +852,38 @@ def dtu_nearest(queries, points, keys, order, grid, max_dist, d2, idx):
             raise RuntimeError(f'{name}: {t.numel()} elements, {Q} expected')
     _lib.call('pp_dtu_nearest', _f(queries, 'queries'), Q, _f(points, 'points'), _ptr(keys, torch.int64, 'keys'), _i(order, 'order'), P,
               *_dtu_grid(grid), ctypes.c_float(max_dist), _f(d2, 'd2'), _i(idx, 'idx'), _stream())
+
+
+# ------------------------------------------------------------------------------------------- image score (SSIM)
+def ssim_tile():
+    """Edge of the output tile one work-group of pp_ssim takes (a pure host call)."""
+    t = ctypes.c_int32()
+    _lib.call('pp_ssim_tile', ctypes.byref(t))
+    return t.value
+
+
+def ssim_workspace(V, H, W, filter_size):
+    """Bytes of device workspace pp_ssim needs for V views of H x W (a pure host call)."""
+    b = ctypes.c_int64()
+    _lib.call('pp_ssim_workspace', int(V), int(H), int(W), int(filter_size), ctypes.byref(b))
+    return b.value
+
+
+def ssim(img0, img1, max_val, filter_size, filter_sigma, k1, k2, work, out, ssim_map=None):
+    """img0, img1 [V,H,W,C] fp32 -> out [V] fp32: the mean SSIM of every view (lib/utils.py rgb_ssim); ssim_map (optional)
+    [V, H - fs + 1, W - fs + 1, C] fp32 receives the map.  work: uint8 [ssim_workspace(...)]."""
+    V = H = W = C = 0
+    if img0 is not None:
+        if img0.dim() != 4:
+            raise RuntimeError('img0 must be [V,H,W,C]')
+        V, H, W, C = (int(x) for x in img0.shape)
+    if img1 is not None and img0 is not None and img1.shape != img0.shape:
+        raise RuntimeError(f'img1: shape {tuple(img1.shape)}, {tuple(img0.shape)} expected')
+    if out is not None and out.numel() != V:
+        raise RuntimeError(f'out: {out.numel()} elements, {V} expected')
+    fs = int(filter_size)
+    if ssim_map is not None and ssim_map.numel() != V * max(H - fs + 1, 0) * max(W - fs + 1, 0) * C:
+        raise RuntimeError(f'ssim_map: {ssim_map.numel()} elements, [{V},{H - fs + 1},{W - fs + 1},{C}] expected')
+    _lib.call('pp_ssim', _f(img0, 'img0'), _f(img1, 'img1'), V, H, W, C, fs, ctypes.c_double(filter_sigma), ctypes.c_double(max_val),
+              ctypes.c_double(k1), ctypes.c_double(k2), _u8(work, 'work'), 0 if work is None else int(work.numel()), _f(out, 'out'),
+              _f(ssim_map, 'ssim_map'), _stream())

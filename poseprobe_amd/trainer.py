@@ -385,6 +385,17 @@ class DualBranchTrainer:
             self.nerf_fine.progress.data.fill_(p)
         return out
 
+    def pose_error(self, pose_GT_w2c):
+        """Rotation (degrees) / translation (x 100) error of the active views' current poses against pose_GT_w2c [>= k,3,4] after
+        aligning them to it (evaluation.evaluate_poses; the number lib/recon_scene.py:664-668 logs): -> (error, aligned, sim3).
+        Not part of train_step; it refreshes the engine's w2c from the pose parameters, as the head of the next step does."""
+        from . import evaluation, ops
+        e = self.joint.obj
+        k = e.V if self.n_active is None else self.n_active
+        ops.pose_fwd(e.se3, e.w2c_init, e.refine_mask, e.w2c, e.c2w, e.jac)
+        GT = torch.as_tensor(pose_GT_w2c)
+        return evaluation.evaluate_poses(e.w2c[:k].detach(), GT[:k, :3])
+
     # ---- `model_last.pth.tar` (renderer.py:1028-1051 save_snapshot, recon_scene.py:827-838 load) ----------------------------
     def _adam_state_dict(self):
         """torch.optim.Adam.state_dict() layout over [nerf.parameters(), nerf_fine.parameters()] (lib/utils.py:294-299)."""
