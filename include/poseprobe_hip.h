@@ -605,6 +605,15 @@ int pp_nerf_bwd(const float* params, const float* ray, const float* depth, const
                 int32_t n_samples, const float* acts, const float* rgb_samples,
                 const float* g_rgb_samples, const float* g_density_samples, float* scratch, float* params_grad,
                 float* g_center, float* g_ray, void* ctx, void* stream);
+/* Backward of pp_nerf_fwd with respect to the rays only (frozen parameters: test-time pose refinement): the launches of
+ * pp_nerf_bwd without its nine weight-gradient products, in both routes of option nerf_chain and both arithmetics.  g_center and
+ * g_ray are bit-identical to pp_nerf_bwd's on the same inputs; no parameter gradient exists (the two thin heads' sums, whose
+ * kernels also record operand maxima the later kernels read, are added into a part of `scratch` that this route leaves
+ * unread).  Same workspaces as pp_nerf_bwd (pp_nerf_workspace is unchanged).  A workspace attached with
+ * pp_nerf_ordered_attach is neither used nor refused: nothing is flushed. */
+int pp_nerf_bwd_input(const float* params, const float* ray, const float* depth, const int32_t* count, int32_t n_rays,
+                      int32_t n_samples, const float* acts, const float* rgb_samples, const float* g_rgb_samples,
+                      const float* g_density_samples, float* scratch, float* g_center, float* g_ray, void* ctx, void* stream);
 /* composite (:290-343): rgb[R,3] (+ 1 - opacity when white_bg), depth[R], opacity[R], weights[R,S], all_cumulated[R]
  * (= T at the second-to-last sample), rgb_var[R], depth_var[R] (the two variances are forward-only outputs). */
 int pp_nerf_composite_fwd(const float* rgb_samples, const float* density_samples, const float* depth, const float* ray,
@@ -623,6 +632,17 @@ int pp_nerf_band_weights(const float* progress, float start, float width, int32_
  * 'mean') over n floats, g_pred[n] = d loss / d pred.  Deterministic (one work-group, fixed summation order). */
 int pp_nerf_huber_loss(const float* pred, const float* label, int32_t n, float delta, float weight, float* loss, float* g_pred,
                        void* stream);
+/* The two per-iteration pieces of test-time pose refinement (eval.py:838-858) beside the network (csrc/pp_pose_refine.hip).
+ * pp_nerf_rays_select: the rays and targets of n_rays chosen pixels of ONE view (utils/camera.py:347-416 + the target gather of
+ * eval.py:851-852).  ray_idx[n_rays] in [0, H * W) indexes the row-major pixels (the caller guarantees the range; an index outside it is clamped, so no read leaves the image); pixel centre
+ * (idx % W + 0.5, idx / W + 0.5); dir_cam = K^-1 [x, y, 1] by the closed form for an UPPER-TRIANGULAR K[3,3] with K[2][2] = 1
+ * (skew K[0][1] included; the caller checks the form); ray = R dir_cam (un-normalised) and center = t of c2w[3,4] = [R | t];
+ * target = image[H,W,3] at the pixel.  c2w, K and image are device memory.  Outputs [n_rays,3] each, overwritten.
+ * pp_nerf_mse_loss: loss[0] = weight * mean((pred - label)^2) over n floats (F.mse_loss, eval.py:853), g_pred[n] its gradient.
+ * Deterministic (one work-group, strided partial sums, then a tree with fixed pairs, as pp_nerf_huber_loss). */
+int pp_nerf_rays_select(const float* c2w, const float* K, const int32_t* ray_idx, int32_t n_rays, int32_t H, int32_t W,
+                        const float* image, float* center, float* ray, float* dir_cam, float* target, void* stream);
+int pp_nerf_mse_loss(const float* pred, const float* label, int32_t n, float weight, float* loss, float* g_pred, void* stream);
 
 /* SPARF correspondence loss on rendered depths (lib/bg_nerf/source/training/core/corres_loss.py:93-222, the re-projection of
  * batched_geometry_utils.py:199-228 and the Huber term of base_losses.py:197-224), forward and backward in one launch.

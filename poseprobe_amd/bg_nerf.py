@@ -384,7 +384,11 @@ class SceneRenderer:
     the coarse samples and inverse-transform samples of the coarse weights.  Returns the same keys (`*_fine` for the second
     pass).  `rand` (optional) replays recorded uniform draws: [coarse [B, N, S, 1], fine grid [Nf + 1]]."""
 
-    def __init__(self, opt, device='cuda'):
+    def __init__(self, opt, device='cuda', nerf=None, nerf_fine=None):
+        """nerf (and nerf_fine): render with these existing networks instead of building new ones (their device is used)."""
+        if nerf is not None:
+            self.opt, self.device, self.nerf, self.nerf_fine = opt, nerf.flat.device, nerf, nerf_fine
+            return
         self.opt, self.device = opt, torch.device(device)
         self.nerf = NeRF(opt, device=device)
         self.nerf_fine = NeRF(opt, is_fine_network=True, device=device) if opt.nerf.fine_sampling else None

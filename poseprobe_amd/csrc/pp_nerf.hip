@@ -819,18 +819,19 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
   return PP_OK;
 }
 
-extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* depth, const int32_t* count,
-                           int32_t n_rays, int32_t n_samples, const float* acts, const float* rgb_samples, const float* g_rgb_samples,
-                           const float* g_density_samples, float* scratch, float* params_grad, float* g_center, float* g_ray,
-                           void* ctx, void* stream) {
+// Host body of pp_nerf_bwd and pp_nerf_bwd_input.  input_only: the backward with respect to the rays alone - the nine
+// weight-gradient products are not launched and params_grad is not touched (it may be NULL); every other launch is the one
+// pp_nerf_bwd issues, so g_center / g_ray are the same bits.  The two thin heads' k_nerf_part_finish launches stay: they also
+// record the operand maxima (MX_DH, MX_P) that the split-precision data-gradient kernels read afterwards.  Their parameter sums
+// then land in a discard area of 657 floats inside `scratch` that no kernel of this route reads: the transposed copy of W1 when
+// the fused chain runs (the chain reads its weights straight from the parameters), else the chain's d(layer 0) block.
+static void nerf_bwd_body(const float* params, const float* ray, const float* depth, const int32_t* count, int32_t n_rays,
+                         int32_t n_samples, const float* acts, const float* rgb_samples, const float* g_rgb_samples,
+                         const float* g_density_samples, float* scratch, float* params_grad, float* g_center, float* g_ray,
+                         bool input_only, void* ctx, void* stream) {
   const NerfRoute rt(pp_options(ctx));
-  PP_REQUIRE(params && ray && depth && count && acts && rgb_samples && g_rgb_samples && g_density_samples && scratch &&
-                 params_grad && g_center && g_ray, "null pointer");
-  PP_REQUIRE(n_rays > 0 && n_samples > 0 && (int64_t)n_rays * n_samples < (1LL << 30), "bad sizes");
   hipStream_t st = pp_stream(stream);
   float* ord = ctx ? static_cast<const PPContext*>(ctx)->nerf_ord : nullptr;
-  PP_REQUIRE(!ord || rt.split, "an ordered-flush workspace is attached (pp_nerf_ordered_attach) and nerf_split = 0 selects the "
-                                 "fp32-instruction weight-gradient kernel, which has no ordered flush");
   const int R = n_rays, S = n_samples, M = R * S;
   const NerfLayout L = nerf_layout();
   NerfActs A = nerf_acts(const_cast<float*>(acts), M);
@@ -871,6 +872,16 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
   const bool chain = rt.chain_bwd;
   float* DY[7];                                    // d(pre-activation of layer l), l = 0 .. 6, for the fused chain
   for (int l = 0; l < 7; ++l) DY[l] = part + NERF_PART_FLOATS + (size_t)l * M * 256;
+  // where k_nerf_part_finish adds the heads' parameter sums: R1 | br1 | wd | bd
+  float* discard = chain ? WT[1] : DY[0];          // input_only: 65536 / at least 7 x 256 floats that this route leaves unread
+  float* g_r1 = input_only ? discard : params_grad + L.r1;
+  float* g_br1 = input_only ? discard + 384 : params_grad + L.br1;
+  float* g_wd = input_only ? discard + 400 : params_grad + L.wd;
+  float* g_bd = input_only ? discard + 656 : params_grad + L.bd;
+  auto gemm_tn = [&](const float* Y, int ldy, int N, const float* X, int ldx, int Kx, int64_t w_off, int64_t b_off, const float* y_max,
+                     const float* x_max) {
+    if (!input_only) nerf_gemm_tn(st, rt.split, Y, ldy, N, X, ldx, Kx, params_grad + w_off, params_grad + b_off, count, M, y_max, x_max, ord);
+  };
   if (chain) {
     // the chain's weights in its order of use, read transposed straight from the parameters: R0 (rows = hidden units), W7 .. W1
     TrunkPackJobs J;
@@ -893,10 +904,10 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
   {
     const int wgs = min(pp_div_up(M, NERF_STRIP), NERF_PART_WGS);
     hipLaunchKernelGGL(k_nerf_rgb_bwd, dim3(wgs), dim3(512), 0, st, params + L.r1, A.h, rgb_samples, g_rgb_samples, M, dH, part);
-    hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(388, 64)), dim3(1024), 0, st, part, wgs, params_grad + L.r1, 384, params_grad + L.br1, 3,
+    hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(388, 64)), dim3(1024), 0, st, part, wgs, g_r1, 384, g_br1, 3,
                        slot(MX_DH));
   }
-  nerf_gemm_tn(st, rt.split, dH, 128, 128, A.a[7], 288, 288, params_grad + L.r0, params_grad + L.br0, count, M, slot(MX_DH), slot(MX_A0 + 7), ord);
+  gemm_tn(dH, 128, 128, A.a[7], 288, 288, L.r0, L.br0, slot(MX_DH), slot(MX_A0 + 7));
   hipLaunchKernelGGL(k_nerf_ray_sum, dim3(R < 512 ? R : 512), dim3(512), 0, st, dH, R, S, dHsum, slot(MX_DHSUM));
   nerf_gemm<EPI_PLAIN>(st, rt.split, dHsum, 128, R0T + 256 * 128, 128, 128, 32, nullptr, nullptr, 0, dView, 32, count, R, slot(MX_DHSUM),
                        slot(MX_R0), nullptr);
@@ -905,7 +916,7 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
     {
       const int wgs = min(pp_div_up(M, NERF_DSTRIP), NERF_PART_WGS);
       hipLaunchKernelGGL(k_nerf_density_bwd, dim3(wgs), dim3(512), 0, st, A.a[6], A.raw, g_density_samples, M, P, part);
-      hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(258, 64)), dim3(1024), 0, st, part, wgs, params_grad + L.wd, 256, params_grad + L.bd, 1,
+      hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(258, 64)), dim3(1024), 0, st, part, wgs, g_wd, 256, g_bd, 1,
                          slot(MX_P));
     }
     // d(layer 7) .. d(layer 0) in one kernel (pp_nerf_trunk.h), each written once for the weight-gradient products below
@@ -927,14 +938,12 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
       const int tiles = pp_div_up(M, 128);
       hipLaunchKernelGGL((k_nerf_trunk<true, true, 8>), dim3(tiles < cus ? tiles : cus), dim3(512), 0, st, T, count, M);
     }
-    nerf_gemm_tn(st, rt.split, P, 288, 256, A.a[6], 256, 256, params_grad + L.w[7], params_grad + L.b[7], count, M, slot(MX_P), slot(MX_A0 + 6), ord);
+    gemm_tn(P, 288, 256, A.a[6], 256, 256, L.w[7], L.b[7], slot(MX_P), slot(MX_A0 + 6));
     for (int l = 6; l >= 1; --l)
-      nerf_gemm_tn(st, rt.split, DY[l], 256, 256, A.a[l - 1], NERF_OUT_LD[l - 1], NERF_IN_LD[l], params_grad + L.w[l], params_grad + L.b[l], count, M,
-                   slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1), ord);
+      gemm_tn(DY[l], 256, 256, A.a[l - 1], NERF_OUT_LD[l - 1], NERF_IN_LD[l], L.w[l], L.b[l], slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1));
     nerf_gemm<EPI_PLAIN>(st, rt.split, DY[4], 256, WT[4] + 256 * 256, 256, 256, 64, nullptr, nullptr, 0, dEncS, 64, count, M,
                          slot(MX_DY6 + 2), slot(MX_W0 + 4), nullptr);
-    nerf_gemm_tn(st, rt.split, DY[0], 256, 256, A.enc, 64, 64, params_grad + L.w[0], params_grad + L.b[0], count, M, slot(MX_DY6 + 6),
-                 slot(MX_ENC), ord);
+    gemm_tn(DY[0], 256, 256, A.enc, 64, 64, L.w[0], L.b[0], slot(MX_DY6 + 6), slot(MX_ENC));
     nerf_gemm<EPI_PLAIN>(st, rt.split, DY[0], 256, WT[0], 256, 256, 64, nullptr, nullptr, 0, dEnc0, 64, count, M, slot(MX_DY6 + 6),
                          slot(MX_W0), nullptr);
   } else {
@@ -944,10 +953,10 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
     {
       const int wgs = min(pp_div_up(M, NERF_DSTRIP), NERF_PART_WGS);
       hipLaunchKernelGGL(k_nerf_density_bwd, dim3(wgs), dim3(512), 0, st, A.a[6], A.raw, g_density_samples, M, P, part);
-      hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(258, 64)), dim3(1024), 0, st, part, wgs, params_grad + L.wd, 256, params_grad + L.bd, 1,
+      hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(258, 64)), dim3(1024), 0, st, part, wgs, g_wd, 256, g_bd, 1,
                          slot(MX_P));
     }
-    nerf_gemm_tn(st, rt.split, P, 288, 256, A.a[6], 256, 256, params_grad + L.w[7], params_grad + L.b[7], count, M, slot(MX_P), slot(MX_A0 + 6), ord);
+    gemm_tn(P, 288, 256, A.a[6], 256, 256, L.w[7], L.b[7], slot(MX_P), slot(MX_A0 + 6));
     nerf_gemm<EPI_MASK>(st, rt.split, P, 288, WT[7], 288, 288, 256, nullptr, A.a[6], 256, Q, 256, count, M, slot(MX_P), slot(MX_W0 + 7),
                         slot(MX_DY6), A.bits[6], wt7_img);
     float* cur = Q;
@@ -955,8 +964,7 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
     for (int l = 6; l >= 1; --l) {                   // cur = d(pre-activation of layer l), [M][256]
       const float* x = A.a[l - 1];
       const int ldx = NERF_OUT_LD[l - 1];            // 320 for layer 4's input (features + skip columns)
-      nerf_gemm_tn(st, rt.split, cur, 256, 256, x, ldx, NERF_IN_LD[l], params_grad + L.w[l], params_grad + L.b[l], count, M,
-                   slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1), ord);
+      gemm_tn(cur, 256, 256, x, ldx, NERF_IN_LD[l], L.w[l], L.b[l], slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1));
       nerf_gemm<EPI_MASK>(st, rt.split, cur, 256, WT[l], 256, 256, 256, nullptr, x, ldx, nxt, 256, count, M, slot(MX_DY6 + 6 - l),
                           slot(MX_W0 + l), slot(MX_DY6 + 7 - l), A.bits[l - 1], wt_img[l]);
       if (l == 4)                                    // skip columns: gradient of the encoding, no activation in between
@@ -964,13 +972,41 @@ extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* d
                              slot(MX_DY6 + 2), slot(MX_W0 + 4), nullptr);
       float* t = cur; cur = nxt; nxt = t;
     }
-    nerf_gemm_tn(st, rt.split, cur, 256, 256, A.enc, 64, 64, params_grad + L.w[0], params_grad + L.b[0], count, M, slot(MX_DY6 + 6),
-                 slot(MX_ENC), ord);
+    gemm_tn(cur, 256, 256, A.enc, 64, 64, L.w[0], L.b[0], slot(MX_DY6 + 6), slot(MX_ENC));
     nerf_gemm<EPI_PLAIN>(st, rt.split, cur, 256, WT[0], 256, 256, 64, nullptr, nullptr, 0, dEnc0, 64, count, M, slot(MX_DY6 + 6),
                          slot(MX_W0), nullptr);
   }
   hipLaunchKernelGGL(k_nerf_encode_bwd, dim3(R), b, 0, st, A.enc, dEnc0, dEncS, dView, A.a[7], ray, depth, R, S, g_center,
                      g_ray);
+}
+
+extern "C" int pp_nerf_bwd(const float* params, const float* ray, const float* depth, const int32_t* count,
+                           int32_t n_rays, int32_t n_samples, const float* acts, const float* rgb_samples, const float* g_rgb_samples,
+                           const float* g_density_samples, float* scratch, float* params_grad, float* g_center, float* g_ray,
+                           void* ctx, void* stream) {
+  PP_REQUIRE(params && ray && depth && count && acts && rgb_samples && g_rgb_samples && g_density_samples && scratch &&
+                 params_grad && g_center && g_ray, "null pointer");
+  PP_REQUIRE(n_rays > 0 && n_samples > 0 && (int64_t)n_rays * n_samples < (1LL << 30), "bad sizes");
+  const float* ord = ctx ? static_cast<const PPContext*>(ctx)->nerf_ord : nullptr;
+  PP_REQUIRE(!ord || NerfRoute(pp_options(ctx)).split,
+             "an ordered-flush workspace is attached (pp_nerf_ordered_attach) and nerf_split = 0 selects the "
+             "fp32-instruction weight-gradient kernel, which has no ordered flush");
+  nerf_bwd_body(params, ray, depth, count, n_rays, n_samples, acts, rgb_samples, g_rgb_samples, g_density_samples, scratch, params_grad,
+                g_center, g_ray, false, ctx, stream);
+  PP_CHECK_LAUNCH();
+  return PP_OK;
+}
+
+extern "C" int pp_nerf_bwd_input(const float* params, const float* ray, const float* depth, const int32_t* count,
+                                 int32_t n_rays, int32_t n_samples, const float* acts, const float* rgb_samples,
+                                 const float* g_rgb_samples, const float* g_density_samples, float* scratch, float* g_center,
+                                 float* g_ray, void* ctx, void* stream) {
+  PP_REQUIRE(params && ray && depth && count && acts && rgb_samples && g_rgb_samples && g_density_samples && scratch && g_center &&
+                 g_ray, "null pointer");
+  PP_REQUIRE(n_rays > 0 && n_samples > 0 && (int64_t)n_rays * n_samples < (1LL << 30), "bad sizes");
+  // (an attached ordered-flush workspace is neither read nor refused: no weight gradient is flushed)
+  nerf_bwd_body(params, ray, depth, count, n_rays, n_samples, acts, rgb_samples, g_rgb_samples, g_density_samples, scratch, nullptr,
+                g_center, g_ray, true, ctx, stream);
   PP_CHECK_LAUNCH();
   return PP_OK;
 }

@@ -11,6 +11,13 @@ SSIM is csrc/pp_ssim.hip (ops.ssim); the PSNRs and the pose functions are torch 
 are on.  The pose functions follow eval.py:539-550 and :699-821 of the reference (poses are [B,3,4] world-to-camera) but keep
 the dtype they are given, where the reference's camera.pose casts to float32.  LPIPS is not provided: its network weights are
 not part of this repository.
+
+    poses = evaluation.refine_test_poses(net, opt, w2c_GT_test, sim3, images, Ks, depth_range)         # eval.py:1398-1408
+    r = evaluation.evaluate_test_views(nerf, nerf_fine, opt, w2c, w2c_GT, w2c_GT_test, images, Ks, depth_range)
+
+The held-out views of the scene branch follow the reference's protocol: their ground-truth poses are carried into the frame of
+the optimised poses and refined photometrically against the frozen networks (pose_refine.py) before they are
+rendered and scored.
 """
 import numpy as np
 import torch
@@ -255,3 +262,80 @@ def evaluate_poses(pose_w2c, pose_GT_w2c):
     else:
         aligned, sim3 = prealign_w2c_small_camera_systems(pose, GT)
     return evaluate_camera_alignment(aligned, GT), aligned, sim3
+
+
+# ------------------------------------------------------------------------------------------------- held-out views (scene branch)
+def _per_view_K(Ks, T):
+    K = Ks if isinstance(Ks, torch.Tensor) else torch.as_tensor(np.asarray(Ks))
+    if K.dim() == 2:
+        K = K[None].expand(T, 3, 3)
+    if tuple(K.shape) != (T, 3, 3):
+        raise ValueError(f'Ks must be [3,3] or [{T},3,3], got {tuple(K.shape)}')
+    return K.float()
+
+
+def refine_test_poses(net, opt, pose_GT_w2c_test, sim3, images, Ks, depth_range, return_losses=False, **refiner_kw):
+    """eval.py:1398-1408: the ground-truth poses of the held-out views [T,3,4] carried into the frame of the optimised poses
+    (backtrack_from_aligning_the_trajectory with `sim3` of evaluate_poses), then one photometric refinement per view against the
+    frozen coarse network `net` (pose_refine.PoseRefiner.refine: 500 Adam steps by default), view after view as the reference runs
+    them -> refined poses [T,3,4] on the networks' device (and, with return_losses, the losses [T, iters]).  images [T,H,W,3];
+    Ks [3,3] or [T,3,3]; refiner_kw: `iters`, `generator` for refine(), the rest for PoseRefiner (rand_rays, lr, betas, eps)."""
+    from . import pose_refine
+    run_kw = {k: refiner_kw.pop(k) for k in ('iters', 'generator') if k in refiner_kw}
+    base = backtrack_from_aligning_the_trajectory(_poses(pose_GT_w2c_test, 'pose_GT_w2c_test').to(net.flat.device), sim3)
+    T = base.shape[0]
+    if len(images) != T:
+        raise ValueError(f'{len(images)} images for {T} poses')
+    K = _per_view_K(Ks, T)
+    H, W = images[0].shape[:2]
+    refiner = pose_refine.PoseRefiner(net, opt, H, W, K[0], depth_range, **refiner_kw)
+    poses, losses = [], []
+    for i in range(T):
+        refiner.set_intrinsics(K[i])
+        image = images[i] if isinstance(images[i], torch.Tensor) else torch.as_tensor(np.asarray(images[i]))
+        out = refiner.refine(base[i].float(), image, **run_kw)
+        poses.append(out['pose_w2c'])
+        losses.append(out['losses'])
+    poses = torch.stack(poses)
+    return (poses, torch.stack(losses)) if return_losses else poses
+
+
+@torch.no_grad()
+def evaluate_test_views(nerf, nerf_fine, opt, pose_w2c_train, pose_GT_w2c_train, pose_GT_w2c_test, images_test, Ks_test, depth_range,
+                        refine=True, **refiner_kw):
+    """The scene branch's share of eval.py:1353-1416: evaluate_poses on the training poses; the held-out views' ground-truth
+    poses backtracked into that frame and (refine=True) refined photometrically against the frozen coarse network; one full-view
+    render per held-out view through bg_nerf.SceneRenderer.render_by_slices in mode 'val' - the fine network's colour where
+    `nerf_fine` exists, else the coarse one; image_metrics.  One host copy, at the end.
+    -> dict: table [T,4] numpy (psnr, psnr_fore, psnr_back, ssim per view; fore / back are 0: no masks), poses_w2c [T,3,4] (device),
+    error (R degrees, t x 100 of the aligned training poses), sim3, losses [T, iters] (device; None without refinement) and
+    rgbs [T,H,W,3] (device).  Out of scope: the object branch's images of these views (evaluate_viewpoints renders them at any
+    pose, poses_w2c included), LPIPS, multi-rank runs."""
+    from . import bg_nerf
+    error, _, sim3 = evaluate_poses(pose_w2c_train, pose_GT_w2c_train)
+    dev = nerf.flat.device
+    losses = None
+    if refine:
+        poses, losses = refine_test_poses(nerf, opt, pose_GT_w2c_test, sim3, images_test, Ks_test, depth_range, return_losses=True,
+                                          **refiner_kw)
+    else:
+        poses = backtrack_from_aligning_the_trajectory(_poses(pose_GT_w2c_test, 'pose_GT_w2c_test').to(dev), sim3).float()
+    T = poses.shape[0]
+    K = _per_view_K(Ks_test, T).to(dev)
+    ropt = opt
+    if nerf_fine is None and opt.nerf.fine_sampling:              # a coarse-only render of a configuration that has a fine pass
+        ropt = bg_nerf.Options(opt)
+        ropt.nerf = bg_nerf.Options(opt.nerf)
+        ropt.nerf.fine_sampling = False
+    renderer = bg_nerf.SceneRenderer(ropt, nerf=nerf, nerf_fine=nerf_fine)
+    keys = ('psnr', 'psnr_fore', 'psnr_back', 'ssim')
+    rgbs, scores = [], []
+    for i in range(T):
+        H, W = images_test[i].shape[:2]
+        ret = renderer.render_by_slices(ropt, poses[i:i + 1], H, W, K[i:i + 1], depth_range, mode='val')
+        rgb = (ret['rgb_fine'] if 'rgb_fine' in ret else ret['rgb']).view(H, W, 3)
+        rgbs.append(rgb)
+        m = image_metrics(rgb, images_test[i])
+        scores.append(torch.stack([m[k] for k in keys]))
+    table = torch.stack(scores).cpu().numpy()                  # the host copy
+    return dict(table=table, poses_w2c=poses, error=error, sim3=sim3, losses=losses, rgbs=torch.stack(rgbs))

@@ -546,6 +546,38 @@ def nerf_bwd(params, ray, depth, count, n_rays, n_samples, acts, rgb_samples, g_
               _f(g_rgb_samples), _f(g_density_samples), _f(scratch), _f(params_grad), _f(g_center), _f(g_ray), _h(ctx), _stream())
 
 
+def nerf_bwd_input(params, ray, depth, count, n_rays, n_samples, acts, rgb_samples, g_rgb_samples, g_density_samples, scratch,
+                   g_center, g_ray, ctx=None):
+    """nerf_bwd with respect to the rays only (pp_nerf_bwd_input): no parameter gradient is formed or touched; g_center / g_ray
+    are the bits nerf_bwd gives."""
+    R, M = int(n_rays), int(n_rays) * int(n_samples)
+    a, s = nerf_workspace(M, R)
+    _rows_at_least(R, (ray, 3, 'ray'), (depth, int(n_samples), 'depth'), (g_center, 3, 'g_center'), (g_ray, 3, 'g_ray'))
+    _rows_at_least(M, (rgb_samples, 3, 'rgb_samples'), (g_rgb_samples, 3, 'g_rgb_samples'), (g_density_samples, 1, 'g_density_samples'))
+    _rows_at_least(1, (acts, a, 'acts'), (scratch, s, 'scratch'))
+    _lib.call('pp_nerf_bwd_input', _f(params), _f(ray), _f(depth), _i(count), R, int(n_samples), _f(acts), _f(rgb_samples),
+              _f(g_rgb_samples), _f(g_density_samples), _f(scratch), _f(g_center), _f(g_ray), _h(ctx), _stream())
+
+
+def nerf_rays_select(c2w, K, ray_idx, H, W, image, center, ray, dir_cam, target):
+    """c2w [3,4], K [3,3] (upper-triangular, K[2,2] = 1: the caller checks), ray_idx [N] int32 in [0, H * W), image [H,W,3] ->
+    center, ray, dir_cam, target [N,3] (pp_nerf_rays_select), all on the device."""
+    N = ray_idx.shape[0]
+    if c2w.numel() != 12 or K.numel() != 9 or image.numel() != H * W * 3:
+        raise RuntimeError('nerf_rays_select: c2w [3,4], K [3,3] and image [H,W,3] expected')
+    _rows_at_least(N, (center, 3, 'center'), (ray, 3, 'ray'), (dir_cam, 3, 'dir_cam'), (target, 3, 'target'))
+    _lib.call('pp_nerf_rays_select', _f(c2w), _f(K), _i(ray_idx), int(N), int(H), int(W), _f(image), _f(center), _f(ray),
+              _f(dir_cam), _f(target), _stream())
+
+
+def nerf_mse_loss(pred, label, weight, loss, g_pred):
+    """loss[0] = weight * mse_loss(pred, label, mean); g_pred = its gradient (eval.py:853)."""
+    n = int(pred.numel())
+    _rows_at_least(n, (label, 1, 'label'), (g_pred, 1, 'g_pred'))
+    _rows_at_least(1, (loss, 1, 'loss'))
+    _lib.call('pp_nerf_mse_loss', _f(pred), _f(label), n, ctypes.c_float(weight), _f(loss), _f(g_pred), _stream())
+
+
 def nerf_composite_fwd(rgb_samples, density_samples, depth, ray, n_rays, n_samples, white_bg, rgb, depth_out, opacity, weights,
                        all_cumulated, rgb_var, depth_var):
     _lib.call('pp_nerf_composite_fwd', _f(rgb_samples), _f(density_samples), _f(depth), _f(ray), int(n_rays), int(n_samples),

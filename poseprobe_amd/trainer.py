@@ -396,6 +396,19 @@ class DualBranchTrainer:
         GT = torch.as_tensor(pose_GT_w2c)
         return evaluation.evaluate_poses(e.w2c[:k].detach(), GT[:k, :3])
 
+    def evaluate_test_views(self, pose_GT_w2c_train, pose_GT_w2c_test, images_test, Ks_test, **kw):
+        """Held-out views by the reference's protocol (eval.py:1353-1416; evaluation.evaluate_test_views with this trainer's
+        networks, the active views' current poses and its depth range): alignment of the training poses, test-time pose
+        refinement against the frozen scene networks (refine=False skips it), full-view renders, PSNR / SSIM.  The networks and
+        the optimiser state are left as they are."""
+        from . import evaluation, ops
+        e = self.joint.obj
+        k = e.V if self.n_active is None else self.n_active
+        ops.pose_fwd(e.se3, e.w2c_init, e.refine_mask, e.w2c, e.c2w, e.jac)
+        GT = torch.as_tensor(pose_GT_w2c_train)
+        return evaluation.evaluate_test_views(self.nerf, self.nerf_fine, self.opt, e.w2c[:k].detach(), GT[:k, :3], pose_GT_w2c_test,
+                                              images_test, Ks_test, self.joint.depth_range, **kw)
+
     # ---- `model_last.pth.tar` (renderer.py:1028-1051 save_snapshot, recon_scene.py:827-838 load) ----------------------------
     def _adam_state_dict(self):
         """torch.optim.Adam.state_dict() layout over [nerf.parameters(), nerf_fine.parameters()] (lib/utils.py:294-299)."""
