@@ -46,7 +46,8 @@ const char* pp_last_error(void);
  * pp_scene gained `sdf_index_exact`; new: pp_sdf_crossing_dense_bwd, pp_context_set_option / pp_context_get_option.  4 (this header): the
  * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
  * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_mc_* group, the pp_pnp_* group,
- * the pp_dtu_* group, the pp_ssim_* group, pp_step_begin, pp_march_loss_bwd / pp_march_loss_workspace.
+ * the pp_dtu_* group, the pp_ssim_* group, pp_step_begin, pp_march_loss_bwd / pp_march_loss_workspace, pp_geometry_plain_fwd /
+ * pp_geometry_plain_bwd, pp_keep_compact / pp_keep_scatter_bwd.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
  * (poseprobe_amd/_lib.py does): the signatures changed, so a stale caller would pass a stream where a pointer is read. */
 #define PP_ABI_VERSION 4
@@ -862,6 +863,40 @@ int pp_ssim_workspace(int32_t V, int32_t H, int32_t W, int32_t filter_size, int6
 int pp_ssim(const float* img0, const float* img1, int32_t V, int32_t H, int32_t W, int32_t C, int32_t filter_size,
             double filter_sigma, double max_val, double k1, double k2, void* work, int64_t work_bytes, float* ssim, float* map,
             void* stream);
+
+/* ---------------------------------------------------------------- the two other branches of Voxurf.forward / Voxurf.inference
+ * (csrc/pp_forward_variants.hip).
+ * Plain-template geometry (use_deform=False, lib/voxurf_coarse.py:986-989, grad_mode 'interpolate' :458-467): no warp net.  With
+ * G = softplus10(alpha) (sigmoid(softplus10(beta) sdf) - 0.5), sdf_final[M] is the trilinear sample of G at pts with
+ * F.grid_sample semantics (align_corners=True, border padding: the coordinate is clipped to the grid) and gradient[M,3] the same
+ * sample of the central differences (G[i+1] - G[i-1]) / 2 / voxel_size, a component being zero on the two boundary planes of its own
+ * axis; alpha[M] is the NeuS alpha of pp_geometry_fwd.  Neither grid is materialised: 32 raw values per sample are mapped and
+ * differenced in registers.  sdf_final may be NULL.  The grid needs two nodes along every axis. */
+int pp_geometry_plain_fwd(const pp_scene* sc, const float* sdf_grid, const float* sdf_ab, const float* pts, const float* viewdirs,
+                          const int32_t* ray_id, const int32_t* count, int32_t capacity, float inv_s, float* alpha, float* gradient,
+                          float* sdf_final, void* stream);
+/* Upstream grads (any may be NULL): g_alpha[M], g_gradient[M,3], g_sdf_final[M].  Outputs: pts_grad[M,3] and viewdir_grad_s[M,3]
+ * (accumulate=1: +=; a coordinate that the border padding clipped, u <= 0 or u >= size - 1, passes no gradient, as
+ * F.grid_sample), sdf_ab_grad[2] (work-group sums, then one atomic += per value and work-group; caller zeroes; may be NULL). */
+int pp_geometry_plain_bwd(const pp_scene* sc, const float* sdf_grid, const float* sdf_ab, const float* pts, const float* viewdirs,
+                          const int32_t* ray_id, const int32_t* count, int32_t capacity, float inv_s, const float* g_alpha,
+                          const float* g_gradient, const float* g_sdf_final, int32_t accumulate, float* pts_grad,
+                          float* viewdir_grad_s, float* sdf_ab_grad, void* stream);
+/* Weight-threshold compaction (fast_color_thres, lib/voxurf_coarse.py:996-1003, :1144-1151): of the samples
+ * [ray_start[r], ray_start[r+1]) of every ray those with weights[i] > thres are kept, in order.  Outputs: kept_idx[j] = original
+ * index of kept sample j, kept_ray_start[n_rays + 1] = the kept samples' exclusive prefix per ray, kept_count[1] = their number
+ * (DEVICE), and the gathered rows pts_k[.,3], ray_id_k, step_k, alpha_k, gradient_k[.,3].  Every buffer holds `capacity` rows;
+ * ray_start entries are read clamped to [0, capacity].  Rows past kept_count are left untouched.  Three launches (count, scan,
+ * fill), one wavefront per ray, no atomics, no host read. */
+int pp_keep_compact(const float* weights, const int32_t* ray_start, int32_t n_rays, int32_t capacity, float thres, const float* pts,
+                    const int32_t* ray_id, const float* step, const float* alpha, const float* gradient, int32_t* kept_idx,
+                    int32_t* kept_ray_start, int32_t* kept_count, float* pts_k, int32_t* ray_id_k, float* step_k, float* alpha_k,
+                    float* gradient_k, void* stream);
+/* Backward of the gather: every non-NULL full-length buffer (g_alpha[capacity], g_gradient / g_pts / g_view [capacity,3]) is zeroed
+ * and row kept_idx[j] then receives row j of its kept twin, j < kept_count (one-to-one: plain stores, no atomics). */
+int pp_keep_scatter_bwd(const int32_t* kept_idx, const int32_t* kept_count, int32_t capacity, const float* g_alpha_k,
+                        const float* g_gradient_k, const float* g_pts_k, const float* g_view_k, float* g_alpha, float* g_gradient,
+                        float* g_pts, float* g_view, void* stream);
 
 #ifdef __cplusplus
 }

@@ -154,6 +154,39 @@ class Workspace:
         self.scratch_rgb = e(self.wsz['rgbnet'][1], **f)   # Ybar of rgbnet: a buffer of its own, so that a lean scope's bytes in
         #                                                              `scratch` depend on the warp chain alone
 
+    def kept_samples(self, backward=False):
+        """Buffers of a pass with fast_color_thres > 0 (allocated on first use, kept): see KeptSamples."""
+        if not hasattr(self, 'kept'):
+            self.kept = KeptSamples(self)
+        if backward:
+            self.kept.alloc_backward()
+        return self.kept
+
+
+class KeptSamples:
+    """The samples of a Workspace whose weight in the first composite exceeds fast_color_thres (ops.keep_compact), at the
+    workspace's capacity: every kernel that reads them stops at the device-side `count`.  The attributes the second composite and
+    the colour stage read carry the names they have on the Workspace (pts, ray_id, step, alpha, gradient, ray_start, count and
+    the four sample gradients), so RenderCore hands one or the other to the same kernels."""
+
+    def __init__(self, ws):
+        f = dict(dtype=torch.float32, device=ws.device)
+        i = dict(dtype=torch.int32, device=ws.device)
+        e, cap, N = torch.empty, ws.cap, ws.N
+        self.cap, self.device = cap, ws.device
+        self.idx, self.ray_start, self.count = e(cap, **i), torch.zeros(N + 1, **i), torch.zeros(1, **i)
+        self.pts, self.ray_id, self.step = e(cap, 3, **f), e(cap, **i), e(cap, **f)
+        self.alpha, self.gradient = e(cap, **f), e(cap, 3, **f)
+        # the first composite, over every sample: its weights decide the mask and nothing else
+        self.weights_all, self.T_all, self.last_all, self.i_end_all = e(cap, **f), e(cap, **f), e(N, **f), e(N, **i)
+
+    def alloc_backward(self):
+        if hasattr(self, 'g_alpha'):
+            return
+        f = dict(dtype=torch.float32, device=self.device)
+        e, cap = torch.empty, self.cap
+        self.g_alpha, self.g_gradient, self.g_pts, self.g_view_s = e(cap, **f), e(cap, 3, **f), e(cap, 3, **f), e(cap, 3, **f)
+
 
 class FlatParams:
     """Packed small parameters: [sdf_ab | rgbnet | warp], each segment padded to 64 floats (16-B aligned sub-blocks)."""
@@ -292,16 +325,39 @@ class RenderCore:
                          ws.pts, ws.ray_id, ws.step_k, ws.step)
 
     def forward(self, ws, k0_cl, sdf, sdf_ab, rgbnet_p, warp_p, inv_s, pe_w, step_w=None, before_k0_use=None, normals=None,
-                side_by_side=False, composite=True):
-        """normals: (nrm [cap,3], normal_marched [N,3]) - the marching kernel composites the unit SDF gradients as well.
+                side_by_side=False, composite=True, use_deform=True, color_thres=0.0):
+        """use_deform=False: the plain-template geometry (ops.geometry_plain_fwd) - the warp net does not run and ws.sdf_deform /
+        ws.grad_deform / ws.warp_out are not written.  color_thres > 0 (fast_color_thres): a first composite over every sample, then
+        the second composite and the colour stage on the samples with weight > color_thres (ws.kept, ops.keep_compact).  Both are
+        for the drop-in module's passes: not with side_by_side, before_k0_use, step_w or composite=False.  Defaults: no launch differs.
+        normals: (nrm [cap,3], normal_marched [N,3]) - the marching kernel composites the unit SDF gradients as well.
         side_by_side (the train step's default path): geometry forward and colour lookup share one launch unless a
         before_k0_use hook has to run between them.
         composite=False (the train step's default path): the pass stops in front of the compositing - the caller composites, takes
         the ray losses and differentiates the composite in one launch (ops.loss_rays(march=...)) and calls backward(march_done=True)."""
         cfg, sc = self.cfg, self.cfg.pp
         nrm, normal_marched = (None, None) if normals is None else normals
-        ops.warp_fwd(warp_p, ws.pts, ws.count, ws.cap, cfg.out_range, ws.warp_acts, ws.warp_out, self.ctx)
-        if side_by_side and before_k0_use is None and (sc.k0_dim, sc.pos_pe, sc.view_pe) == (12, 5, 1):
+        variant = (not use_deform) or color_thres > 0
+        if variant and (side_by_side or before_k0_use is not None or step_w is not None or not composite):
+            raise ValueError('use_deform=False / color_thres > 0 are passes of the drop-in module: not inside the fused train step '
+                             '(side_by_side, before_k0_use, step_w, composite=False)')
+        s = ws                  # whose samples the colour stage and the (second) composite read
+        if use_deform:
+            ops.warp_fwd(warp_p, ws.pts, ws.count, ws.cap, cfg.out_range, ws.warp_acts, ws.warp_out, self.ctx)
+        if variant:
+            if use_deform:
+                ops.geometry_fwd(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
+                                 ws.alpha, ws.gradient, ws.sdf_final, ws.sdf_deform, ws.grad_deform)
+            else:
+                ops.geometry_plain_fwd(sc, sdf, sdf_ab, ws.pts, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s, ws.alpha,
+                                       ws.gradient, ws.sdf_final)
+            if color_thres > 0:
+                s = ws.kept_samples()
+                ops.alpha2weight_fwd(ws.alpha, ws.ray_start, ws.N, s.weights_all, s.T_all, s.last_all, s.i_end_all)
+                ops.keep_compact(s.weights_all, ws.ray_start, ws.N, ws.cap, color_thres, ws.pts, ws.ray_id, ws.step, ws.alpha,
+                                 ws.gradient, s.idx, s.ray_start, s.count, s.pts, s.ray_id, s.step, s.alpha, s.gradient)
+            ops.color_feat_fwd(sc, k0_cl, s.pts, ws.viewdirs, s.ray_id, s.gradient, pe_w, s.count, ws.cap, ws.feat)
+        elif side_by_side and before_k0_use is None and (sc.k0_dim, sc.pos_pe, sc.view_pe) == (12, 5, 1):
             # only the normal columns of feat need the geometry: the colour lookup runs beside it, in the same launch
             ops.geometry_color_feat_fwd(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
                                         ws.alpha, ws.gradient, ws.sdf_final, ws.sdf_deform, ws.grad_deform, k0_cl, pe_w, ws.feat)
@@ -311,41 +367,52 @@ class RenderCore:
             if before_k0_use is not None:
                 before_k0_use()             # multi-GPU: the all-gather of the updated grid overlaps everything above
             ops.color_feat_fwd(sc, k0_cl, ws.pts, ws.viewdirs, ws.ray_id, ws.gradient, pe_w, ws.count, ws.cap, ws.feat)
-        ops.rgbnet_fwd(rgbnet_p, ws.feat, ws.count, ws.cap, ws.rgb_acts, ws.rgb, self.ctx)
+        ops.rgbnet_fwd(rgbnet_p, ws.feat, s.count, ws.cap, ws.rgb_acts, ws.rgb, self.ctx)
         if nrm is not None:
             # rows past the count hold stale values: harmless, the marching kernel walks ray_start ranges only
-            torch.div(ws.gradient, ws.gradient.norm(2, -1, keepdim=True) + 1e-6, out=nrm)
+            torch.div(s.gradient, s.gradient.norm(2, -1, keepdim=True) + 1e-6, out=nrm)
         if not composite:
             if normals is not None or step_w is not None:
                 raise ValueError('composite=False: the fused ray launch composites neither normals nor a step_w of the caller')
             return
-        ops.march_fwd(ws.alpha, ws.rgb, ws.step if step_w is None else step_w, nrm, ws.ray_start, ws.N, cfg.bg,
+        ops.march_fwd(s.alpha, ws.rgb, s.step if step_w is None else step_w, nrm, s.ray_start, ws.N, cfg.bg,
                       ws.weights, ws.T, ws.alphainv_last, ws.i_end, ws.rgb_marched, ws.rgb_pre, ws.cum_weights,
                       ws.depth_acc, normal_marched)
 
     # -- backward ------------------------------------------------------------------------------------------
     def backward(self, ws, k0_cl, sdf, sdf_ab, rgbnet_p, warp_p, inv_s, pe_w, k0_grad_cl, sdf_ab_grad, rgbnet_grad,
                  warp_grad, g_depth=None, g_weights=None, g_gradient_ext=None, g_sdf_deform=None, g_grad_deform=None,
-                 g_correction=None, g_alpha_ext=None, g_rgb_ext=None, after_k0_grad=None, priors=None, march_done=False):
+                 g_correction=None, g_alpha_ext=None, g_rgb_ext=None, after_k0_grad=None, priors=None, march_done=False,
+                 use_deform=True, color_thres=0.0):
         """Consumes ws.g_rgbm / ws.g_last / ws.g_cw (+ optional per-sample upstream grads), accumulates parameter
         grads (atomic +=) and leaves d/d ray_pts in ws.g_pts and the per-sample viewdir grads in ws.g_view_s.
-        march_done: the caller ran ops.loss_rays(march=...) after forward(composite=False) - ws.g_alpha / ws.g_rgb are in place."""
+        march_done: the caller ran ops.loss_rays(march=...) after forward(composite=False) - ws.g_alpha / ws.g_rgb are in place.
+        use_deform / color_thres: as handed to forward().  color_thres > 0: g_weights, g_alpha_ext, g_rgb_ext and what
+        g_gradient_ext adds are gradients of the KEPT samples (g_gradient_ext receives ws.kept); the composite and the colour stage
+        are differentiated there, ops.keep_scatter_bwd carries their sample gradients to the original rows (exact zeros on the
+        dropped ones) and the geometry backward runs over every sample.  The first composite carries no gradient: it only decides
+        the mask.  use_deform=False: neither warp_grad nor ws.g_warp_out is touched."""
         cfg, sc = self.cfg, self.cfg.pp
+        variant = (not use_deform) or color_thres > 0
+        if variant and (priors is not None or march_done or after_k0_grad is not None):
+            raise ValueError('use_deform=False / color_thres > 0 are passes of the drop-in module: not inside the fused train step '
+                             '(priors, march_done, after_k0_grad)')
+        s = ws.kept_samples(backward=True) if color_thres > 0 else ws
         if march_done:
             if not (g_depth is None and g_weights is None and g_alpha_ext is None and g_rgb_ext is None):
                 raise ValueError('march_done: the fused ray launch takes no upstream gradients beside the ray losses')
         else:
-            ops.march_bwd(ws.alpha, ws.rgb, ws.step, ws.weights, ws.T, ws.alphainv_last, ws.ray_start, ws.i_end, ws.N, cfg.bg,
-                          ws.rgb_pre, ws.g_rgbm, ws.g_cw, ws.g_last, g_depth, g_weights, ws.g_alpha, ws.g_rgb)
+            ops.march_bwd(s.alpha, ws.rgb, s.step, ws.weights, ws.T, ws.alphainv_last, s.ray_start, ws.i_end, ws.N, cfg.bg,
+                          ws.rgb_pre, ws.g_rgbm, ws.g_cw, ws.g_last, g_depth, g_weights, s.g_alpha, ws.g_rgb)
         if g_alpha_ext is not None:
-            ws.g_alpha.add_(g_alpha_ext)
+            s.g_alpha.add_(g_alpha_ext)
         if g_rgb_ext is not None:
             ws.g_rgb.add_(g_rgb_ext)
         ctx = self.ctx
-        ops.rgbnet_bwd(rgbnet_p, ws.feat, ws.rgb_acts, ws.rgb, ws.g_rgb, ws.count, ws.cap, ws.scratch_rgb,
+        ops.rgbnet_bwd(rgbnet_p, ws.feat, ws.rgb_acts, ws.rgb, ws.g_rgb, s.count, ws.cap, ws.scratch_rgb,
                        rgbnet_grad, ws.g_feat, ctx)
-        ops.color_feat_bwd(sc, k0_cl, ws.pts, ws.viewdirs, ws.ray_id, ws.gradient, pe_w, ws.count, ws.cap, ws.g_feat,
-                           k0_grad_cl, ws.g_pts, ws.g_gradient, ws.g_view_s)
+        ops.color_feat_bwd(sc, k0_cl, s.pts, ws.viewdirs, s.ray_id, s.gradient, pe_w, s.count, ws.cap, ws.g_feat,
+                           k0_grad_cl, s.g_pts, s.g_gradient, s.g_view_s)
         if after_k0_grad is not None:
             after_k0_grad()             # multi-GPU: the grid reduce-scatter overlaps the rest of the backward
         if priors is not None:
@@ -364,12 +431,20 @@ class RenderCore:
                 raise ValueError('an ordered RenderCore differentiates the fused step only (priors=...): the separate '
                                  'geometry backward keeps its float atomics')
             if g_gradient_ext is not None:
-                g_gradient_ext(ws)      # callable adding loss terms into ws.g_gradient etc.
-            ops.geometry_bwd(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
-                             ws.g_alpha, ws.g_gradient, None, g_sdf_deform, g_grad_deform, g_correction, 1, ws.g_warp_out,
-                             ws.g_pts, ws.g_view_s, sdf_ab_grad)
-        ops.warp_bwd(warp_p, ws.pts, ws.warp_acts, ws.g_warp_out, ws.count, ws.cap, cfg.out_range, ws.scratch, warp_grad,
-                     ws.g_pts, ctx)
+                g_gradient_ext(s)       # callable adding loss terms into g_gradient etc. (of the kept samples when color_thres > 0)
+            if s is not ws:
+                ops.keep_scatter_bwd(s.idx, s.count, ws.cap, s.g_alpha, s.g_gradient, s.g_pts, s.g_view_s, ws.g_alpha,
+                                     ws.g_gradient, ws.g_pts, ws.g_view_s)
+            if use_deform:
+                ops.geometry_bwd(sc, sdf, sdf_ab, ws.pts, ws.warp_out, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s,
+                                 ws.g_alpha, ws.g_gradient, None, g_sdf_deform, g_grad_deform, g_correction, 1, ws.g_warp_out,
+                                 ws.g_pts, ws.g_view_s, sdf_ab_grad)
+            else:
+                ops.geometry_plain_bwd(sc, sdf, sdf_ab, ws.pts, ws.viewdirs, ws.ray_id, ws.count, ws.cap, inv_s, ws.g_alpha,
+                                       ws.g_gradient, None, 1, ws.g_pts, ws.g_view_s, sdf_ab_grad)
+        if use_deform:
+            ops.warp_bwd(warp_p, ws.pts, ws.warp_acts, ws.g_warp_out, ws.count, ws.cap, cfg.out_range, ws.scratch, warp_grad,
+                         ws.g_pts, ctx)
 
 
 class TrainEngine:

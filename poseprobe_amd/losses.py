@@ -138,7 +138,10 @@ def object_losses(model_output, cfg_train, target, mask, iteration, total_iterat
     """lib/losses.py:34-74: (loss_scalars, loss_weight, loss).  CUDA inputs with use_deform take the two-kernel path
     (_FusedObjectLosses); everything else the op-by-op torch expressions."""
     rgb = model_output['rgb_marched']
-    if not (use_deform and rgb.is_cuda and all(k in model_output for k in ('grad_deform', 'sdf_correct', 'sdf_deform'))):
+    fused = use_deform and rgb.is_cuda and all(k in model_output for k in ('grad_deform', 'sdf_correct', 'sdf_deform'))
+    # fast_color_thres > 0: `gradient` has the kept samples' rows, the three deformation outputs every sample's - the sample kernel
+    # takes one row count, so such a dict goes the torch route
+    if not fused or model_output['gradient'].shape[0] != model_output['sdf_deform'].shape[0]:
         return _object_losses_torch(model_output, cfg_train, target, mask, iteration, total_iterations, use_deform)
     w_dyn = dynamic_weight(1e-1, 1e-3, iteration, total_iterations)
     weights = (float(cfg_train.weight_main), 0.01, float(cfg_train.weight_mask), 1.0, float(w_dyn))

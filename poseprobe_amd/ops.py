@@ -215,6 +215,34 @@ def geometry_color_feat_fwd(sc, sdf_grid, sdf_ab, pts, warp_out, viewdirs, ray_i
               _f(grad_deform), _f(k0_cl), _f(pe_w), _f(feat), _stream())
 
 
+# ------------------------------------------------------------------------------------------- forward variants
+def geometry_plain_fwd(sc, sdf_grid, sdf_ab, pts, viewdirs, ray_id, count, capacity, inv_s, alpha, gradient, sdf_final=None):
+    """Geometry of Voxurf.forward(use_deform=False): grid_sample lookups of the mapped template and of its central differences."""
+    _lib.call('pp_geometry_plain_fwd', ctypes.byref(sc), _f(sdf_grid), _f(sdf_ab), _f(pts), _f(viewdirs), _i(ray_id), _i(count),
+              capacity, float(inv_s), _f(alpha), _f(gradient), _f(sdf_final), _stream())
+
+
+def geometry_plain_bwd(sc, sdf_grid, sdf_ab, pts, viewdirs, ray_id, count, capacity, inv_s, g_alpha, g_gradient, g_sdf_final,
+                       accumulate, pts_grad, vgrad_s, sdf_ab_grad):
+    _lib.call('pp_geometry_plain_bwd', ctypes.byref(sc), _f(sdf_grid), _f(sdf_ab), _f(pts), _f(viewdirs), _i(ray_id), _i(count),
+              capacity, float(inv_s), _f(g_alpha), _f(g_gradient), _f(g_sdf_final), int(accumulate), _f(pts_grad), _f(vgrad_s),
+              _f(sdf_ab_grad), _stream())
+
+
+def keep_compact(weights, ray_start, n_rays, capacity, thres, pts, ray_id, step, alpha, gradient, kept_idx, kept_ray_start,
+                 kept_count, pts_k, ray_id_k, step_k, alpha_k, gradient_k):
+    """The samples with weights > thres of every ray, in order: indices, new ray_start, device-side count, gathered rows."""
+    _lib.call('pp_keep_compact', _f(weights), _i(ray_start), int(n_rays), int(capacity), float(thres), _f(pts), _i(ray_id), _f(step),
+              _f(alpha), _f(gradient), _i(kept_idx), _i(kept_ray_start), _i(kept_count), _f(pts_k), _i(ray_id_k), _f(step_k),
+              _f(alpha_k), _f(gradient_k), _stream())
+
+
+def keep_scatter_bwd(kept_idx, kept_count, capacity, g_alpha_k, g_gradient_k, g_pts_k, g_view_k, g_alpha, g_gradient, g_pts, g_view):
+    """Rows of the kept gradients back to their original rows, exact zeros everywhere else."""
+    _lib.call('pp_keep_scatter_bwd', _i(kept_idx), _i(kept_count), int(capacity), _f(g_alpha_k), _f(g_gradient_k), _f(g_pts_k),
+              _f(g_view_k), _f(g_alpha), _f(g_gradient), _f(g_pts), _f(g_view), _stream())
+
+
 # ------------------------------------------------------------------------------------------- ordered gradient flushes
 def ordered_workspace(work_groups, capacity, n_rays):
     """Bytes of the ordered-flush workspace (pp_ordered_workspace): work_groups = the largest persistent grid the MLP kernels

@@ -117,6 +117,12 @@ class Alphas2Weights(torch.autograd.Function):
         return g, None, None
 
 
+# keys of the dict Voxurf.forward returns (voxurf_coarse.py:1069-1091); the second group only with use_deform=True
+FORWARD_KEYS = ('alphainv_cum', 'weights', 'cum_weights', 'rgb_marched', 'normal_marched', 'raw_alpha', 'raw_rgb', 'depth', 'disp',
+                'mask', 'mask_outbbox', 'gradient', 's_val', 'k0_tv')
+FORWARD_DEFORM_KEYS = ('sdf_deform', 'grad_deform', 'sdf_correct')
+
+
 # ---------------------------------------------------------------------------------------------------------------
 class _VoxurfRender(torch.autograd.Function):
     """One autograd node for Voxurf.forward: inputs rays + every trainable tensor, outputs the render dict."""
@@ -128,15 +134,26 @@ class _VoxurfRender(torch.autograd.Function):
         flat.load_reference(sdf_alpha, sdf_beta, list(zip(mlp[0:8:2], mlp[1:8:2])), list(zip(mlp[8::2], mlp[9::2])))
         k0_cl = channels_last_view(k0)
         sdf_g = model.sdf.grid.detach()[0, 0].contiguous()
-        core.forward(ws, k0_cl, sdf_g, flat.view('sdf_ab'), flat.view('rgbnet'), flat.view('warp'), inv_s, pe_w)
+        # the two switches of Voxurf.forward travel on the workspace (ws.use_deform, ws.color_thres); with their defaults the pass
+        # below is the one it always was
+        deform, thres = ws.use_deform, ws.color_thres
+        core.forward(ws, k0_cl, sdf_g, flat.view('sdf_ab'), flat.view('rgbnet'), flat.view('warp'), inv_s, pe_w,
+                     use_deform=deform, color_thres=thres)
         ctx.model, ctx.ws, ctx.flat, ctx.inv_s, ctx.pe_w = model, ws, flat, inv_s, pe_w
         ctx.k0, ctx.sdf_g = k0, sdf_g
         ctx.set_materialize_grads(False)        # outputs the loss does not use arrive as None in backward, not as zero tensors
         M = ws.M
+        s, Mk = ws, M
+        if thres > 0:
+            s = ws.kept
+            Mk = int(s.count.item())            # a second host round trip beside the sampler's, as the reference's boolean mask
+        ws.Mk = Mk
         depth = ws.t_min / rays_d.detach().norm(dim=-1) + ws.depth_acc
-        outs = (ws.rgb_marched, ws.alphainv_last, ws.cum_weights.unsqueeze(-1), ws.weights[:M], ws.alpha[:M], ws.rgb[:M],
-                depth, ws.gradient[:M], ws.sdf_deform[:M], ws.grad_deform[:M].reshape(M, 3, 3),
-                ws.warp_out[:M, 3:4], ws.depth_acc)
+        none = ws.alpha[:0]                     # use_deform=False has no deformation outputs (voxurf_coarse.py:1086-1091)
+        outs = (ws.rgb_marched, ws.alphainv_last, ws.cum_weights.unsqueeze(-1), ws.weights[:Mk], s.alpha[:Mk], ws.rgb[:Mk],
+                depth, s.gradient[:Mk], ws.sdf_deform[:M] if deform else none,
+                ws.grad_deform[:M].reshape(M, 3, 3) if deform else none,
+                ws.warp_out[:M, 3:4] if deform else none, ws.depth_acc)
         # k0_tv (lib/voxurf_coarse.py:1067: evaluated on every forward) rides on this node: its gradient is then ADDED IN PLACE to
         # the colour-grid gradient the render backward produces - a node of its own hands autograd a second dense 196 MB gradient
         # to allocate, zero-fill and sum (0.3 ms per step at 160^3)
@@ -150,10 +167,14 @@ class _VoxurfRender(torch.autograd.Function):
     def backward(ctx, g_rgbm, g_last, g_cw, g_w, g_alpha, g_rgb, g_depth, g_grad, g_sdfd, g_gdef, g_corr, g_nstep, g_tv):
         model, ws, flat = ctx.model, ctx.ws, ctx.flat
         core, M, cap = model._core, ws.M, ws.cap
+        deform, thres = ws.use_deform, ws.color_thres
+        Mk = ws.Mk                              # rows of weights / raw_alpha / raw_rgb / gradient: the kept samples (= M without a threshold)
+        if not deform:
+            g_sdfd = g_gdef = g_corr = None     # the three placeholders are not outputs of the pass
         ws.alloc_backward(False)
         dev = ws.rays_o.device
 
-        def padded(t, width=None):
+        def padded(t, width=None, M=M):
             """upstream [M,...] gradient as the kernels want it: contiguous fp32, NO copy into a capacity-sized buffer - every
             kernel stops at the device-side sample count (M rows), so M rows are all that is ever read; None stays None (NULL =
             'no gradient')."""
@@ -174,27 +195,28 @@ class _VoxurfRender(torch.autograd.Function):
             g_depth_all = g_depth
         else:
             g_depth_all = g_nstep.contiguous().float() if g_depth is None else g_depth + g_nstep.contiguous().float()
-        gg = padded(g_grad, 3)
+        gg = padded(g_grad, 3, M=Mk)
 
         def capacity_sized(t, width=None):
             """the two upstream gradients that are ADDED to capacity-sized buffers by a torch op (rare: raw_alpha / raw_rgb in a loss)"""
             if t is None:
                 return None
             b = torch.zeros((cap,) if width is None else (cap, width), device=dev)
-            b[:M] = t.reshape(M, -1) if width else t.reshape(M)
+            b[:Mk] = t.reshape(Mk, -1) if width else t.reshape(Mk)
             return b
 
         def add_gradient(w):
             if gg is not None:
-                w.g_gradient[:M].add_(gg)
+                w.g_gradient[:Mk].add_(gg)
 
         k0_grad = torch.zeros_like(ctx.k0, memory_format=torch.channels_last_3d)
         core.backward(ws, channels_last_view(ctx.k0), ctx.sdf_g, flat.view('sdf_ab'), flat.view('rgbnet'), flat.view('warp'),
                       ctx.inv_s, ctx.pe_w, channels_last_view(k0_grad), flat.view('sdf_ab', 'grad'),
                       flat.view('rgbnet', 'grad'), flat.view('warp', 'grad'),
-                      g_depth=g_depth_all, g_weights=padded(g_w),
+                      g_depth=g_depth_all, g_weights=padded(g_w, M=Mk),
                       g_gradient_ext=add_gradient, g_sdf_deform=padded(g_sdfd), g_grad_deform=padded(g_gdef, 9),
-                      g_correction=padded(g_corr), g_alpha_ext=capacity_sized(g_alpha), g_rgb_ext=capacity_sized(g_rgb, 3))
+                      g_correction=padded(g_corr), g_alpha_ext=capacity_sized(g_alpha), g_rgb_ext=capacity_sized(g_rgb, 3),
+                      use_deform=deform, color_thres=thres)
         if g_tv is not None:                 # d k0_tv / d k0 added in place (read-modify-write of the gradient the scatter just filled)
             C, (X, Y, Z) = ctx.k0.shape[1], ctx.k0.shape[2:]
             ops.grid_tv_grad(channels_last_view(ctx.k0), (X, Y, Z), C, 1.0 / (3 * ctx.k0.numel()), g_tv.reshape(1).contiguous().float(),
@@ -204,8 +226,10 @@ class _VoxurfRender(torch.autograd.Function):
                               ws.g_pts, ws.step, ws.g_view_s, None, None, None, g_depth, go, gd, gv, None)
         g = flat.export_grads()
         mlp_grads = []
-        for W, b in g['rgbnet'] + g['warp']:
+        for W, b in g['rgbnet']:
             mlp_grads += [W.contiguous(), b.contiguous()]
+        for W, b in g['warp']:                  # use_deform=False: the warp net did not run - no gradient, not a zero one
+            mlp_grads += [W.contiguous(), b.contiguous()] if deform else [None, None]
         return (None, None, None, None, go, gd, gv, k0_grad, g['sdf_alpha'], g['sdf_beta'], *mlp_grads)
 
 
@@ -401,7 +425,7 @@ class Voxurf(torch.nn.Module):
 
     def k0_total_variation(self, k0_tv=1., k0_grad_tv=0.):
         if k0_grad_tv > 0:
-            raise NotImplementedError
+            raise NotImplementedError('k0_grad_tv > 0 (the reference raises here too, voxurf_coarse.py:454-455)')
         return total_variation(self.k0.grid) if k0_tv > 0 else 0
 
     # ---- parameter gathering ----------------------------------------------------------------------------------
@@ -560,9 +584,10 @@ class Voxurf(torch.nn.Module):
     def query_sdf_point_wocuda_render(self, rays_o, rays_d, global_step=None, keep_dim=False, return_depth=False,
                                       use_deform=True, **render_kwargs):
         """voxurf_coarse.py:839-920: expected depth from the rendering weights; differentiable (pose, warp, grid) because
-        it runs through the same autograd node as forward()."""
+        it runs through the same autograd node as forward().  use_deform=False: the plain template (:894-897).  The weights are those
+        of ONE composite over every sample, whatever fast_color_thres is (:903)."""
         viewdirs = rays_d / rays_d.norm(dim=-1, keepdim=True)
-        out = self.forward(rays_o, rays_d, viewdirs, use_deform=use_deform, global_step=global_step, **render_kwargs)
+        out = self._render(rays_o, rays_d, viewdirs, use_deform, global_step, 0.0, render_kwargs)
         nrm = rays_d.norm(dim=-1)
         n_step = out['_n_step']                                            # = sum_i w_i step_i (differentiable)
         t_min = self._entry_distance(rays_o, rays_d, render_kwargs['near'], render_kwargs['far'])
@@ -587,11 +612,21 @@ class Voxurf(torch.nn.Module):
     # ---- forward ----------------------------------------------------------------------------------------------
     def forward(self, rays_o, rays_d, viewdirs, use_deform=True, global_step=None, **render_kwargs):
         """voxurf_coarse.py:922-1092.  Extension: render_kwargs['jitter'] ([N] in [0,1)) overrides the internally drawn
-        per-ray jitter (the reference draws it from the global CUDA generator, :713)."""
-        if not use_deform:
-            raise NotImplementedError('use_deform=False is never taken on the live path (recon_scene.py:603)')
-        if self.fast_color_thres > 0:
-            raise NotImplementedError('fast_color_thres > 0 (all shipped configs use 0)')
+        per-ray jitter (the reference draws it from the global CUDA generator, :713).
+        use_deform=False (:986-989): the fixed template - no warp net, normals from the central differences of the mapped grid, no
+        'sdf_deform' / 'grad_deform' / 'sdf_correct' in the dict.  fast_color_thres > 0 (:996-1003): the colour stage and a second
+        composite on the samples whose weight exceeds it; 'weights', 'raw_alpha', 'raw_rgb', 'gradient' then have the kept length and
+        'mask' is the weight mask over the in-box samples.  DESIGN 21."""
+        return self._render(rays_o, rays_d, viewdirs, use_deform, global_step, float(self.fast_color_thres), render_kwargs)
+
+    def _check_template_mode(self, use_deform):
+        if not use_deform and self.grad_mode != 'interpolate':
+            raise NotImplementedError(f"use_deform=False with grad_mode='{self.grad_mode}': the plain-template kernels form the "
+                                      "central differences of grad_mode='interpolate' only (voxurf_coarse.py:463-467)")
+
+    def _render(self, rays_o, rays_d, viewdirs, use_deform, global_step, color_thres, render_kwargs):
+        """forward() with the threshold as an argument: query_sdf_point_wocuda_render composites every sample (:903)."""
+        self._check_template_mode(use_deform)
         self._check_inputs(rays_o, rays_d, viewdirs)
         core = self._scene(render_kwargs)
         cfg = core.cfg
@@ -608,6 +643,7 @@ class Voxurf(torch.nn.Module):
         cap = max((M + 4095) // 4096 * 4096, 4096)
         ws = Workspace(N, cap, ro.device, backward=False, ctx=core.ctx, samples=sb)
         ws.M = M
+        ws.use_deform, ws.color_thres = bool(use_deform), color_thres
         ws.rays_o, ws.rays_d, ws.viewdirs = ro.detach(), rd.detach(), vd.detach()
         s_val, inv_s = self._inv_s(global_step, is_train)
         pe_w = self._pe_weights(cfg, progress, ro.device)
@@ -622,16 +658,23 @@ class Voxurf(torch.nn.Module):
         normal_marched = None
         if render_kwargs.get('render_grad', False):
             normal = gradient.detach() / (gradient.detach().norm(2, -1, keepdim=True) + 1e-6)
-            normal_marched = torch.zeros(N, 3, device=ro.device).index_add_(0, ws.ray_id[:M].long(),
+            kept_ray = ws.ray_id[:M] if color_thres <= 0 else ws.kept.ray_id[:ws.Mk]
+            normal_marched = torch.zeros(N, 3, device=ro.device).index_add_(0, kept_ray.long(),
                                                                              weights.detach().unsqueeze(-1) * normal)
-        return {
+        mask = sb['keep'].bool()
+        if color_thres > 0:                     # the reference's `mask` is rebound to the weight mask of the in-box samples (:997, :1079)
+            mask = torch.zeros(M, dtype=torch.bool, device=ro.device)
+            mask[ws.kept.idx[:ws.Mk].long()] = True
+        ret = {
             'alphainv_cum': alphainv_last, 'weights': weights, 'cum_weights': cum_weights, 'rgb_marched': rgb_marched,
             'normal_marched': normal_marched, 'raw_alpha': alpha, 'raw_rgb': rgb, 'depth': depth, 'disp': 1 / depth,
-            'mask': sb['keep'].bool(), 'mask_outbbox': torch.zeros(M, dtype=torch.bool, device=ro.device),
-            'gradient': gradient, 's_val': s_val, 'k0_tv': k0_tv, 'sdf_deform': sdf_deform,
-            'grad_deform': grad_deform, 'sdf_correct': correction,
-            '_t_min': ws.t_min, '_n_step': n_step,   # extras (not in the reference dict) for query_sdf_point_wocuda_render
+            'mask': mask, 'mask_outbbox': torch.zeros(M, dtype=torch.bool, device=ro.device),
+            'gradient': gradient, 's_val': s_val, 'k0_tv': k0_tv,
         }
+        if use_deform:
+            ret.update({'sdf_deform': sdf_deform, 'grad_deform': grad_deform, 'sdf_correct': correction})
+        ret.update({'_t_min': ws.t_min, '_n_step': n_step})   # extras (not in the reference dict) for query_sdf_point_wocuda_render
+        return ret
 
     def _inference_pass(self, rays_o, rays_d, viewdirs, global_step, render_kwargs, per_ray):
         """What inference and inference_rays share: checks, variable-length sampler (sample_pts_on_rays semantics), step distances,
@@ -683,25 +726,30 @@ class Voxurf(torch.nn.Module):
         with core.pass_scope(flat, pack):       # the weights are packed once per call and the record is dropped before returning
             core.forward(ws, channels_last_view(self.k0.grid), self.sdf.grid[0, 0].contiguous(), flat.view('sdf_ab'),
                          flat.view('rgbnet'), flat.view('warp'), inv_s, pe_w,
-                         normals=(ws.nrm, ws.normal_marched) if per_ray else None)
+                         normals=(ws.nrm, ws.normal_marched) if per_ray else None, color_thres=float(self.fast_color_thres))
         return ws, s_val
 
     @torch.no_grad()
     def inference(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
         """voxurf_coarse.py:1094-1222: variable-length sampler (sample_pts_on_rays semantics), forward chain only."""
         ws, s_val = self._inference_pass(rays_o, rays_d, viewdirs, global_step, render_kwargs, per_ray=False)
-        M, ray_id, step_id = ws.M, ws.ray_id, ws.step_k
-        gradient = ws.gradient[:M]
+        M, ray_id, step_id, s = ws.M, ws.ray_id, ws.step_k, ws
+        # the eikonal figure is taken over every sample, in front of the weight mask (:1138)
+        gradient_error = ((torch.linalg.norm(ws.gradient[:M], ord=2, dim=-1) - 1.0) ** 2).mean()
+        if self.fast_color_thres > 0:           # the kept samples (:1144-1151)
+            s = ws.kept
+            M = int(s.count.item())             # the one extra host read of this path
+            ray_id, step_id = s.ray_id, ws.step_k[s.idx[:M].long()]
+        gradient = s.gradient[:M]
         normal = gradient / (gradient.norm(2, -1, keepdim=True) + 1e-6)
         weights = ws.weights[:M]
         normal_marched = torch.zeros(ws.N, 3, device=rays_o.device).index_add_(0, ray_id[:M].long(), weights.unsqueeze(-1) * normal)
         depth = ws.depth_acc.clone()
         return {
             'alphainv_cum': ws.alphainv_last, 'weights': weights, 'cum_weights': ws.cum_weights.unsqueeze(-1),
-            'rgb_marched': ws.rgb_marched, 'normal_marched': normal_marched, 'raw_alpha': ws.alpha[:M],
+            'rgb_marched': ws.rgb_marched, 'normal_marched': normal_marched, 'raw_alpha': s.alpha[:M],
             'raw_rgb': ws.rgb[:M], 'depth': depth, 'disp': 1 / depth, 'mask': torch.ones_like(step_id[:M]).long(),
-            'mask_outbbox': None, 'gradient': gradient,
-            'gradient_error': ((torch.linalg.norm(gradient, ord=2, dim=-1) - 1.0) ** 2).mean(), 's_val': s_val,
+            'mask_outbbox': None, 'gradient': gradient, 'gradient_error': gradient_error, 's_val': s_val,
             'ray_id': ray_id[:M].long(), 'step_id': step_id[:M].long(),
         }
 
