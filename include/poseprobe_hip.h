@@ -229,7 +229,7 @@ int pp_color_feat_bwd(const pp_scene* sc, const float* k0_cl, const float* pts, 
  * Names (meaning and ranges: csrc/pp_common.h, csrc/pp_error.hip):
  *   arithmetic   mlp_split (bit mask: object-branch MLP kernels as 3 fp16 products per fp32 product; 0 = fp32 MFMA instructions),
  *                nerf_split (scene branch likewise), mlp_fused, nerf_chain
- *   scheduling   mlp_wgs, grid_chunks, nerf_chain_nw, nerf_chain_head, mlp_pack (see pp_mlp_pack),
+ *   scheduling   mlp_wgs, grid_chunks, nerf_chain_head, mlp_pack (see pp_mlp_pack),
  *                warp_lean (see pp_warp_lean_begin)
  * pp_nerf_fwd and pp_nerf_bwd of one pass (and the two stages of a two-stage backward) must see the same option values.
  * Unknown names / out-of-range values are refused; pp_context_get_option(NULL, ...) reads the defaults. */
@@ -609,8 +609,8 @@ int pp_nerf_bwd(const float* params, const float* ray, const float* depth, const
 /* Backward of pp_nerf_fwd with respect to the rays only (frozen parameters: test-time pose refinement): the launches of
  * pp_nerf_bwd without its nine weight-gradient products, in both routes of option nerf_chain and both arithmetics.  g_center and
  * g_ray are bit-identical to pp_nerf_bwd's on the same inputs; no parameter gradient exists (the two thin heads' sums, whose
- * kernels also record operand maxima the later kernels read, are added into a part of `scratch` that this route leaves
- * unread).  Same workspaces as pp_nerf_bwd (pp_nerf_workspace is unchanged).  A workspace attached with
+ * kernels also record operand maxima the later kernels read, are added into a part of `scratch` that nothing reads before
+ * the data-gradient kernels of either route overwrite it).  Same workspaces as pp_nerf_bwd (pp_nerf_workspace is unchanged).  A workspace attached with
  * pp_nerf_ordered_attach is neither used nor refused: nothing is flushed. */
 int pp_nerf_bwd_input(const float* params, const float* ray, const float* depth, const int32_t* count, int32_t n_rays,
                       int32_t n_samples, const float* acts, const float* rgb_samples, const float* g_rgb_samples,

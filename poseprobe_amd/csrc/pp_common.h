@@ -24,7 +24,6 @@ enum PPOption {
   PP_OPT_MLP_WGS,              // work-groups of the persistent object-branch MLP kernels (0 = one per CU); fewer leave CUs to a concurrent HBM-bound kernel
   PP_OPT_NERF_CHAIN,           // scene branch: bit 1 = the eight feature layers + density head of the forward pass as one kernel with the tile resident in LDS
                                // (pp_nerf_trunk.h), 3 = the data-gradient chain of the backward pass too (0 = one GEMM per layer)
-  PP_OPT_NERF_CHAIN_NW,        // scene branch: wavefronts per work-group of the fused chains (8: one 128-sample tile per CU, 4: two 64-sample tiles per CU)
   PP_OPT_NERF_CHAIN_HEAD,      // scene branch: 1 = the colour head's hidden layer as a ninth stage of the fused forward chain
   PP_OPT_MLP_PACK,             // 1: the split-precision object-branch MLP kernels read a weight pack recorded in the context by pp_mlp_pack
                                // for the params pointer they are given, 0: they always derive it in their prologues

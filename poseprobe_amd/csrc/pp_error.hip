@@ -20,8 +20,7 @@ struct PPOptionDef { const char* name; int dflt, lo, hi; };
 static const PPOptionDef g_opt_def[PP_OPT_COUNT] = {
     {"mlp_fused", 1, 0, 1},          {"grid_chunks", 0, 0, 4096},  {"nerf_split", 1, 0, 1},
     {"mlp_split", 31, 0, 31},        {"mlp_wgs", 0, 0, 4096},      {"nerf_chain", 3, 0, 3},
-    {"nerf_chain_nw", 4, 4, 8},      {"nerf_chain_head", 1, 0, 1}, {"mlp_pack", 1, 0, 1},
-    {"warp_lean", 1, 0, 1},
+    {"nerf_chain_head", 1, 0, 1},    {"mlp_pack", 1, 0, 1},        {"warp_lean", 1, 0, 1},
 };
 // compiled-in defaults: constants, never written after static initialisation
 static const struct PPDefaults {

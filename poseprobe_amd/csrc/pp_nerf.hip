@@ -83,14 +83,48 @@ static const int64_t NERF_WIMG_FLOATS = 256 * (64 + 256 * 6 + 320) + 10 * 8192; 
 static int64_t nerf_acts_floats(int64_t M) {
   return M * (64 + 256 * 6 + 320 + 288 + 128 + 1) + MX_SLOTS + (M + 127) / 128 * 128 * 64 + NERF_WIMG_FLOATS;
 }
-static const int64_t NERF_WT_FLOATS = 5 * 65536 + 320 * 256 + 256 * 288 + 64 * 256 + 288 * 128;
-// images of the transposed weights for the data-gradient GEMMs: R0^T (K = 128), W7^T (K = 288), W1^T .. W6^T (K = 256)
-static const int64_t NERF_WTIMG_FLOATS = 256 * (128 + 288 + 6 * 256);
 static const int64_t NERF_PART_FLOATS = 512 * 392;       // NERF_PART_WGS x NERF_PART_LD: partial rows of the thin heads' backward kernels
-static int64_t nerf_scratch_floats(int64_t M, int64_t R) {
-  // (the last term: d(layer 6) .. d(layer 0) side by side for the fused data-gradient chain, whose weight-gradient products run after it)
-  return M * (320 * 2 + 64 * 2) + R * (128 + 32) + NERF_WT_FLOATS + NERF_WTIMG_FLOATS + NERF_PART_FLOATS + M * 256 * 7;
+
+// scratch of the backward pass; M = samples, R = rays.  Both routes (NerfRoute::chain_bwd) use d7, dH, dEnc0 .. dView, part, DY and
+// of the transposed weights WT[0], WT[4] (encoding gradients) and R0T (view gradient); both fill all of WT.  The rest of WT and the
+// three image groups as such feed the layer-by-layer data-gradient GEMMs only: the fused chain reads its weights through
+// k_pack_trunk's stream, which starts at r0t_img and runs over the three groups (TR_STEPS x TR_WSTEP bytes, less than their sum).
+// d7: d(layer 7), 288 of the 320 columns used (0 .. 255 through the colour head, 256 = d raw from the density head, 257 .. 287 zero)
+// dH: d(hidden layer of the colour head), [M][128] at the head of an [M][320] block; the other 192 M floats are unused (the block
+//     used to take turns with d7 as a data-gradient buffer: giving it back changes pp_nerf_workspace's numbers)
+// DY[l]: d(layer l), l = 0 .. 6, side by side: the weight-gradient products run after the whole data-gradient chain
+// floats: where the walk ends = the size of the block
+struct NerfScratch {
+  float* d7; float* dH; float* dEnc0; float* dEncS; float* dHsum; float* dView;
+  float* WT[8]; float* R0T;                                 // W_l^T [in][256] (l = 7: [256][288] with the density column), R0^T [288][128]
+  _Float16* r0t_img; _Float16* wt7_img; _Float16* wt_img[7]; // split-precision images (pp_gemm_planes.h) of R0^T (K = 128), W7^T (K = 288), W1^T .. W6^T (K = 256); [0] unused
+  float* part;                                              // [NERF_PART_WGS][NERF_PART_LD]
+  float* DY[7];
+  int64_t floats;
+};
+static NerfScratch nerf_scratch(float* base, int64_t M, int64_t R) {      // base == nullptr: only `floats` means anything
+  NerfScratch X;
+  int64_t o = 0;
+  auto take = [&](int64_t n) { float* p = base ? base + o : nullptr; o += n; return p; };
+  auto take_img = [&](int64_t K) { return reinterpret_cast<_Float16*>(take(256 * K)); };      // hi + lo halfs = 4 B per weight
+  X.d7 = take(M * 320);
+  X.dH = take(M * 320);
+  X.dEnc0 = take(M * 64);
+  X.dEncS = take(M * 64);
+  X.dHsum = take(R * 128);
+  X.dView = take(R * 32);
+  for (int l = 0; l < 8; ++l) X.WT[l] = take(256 * (l == 7 ? 288 : NERF_IN_LD[l]));
+  X.R0T = take(288 * 128);
+  X.r0t_img = take_img(128);
+  X.wt7_img = take_img(288);
+  X.wt_img[0] = nullptr;
+  for (int l = 1; l <= 6; ++l) X.wt_img[l] = take_img(256);
+  X.part = take(NERF_PART_FLOATS);
+  for (int l = 0; l < 7; ++l) X.DY[l] = take(M * 256);
+  X.floats = o;
+  return X;
 }
+static int64_t nerf_scratch_floats(int64_t M, int64_t R) { return nerf_scratch(nullptr, M, R).floats; }
 
 extern "C" int pp_nerf_workspace(int64_t n_samples, int64_t n_rays, int64_t* acts_floats, int64_t* scratch_floats) {
   PP_REQUIRE(acts_floats && scratch_floats && n_samples > 0 && n_rays > 0, "bad arguments");
@@ -673,15 +707,19 @@ struct NerfRoute {
   // nerf_chain = 3: the data-gradient chain of the backward pass likewise; the ReLU masks then travel in the fused kernels' own
   // layout, so both passes of a step must see the same value
   bool chain_bwd;
-  // nerf_chain_nw: wavefronts per work-group of the fused chains: 8 = one work-group on a 128-sample tile per CU, 4 = two
-  // work-groups on 64-sample tiles per CU (one's epilogue beside the other's matrix instructions; twice the weight traffic from L2)
-  int nw;
   // nerf_chain_head: the colour head's 288 -> 128 layer rides as a ninth stage of the fused forward chain
   bool head;
   explicit NerfRoute(const int* o)
       : split(o[PP_OPT_NERF_SPLIT] == 1), chain_fwd(split && (o[PP_OPT_NERF_CHAIN] & 1)), chain_bwd(split && o[PP_OPT_NERF_CHAIN] == 3),
-        nw(o[PP_OPT_NERF_CHAIN_NW] == 4 ? 4 : 8), head(chain_fwd && o[PP_OPT_NERF_CHAIN_HEAD] == 1) {}
+        head(chain_fwd && o[PP_OPT_NERF_CHAIN_HEAD] == 1) {}
 };
+
+// a fused chain (pp_nerf_trunk.h): 64-row tiles on four wavefronts, two work-groups per CU
+template <bool BWD, bool MROW>
+static void launch_trunk(const TrunkArgs& T, const int32_t* count, int M, hipStream_t st) {
+  const int tiles = pp_div_up(M, 64), cus = pp_num_cus();
+  hipLaunchKernelGGL((k_nerf_trunk<BWD, MROW>), dim3(tiles < 2 * cus ? tiles : 2 * cus), dim3(256), 0, st, T, count, M);
+}
 
 template <int EPI>
 static void nerf_gemm(hipStream_t st, bool split, const float* A, int lda, const float* W, int ldw, int K, int Nout, const float* bias,
@@ -764,7 +802,7 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
       TrunkPackJobs P;
       for (int l = 0; l < 8; ++l) { P.src[l] = params + L.w[l]; P.ld[l] = NERF_IN_LD[l]; P.mx_w[l] = MX_W0 + l; }
       P.src[8] = params + L.r0; P.ld[8] = 288; P.mx_w[8] = MX_R0;        // the colour head's hidden layer rides as a ninth stage
-      P.nsteps = rt.head ? TR_STEPS + 10 : TR_STEPS; P.nw = rt.nw;
+      P.nsteps = rt.head ? TR_STEPS + 10 : TR_STEPS;
       hipLaunchKernelGGL(k_pack_trunk<false>, dim3(P.nsteps * 4), dim3(256), 0, st, P, mx, reinterpret_cast<unsigned char*>(A.wimg[0]));
     } else {
       PlanePackJobs P;
@@ -789,16 +827,8 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
     T.wd = params + L.wd; T.bd = params + L.bd; T.raw = A.raw; T.density = density_samples;
     T.mx = mx; T.mx_in = MX_ENC;
     T.head = rt.head; T.out[8] = A.h; T.ld[8] = 128; T.bias[8] = params + L.br0; T.mx_w[8] = MX_R0; T.in2 = A.a[7] + 256; T.in2_ld = 288;
-    const int cus = pp_num_cus();
-    if (rt.nw == 4) {                       // 64-row tiles, two work-groups per CU
-      const int tiles = pp_div_up(M, 64), grid = tiles < 2 * cus ? tiles : 2 * cus;
-      if (rt.chain_bwd) hipLaunchKernelGGL((k_nerf_trunk<false, true, 4>), dim3(grid), dim3(256), 0, st, T, count, M);
-      else hipLaunchKernelGGL((k_nerf_trunk<false, false, 4>), dim3(grid), dim3(256), 0, st, T, count, M);
-    } else {
-      const int tiles = pp_div_up(M, 128), grid = tiles < cus ? tiles : cus;
-      if (rt.chain_bwd) hipLaunchKernelGGL((k_nerf_trunk<false, true, 8>), dim3(grid), dim3(512), 0, st, T, count, M);
-      else hipLaunchKernelGGL((k_nerf_trunk<false, false, 8>), dim3(grid), dim3(512), 0, st, T, count, M);
-    }
+    if (rt.chain_bwd) launch_trunk<false, true>(T, count, M, st);       // masks in the layout the fused backward chain reads
+    else launch_trunk<false, false>(T, count, M, st);
   } else {
     const float* in = A.enc;
     for (int l = 0; l < 8; ++l) {
@@ -823,8 +853,14 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
 // weight-gradient products are not launched and params_grad is not touched (it may be NULL); every other launch is the one
 // pp_nerf_bwd issues, so g_center / g_ray are the same bits.  The two thin heads' k_nerf_part_finish launches stay: they also
 // record the operand maxima (MX_DH, MX_P) that the split-precision data-gradient kernels read afterwards.  Their parameter sums
-// then land in a discard area of 657 floats inside `scratch` that no kernel of this route reads: the transposed copy of W1 when
-// the fused chain runs (the chain reads its weights straight from the parameters), else the chain's d(layer 0) block.
+// then land in a discard area: the first 657 floats of the DY block (1792 M floats, so it fits for every M >= 1; at M = 2 it reaches
+// past DY[0] into DY[1]).  Nothing reads DY before stage 2 - the only kernels between the two k_nerf_part_finish launches and
+// stage 2 are the colour head's and the density head's, which work on dH, d7, dHsum, dView and part - and stage 2 of either route
+// writes every row of DY[6] .. DY[0] that a later kernel reads.
+//
+// Three stages.  1: the heads - d(hidden of the colour head) in dH, d raw in column 256 of d7.  2: the data gradients, the one
+// route-specific part - d(layer 7) into d7, d(layer l) into DY[l], by one k_nerf_trunk launch or by eight GEMMs.  3: the weight
+// gradients of W7 .. W0 and the encoding gradients, on d7 / DY whichever route filled them.
 static void nerf_bwd_body(const float* params, const float* ray, const float* depth, const int32_t* count, int32_t n_rays,
                          int32_t n_samples, const float* acts, const float* rgb_samples, const float* g_rgb_samples,
                          const float* g_density_samples, float* scratch, float* params_grad, float* g_center, float* g_ray,
@@ -835,25 +871,14 @@ static void nerf_bwd_body(const float* params, const float* ray, const float* de
   const int R = n_rays, S = n_samples, M = R * S;
   const NerfLayout L = nerf_layout();
   NerfActs A = nerf_acts(const_cast<float*>(acts), M);
-  float* P = scratch;
-  float* Q = P + (size_t)M * 320;
-  float* dEnc0 = Q + (size_t)M * 320;
-  float* dEncS = dEnc0 + (size_t)M * 64;
-  float* dHsum = dEncS + (size_t)M * 64;
-  float* dView = dHsum + (size_t)R * 128;
-  float* wt = dView + (size_t)R * 32;
-  float* WT[8];
-  {
-    float* p = wt;
-    for (int l = 0; l < 8; ++l) { WT[l] = p; p += (l == 7) ? 256 * 288 : 256 * NERF_IN_LD[l]; }
-  }
-  float* R0T = WT[7] + 256 * 288;                  // [288][128]
-  _Float16* r0t_img = reinterpret_cast<_Float16*>(wt + NERF_WT_FLOATS);
-  float* part = wt + NERF_WT_FLOATS + NERF_WTIMG_FLOATS;      // [NERF_PART_WGS][NERF_PART_LD]
-  _Float16* wt7_img = r0t_img + 2 * 256 * 128;
-  _Float16* wt_img[7];
-  for (int l = 1; l <= 6; ++l) wt_img[l] = wt7_img + 2 * 256 * 288 + (size_t)(l - 1) * 2 * 256 * 256;
+  const NerfScratch Sc = nerf_scratch(scratch, M, R);
+  float* const* WT = Sc.WT;
+  float* const* DY = Sc.DY;
+  float* const d7 = Sc.d7;
+  float* const dH = Sc.dH;
   dim3 b(256);
+
+  // ---- stage 1: the heads
   // transposed weights for the data-gradient GEMMs (2 MB, L2 resident)
   {
     NerfTransposeJobs J;
@@ -861,7 +886,7 @@ static void nerf_bwd_body(const float* params, const float* ray, const float* de
       J.src[l] = params + L.w[l]; J.dst[l] = WT[l]; J.lds[l] = NERF_IN_LD[l]; J.rows[l] = 256; J.cols[l] = NERF_IN_LD[l];
       J.ldd[l] = (l == 7) ? 288 : 256;
     }
-    J.src[8] = params + L.r0; J.dst[8] = R0T; J.lds[8] = 288; J.rows[8] = 128; J.cols[8] = 288; J.ldd[8] = 128;
+    J.src[8] = params + L.r0; J.dst[8] = Sc.R0T; J.lds[8] = 288; J.rows[8] = 128; J.cols[8] = 288; J.ldd[8] = 128;
     hipLaunchKernelGGL(k_nerf_transpose_all, dim3(64, 9), b, 0, st, J);
   }
   hipLaunchKernelGGL(k_nerf_wd_column, dim3(1), b, 0, st, params + L.wd, WT[7]);
@@ -870,10 +895,8 @@ static void nerf_bwd_body(const float* params, const float* ray, const float* de
   float* mx = rt.split ? A.mx : nullptr;
   if (mx) hipMemsetAsync(mx + MX_DH, 0, (MX_DHSUM - MX_DH + 1) * sizeof(float), st);
   const bool chain = rt.chain_bwd;
-  float* DY[7];                                    // d(pre-activation of layer l), l = 0 .. 6, for the fused chain
-  for (int l = 0; l < 7; ++l) DY[l] = part + NERF_PART_FLOATS + (size_t)l * M * 256;
   // where k_nerf_part_finish adds the heads' parameter sums: R1 | br1 | wd | bd
-  float* discard = chain ? WT[1] : DY[0];          // input_only: 65536 / at least 7 x 256 floats that this route leaves unread
+  float* discard = DY[0];                          // input_only: the head of the DY block (see above)
   float* g_r1 = input_only ? discard : params_grad + L.r1;
   float* g_br1 = input_only ? discard + 384 : params_grad + L.br1;
   float* g_wd = input_only ? discard + 400 : params_grad + L.wd;
@@ -887,96 +910,71 @@ static void nerf_bwd_body(const float* params, const float* ray, const float* de
     TrunkPackJobs J;
     J.src[0] = params + L.r0; J.ld[0] = 288; J.mx_w[0] = MX_R0;
     for (int s_ = 1; s_ < 8; ++s_) { J.src[s_] = params + L.w[8 - s_]; J.ld[s_] = NERF_IN_LD[8 - s_]; J.mx_w[s_] = MX_W0 + 8 - s_; }
-    J.nsteps = TR_STEPS; J.nw = 0;
-    hipLaunchKernelGGL(k_pack_trunk<true>, dim3(TR_STEPS * 4), dim3(256), 0, st, J, mx, reinterpret_cast<unsigned char*>(r0t_img));
+    J.nsteps = TR_STEPS;
+    hipLaunchKernelGGL(k_pack_trunk<true>, dim3(TR_STEPS * 4), dim3(256), 0, st, J, mx, reinterpret_cast<unsigned char*>(Sc.r0t_img));
   } else if (mx) {
     PlanePackJobs P;
     P.n = 8;
-    P.src[0] = R0T; P.dst[0] = r0t_img; P.ld[0] = 128; P.K[0] = 128; P.mx_slot[0] = MX_R0;
-    P.src[7] = WT[7]; P.dst[7] = wt7_img; P.ld[7] = 288; P.K[7] = 288; P.mx_slot[7] = MX_W0 + 7;
-    for (int l = 1; l <= 6; ++l) { P.src[l] = WT[l]; P.dst[l] = wt_img[l]; P.ld[l] = 256; P.K[l] = 256; P.mx_slot[l] = MX_W0 + l; }
+    P.src[0] = Sc.R0T; P.dst[0] = Sc.r0t_img; P.ld[0] = 128; P.K[0] = 128; P.mx_slot[0] = MX_R0;
+    P.src[7] = WT[7]; P.dst[7] = Sc.wt7_img; P.ld[7] = 288; P.K[7] = 288; P.mx_slot[7] = MX_W0 + 7;
+    for (int l = 1; l <= 6; ++l) { P.src[l] = WT[l]; P.dst[l] = Sc.wt_img[l]; P.ld[l] = 256; P.K[l] = 256; P.mx_slot[l] = MX_W0 + l; }
     hipLaunchKernelGGL(k_pack_planes, dim3(16, 8), dim3(256), 0, st, P, mx);
   }
   auto slot = [&](int i) -> float* { return mx ? mx + i : nullptr; };
 
   // colour head
-  float* dH = Q;                                   // [M][128]
   {
     const int wgs = min(pp_div_up(M, NERF_STRIP), NERF_PART_WGS);
-    hipLaunchKernelGGL(k_nerf_rgb_bwd, dim3(wgs), dim3(512), 0, st, params + L.r1, A.h, rgb_samples, g_rgb_samples, M, dH, part);
-    hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(388, 64)), dim3(1024), 0, st, part, wgs, g_r1, 384, g_br1, 3,
+    hipLaunchKernelGGL(k_nerf_rgb_bwd, dim3(wgs), dim3(512), 0, st, params + L.r1, A.h, rgb_samples, g_rgb_samples, M, dH, Sc.part);
+    hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(388, 64)), dim3(1024), 0, st, Sc.part, wgs, g_r1, 384, g_br1, 3,
                        slot(MX_DH));
   }
   gemm_tn(dH, 128, 128, A.a[7], 288, 288, L.r0, L.br0, slot(MX_DH), slot(MX_A0 + 7));
-  hipLaunchKernelGGL(k_nerf_ray_sum, dim3(R < 512 ? R : 512), dim3(512), 0, st, dH, R, S, dHsum, slot(MX_DHSUM));
-  nerf_gemm<EPI_PLAIN>(st, rt.split, dHsum, 128, R0T + 256 * 128, 128, 128, 32, nullptr, nullptr, 0, dView, 32, count, R, slot(MX_DHSUM),
-                       slot(MX_R0), nullptr);
-  if (chain) {
-    // d raw (column 256 of P) and the density head's own gradients first: the chain reads that column
-    {
-      const int wgs = min(pp_div_up(M, NERF_DSTRIP), NERF_PART_WGS);
-      hipLaunchKernelGGL(k_nerf_density_bwd, dim3(wgs), dim3(512), 0, st, A.a[6], A.raw, g_density_samples, M, P, part);
-      hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(258, 64)), dim3(1024), 0, st, part, wgs, g_wd, 256, g_bd, 1,
-                         slot(MX_P));
-    }
-    // d(layer 7) .. d(layer 0) in one kernel (pp_nerf_trunk.h), each written once for the weight-gradient products below
+  hipLaunchKernelGGL(k_nerf_ray_sum, dim3(R < 512 ? R : 512), dim3(512), 0, st, dH, R, S, Sc.dHsum, slot(MX_DHSUM));
+  nerf_gemm<EPI_PLAIN>(st, rt.split, Sc.dHsum, 128, Sc.R0T + 256 * 128, 128, 128, 32, nullptr, nullptr, 0, Sc.dView, 32, count, R,
+                       slot(MX_DHSUM), slot(MX_R0), nullptr);
+  // density head: d raw (column 256 of d7, zeros in 257 .. 287) and its own gradients.  In front of stage 2: the fused chain reads
+  // that column; the layer-by-layer route's first GEMM writes columns 0 .. 255 only, and MX_P takes both maxima in either order
+  {
+    const int wgs = min(pp_div_up(M, NERF_DSTRIP), NERF_PART_WGS);
+    hipLaunchKernelGGL(k_nerf_density_bwd, dim3(wgs), dim3(512), 0, st, A.a[6], A.raw, g_density_samples, M, d7, Sc.part);
+    hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(258, 64)), dim3(1024), 0, st, Sc.part, wgs, g_wd, 256, g_bd, 1,
+                       slot(MX_P));
+  }
+
+  // ---- stage 2: d(layer 7) into columns 0 .. 255 of d7, d(layer l) into DY[l], each written once (slots MX_P, MX_DY6 + 6 - l)
+  if (chain) {                                       // one kernel (pp_nerf_trunk.h)
     TrunkArgs T;
     memset(&T, 0, sizeof(T));
     T.in = dH; T.in_ld = 128;
-    T.out[0] = P; T.ld[0] = 288; T.mx_w[0] = MX_R0; T.mx_out[0] = MX_P; T.bitsr[0] = A.bits[7];
+    T.out[0] = d7; T.ld[0] = 288; T.mx_w[0] = MX_R0; T.mx_out[0] = MX_P; T.bitsr[0] = A.bits[7];
     for (int s_ = 1; s_ < 8; ++s_) {
       T.out[s_] = DY[7 - s_]; T.ld[s_] = 256; T.mx_w[s_] = MX_W0 + 8 - s_; T.mx_out[s_] = MX_DY6 + s_ - 1; T.bitsr[s_] = A.bits[7 - s_];
     }
-    T.wstream = reinterpret_cast<const unsigned char*>(r0t_img);
-    T.wd = params + L.wd; T.draw = P + 256; T.draw_ld = 288;
+    T.wstream = reinterpret_cast<const unsigned char*>(Sc.r0t_img);
+    T.wd = params + L.wd; T.draw = d7 + 256; T.draw_ld = 288;
     T.mx = mx; T.mx_in = MX_DH;
-    const int cus = pp_num_cus();
-    if (rt.nw == 4) {
-      const int tiles = pp_div_up(M, 64);
-      hipLaunchKernelGGL((k_nerf_trunk<true, true, 4>), dim3(tiles < 2 * cus ? tiles : 2 * cus), dim3(256), 0, st, T, count, M);
-    } else {
-      const int tiles = pp_div_up(M, 128);
-      hipLaunchKernelGGL((k_nerf_trunk<true, true, 8>), dim3(tiles < cus ? tiles : cus), dim3(512), 0, st, T, count, M);
-    }
-    gemm_tn(P, 288, 256, A.a[6], 256, 256, L.w[7], L.b[7], slot(MX_P), slot(MX_A0 + 6));
-    for (int l = 6; l >= 1; --l)
-      gemm_tn(DY[l], 256, 256, A.a[l - 1], NERF_OUT_LD[l - 1], NERF_IN_LD[l], L.w[l], L.b[l], slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1));
-    nerf_gemm<EPI_PLAIN>(st, rt.split, DY[4], 256, WT[4] + 256 * 256, 256, 256, 64, nullptr, nullptr, 0, dEncS, 64, count, M,
-                         slot(MX_DY6 + 2), slot(MX_W0 + 4), nullptr);
-    gemm_tn(DY[0], 256, 256, A.enc, 64, 64, L.w[0], L.b[0], slot(MX_DY6 + 6), slot(MX_ENC));
-    nerf_gemm<EPI_PLAIN>(st, rt.split, DY[0], 256, WT[0], 256, 256, 64, nullptr, nullptr, 0, dEnc0, 64, count, M, slot(MX_DY6 + 6),
-                         slot(MX_W0), nullptr);
-  } else {
-    // last feature layer: columns 0..255 through the colour head, column 256 from the density
-    nerf_gemm<EPI_MASK>(st, rt.split, dH, 128, R0T, 128, 128, 256, nullptr, A.a[7], 288, P, 288, count, M, slot(MX_DH), slot(MX_R0),
-                        slot(MX_P), A.bits[7], r0t_img);
-    {
-      const int wgs = min(pp_div_up(M, NERF_DSTRIP), NERF_PART_WGS);
-      hipLaunchKernelGGL(k_nerf_density_bwd, dim3(wgs), dim3(512), 0, st, A.a[6], A.raw, g_density_samples, M, P, part);
-      hipLaunchKernelGGL(k_nerf_part_finish, dim3(pp_div_up(258, 64)), dim3(1024), 0, st, part, wgs, g_wd, 256, g_bd, 1,
-                         slot(MX_P));
-    }
-    gemm_tn(P, 288, 256, A.a[6], 256, 256, L.w[7], L.b[7], slot(MX_P), slot(MX_A0 + 6));
-    nerf_gemm<EPI_MASK>(st, rt.split, P, 288, WT[7], 288, 288, 256, nullptr, A.a[6], 256, Q, 256, count, M, slot(MX_P), slot(MX_W0 + 7),
-                        slot(MX_DY6), A.bits[6], wt7_img);
-    float* cur = Q;
-    float* nxt = P;
-    for (int l = 6; l >= 1; --l) {                   // cur = d(pre-activation of layer l), [M][256]
-      const float* x = A.a[l - 1];
-      const int ldx = NERF_OUT_LD[l - 1];            // 320 for layer 4's input (features + skip columns)
-      gemm_tn(cur, 256, 256, x, ldx, NERF_IN_LD[l], L.w[l], L.b[l], slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1));
-      nerf_gemm<EPI_MASK>(st, rt.split, cur, 256, WT[l], 256, 256, 256, nullptr, x, ldx, nxt, 256, count, M, slot(MX_DY6 + 6 - l),
-                          slot(MX_W0 + l), slot(MX_DY6 + 7 - l), A.bits[l - 1], wt_img[l]);
-      if (l == 4)                                    // skip columns: gradient of the encoding, no activation in between
-        nerf_gemm<EPI_PLAIN>(st, rt.split, cur, 256, WT[4] + 256 * 256, 256, 256, 64, nullptr, nullptr, 0, dEncS, 64, count, M,
-                             slot(MX_DY6 + 2), slot(MX_W0 + 4), nullptr);
-      float* t = cur; cur = nxt; nxt = t;
-    }
-    gemm_tn(cur, 256, 256, A.enc, 64, 64, L.w[0], L.b[0], slot(MX_DY6 + 6), slot(MX_ENC));
-    nerf_gemm<EPI_PLAIN>(st, rt.split, cur, 256, WT[0], 256, 256, 64, nullptr, nullptr, 0, dEnc0, 64, count, M, slot(MX_DY6 + 6),
-                         slot(MX_W0), nullptr);
+    launch_trunk<true, true>(T, count, M, st);
+  } else {                                           // one GEMM per layer, masked by the ReLU bits of its output's layer
+    nerf_gemm<EPI_MASK>(st, rt.split, dH, 128, Sc.R0T, 128, 128, 256, nullptr, A.a[7], 288, d7, 288, count, M, slot(MX_DH), slot(MX_R0),
+                        slot(MX_P), A.bits[7], Sc.r0t_img);
+    nerf_gemm<EPI_MASK>(st, rt.split, d7, 288, WT[7], 288, 288, 256, nullptr, A.a[6], 256, DY[6], 256, count, M, slot(MX_P),
+                        slot(MX_W0 + 7), slot(MX_DY6), A.bits[6], Sc.wt7_img);
+    for (int l = 6; l >= 1; --l)                     // (ldm 320: layer 3's output carries the skip columns)
+      nerf_gemm<EPI_MASK>(st, rt.split, DY[l], 256, WT[l], 256, 256, 256, nullptr, A.a[l - 1], NERF_OUT_LD[l - 1], DY[l - 1], 256, count, M,
+                          slot(MX_DY6 + 6 - l), slot(MX_W0 + l), slot(MX_DY6 + 7 - l), A.bits[l - 1], Sc.wt_img[l]);
   }
-  hipLaunchKernelGGL(k_nerf_encode_bwd, dim3(R), b, 0, st, A.enc, dEnc0, dEncS, dView, A.a[7], ray, depth, R, S, g_center,
+
+  // ---- stage 3: weight gradients of W7 .. W0; encoding gradients through the skip columns of W4 and through W0 (no activation in between)
+  gemm_tn(d7, 288, 256, A.a[6], 256, 256, L.w[7], L.b[7], slot(MX_P), slot(MX_A0 + 6));
+  for (int l = 6; l >= 1; --l)
+    gemm_tn(DY[l], 256, 256, A.a[l - 1], NERF_OUT_LD[l - 1], NERF_IN_LD[l], L.w[l], L.b[l], slot(MX_DY6 + 6 - l), slot(MX_A0 + l - 1));
+  nerf_gemm<EPI_PLAIN>(st, rt.split, DY[4], 256, WT[4] + 256 * 256, 256, 256, 64, nullptr, nullptr, 0, Sc.dEncS, 64, count, M,
+                       slot(MX_DY6 + 2), slot(MX_W0 + 4), nullptr);
+  gemm_tn(DY[0], 256, 256, A.enc, 64, 64, L.w[0], L.b[0], slot(MX_DY6 + 6), slot(MX_ENC));
+  nerf_gemm<EPI_PLAIN>(st, rt.split, DY[0], 256, WT[0], 256, 256, 64, nullptr, nullptr, 0, Sc.dEnc0, 64, count, M, slot(MX_DY6 + 6),
+                       slot(MX_W0), nullptr);
+  hipLaunchKernelGGL(k_nerf_encode_bwd, dim3(R), b, 0, st, A.enc, Sc.dEnc0, Sc.dEncS, Sc.dView, A.a[7], ray, depth, R, S, g_center,
                      g_ray);
 }
 

@@ -1,5 +1,5 @@
 // The eight 256-wide feature layers of the scene-branch NeRF (lib/bg_nerf/source/models/frequency_nerf.py:152-170: 63 -> 256 x 8,
-// skip connection at layer 4) as ONE kernel, and their data-gradient chain as one more: a work-group carries a 128-sample tile
+// skip connection at layer 4) as ONE kernel, and their data-gradient chain as one more: a work-group carries a 64-sample tile
 // through all eight stages, so a stage's input never comes back from HBM - every stage's output is still WRITTEN (the backward
 // pass / the weight-gradient products need it), which halves the activation traffic of the layer-by-layer path
 // (pp_gemm_planes.h: 1 KB in + 1 KB out per sample and layer) and removes its per-K-chunk barriers.  Same arithmetic: three
@@ -7,16 +7,16 @@
 //
 // Data flow per tile
 //   * the activation tile lives in LDS as the split-precision image the matrix instructions read: 8 K-chunks of
-//     [128 rows][32 hi | 32 lo halfs], 16-byte slots XOR-swizzled (pl_slot_off), 128 KB;
+//     [64 rows][32 hi | 32 lo halfs], 16-byte slots XOR-swizzled (pl_slot_off), 64 KB;
 //   * what enters a chain from HBM - the 64 encoded-point columns (input of layer 0, skip input of layer 4), the 128 columns of
-//     the colour head's hidden gradient in the backward chain - goes through a separate one-chunk image E (16 KB), fetched into
+//     the colour head's hidden gradient in the backward chain - goes through a separate one-chunk image E (8 KB), fetched into
 //     registers well ahead of its use;
-//   * wavefront w of eight owns output columns 32 w .. 32 w + 31 of all 128 rows.  The matrix instructions run TRANSPOSED,
+//   * wavefront w of four owns the 32-column blocks 2 w and 2 w + 1 of all 64 rows.  The matrix instructions run TRANSPOSED,
 //     D[n][row] = sum_k W[n][k] X[row][k]: the weights are the first operand and come straight from L2 into registers
-//     (k_pack_trunk lays them out in the order of use, so a wavefront's stream is linear: 4 KB per step, double-buffered one
+//     (k_pack_trunk lays them out in the order of use, so a wavefront's stream is linear: 8 KB per step, double-buffered one
 //     step ahead), the activations are the second operand, read from the LDS image.  A lane then holds 4 x 4 CONSECUTIVE
-//     output columns of one row per 32 x 32 block: the stage's output goes into chunk w of the NEXT stage's image as 8-byte
-//     LDS writes - wavefront w's columns are exactly K-chunk w of the next stage - and from there to HBM while the next stage
+//     output columns of one row per 32 x 32 block: the stage's output goes into the NEXT stage's image as 8-byte LDS writes
+//     - column block c is exactly K-chunk c of the next stage - and from there to HBM while the next stage
 //     runs (see the note at the resident chunks); the last stage's output is stored from the accumulators;
 //   * no barrier inside a stage (the image is read-only while a stage runs, weights are private to a wavefront): two per
 //     stage around the in-place rewrite of the image, two per streamed chunk.
@@ -27,7 +27,7 @@
 // layer-by-layer data-gradient kernels read (pp_gemm.h gemm_epilogue: 16 rows of a column per 16-bit word; a lane holds 16
 // columns of one row here, so the 32 x 32 bit block of a wavefront is transposed with v_cmp - the 64-lane mask of one
 // accumulator register = two columns x 32 rows -, v_writelane and a nibble shuffle); MROW = true writes the lane's own 16
-// columns as one word, [row][wavefront][lane half], which is what the fused backward chain reads back in the same lane.
+// columns as one word, [row][column block][lane half], which is what the fused backward chain reads back in the same lane.
 // The density head (row 0 of the reference's last feature layer applied to layer 6's output) is folded into layer 6's
 // epilogue: per-wavefront partial dot products through LDS, summed in a fixed order; its gradient enters the backward chain
 // as the rank-1 term d raw[row] * wd[k] in the epilogue of the stage that produces d(layer 6).
@@ -45,7 +45,7 @@ struct TrunkArgs {
   int ld[9];
   const float* bias[9];                 // forward
   uint32_t* bits[8];                    // forward, MROW = false: ReLU masks in the layer-by-layer layout (pairs of its 16-bit words)
-  uint16_t* bitsr[8];                   // MROW: [row][8 wavefronts][2 lane halves] words; forward writes stage s's, backward reads the mask of stage s's OUTPUT
+  uint16_t* bitsr[8];                   // MROW: [row][8 column blocks][2 lane halves] words; forward writes stage s's, backward reads the mask of stage s's OUTPUT
   const unsigned char* wstream;         // k_pack_trunk's image
   const float* wd;                      // density head weights (forward: NULL = not folded; backward: the rank-1 term)
   const float* bd;
@@ -73,7 +73,7 @@ __host__ __device__ __forceinline__ void tr_step_layer(int g, int& l, int& kc) {
 // backward  stage s = 0: R0[i][o], stages 1 .. 7: W_{8 - s}[i][o] with o = 32 w + (lane & 31), i = 32 kc + 16 ks + 8 (lane >> 5) .. + 7
 //           (src[s] = the stage's matrix with rows i, [.][ld]: the transposed read happens here, once per pass)
 // scaled by the matrix' power of two (slot mx_w[stage])
-struct TrunkPackJobs { const float* src[9]; int ld[9]; int mx_w[9]; int nsteps; int nw; };
+struct TrunkPackJobs { const float* src[9]; int ld[9]; int mx_w[9]; int nsteps; };
 template <bool BWD>
 static __global__ __launch_bounds__(256) void k_pack_trunk(TrunkPackJobs J, const float* __restrict__ mx, unsigned char* __restrict__ dst) {
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -84,14 +84,11 @@ static __global__ __launch_bounds__(256) void k_pack_trunk(TrunkPackJobs J, cons
   else if (g < TR_STEPS) tr_step_layer(g, l, kc);
   else { l = 8; kc = g == TR_STEPS ? 8 : g - TR_STEPS - 2; }          // head: the view chunk (input columns 256 .. 287), a zero step, chunks 0 .. 7
   const float s = pp_split_scale(mx[J.mx_w[l]]);
-  // column block this slot of the stream feeds: the wavefront's own everywhere except in the head stage, whose 128 columns are
-  // blocks 0 .. 3: with four wavefronts (two slots each) wavefront w takes block w in its FIRST slot, with eight wavefront w < 4 block w
+  // column block this slot of the stream feeds (slots 2 w', 2 w' + 1 belong to wavefront w' of the chain): the slot's own
+  // everywhere except in the head stage, whose 128 columns are blocks 0 .. 3: wavefront w' takes block w' in its FIRST slot
   int blk = w;
   bool zero = false;
-  if (!BWD && l == 8) {
-    if (J.nw == 4) { blk = w >> 1; zero = (w & 1) != 0; } else zero = w >= 4;
-    if (g == TR_STEPS + 1) zero = true;
-  }
+  if (!BWD && l == 8) { blk = w >> 1; zero = (w & 1) != 0 || g == TR_STEPS + 1; }
   const int o = 32 * blk + (lane & 31), i0 = kc * 32 + ks * 16 + (lane >> 5) * 8;
   float v[8];
   if (zero) {
@@ -150,16 +147,16 @@ __device__ __forceinline__ void tr_step(const unsigned char* img, const pp_half8
 // BWD = false: stages = layers 0 .. 7 (bias, ReLU, masks out, density head at layer 6), streamed chunks: 2 in front of layers 0 and 4
 // BWD = true:  stage 0 = d(layer 7) from d(hidden) through R0 (4 streamed chunks), stage s = d(layer 7 - s) through W_{8 - s};
 //              epilogue = the mask of the stage's output (+ the density term at stage 1)
-// NW = 8: eight wavefronts on a 128-row tile, one work-group per CU (wavefront w: column block w, all four 32-row blocks);
-// NW = 4: four wavefronts on a 64-row tile, TWO work-groups per CU (wavefront w: column blocks 2 w and 2 w + 1, two row blocks).
-//         Every output element costs ~10 vector instructions of epilogue (scale, bias, ReLU, mask bit, split into hi / lo) against
-//         768 multiply-adds on the matrix pipe, so with both wavefronts of a SIMD in the same work-group - in the epilogue at
-//         the same time, behind the same barriers - the matrix pipe idles for 45 % of a stage (phase timers: 12.4 k ticks of
-//         steps, 11.5 k of epilogue + conversion per stage and tile).  Two independent work-groups per CU drift apart, so one
-//         wavefront's epilogue runs beside the other's matrix instructions; the price is that each streams the weights for half
-//         as many rows (2 x the L2 -> CU weight traffic).
-template <bool BWD, bool MROW, int NW>
-__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkArgs T, const int32_t* __restrict__ count, int rcap) {
+// Four wavefronts on a 64-row tile, TWO work-groups per CU (wavefront w: column blocks 2 w and 2 w + 1, both 32-row blocks).
+// Every output element costs ~10 vector instructions of epilogue (scale, bias, ReLU, mask bit, split into hi / lo) against 768
+// multiply-adds on the matrix pipe; two wavefronts of a SIMD in the same work-group are in the epilogue at the same time, behind
+// the same barriers, and the matrix pipe idles meanwhile.  Two independent work-groups per CU drift apart, so one wavefront's
+// epilogue runs beside the other's matrix instructions; the price is that each streams the weights for half as many rows
+// (2 x the L2 -> CU weight traffic).  The form with eight wavefronts on a 128-row tile, one work-group per CU, measured equal and
+// is gone.
+template <bool BWD, bool MROW>
+__global__ __launch_bounds__(256, 2) void k_nerf_trunk(TrunkArgs T, const int32_t* __restrict__ count, int rcap) {
+  constexpr int NW = 4;                 // wavefronts of a work-group
   constexpr int TM = NW / 2;            // 32-row blocks of a tile
   constexpr int TU = 8 / NW;            // 32-column blocks of a wavefront
   constexpr int TR = 32 * TM;           // rows of a tile
@@ -355,7 +352,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_nerf_trunk(TrunkAr
       for (int u = 0; u < TU; ++u) {
         // (head stage: the slots without a block still run the arithmetic on zeros - skipping it would make the 64 accumulators
         // conditionally updated values, which the register allocator pays for with spills - and store nothing)
-        const bool live = !hstage || (u == 0 && (NW == 4 || w < 4));
+        const bool live = !hstage || u == 0;
         const int cb = hstage ? (w & 3) : TU * w + u;   // 32-column block of the stage's output = K-chunk of the next stage
         const float* const bias = bl + bp * 256 + 32 * cb + 4 * lh;
         const float* const wdl = wdl_ + 32 * cb + 4 * lh;

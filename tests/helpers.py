@@ -47,6 +47,15 @@ def oracle_step_from_golden(d):
     return out, S, loss, P, se3, dict(rays_o=ro, rays_d=rd, viewdirs=vd, target=target, mask=mask, c2w=c2w, w2c=w2c)
 
 
+def nerf_workspace_of_the_parent(M, R):
+    """(acts_floats, scratch_floats) of pp_nerf_workspace as closed forms, M samples on R rays: the sizes callers allocate by,
+    pinned so that a change of the layout code cannot move them unnoticed."""
+    acts = M * (64 + 256 * 6 + 320 + 288 + 128 + 1) + 64 + (M + 127) // 128 * 128 * 64 + 256 * (64 + 256 * 6 + 320) + 10 * 8192
+    scratch = (M * (320 * 2 + 64 * 2) + R * (128 + 32) + (5 * 65536 + 320 * 256 + 256 * 288 + 64 * 256 + 288 * 128)
+               + 256 * (128 + 288 + 6 * 256) + 512 * 392 + M * 256 * 7)
+    return acts, scratch
+
+
 def assert_close(a, b, rtol=1e-5, atol=1e-6, name='', scaled=0.0):
     """|a-b| <= atol + rtol*|b| + scaled*max|b|.  `scaled` expresses an error budget relative to the
     largest magnitude in the tensor (fp32 sums of large terms leave absolute errors on small entries)."""

@@ -66,6 +66,8 @@ def test_options_live_in_caller_owned_contexts():
     with pytest.raises(_lib.PoseProbeError):
         a.set('side_stream', 2)             # retired option
     with pytest.raises(_lib.PoseProbeError):
+        a.set('nerf_chain_nw', 4)           # retired option
+    with pytest.raises(_lib.PoseProbeError):
         a.set('mlp_split', 64)
     assert set(a.options()) == set(_lib.OPTION_NAMES)
 

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from tests import pose_refine_reference as PR
-from tests.helpers import assert_close
+from tests.helpers import assert_close, nerf_workspace_of_the_parent
 
 pytestmark = pytest.mark.gpu
 
@@ -39,16 +39,9 @@ def _bits(t):
 
 
 # ------------------------------------------------------------------------------------------------ 1. frozen backward = full backward
-def _workspace_of_the_parent(M, R):
-    acts = M * (64 + 256 * 6 + 320 + 288 + 128 + 1) + 64 + (M + 127) // 128 * 128 * 64 + 256 * (64 + 256 * 6 + 320) + 10 * 8192
-    scratch = (M * (320 * 2 + 64 * 2) + R * (128 + 32) + (5 * 65536 + 320 * 256 + 256 * 288 + 64 * 256 + 288 * 128)
-               + 256 * (128 + 288 + 6 * 256) + 512 * 392 + M * 256 * 7)
-    return acts, scratch
-
-
 @pytest.mark.parametrize('nerf_chain', [3, 0])
 @pytest.mark.parametrize('nerf_split', [1, 0])
-@pytest.mark.parametrize('R,S_', [(16, 8), (37, 200), (96, 40)])
+@pytest.mark.parametrize('R,S_', [(16, 8), (37, 200), (96, 40), (1, 2)])
 def test_frozen_backward_gives_the_bits_of_the_full_backward(R, S_, nerf_split, nerf_chain):
     """pp_nerf_bwd_input issues pp_nerf_bwd's launches minus the nine weight-gradient products: the same kernels read the same
     bytes and every sum on the way to the rays is order-free, so g_center and g_ray are EQUAL - no tolerance.  No parameter
@@ -60,7 +53,7 @@ def test_frozen_backward_gives_the_bits_of_the_full_backward(R, S_, nerf_split, 
     eng.grad.fill_(-7.25)
     canary = torch.full_like(net.flat, 3.5)
     M = R * S_
-    assert ops.nerf_workspace(M, R) == _workspace_of_the_parent(M, R)
+    assert ops.nerf_workspace(M, R) == nerf_workspace_of_the_parent(M, R)
     g = torch.Generator().manual_seed(R * 1000 + S_)
     center = (torch.randn(R, 3, generator=g) * 0.3).cuda()
     ray = (torch.nn.functional.normalize(torch.randn(R, 3, generator=g), dim=-1) * (0.7 + torch.rand(R, 1, generator=g))).cuda()

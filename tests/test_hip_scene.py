@@ -711,9 +711,48 @@ def test_scene_kernels_stay_inside_their_buffers(nerf_split):
         torch.cuda.empty_cache()
 
 
-@pytest.mark.parametrize('R,S,chain,nw,head', [(1023, 128, 3, 4, 1), (1023, 128, 3, 8, 1), (1023, 128, 1, 4, 0), (37, 50, 3, 4, 0), (37, 50, 1, 8, 1),
-                                                (1, 2, 3, 4, 1)])
-def test_scene_trunk_kernel_equals_layer_by_layer_path(R, S, chain, nw, head):
+def mask_states_rows(b, M):
+    """One mask plane of the fused chains' layout (int32 view: [row][column block][lane half] 16-bit words, bit j <-> column
+    32 block + 4 half + (j & 3) + 8 (j >> 2)) -> [M, 256] bool."""
+    Mp, dev = (M + 127) // 128 * 128, b.device
+    wds = torch.stack([b & 0xFFFF, (b >> 16) & 0xFFFF], -1).view(Mp, 8, 2)                   # [row][w][half]
+    j = torch.arange(16, device=dev)
+    bits = ((wds[..., None] >> j) & 1).bool()                                                  # [row, w, half, j]
+    col = (32 * torch.arange(8, device=dev)[:, None, None] + 4 * torch.arange(2, device=dev)[None, :, None]
+           + ((j & 3) + 8 * (j >> 2))[None, None, :]).reshape(-1)
+    out = torch.zeros(Mp, 256, dtype=torch.bool, device=dev)
+    out[:, col] = bits.reshape(Mp, 256)
+    return out[:M]
+
+
+def mask_pack_cols(st):
+    """[M, 256] bool -> one mask plane of the layer-by-layer layout, as int64 values of its 32-bit words [row group of 32][column]."""
+    M, dev = st.shape[0], st.device
+    Mp = (M + 127) // 128 * 128
+    full = torch.zeros(Mp, 256, dtype=torch.bool, device=dev)
+    full[:M] = st
+    j = torch.arange(16, device=dev)
+    rows = ((j & 3) + 8 * (j >> 2))[None, :] + 4 * torch.arange(2, device=dev)[:, None]          # [half, j]
+    x = full.view(Mp // 32, 32, 256)[:, rows.reshape(-1), :].view(Mp // 32, 2, 16, 256)          # [g, half, j, col]
+    wds = (x.to(torch.int64) << j[None, None, :, None]).sum(2)                                    # [g, half, col]
+    return (wds[:, 0] | (wds[:, 1] << 16)).to(torch.int64).view(-1)                              # [g * 256 + col]
+
+
+def repack_masks_for_the_layer_by_layer_backward(acts, M):
+    """Copy of a fused forward's activation block (nerf_chain = 3) with its eight mask planes re-packed into the layout the
+    layer-by-layer data-gradient kernels read: the same ReLU states, so both backward routes can run on one forward state."""
+    Mp = (M + 127) // 128 * 128
+    out = acts.clone()
+    off_b = M * (64 + 256 * 6 + 320 + 288 + 128 + 1) + 64
+    for l in range(8):
+        words = mask_pack_cols(mask_states_rows(acts[off_b:off_b + Mp * 8].view(torch.int32), M))
+        out[off_b:off_b + Mp * 8] = ((words + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32).view(torch.float32)   # same 32 bits
+        off_b += Mp * 8
+    return out
+
+
+@pytest.mark.parametrize('R,S,chain,head', [(1023, 128, 3, 1), (1023, 128, 1, 0), (37, 50, 3, 0), (37, 50, 1, 1), (1, 2, 3, 1)])
+def test_scene_trunk_kernel_equals_layer_by_layer_path(R, S, chain, head):
     """Option nerf_chain (csrc/pp_nerf_trunk.h: the eight feature layers + density head as one kernel, tile resident in LDS)
     against the layer-by-layer GEMMs on the same inputs: every stored activation, the raw density and the sample outputs
     agree to fp32 rounding of a 256..320-term sum (the two paths scale their fp16 operand pairs by different powers of two -
@@ -722,14 +761,13 @@ def test_scene_trunk_kernel_equals_layer_by_layer_path(R, S, chain, nw, head):
     for the backward pass agree.  Sizes: four tiles per work-group, a ragged last tile, less than one tile.  chain = 1: fused
     forward writing the masks in the layer-by-layer layout; chain = 3: in the fused chains' own layout ([row][wavefront][lane
     half], bit j <-> column 32 w + 4 half + (j & 3) + 8 (j >> 2)), followed by a backward pass of both paths on the same
-    upstream gradients (parameter, centre and ray gradients).  nw: wavefronts per work-group of the fused kernels (8 on a
-    128-sample tile, one work-group per CU; 4 on a 64-sample tile, two per CU); head: the colour head's hidden layer as the
-    forward chain's ninth stage (compared through the sample colours)."""
+    upstream gradients (parameter, centre and ray gradients).  head: the colour head's hidden layer as the forward chain's
+    ninth stage (compared through the sample colours)."""
     from poseprobe_amd import bg_nerf, ops
     dev = 'cuda'
     opt = bg_nerf.default_options(sample_intvs=S)
     torch.manual_seed(5)
-    nets = [bg_nerf.NeRF(opt, device=dev, options={'nerf_chain': c, 'nerf_chain_nw': nw, 'nerf_chain_head': head}) for c in (chain, 0)]
+    nets = [bg_nerf.NeRF(opt, device=dev, options={'nerf_chain': c, 'nerf_chain_head': head}) for c in (chain, 0)]
     g = torch.Generator().manual_seed(R + S)
     with torch.no_grad():
         for lin in list(nets[0].mlp_feat) + list(nets[0].mlp_rgb):
@@ -780,16 +818,7 @@ def test_scene_trunk_kernel_equals_layer_by_layer_path(R, S, chain, nw, head):
             out = torch.zeros(Mp // 32, 32, 256, dtype=torch.bool, device=dev)
             out[:, rows.reshape(-1), :] = bits.permute(0, 2, 3, 1).reshape(Mp // 32, 32, 256)
             return out.view(Mp, 256)[:M]
-        def states_rows(b):
-            wds = torch.stack([b & 0xFFFF, (b >> 16) & 0xFFFF], -1).view(Mp, 8, 2)                   # [row][w][half]
-            j = torch.arange(16, device=dev)
-            bits = ((wds[..., None] >> j) & 1).bool()                                                  # [row, w, half, j]
-            col = (32 * torch.arange(8, device=dev)[:, None, None] + 4 * torch.arange(2, device=dev)[None, :, None]
-                   + ((j & 3) + 8 * (j >> 2))[None, None, :]).reshape(-1)
-            out = torch.zeros(Mp, 256, dtype=torch.bool, device=dev)
-            out[:, col] = bits.reshape(Mp, 256)
-            return out[:M]
-        s1, s0 = (states_rows(b1) if chain == 3 else states(b1)), states(b0)
+        s1, s0 = (mask_states_rows(b1, M) if chain == 3 else states(b1)), states(b0)
         x1, x0 = acts_l[l]
         assert torch.equal(s1, x1 > 0), f'layer {l}: mask bits of the fused kernel are not the states of its own activations'
         assert torch.equal(s0, x0 > 0)
@@ -801,20 +830,7 @@ def test_scene_trunk_kernel_equals_layer_by_layer_path(R, S, chain, nw, head):
     # backward of both paths on the SAME forward state: the fused forward's activation block, with its mask planes re-packed
     # into the layer-by-layer layout for the layer-by-layer backward - identical ReLU states, so the gradients must agree
     # to rounding (no allowance for flipped states)
-    def pack_cols(st):                                                # [M,256] bool -> int32 words of the layer-by-layer layout
-        full = torch.zeros(Mp, 256, dtype=torch.bool, device=dev)
-        full[:M] = st
-        j = torch.arange(16, device=dev)
-        rows = ((j & 3) + 8 * (j >> 2))[None, :] + 4 * torch.arange(2, device=dev)[:, None]          # [half, j]
-        x = full.view(Mp // 32, 32, 256)[:, rows.reshape(-1), :].view(Mp // 32, 2, 16, 256)          # [g, half, j, col]
-        wds = (x.to(torch.int64) << j[None, None, :, None]).sum(2)                                    # [g, half, col]
-        return (wds[:, 0] | (wds[:, 1] << 16)).to(torch.int64).view(-1)                              # [g * 256 + col]
-    a_conv = a1.clone()
-    off_b = M * (64 + sum(OUT_LD) + 128 + 1) + 64
-    for l in range(8):
-        words = pack_cols(states_rows(a1[off_b:off_b + Mp * 8].view(torch.int32)))
-        a_conv[off_b:off_b + Mp * 8] = ((words + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32).view(torch.float32)   # same 32 bits
-        off_b += Mp * 8
+    a_conv = repack_masks_for_the_layer_by_layer_backward(a1, M)
     g_rgb = torch.randn(M, 3, generator=g).to(dev)
     g_den = torch.randn(M, generator=g).to(dev)
     grads = []

@@ -357,6 +357,54 @@ def test_deterministic_pass_stays_inside_its_buffers_at_a_ragged_size():
         assert_close(a, b, name=f'ordered vs atomic flush: g.{name}', **ORDER_TOL)
 
 
+def test_layer_by_layer_backward_with_the_ordered_flush_repeats_its_bits():
+    """The layer-by-layer backward (nerf_chain = 0) at 37 x 50 (ragged last tile) with an ordered-flush workspace attached: its nine
+    weight-gradient products run back to back, behind the data gradients, through the one set of ordered slots.  Two calls on
+    the same inputs give the same bits in params_grad, g_center and g_ray; against the fused route on the same forward state (the
+    fused forward's activation block, mask planes re-packed) they agree within the tolerances of
+    tests/test_hip_scene.py::test_scene_trunk_kernel_equals_layer_by_layer_path."""
+    from poseprobe_amd import bg_nerf, ops
+    from tests.test_hip_scene import repack_masks_for_the_layer_by_layer_backward
+    R, S = 37, 50
+    M = R * S
+    opt = bg_nerf.default_options(sample_intvs=S)
+    torch.manual_seed(3)
+    fused, layered = (bg_nerf.NeRF(opt, device='cuda', options={'nerf_chain': c}) for c in (3, 0))
+    with torch.no_grad():
+        layered.flat.copy_(fused.flat)
+    for n in (fused, layered):
+        n.progress.data.fill_(0.7)
+    g = torch.Generator().manual_seed(23)
+    center, ray = (torch.randn(R, 3, generator=g) * 0.3).cuda(), torch.randn(R, 3, generator=g).cuda()
+    depth = ((torch.rand(R, S, generator=g) + torch.arange(S)) / S * 2.0 + 0.4).cuda().contiguous()
+    g_rgb, g_den = torch.randn(M, 3, generator=g).cuda(), torch.randn(M, generator=g).cuda()
+    count = torch.tensor([M], dtype=torch.int32, device='cuda')
+    n_acts, n_scr = ops.nerf_workspace(M, R)
+    acts = torch.zeros(n_acts, device='cuda')
+    rgb_s, dens = torch.empty(M, 3, device='cuda'), torch.empty(M, device='cuda')
+    ops.nerf_fwd(fused.flat, center, ray, depth, fused.band_weights(), count, R, S, acts, rgb_s, dens, fused.ctx)
+    acts_l = repack_masks_for_the_layer_by_layer_backward(acts, M)
+
+    def backward(net, a):
+        pg = torch.zeros_like(net.flat)
+        gc, gr = torch.full((R, 3), float('nan'), device='cuda'), torch.full((R, 3), float('nan'), device='cuda')
+        ops.nerf_bwd(net.flat, ray, depth, count, R, S, a, rgb_s, g_rgb, g_den, torch.zeros(n_scr, device='cuda'), pg, gc, gr, net.ctx)
+        torch.cuda.synchronize()
+        return pg, gc, gr
+
+    ref = backward(fused, acts)
+    work = torch.empty(ops.nerf_ordered_workspace(), dtype=torch.uint8, device='cuda')
+    ops.nerf_ordered_attach(layered.ctx, work)
+    one, two = backward(layered, acts_l), backward(layered, acts_l)
+    ops.nerf_ordered_attach(layered.ctx, None)
+    assert float(one[0].abs().max()) > 0
+    for name, a, b, r in zip(('params_grad', 'g_center', 'g_ray'), one, two, ref):
+        assert bool(torch.isfinite(a).all())
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), f'{name}: two calls differ in {int((a != b).sum())} of {a.numel()} entries'
+        print(f'layer-by-layer (ordered) vs fused {name}: max |diff| {float((a - r).abs().max()):.3e}, max |ref| {float(r.abs().max()):.3e}')
+        assert_close(a, r, rtol=2e-5, scaled=2e-5, name=f'layer-by-layer (ordered) vs fused: {name}')
+
+
 # ------------------------------------------------------------------------------------------------ 6. pose fold
 def fold_inputs(V=3, N=1024, seed=7):
     g = torch.Generator().manual_seed(seed)

@@ -53,6 +53,17 @@ def test_layout_table_sums_to_the_library_parameter_counts():
     assert [len(MLP_LAYOUT[net]) for net in ('rgbnet', 'warp')] == [4, 5] and MLP_LAYOUT['rgbnet'][0][1:3] == (57, 64)
 
 
+def test_scene_workspace_sizes_are_the_closed_forms():
+    """pp_nerf_workspace walks the two blocks' layouts (csrc/pp_nerf.hip: nerf_acts, nerf_scratch); the sizes it ends at are the
+    closed forms callers have allocated by: one sample, one and two rows (M = 2 is one ray of two samples), around a 128-row
+    tile, a ragged batch, the training batch."""
+    from poseprobe_amd import ops
+    from tests.helpers import nerf_workspace_of_the_parent
+    for M in (1, 2, 127, 128, 129, 1850, 130944):
+        for R in (1, 37, 1023):
+            assert ops.nerf_workspace(M, R) == nerf_workspace_of_the_parent(M, R), (M, R)
+
+
 def test_scene_scalars_are_the_fp32_expressions():
     from poseprobe_amd import synthetic as syn
     from poseprobe_amd.engine import SceneConfig
