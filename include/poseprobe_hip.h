@@ -615,6 +615,18 @@ int pp_nerf_bwd(const float* params, const float* ray, const float* depth, const
 int pp_nerf_bwd_input(const float* params, const float* ray, const float* depth, const int32_t* count, int32_t n_rays,
                       int32_t n_samples, const float* acts, const float* rgb_samples, const float* g_rgb_samples,
                       const float* g_density_samples, float* scratch, float* g_center, float* g_ray, void* ctx, void* stream);
+/* Forward pass that keeps no activations (whole views, validation images, novel-view sequences): pp_nerf_fwd's arguments with
+ * `work` (pp_nerf_infer_workspace floats) in place of `acts`; rgb_samples[M,3] and density_samples[M] are bit-identical to
+ * pp_nerf_fwd's on the same inputs and context (same operand scales, same accumulation, same summation order).  No layer
+ * output and no ReLU mask is written to memory: work = 224 floats per sample (encoded points 64, view encoding 32, the colour
+ * head's hidden layer 128) + the operand-maximum slots and the packed weight stream (573 504 floats, independent of the sample
+ * count), against pp_nerf_workspace's 2337 floats + 256 mask bytes per sample.  Only the default route has this form: a context
+ * with nerf_split != 1, the forward bit of nerf_chain clear or nerf_chain_head != 1 is refused with PP_ERR_INVALID_ARG (use
+ * pp_nerf_fwd there).  pp_nerf_bwd cannot follow this call. */
+int pp_nerf_infer_workspace(int64_t n_samples, int64_t n_rays, int64_t* work_floats);
+int pp_nerf_infer(const float* params, const float* center, const float* ray, const float* depth, const float* bands,
+                  const int32_t* count, int32_t n_rays, int32_t n_samples, float* work, float* rgb_samples,
+                  float* density_samples, void* ctx, void* stream);
 /* composite (:290-343): rgb[R,3] (+ 1 - opacity when white_bg), depth[R], opacity[R], weights[R,S], all_cumulated[R]
  * (= T at the second-to-last sample), rgb_var[R], depth_var[R] (the two variances are forward-only outputs). */
 int pp_nerf_composite_fwd(const float* rgb_samples, const float* density_samples, const float* depth, const float* ray,

@@ -9,7 +9,8 @@ Same constructor arguments (`opt` tree), same parameter names (`mlp_feat.{0..7}.
     composite(opt, ray, pred_dict, depth_samples)  -> rgb, rgb_var, depth, depth_var, opacity, weights, all_cumulated
 
 Everything numerical runs in the HIP kernels of csrc/pp_nerf.hip through the C ABI (pp_nerf_fwd / pp_nerf_bwd /
-pp_nerf_composite_fwd / pp_nerf_composite_bwd); there is no eager fallback.  The parameters are views into ONE packed
+pp_nerf_composite_fwd / pp_nerf_composite_bwd; pp_nerf_infer for the forward-only whole-view path, SceneRenderer.render_view /
+render_rays); there is no eager fallback.  The parameters are views into ONE packed
 device buffer in the layout the kernels read (`pp_nerf_layout`), so nothing is repacked per step and the whole network is a
 single flat tensor for the fused Adam kernel (SceneEngine below).
 
@@ -138,6 +139,48 @@ class _Workspace:
 
     def new_acts(self):
         return torch.empty(self.acts_floats, dtype=torch.float32, device=self.dev)
+
+
+class _InferWorkspace:
+    """Buffers of one forward-only pass shape (R rays x S samples): pp_nerf_infer's workspace - 224 floats per sample against the
+    2337 + 256 mask bytes of a pass that a backward may follow -, the sample outputs and the compositing outputs.  Nothing in
+    here is read by any backward pass."""
+
+    def __init__(self, R, S, dev):
+        M = R * S
+        f = dict(dtype=torch.float32, device=dev)
+        self.R, self.S, self._work = R, S, None
+        self.count = torch.tensor([M], dtype=torch.int32, device=dev)
+        self.rgb_s, self.dens = torch.empty(M, 3, **f), torch.empty(M, **f)
+        self.rgb, self.w = torch.empty(R, 3, **f), torch.empty(R, S, **f)
+        self.d, self.op, self.cum, self.rv, self.dv = (torch.empty(R, **f) for _ in range(5))
+
+    @property
+    def work(self):                       # (a network on another route never asks for it)
+        if self._work is None:
+            self._work = torch.empty(ops.nerf_infer_workspace(self.R * self.S, self.R), dtype=torch.float32, device=self.rgb.device)
+        return self._work
+
+
+def plan_chunks(n_rays, chunk_rays):
+    """[(first ray, rays)] of a walk over n_rays rays in chunks of chunk_rays; the last chunk may be ragged."""
+    n_rays, chunk_rays = int(n_rays), int(chunk_rays)
+    if chunk_rays < 1:
+        raise ValueError(f'chunk_rays = {chunk_rays}: at least one ray per chunk')
+    if n_rays < 1:
+        raise ValueError(f'n_rays = {n_rays}: nothing to render')
+    return [(c, min(chunk_rays, n_rays - c)) for c in range(0, n_rays, chunk_rays)]
+
+
+VIEW_MODES = ('val', 'eval', 'test')
+VIEW_KEYS = ('rgb', 'rgb_var', 'depth', 'depth_var', 'opacity', 'all_cumulated')
+
+
+def _check_view_args(mode, n_rays, chunk_rays):
+    if mode not in VIEW_MODES:
+        raise ValueError(f"mode {mode!r}: render_view / render_rays are forward-only and deterministic, mode must be one of "
+                         f"{VIEW_MODES} (render / render_by_slices serve the stochastic ones)")
+    return plan_chunks(n_rays, chunk_rays)
 
 
 class _NerfSamples(torch.autograd.Function):
@@ -320,6 +363,38 @@ class NeRF(torch.nn.Module):
             ws = self._ws[(R, S)] = _Workspace(R, S, self.flat.device)
         return ws
 
+    def infer_route(self):
+        """True when this network's context selects the route pp_nerf_infer has (nerf_split = 1, the forward bit of nerf_chain,
+        nerf_chain_head = 1: the defaults); otherwise forward-only passes go through pp_nerf_fwd and the shared block."""
+        from . import _lib
+        c = self.ctx if self.ctx is not None else _lib.default_context()
+        return c.get('nerf_split') == 1 and (c.get('nerf_chain') & 1) == 1 and c.get('nerf_chain_head') == 1
+
+    def _infer_workspace(self, R, S):
+        cache = self.__dict__.setdefault('_iws', {})
+        ws = cache.get((R, S))
+        if ws is None:
+            if len(cache) >= 4:
+                cache.clear()
+            ws = cache[(R, S)] = _InferWorkspace(R, S, self.flat.device)
+        return ws
+
+    @torch.no_grad()
+    def infer_composite(self, opt, center, ray, depth):
+        """center, ray [R,3], depth [R,S], contiguous fp32 -> the _InferWorkspace of the shape, holding rgb_s, dens and the
+        compositing outputs of this call (overwritten by the next call of the same shape).  Forward only: pp_nerf_infer (or, on
+        another route, pp_nerf_fwd into the shared activation block) and pp_nerf_composite_fwd."""
+        R, S = depth.shape
+        b = self._infer_workspace(R, S)
+        if self.infer_route():
+            ops.nerf_infer(self.flat, center, ray, depth, self.band_weights(), b.count, R, S, b.work, b.rgb_s, b.dens, self.ctx)
+        else:
+            ops.nerf_fwd(self.flat, center, ray, depth, self.band_weights(), b.count, R, S, self._workspace(R, S).acts, b.rgb_s,
+                         b.dens, self.ctx)
+        white = bool(opt.nerf.setbg_opaque or opt.mask_img)
+        ops.nerf_composite_fwd(b.rgb_s, b.dens, depth, ray, R, S, white, b.rgb, b.d, b.op, b.w, b.cum, b.rv, b.dv)
+        return b
+
     def _params(self):
         return [p for lin in list(self.mlp_feat) + list(self.mlp_rgb) for p in (lin.weight, lin.bias)]
 
@@ -468,6 +543,75 @@ class SceneRenderer:
                 if k in ret:
                     parts.setdefault(k, []).append(ret[k])
         return Options({k: torch.cat(v, dim=1) for k, v in parts.items()})
+
+
+    # ---- forward-only whole views ------------------------------------------------------------------------------------------
+    def _fine_active(self, opt, iter):
+        start = getattr(opt.nerf, 'ratio_start_fine_sampling_at_x', None)
+        skip_fine = start is not None and iter is not None and iter < opt.max_iter * start
+        return bool(opt.nerf.fine_sampling and not skip_fine)
+
+    def _render_chunk(self, opt, center, ray, depth_range, mode, fine, out, c):
+        """One chunk - center, ray [B, n, 3], the rays c .. c + n - 1 of every pose - through render's sequence of functions on
+        render's shapes (the B * n rays of a chunk are one pass, as in render), written into out[key][:, c:c + n]."""
+        B, n = ray.shape[:2]
+        S = opt.nerf.sample_intvs
+        cen, r = center.reshape(B * n, 3).contiguous().float(), ray.reshape(B * n, 3).contiguous().float()
+        depth = sample_depth(opt, B, n, S, depth_range, mode=mode, device=self.device)
+        passes = [('', self.nerf.infer_composite(opt, cen, r, depth.reshape(B * n, S).contiguous().float()))]
+        if fine:
+            fine_t = sample_depth_from_pdf(passes[0][1].w.view(B, n, S), S, opt.nerf.sample_intvs_fine, depth_range, det=True)
+            depth = torch.cat([depth, fine_t], dim=2).sort(dim=2).values
+            passes.append(('_fine', self.nerf_fine.infer_composite(opt, cen, r, depth.reshape(B * n, -1).contiguous().float())))
+        for sfx, b in passes:
+            for k, t in (('rgb', b.rgb), ('rgb_var', b.rv), ('depth', b.d), ('depth_var', b.dv), ('opacity', b.op),
+                         ('all_cumulated', b.cum)):
+                o = out[k + sfx][:, c:c + n]
+                o.copy_(t.view(o.shape))
+
+    def _render_chunks(self, opt, center, ray, depth_range, mode, chunks, iter):
+        if opt.camera.ndc:
+            raise NotImplementedError('bg_nerf: NDC rays are not used by any PoseProbe configuration')
+        B, N = ray.shape[:2]
+        fine = self._fine_active(opt, iter)
+        if fine and self.nerf_fine is None:
+            raise ValueError('fine_sampling is active but this renderer has no fine network')
+        f = dict(dtype=torch.float32, device=self.device)
+        out = Options()
+        for sfx in ('', '_fine') if fine else ('',):
+            for k in VIEW_KEYS:
+                out[k + sfx] = torch.empty((B, N) if k == 'all_cumulated' else (B, N, 3 if k == 'rgb' else 1), **f)
+        for c, n in chunks:
+            self._render_chunk(opt, center[:, c:c + n], ray[:, c:c + n], depth_range, mode, fine, out, c)
+        return out
+
+    @torch.no_grad()
+    def render_rays(self, opt, center, ray, depth_range, mode='val', chunk_rays=8192, iter=None):
+        """Forward-only render of given rays: center, ray [N,3] on the device -> render_by_slices' keys with B = 1 ([1,N,3],
+        [1,N,1], all_cumulated [1,N]; `*_fine` when the fine pass is active).  Deterministic modes only (mid-point samples,
+        det=True inverse-transform samples).  Per chunk of chunk_rays rays: sample_depth, pp_nerf_infer on the coarse network,
+        pp_nerf_composite_fwd, sample_depth_from_pdf, concatenate + sort, pp_nerf_infer on the fine network,
+        pp_nerf_composite_fwd - render's functions on render's per-ray inputs, with no activation kept (224 floats of workspace
+        per sample instead of 2337 + 256 bytes), one workspace per chunk shape reused across chunks and calls, outputs written in
+        place, no host read.  A network whose context selects another route than the default goes through pp_nerf_fwd and its
+        shared activation block at the same chunking."""
+        if center.dim() != 2 or center.shape != ray.shape or ray.shape[-1] != 3:
+            raise ValueError('render_rays: center and ray must both be [N,3]')
+        chunks = _check_view_args(mode, ray.shape[0], chunk_rays)
+        return self._render_chunks(opt, center[None].to(self.device), ray[None].to(self.device), depth_range, mode, chunks, iter)
+
+    @torch.no_grad()
+    def render_view(self, opt, pose, H, W, intr, depth_range, mode='val', chunk_rays=8192, iter=None):
+        """Forward-only render of whole H x W views: pose [1,3,4] or [B,3,4] (world to camera), intr [B,3,3] -> what
+        render_by_slices returns (same keys, same shapes; bit-identical to it with opt.nerf.rand_rays = chunk_rays).  The rays are
+        formed ONCE per call (render_by_slices forms all H * W of them again for every slice), then walked in chunks of
+        chunk_rays rays per pose as in render_rays.  The default 8192 keeps the fine pass's workspace under 2 GiB at 256 samples
+        per ray."""
+        if pose.dim() != 3 or tuple(pose.shape[1:]) != (3, 4):
+            raise ValueError('render_view: pose must be [B,3,4]')
+        chunks = _check_view_args(mode, int(H) * int(W), chunk_rays)
+        center, ray = get_center_and_ray(pose.to(self.device), H, W, intr.to(self.device))
+        return self._render_chunks(opt, center, ray, depth_range, mode, chunks, iter)
 
 
 def photometric_loss(rgb, image, huber=True):

@@ -4,6 +4,8 @@
 Jacobian d c2w / d se3, consumed in the backward); compose / invert of [...,3,4] matrices are two tiny matmuls and
 stay torch expressions (they are bookkeeping on V<=8 matrices, not part of the per-ray path).
 """
+import math
+
 import torch
 
 from . import ops
@@ -105,3 +107,24 @@ class Lie:
 
 pose = Pose()
 lie = Lie()
+
+
+def angle_to_rotation_matrix(a, axis):
+    """Rotation by the angles `a` [...] about 'X', 'Y' or 'Z' -> [...,3,3] (lib/camera.py:263-272)."""
+    c, s, zero, one = a.cos(), a.sin(), torch.zeros_like(a), torch.ones_like(a)
+    rows = {'X': ((one, zero, zero), (zero, c, -s), (zero, s, c)),
+            'Y': ((c, zero, s), (zero, one, zero), (-s, zero, c)),
+            'Z': ((c, -s, zero), (s, c, zero), (zero, zero, one))}[axis]
+    return torch.stack([torch.stack(r, dim=-1) for r in rows], dim=-2)
+
+
+def get_novel_view_poses(opt, pose_anchor, N=60, scale=1):
+    """N world-to-camera poses [N,3,4] on a small closed oscillation around `pose_anchor` [3,4] (lib/camera.py:371-381): the
+    camera is pulled back by 4 * scale, turned by asin(0.1 sin) about X and asin(0.1 cos) about Y, pushed forward by 3.8 * scale,
+    then the anchor is applied.  float32 on the anchor's device, like the reference's pose algebra; `opt` is not read."""
+    dev = pose_anchor.device
+    theta = torch.arange(N, device=dev) / N * 2 * math.pi
+    turn = pose(R=angle_to_rotation_matrix((theta.cos() * 0.1).asin(), 'Y') @ angle_to_rotation_matrix((theta.sin() * 0.1).asin(), 'X'))
+    back = pose(t=torch.tensor([0, 0, -4 * scale], device=dev))
+    forth = pose(t=torch.tensor([0, 0, 3.8 * scale], device=dev))
+    return pose.compose([back, turn, forth, pose_anchor[None]])

@@ -136,7 +136,8 @@ extern "C" int pp_nerf_workspace(int64_t n_samples, int64_t n_rays, int64_t* act
 // ------------------------------------------------------------------------------------------------ encoding
 // One wavefront per sample: lane j produces element j of the 64-wide (63 used) encoded point and the 32-wide (27 used)
 // encoded unit view direction; both are written where the consuming layers read them (layer 0 input, the skip columns of
-// layer 4's input, the view columns of the colour head's input), 256-byte coalesced rows.
+// layer 4's input, the view columns of the colour head's input), 256-byte coalesced rows.  KEEP = false (pp_nerf_infer) writes
+// only what the fused forward chain reads: the points once, [M][64], and the view encoding as a dense [M][32] block at a7.
 __device__ __forceinline__ float nerf_enc_elem(int j, int L, const float* __restrict__ x, const float* __restrict__ w) {
   if (j < 3) return x[j];
   const int q = j - 3;
@@ -146,6 +147,7 @@ __device__ __forceinline__ float nerf_enc_elem(int j, int L, const float* __rest
   return (s == 0 ? sinf(ph) : cosf(ph)) * w[l];
 }
 
+template <bool KEEP = true>
 __global__ __launch_bounds__(256) void k_nerf_encode(const float* __restrict__ center, const float* __restrict__ ray,
                                                      const float* __restrict__ depth, const float* __restrict__ bands, int M, int S,
                                                      float* __restrict__ enc, float* __restrict__ a3, float* __restrict__ a7) {
@@ -176,8 +178,10 @@ __global__ __launch_bounds__(256) void k_nerf_encode(const float* __restrict__ c
     for (int c = 0; c < 3; ++c) x[c] = o[c] + d[c] * t;
     const float e = nerf_enc_elem(j, NERF_L3D, x, bands);
     enc[(size_t)m * 64 + j] = e;
-    a3[(size_t)m * 320 + 256 + j] = e;
-    if (j < 32) a7[(size_t)m * 288 + 256 + j] = ve;
+    if (KEEP) {
+      a3[(size_t)m * 320 + 256 + j] = e;
+      if (j < 32) a7[(size_t)m * 288 + 256 + j] = ve;
+    } else if (j < 32) a7[(size_t)m * 32 + j] = ve;
   }
 }
 
@@ -715,10 +719,10 @@ struct NerfRoute {
 };
 
 // a fused chain (pp_nerf_trunk.h): 64-row tiles on four wavefronts, two work-groups per CU
-template <bool BWD, bool MROW>
+template <bool BWD, bool MROW, bool KEEP = true>
 static void launch_trunk(const TrunkArgs& T, const int32_t* count, int M, hipStream_t st) {
   const int tiles = pp_div_up(M, 64), cus = pp_num_cus();
-  hipLaunchKernelGGL((k_nerf_trunk<BWD, MROW>), dim3(tiles < 2 * cus ? tiles : 2 * cus), dim3(256), 0, st, T, count, M);
+  hipLaunchKernelGGL((k_nerf_trunk<BWD, MROW, KEEP>), dim3(tiles < 2 * cus ? tiles : 2 * cus), dim3(256), 0, st, T, count, M);
 }
 
 template <int EPI>
@@ -813,7 +817,7 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
       hipLaunchKernelGGL(k_pack_planes, dim3(16, 8), dim3(256), 0, st, P, mx);
     }
   }
-  hipLaunchKernelGGL(k_nerf_encode, dim3(pp_div_up(M, 16)), dim3(256), 0, st, center, ray, depth, bands, M,
+  hipLaunchKernelGGL(k_nerf_encode<true>, dim3(pp_div_up(M, 16)), dim3(256), 0, st, center, ray, depth, bands, M,
                      n_samples, A.enc, A.a[3], A.a[7]);
   if (rt.chain_fwd) {
     TrunkArgs T;
@@ -844,6 +848,74 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
     nerf_gemm<EPI_RELU>(st, rt.split, A.a[7], 288, params + L.r0, 288, 288, 128, params + L.br0, nullptr, 0, A.h, 128, count, M,
                         mx ? mx + MX_A0 + 7 : nullptr, mx ? mx + MX_R0 : nullptr, nullptr);
   hipLaunchKernelGGL(k_nerf_rgb_fwd, dim3(pp_div_up(M * 16, 256)), dim3(256), 0, st, params + L.r1, params + L.br1, A.h, M,
+                     rgb_samples);
+  PP_CHECK_LAUNCH();
+  return PP_OK;
+}
+
+// Forward pass that nobody differentiates (whole views, validation images, novel-view sequences): pp_nerf_fwd's default route -
+// operand maxima, packed weight stream, encoding, the fused chain with the colour head's hidden layer as its ninth stage,
+// k_nerf_rgb_fwd - with the KEEP = false forms of the encoding and the chain, so that the only per-sample memory is what one
+// kernel hands to the next: enc [M][64] (read by stage 0 and again as the skip input of stage 4), view [M][32], h [M][128].
+// Same operand scales, same accumulation, same summation order in the colour layer: the outputs are pp_nerf_fwd's bits.
+struct NerfInferWork { float* enc; float* view; float* h; float* mx; unsigned char* wstream; int64_t floats; };
+static NerfInferWork nerf_infer_work(float* base, int64_t M) {              // base == nullptr: only `floats` means anything
+  NerfInferWork X;
+  int64_t o = 0;
+  auto take = [&](int64_t n) { float* p = base ? base + o : nullptr; o += n; return p; };
+  X.mx = take(MX_SLOTS);                                                    // the fixed part first: every block stays 16-byte aligned
+  X.wstream = reinterpret_cast<unsigned char*>(take((int64_t)(TR_STEPS + 10) * TR_WSTEP / 4));
+  X.enc = take(M * 64);
+  X.view = take(M * 32);
+  X.h = take(M * 128);
+  X.floats = o;
+  return X;
+}
+
+extern "C" int pp_nerf_infer_workspace(int64_t n_samples, int64_t n_rays, int64_t* work_floats) {
+  PP_REQUIRE(work_floats && n_samples > 0 && n_rays > 0, "bad arguments");
+  *work_floats = nerf_infer_work(nullptr, n_samples).floats;
+  return PP_OK;
+}
+
+extern "C" int pp_nerf_infer(const float* params, const float* center, const float* ray, const float* depth,
+                             const float* bands, const int32_t* count, int32_t n_rays, int32_t n_samples, float* work,
+                             float* rgb_samples, float* density_samples, void* ctx, void* stream) {
+  const NerfRoute rt(pp_options(ctx));
+  PP_REQUIRE(params && center && ray && depth && bands && count && work && rgb_samples && density_samples, "null pointer");
+  PP_REQUIRE(n_rays > 0 && n_samples > 0 && (int64_t)n_rays * n_samples < (1LL << 30), "bad sizes");
+  PP_REQUIRE(rt.split && rt.chain_fwd && rt.head,
+             "only the default route (nerf_split = 1, the forward bit of nerf_chain, nerf_chain_head = 1) has a forward-only "
+             "form: use pp_nerf_fwd");
+  hipStream_t st = pp_stream(stream);
+  const int M = n_rays * n_samples;
+  const NerfLayout L = nerf_layout();
+  const NerfInferWork X = nerf_infer_work(work, M);
+  float* mx = X.mx;
+  hipMemsetAsync(mx, 0, MX_SLOTS * sizeof(float), st);
+  NerfWmaxJobs J;
+  for (int l = 0; l < 7; ++l) { J.src[l] = params + L.w[l]; J.n[l] = 256 * NERF_IN_LD[l]; }
+  J.src[7] = params + L.wd; J.n[7] = 257 * 256;
+  J.src[8] = params + L.r0; J.n[8] = 128 * 288;
+  hipLaunchKernelGGL(k_nerf_wmax, dim3(16, 9), dim3(256), 0, st, J, mx);
+  hipLaunchKernelGGL(k_nerf_enc_bound, dim3(n_rays < 256 ? pp_div_up(n_rays, 4) : 64), dim3(256), 0, st, center, ray, depth, n_rays, n_samples, mx);
+  TrunkPackJobs P;
+  for (int l = 0; l < 8; ++l) { P.src[l] = params + L.w[l]; P.ld[l] = NERF_IN_LD[l]; P.mx_w[l] = MX_W0 + l; }
+  P.src[8] = params + L.r0; P.ld[8] = 288; P.mx_w[8] = MX_R0;
+  P.nsteps = TR_STEPS + 10;
+  hipLaunchKernelGGL(k_pack_trunk<false>, dim3(P.nsteps * 4), dim3(256), 0, st, P, mx, X.wstream);
+  hipLaunchKernelGGL(k_nerf_encode<false>, dim3(pp_div_up(M, 16)), dim3(256), 0, st, center, ray, depth, bands, M, n_samples,
+                     X.enc, static_cast<float*>(nullptr), X.view);
+  TrunkArgs T;
+  memset(&T, 0, sizeof(T));
+  T.in = X.enc; T.in_ld = 64;
+  for (int l = 0; l < 8; ++l) { T.bias[l] = params + L.b[l]; T.mx_w[l] = MX_W0 + l; T.mx_out[l] = MX_A0 + l; }
+  T.wstream = X.wstream;
+  T.wd = params + L.wd; T.bd = params + L.bd; T.density = density_samples;
+  T.mx = mx; T.mx_in = MX_ENC;
+  T.head = 1; T.out[8] = X.h; T.ld[8] = 128; T.bias[8] = params + L.br0; T.mx_w[8] = MX_R0; T.in2 = X.view; T.in2_ld = 32;
+  launch_trunk<false, true, false>(T, count, M, st);
+  hipLaunchKernelGGL(k_nerf_rgb_fwd, dim3(pp_div_up(M * 16, 256)), dim3(256), 0, st, params + L.r1, params + L.br1, X.h, M,
                      rgb_samples);
   PP_CHECK_LAUNCH();
   return PP_OK;

@@ -154,7 +154,10 @@ __device__ __forceinline__ void tr_step(const unsigned char* img, const pp_half8
 // epilogue runs beside the other's matrix instructions; the price is that each streams the weights for half as many rows
 // (2 x the L2 -> CU weight traffic).  The form with eight wavefronts on a 128-row tile, one work-group per CU, measured equal and
 // is gone.
-template <bool BWD, bool MROW>
+// KEEP = false (forward only, pp_nerf_infer): nothing a backward pass would read leaves the work-group - no stage output is sent
+// to HBM from the image (TR_DRAIN), no mask word is formed, raw is not stored; what remains are the last stage's rows (the colour
+// head's hidden layer) and the densities.  The arithmetic of every stage is the one of KEEP = true, so these are the same bits.
+template <bool BWD, bool MROW, bool KEEP = true>
 __global__ __launch_bounds__(256, 2) void k_nerf_trunk(TrunkArgs T, const int32_t* __restrict__ count, int rcap) {
   constexpr int NW = 4;                 // wavefronts of a work-group
   constexpr int TM = NW / 2;            // 32-row blocks of a tile
@@ -337,7 +340,10 @@ __global__ __launch_bounds__(256, 2) void k_nerf_trunk(TrunkArgs T, const int32_
         for (int kc = 0; kc < 8; ++kc) {
           if (kc & 1) { tr_step<TM, TU>(Img + kc * CH, wb1, acc, l31, lh); TR_WLOAD(wb1); }
           else { tr_step<TM, TU>(Img + kc * CH, wb0, acc, l31, lh); TR_WLOAD(wb0); }
-          TR_DRAIN(kc);
+          if (KEEP) TR_DRAIN(kc);
+          // without the drain's loads and stores behind it, the scheduler sinks the weight loads of step kc + 2 down to their
+          // first use (every wait became vmcnt(0) / (1): no prefetch, 17 % slower than the storing form): pin them here
+          else __builtin_amdgcn_sched_barrier(0);
         }
 #undef TR_DRAIN
       }
@@ -389,7 +395,7 @@ __global__ __launch_bounds__(256, 2) void k_nerf_trunk(TrunkArgs T, const int32_
           }
         }
       }
-      if (!BWD && !hstage) {
+      if (KEEP && !BWD && !hstage) {
         if (MROW) {
           uint16_t* __restrict__ br = T.bitsr[l];
 #pragma unroll
@@ -472,7 +478,7 @@ __global__ __launch_bounds__(256, 2) void k_nerf_trunk(TrunkArgs T, const int32_
         float s = wdl_[256];
 #pragma unroll
         for (int u = 0; u < 8; ++u) s += dpart[u * TR + tid];
-        if (r0 + tid < R) { T.raw[r0 + tid] = s; T.density[r0 + tid] = s > 20.f ? s : log1pf(expf(s)); }
+        if (r0 + tid < R) { if (KEEP) T.raw[r0 + tid] = s; T.density[r0 + tid] = s > 20.f ? s : log1pf(expf(s)); }
       }
       if (!last) {
         // layer 4 reads the encoded points, the head the view encoding (bounded by 1), at the same scale as the tile

@@ -302,16 +302,20 @@ def refine_test_poses(net, opt, pose_GT_w2c_test, sim3, images, Ks, depth_range,
 
 @torch.no_grad()
 def evaluate_test_views(nerf, nerf_fine, opt, pose_w2c_train, pose_GT_w2c_train, pose_GT_w2c_test, images_test, Ks_test, depth_range,
-                        refine=True, **refiner_kw):
+                        refine=True, render='slices', chunk_rays=8192, **refiner_kw):
     """The scene branch's share of eval.py:1353-1416: evaluate_poses on the training poses; the held-out views' ground-truth
     poses backtracked into that frame and (refine=True) refined photometrically against the frozen coarse network; one full-view
     render per held-out view through bg_nerf.SceneRenderer.render_by_slices in mode 'val' - the fine network's colour where
     `nerf_fine` exists, else the coarse one; image_metrics.  One host copy, at the end.
+    render='view': the renders go through SceneRenderer.render_view instead - forward-only kernels that keep no activation, the
+    rays formed once per view, chunks of `chunk_rays` rays; the same images as 'slices' with opt.nerf.rand_rays = chunk_rays.
     -> dict: table [T,4] numpy (psnr, psnr_fore, psnr_back, ssim per view; fore / back are 0: no masks), poses_w2c [T,3,4] (device),
     error (R degrees, t x 100 of the aligned training poses), sim3, losses [T, iters] (device; None without refinement) and
     rgbs [T,H,W,3] (device).  Out of scope: the object branch's images of these views (evaluate_viewpoints renders them at any
     pose, poses_w2c included), LPIPS, multi-rank runs."""
     from . import bg_nerf
+    if render not in ('slices', 'view'):
+        raise ValueError(f"render = {render!r}: 'slices' or 'view'")
     error, _, sim3 = evaluate_poses(pose_w2c_train, pose_GT_w2c_train)
     dev = nerf.flat.device
     losses = None
@@ -332,7 +336,10 @@ def evaluate_test_views(nerf, nerf_fine, opt, pose_w2c_train, pose_GT_w2c_train,
     rgbs, scores = [], []
     for i in range(T):
         H, W = images_test[i].shape[:2]
-        ret = renderer.render_by_slices(ropt, poses[i:i + 1], H, W, K[i:i + 1], depth_range, mode='val')
+        if render == 'view':
+            ret = renderer.render_view(ropt, poses[i:i + 1], H, W, K[i:i + 1], depth_range, mode='val', chunk_rays=chunk_rays)
+        else:
+            ret = renderer.render_by_slices(ropt, poses[i:i + 1], H, W, K[i:i + 1], depth_range, mode='val')
         rgb = (ret['rgb_fine'] if 'rgb_fine' in ret else ret['rgb']).view(H, W, 3)
         rgbs.append(rgb)
         m = image_metrics(rgb, images_test[i])

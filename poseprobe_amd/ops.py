@@ -568,6 +568,24 @@ def nerf_fwd(params, center, ray, depth, bands, count, n_rays, n_samples, acts, 
               _f(acts), _f(rgb_samples), _f(density_samples), _h(ctx), _stream())
 
 
+def nerf_infer_workspace(n_samples, n_rays):
+    """Floats of pp_nerf_infer's workspace: 224 per sample + a part that does not depend on the sample count."""
+    w = ctypes.c_int64()
+    _lib.call('pp_nerf_infer_workspace', ctypes.c_int64(n_samples), ctypes.c_int64(n_rays), ctypes.byref(w))
+    return w.value
+
+
+def nerf_infer(params, center, ray, depth, bands, count, n_rays, n_samples, work, rgb_samples, density_samples, ctx=None):
+    """nerf_fwd that keeps no activations (pp_nerf_infer): the same rgb_samples / density_samples bits; `work` of
+    nerf_infer_workspace floats; default route only (another one raises PoseProbeError: use nerf_fwd)."""
+    R, M = int(n_rays), int(n_rays) * int(n_samples)
+    _rows_at_least(R, (center, 3, 'center'), (ray, 3, 'ray'), (depth, int(n_samples), 'depth'))
+    _rows_at_least(M, (rgb_samples, 3, 'rgb_samples'), (density_samples, 1, 'density_samples'))
+    _rows_at_least(1, (work, nerf_infer_workspace(M, R), 'work'))
+    _lib.call('pp_nerf_infer', _f(params), _f(center), _f(ray), _f(depth), _f(bands), _i(count), R, int(n_samples),
+              _f(work), _f(rgb_samples), _f(density_samples), _h(ctx), _stream())
+
+
 def nerf_bwd(params, ray, depth, count, n_rays, n_samples, acts, rgb_samples, g_rgb_samples, g_density_samples, scratch,
              params_grad, g_center, g_ray, ctx=None):
     _lib.call('pp_nerf_bwd', _f(params), _f(ray), _f(depth), _i(count), int(n_rays), int(n_samples), _f(acts), _f(rgb_samples),

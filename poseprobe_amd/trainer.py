@@ -400,7 +400,8 @@ class DualBranchTrainer:
         """Held-out views by the reference's protocol (eval.py:1353-1416; evaluation.evaluate_test_views with this trainer's
         networks, the active views' current poses and its depth range): alignment of the training poses, test-time pose
         refinement against the frozen scene networks (refine=False skips it), full-view renders, PSNR / SSIM.  The networks and
-        the optimiser state are left as they are."""
+        the optimiser state are left as they are.  render='view' (optionally chunk_rays=) renders through the forward-only
+        SceneRenderer.render_view."""
         from . import evaluation, ops
         e = self.joint.obj
         k = e.V if self.n_active is None else self.n_active
@@ -408,6 +409,18 @@ class DualBranchTrainer:
         GT = torch.as_tensor(pose_GT_w2c_train)
         return evaluation.evaluate_test_views(self.nerf, self.nerf_fine, self.opt, e.w2c[:k].detach(), GT[:k, :3], pose_GT_w2c_test,
                                               images_test, Ks_test, self.joint.depth_range, **kw)
+
+    def novel_views(self, intr, H, W, dataset='dtu', n_frames=60, chunk_rays=8192):
+        """The novel-view sequence of the reference's generate_videos_synthesis (renderer.py:1213-1310) around the active views'
+        current poses, rendered by this trainer's networks at its depth range (gen_videos.render_novel_views):
+        -> dict(poses_w2c [F,3,4], rgb [F,H,W,3], depth [F,H,W]) on the device.  Networks and optimiser state are not written."""
+        from . import gen_videos, ops
+        e = self.joint.obj
+        k = e.V if self.n_active is None else self.n_active
+        ops.pose_fwd(e.se3, e.w2c_init, e.refine_mask, e.w2c, e.c2w, e.jac)
+        renderer = bg_nerf.SceneRenderer(self.opt, nerf=self.nerf, nerf_fine=self.nerf_fine)
+        return gen_videos.render_novel_views(renderer, self.opt, e.w2c[:k].detach(), intr, H, W, self.joint.depth_range,
+                                             dataset=dataset, n_frames=n_frames, chunk_rays=chunk_rays)
 
     # ---- `model_last.pth.tar` (renderer.py:1028-1051 save_snapshot, recon_scene.py:827-838 load) ----------------------------
     def _adam_state_dict(self):
