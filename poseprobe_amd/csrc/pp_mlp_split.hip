@@ -47,6 +47,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define LDH2 136                // halfs per row of a split tile
 #define PLANE (TILE_ROWS * LDH2)
 #define PP_WAIT_VMEM() do { __builtin_amdgcn_s_waitcnt(0x0F70); asm volatile("" ::: "memory"); } while (0)
+// at most N (< 16) vector-memory operations of this wavefront still outstanding: they retire in the order of their issue, so
+// everything issued before the N youngest has landed
+#define PP_WAIT_VMEM_N(N) do { __builtin_amdgcn_s_waitcnt(0x0F70 | (N)); asm volatile("" ::: "memory"); } while (0)
 
 namespace {
 
@@ -616,6 +619,22 @@ struct HalfEpilogueB {
 #define PP_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define PP_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
+// LDS-direct loads the compiler does not track (64 lanes x 16 / 4 bytes from the lanes' addresses `g` to `lds` onwards), for the
+// two data-gradient kernels, whose loads stay in flight across stages and barriers.  Behind the builtin the compiler drains the
+// vector-memory counter before every __syncthreads() and in front of every LDS read it cannot prove disjoint from a load still in
+// flight; behind these every wait is the kernel's own (PP_WAIT_VMEM, PP_WAIT_VMEM_N), __syncthreads() orders LDS accesses only,
+// and a reader of the bytes sits behind such a wait of the issuing wavefronts AND a barrier.  An ordinary global load inside the
+// span stays correct but drains it: the compiler's counted wait for it does not count these, so it waits for all of them as well.
+// `lds` must be wavefront-uniform.
+__device__ __forceinline__ void lds_load16(const float* g, const float* lds) {
+  const unsigned a = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(const __attribute__((address_space(3))) float*)lds);
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(a), "v"(g) : "memory");
+}
+__device__ __forceinline__ void lds_load4(const float* g, const float* lds) {
+  const unsigned a = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(const __attribute__((address_space(3))) float*)lds);
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" ::"s"(a), "v"(g) : "memory");
+}
+
 }  // namespace
 
 // LEAN: Ybar3 is NOT stored.  Instead the tile's 16 output gradients per sample, times out_range, go to the start of `ybar`
@@ -667,18 +686,12 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
     ew1 = load_w_cols_split(w1, l1_1, params + WPF_W1, col, lh, red4, tid, phase);
   }
   // (the output layer's quantities carry out_range, a per-call argument: they stay here)
-  // output layer backward as a K = 16 product: A = [w4_0 w4_1 w4_2 w4_3 0 ...] * out_range of feature `col` (lanes lh = 0),
-  // B = the row's four out_grad entries
+  // output layer backward as two v_mfma_f32_32x32x2_f32 (K = 4, fp32 operands: a thin product has no long sum to hide the 22 bits
+  // of a split operand under): A = w4_k * out_range of feature `col`, B = the row's out_grad entry k, k = lh and 2 + lh
   const float w4a = params[WPF_W4 + col] * out_range, w4b = params[WPF_W4 + 128 + col] * out_range,
               w4c = params[WPF_W4 + 256 + col] * out_range, w4d = params[WPF_W4 + 384 + col] * out_range;
   const float w4l1 = block_max((fabsf(w4a) + fabsf(w4b)) + (fabsf(w4c) + fabsf(w4d)), red4, tid, phase) * 1.0001f;
-  const int ew4 = scale_exp(block_max(fmaxf(fmaxf(fabsf(w4a), fabsf(w4b)), fmaxf(fabsf(w4c), fabsf(w4d))), red4, tid, phase));
-  pp_half8 a4h, a4l;
-  {
-    const float z = 0.f;
-    const float4 wa = lh == 0 ? make_float4(w4a, w4b, w4c, w4d) : make_float4(z, z, z, z);
-    split8(wa, make_float4(z, z, z, z), pow2(ew4), a4h, a4l);
-  }
+  const float a4k0 = lh ? w4b : w4a, a4k1 = lh ? w4d : w4c;
   const int j0 = tid & 127, h0 = tid >> 7;
   for (int i = tid; i < 512; i += 256) {
     const int r = i >> 7, j = i & 127;
@@ -693,20 +706,20 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
     if (i < 8) {
       const int rl = 16 * wid + 2 * i;
       const int row = min(rn0 + rl + lh, R - 1);
-      __builtin_amdgcn_global_load_lds(PP_GLOBAL_PTR(X3 + (size_t)row * 128 + l31 * 4), PP_LDS_PTR(&XS[rl * 128]), 16, 0, 0);
+      lds_load16(X3 + (size_t)row * 128 + l31 * 4, &XS[rl * 128]);
     } else if (i == 8) {
       const int e = min(sn0 * 16 + tid, M * 16 - 1);
-      __builtin_amdgcn_global_load_lds(PP_GLOBAL_PTR(out_grad + e), PP_LDS_PTR(&G[b][wid * 64]), 4, 0, 0);
+      lds_load4(out_grad + e, &G[b][wid * 64]);
     } else if (wid == 0) {
       const int e = min(sn0 * 3 + lane, M * 3 - 1);
-      __builtin_amdgcn_global_load_lds(PP_GLOBAL_PTR(pts + e), PP_LDS_PTR(&Ps[b][0]), 4, 0, 0);
+      lds_load4(pts + e, &Ps[b][0]);
     }
   };
   // primal rows (every fourth) of activation X of tile rows r0.. -> GT[gb]: 16 rows x 512 B, two pieces per wavefront
   auto stage_gate_piece = [&](const float* __restrict__ X, int r0, int gb, int i) {
     const int prow = 4 * wid + 2 * i;
     const int row = min(r0 + 4 * (prow + lh), R - 1);
-    __builtin_amdgcn_global_load_lds(PP_GLOBAL_PTR(X + (size_t)row * 128 + l31 * 4), PP_LDS_PTR(&GT[gb][prow * 128]), 16, 0, 0);
+    lds_load16(X + (size_t)row * 128 + l31 * 4, &GT[gb][prow * 128]);
   };
   // samples past M contribute nothing; largest |out_grad| of the tile into its slot
   auto prepare_grad = [&](int t, int b) {
@@ -726,28 +739,23 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
       if (j0 < 4 && (r & 3) == 0) bacc4 += G[b][(h0 * 32 + r) * 4 + j0];
     }
   };
-  // Ybar3 (pre-gate) of half t of the staged tile: three MFMAs
-  auto out_layer = [&](int b, int t, float sg, f32x16& acc) {
-    float4 x = *reinterpret_cast<const float4*>(&G[b][(t * 32 + l31) * 4]);
-    if (lh != 0) x = make_float4(0.f, 0.f, 0.f, 0.f);
-    pp_half8 xh, xl;
-    split8(x, make_float4(0.f, 0.f, 0.f, 0.f), sg, xh, xl);
+  // Ybar3 (pre-gate) of half t of the staged tile: two fp32 MFMAs
+  auto out_layer = [&](int b, int t, f32x16& acc) {
+    const float4 x = *reinterpret_cast<const float4*>(&G[b][(t * 32 + l31) * 4]);
     zero16(acc);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a4h, xl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a4l, xh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a4h, xh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4k0, lh ? x.y : x.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4k1, lh ? x.w : x.z, acc, 0, 0, 0);
   };
   // Ybar3 of the staged tile (parity b) into LDS tile 0 and `ybar`: both halves; returns the exponents of the two images
   int e3n0 = 0, e3n1 = 0;
   auto out_layer_bwd = [&](int t, int b) {
     const float gmx = slot_get(&Mx[b][6]);
-    const int eg = scale_exp(gmx);
     const int e3 = scale_exp(gmx * w4l1);
-    const float sg = pow2(eg), s3 = pow2(e3), inv = pow2(-(eg + ew4)), n3 = pow2(-e3);
+    const float s3 = pow2(e3), inv = 1.f, n3 = pow2(-e3);
     const int r0 = t * TILE_ROWS;
     f32x16 a0, a1;
-    out_layer(b, 0, sg, a0);
-    out_layer(b, 1, sg, a1);
+    out_layer(b, 0, a0);
+    out_layer(b, 1, a1);
     HalfEpilogueB<true> eb;
     float* crow = LEAN ? nullptr : ybar + (size_t)(r0 + l31) * 128 + fb;
     if (LEAN && t * 16 + (tid >> 4) < M) ybar[(size_t)t * 256 + tid] = G[b][tid] * out_range;
@@ -793,7 +801,9 @@ __global__ __launch_bounds__(256) void k_warp_fused_bwd_s(const float* __restric
       if (ks < 2) stage_gate_piece(X2, r0, 0, ks);
       if (more) { stage_piece(tnext, par ^ 1, ks); if (ks < 2) stage_piece(tnext, par ^ 1, 8 + ks); }
     });
-    PP_WAIT_VMEM();
+    // the X2 gates and the next tile's out_grad have landed once nothing but the seven (wavefront 0: eight) pieces issued after
+    // them is outstanding; the next tile's X3 rows stay in flight until stage A2 drains them
+    if (more) PP_WAIT_VMEM_N(7); else PP_WAIT_VMEM();
     __syncthreads();
     // ---- stage B3: layer 3 on half 1  ||  epilogue of (Ybar2, half 0); loads: gates X1 -> GT[1]
     const int e20 = scale_exp(slot_get(&Mx[par][0]) * l1_3), e21 = scale_exp(slot_get(&Mx[par][1]) * l1_3);
@@ -1180,6 +1190,11 @@ int pp_launch_rgb_fused_fwd_s(const float* params, const float* feat, const int3
 // Gates are per element (the layer input's own activation); the tile of gating activations arrives by LDS-direct loads into ONE
 // buffer (H1, then H0 - a second 32 KB buffer does not fit beside the two images and the next tile's H2), so the two halves of
 // Ybar0 are written out without MFMAs beside them.
+// Loads.  No load is waited for in the stage that issues it: H1 of a tile is issued in the tile BEFORE it, as soon as the gate
+// buffer is free, and waited for after the tile's first stage; the next tile's H2 / rgb / rgb_grad are issued at the top and
+// drained four stages later; H0 arrives as two 32-row halves, rows 0-31 into a buffer of their own (16 KB) at the top, rows 32-63
+// into the gate buffer's rows 0-31 once every wavefront holds those H1 gates in registers.  The waits are counted (PP_WAIT_VMEM_N:
+// everything but the N youngest operations), so a load that is not needed yet stays in flight across stages and barriers.
 template <bool PACK>
 __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict__ params, const float* __restrict__ acts,
                                                          const float* __restrict__ rgb, const float* __restrict__ rgb_grad,
@@ -1189,7 +1204,8 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
                                                          float* __restrict__ part, const float* __restrict__ pack) {
   __shared__ __attribute__((aligned(16))) _Float16 At[2][2 * PLANE];
   __shared__ __attribute__((aligned(16))) float XS[TILE_ROWS * 128];      // H2 of the NEXT tile
-  __shared__ __attribute__((aligned(16))) float GT[TILE_ROWS * 128];      // gates of the current layer (H1, then H0)
+  __shared__ __attribute__((aligned(16))) float GT[TILE_ROWS * 128];      // gates: H1 of the tile, then H0 rows 32-63 in its rows 0-31
+  __shared__ __attribute__((aligned(16))) float G0[32 * 128];             // gates: H0 rows 0-31
   __shared__ __attribute__((aligned(16))) float RG[2][2][192];            // [parity][rgb | rgb_grad] of a tile
   __shared__ __attribute__((aligned(16))) float GL[TILE_ROWS * 4];        // d loss / d logits of the staged tile
   __shared__ unsigned Mx[2][8];      // per parity: max |Ybar2| (halves 0, 1), |Ybar1| (0, 1), max |d logits| of the tile
@@ -1212,29 +1228,24 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
   // last product: feat_grad[64 rows][64] = Ybar0 . W0, wavefront = (row half wid >> 1, feature block wid & 1); A operand =
   // transposed W0 (k = hidden feature, value W0[k][f]) of input feature f = 32 (wid & 1) + l31
   const int rb = wid >> 1, fcol = (wid & 1) * 32 + l31;
-  // output layer backward as a K = 16 product: A = [w3_0 w3_1 w3_2 0 ...] of feature `col` (lanes lh = 0), B = d loss / d logits
+  // output layer backward as two v_mfma_f32_32x32x2_f32 (K = 3 padded to 4, fp32 operands: see the warp kernel): A = w3_k of
+  // feature `col`, B = d loss / d logit k of the row, k = lh and 2 + lh
   const float w3a = params[RGF_W3 + col], w3b = params[RGF_W3 + 128 + col], w3c = params[RGF_W3 + 256 + col];
-  int ew2, ew1, ew0, ew3;
+  int ew2, ew1, ew0;
   float w3l1;
   if (PACK) {
     load_w_packed<8>(w2, pack + PK_RGB_W1 + 2 * PK_IMG, tid);
     load_w_packed<8>(w1, pack + PK_RGB_W1 + 3 * PK_IMG, tid);
     load_w_packed<8>(w0, pack + PK_RGB_W1 + 4 * PK_IMG, tid);
-    ew2 = pk_int(pack, PKR_EW2C); ew1 = pk_int(pack, PKR_EW1C); ew0 = pk_int(pack, PKR_EW0T); ew3 = pk_int(pack, PKR_EW3);
+    ew2 = pk_int(pack, PKR_EW2C); ew1 = pk_int(pack, PKR_EW1C); ew0 = pk_int(pack, PKR_EW0T);
     l1_2 = pack[PKR_L1_2C]; l1_1 = pack[PKR_L1_1C]; w3l1 = pack[PKR_W3L1];
   } else {
     ew2 = load_w_cols_split(w2, l1_2, params + RGF_W2, col, lh, red4, tid, phase);
     ew1 = load_w_cols_split(w1, l1_1, params + RGF_W1, col, lh, red4, tid, phase);
     ew0 = load_w0_cols_split(w0, params + RGF_W0, fcol, lh, red4, tid, phase);
     w3l1 = block_max((fabsf(w3a) + fabsf(w3b)) + fabsf(w3c), red4, tid, phase) * 1.0001f;
-    ew3 = scale_exp(block_max(fmaxf(fmaxf(fabsf(w3a), fabsf(w3b)), fabsf(w3c)), red4, tid, phase));
   }
-  pp_half8 a3h, a3l;
-  {
-    const float z = 0.f;
-    const float4 wa = lh == 0 ? make_float4(w3a, w3b, w3c, z) : make_float4(z, z, z, z);
-    split8(wa, make_float4(z, z, z, z), pow2(ew3), a3h, a3l);
-  }
+  const float a3k0 = lh ? w3b : w3a, a3k1 = lh ? 0.f : w3c;
   const int j0 = tid & 127, h0 = tid >> 7;
   float wacc3[3] = {0.f, 0.f, 0.f}, bacc3 = 0.f;
 
@@ -1243,7 +1254,15 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
     for (int i = 0; i < 8; ++i) {
       const int rl = 16 * wid + 2 * i;
       const int row = min(r0 + rl + lh, R - 1);
-      __builtin_amdgcn_global_load_lds(PP_GLOBAL_PTR(X + (size_t)row * 128 + l31 * 4), PP_LDS_PTR(dst + rl * 128), 16, 0, 0);
+      lds_load16(X + (size_t)row * 128 + l31 * 4, dst + rl * 128);
+    }
+  };
+  auto stage_half = [&](const float* __restrict__ X, int r0, float* dst, int hh) {       // rows 32 hh .. 32 hh + 31 -> dst[32][128]
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int rl = 8 * wid + 2 * i;
+      const int row = min(r0 + 32 * hh + rl + lh, R - 1);
+      lds_load16(X + (size_t)row * 128 + l31 * 4, dst + rl * 128);
     }
   };
   auto stage = [&](int t, int b) {              // H2 rows, rgb and rgb_grad of tile t
@@ -1251,8 +1270,8 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
     stage_tile(H2, r0, XS);
     if (wid < 3) {
       const int e = min(r0 * 3 + tid, R * 3 - 1);
-      __builtin_amdgcn_global_load_lds(PP_GLOBAL_PTR(rgb + e), PP_LDS_PTR(&RG[b][0][wid * 64]), 4, 0, 0);
-      __builtin_amdgcn_global_load_lds(PP_GLOBAL_PTR(rgb_grad + e), PP_LDS_PTR(&RG[b][1][wid * 64]), 4, 0, 0);
+      lds_load4(rgb + e, &RG[b][0][wid * 64]);
+      lds_load4(rgb_grad + e, &RG[b][1][wid * 64]);
     }
   };
   // d loss / d logit = rgb_grad * rgb * (1 - rgb); zero for rows past the end; its largest magnitude into the tile's slot
@@ -1285,23 +1304,18 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
   int e2n = 0;
   auto out_layer_bwd = [&](int t, int b, _Float16* dst) {
     const float gmx = slot_get(&Mx[b][4]);
-    const int eg = scale_exp(gmx);
     const int e2 = scale_exp(gmx * w3l1);
-    const float sg = pow2(eg), s2 = pow2(e2), inv = pow2(-(eg + ew3)), n2 = pow2(-e2);
+    const float s2 = pow2(e2), inv = 1.f, n2 = pow2(-e2);
     const int r0 = t * TILE_ROWS;
     float* crow = ybar + (size_t)(r0 + l31) * 128 + fb;
     HalfEpilogueB<true> eb;
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
-      float4 x = *reinterpret_cast<const float4*>(&GL[(hh * 32 + l31) * 4]);
-      if (lh != 0) x = make_float4(0.f, 0.f, 0.f, 0.f);
-      pp_half8 xh, xl;
-      split8(x, make_float4(0.f, 0.f, 0.f, 0.f), sg, xh, xl);
+      const float4 x = *reinterpret_cast<const float4*>(&GL[(hh * 32 + l31) * 4]);      // (entry 3 is zero)
       f32x16 a;
       zero16(a);
-      a = __builtin_amdgcn_mfma_f32_32x32x16_f16(a3h, xl, a, 0, 0, 0);
-      a = __builtin_amdgcn_mfma_f32_32x32x16_f16(a3l, xh, a, 0, 0, 0);
-      a = __builtin_amdgcn_mfma_f32_32x32x16_f16(a3h, xh, a, 0, 0, 0);
+      a = __builtin_amdgcn_mfma_f32_32x32x2f32(a3k0, lh ? x.y : x.x, a, 0, 0, 0);
+      a = __builtin_amdgcn_mfma_f32_32x32x2f32(a3k1, lh ? x.w : x.z, a, 0, 0, 0);
       eb.begin(&XS[(hh * 32 + l31) * 128 + fb]);
       eb.all(a, inv, s2, r0 + hh * 32 + l31 < R, crow + hh * 32 * 128, dst + (hh * 32 + l31) * LDH2 + fb);
       slot_max(&Mx[b][hh], eb.vmax(n2), lane);
@@ -1313,6 +1327,7 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
   stage(blockIdx.x, 0);
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
+  stage_tile(H1, blockIdx.x * TILE_ROWS, GT);      // the first tile's H1 gates (every later tile's: from the tile before it)
   logit_grads(blockIdx.x, 0);
   __syncthreads();
   w3_accumulate();
@@ -1333,11 +1348,13 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
     HalfEpilogueB<true> eb;
     if (tid < 5) Mx[par ^ 1][tid] = 0u;
     if (more) stage(tnext, par ^ 1);             // XS / RG[par^1]: consumed at the bottom of this iteration
-    stage_tile(H1, r0, GT);
+    stage_half(H0, r0, G0, 0);                   // gates of (Ybar0, half 0): read three stages from here
     // ---- layer 2 on half 0
     zero16(acc0);
     mma_half(Aa, w2, acc0, l31, lh);
-    PP_WAIT_VMEM();
+    // this tile's H1 gates, issued a stage ago, have landed once nothing but the loads issued above is outstanding: at least
+    // 8 + 4 of them per wavefront with a next tile, 4 without one (loads and stores retire in the order of their issue)
+    if (more) PP_WAIT_VMEM_N(12); else PP_WAIT_VMEM_N(4);
     __syncthreads();                             // gates come from all four wavefronts' loads
     // ---- layer 2 on half 1  ||  epilogue of (Ybar1, half 0)
     const int e10 = scale_exp(slot_get(&Mx[par][0]) * l1_2), e11 = scale_exp(slot_get(&Mx[par][1]) * l1_2);
@@ -1347,29 +1364,31 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
       eb.step(ks, acc0, pow2(-(e2 + ew2)), pow2(e10), ok0, crow + LS, Ab + l31 * LDH2 + fb);
     });
     slot_max(&Mx[par][2], eb.vmax(pow2(-e10)), lane);
-    __syncthreads();
-    // ---- layer 1 on half 0  ||  epilogue of (Ybar1, half 1)
+    __syncthreads();                             // GT rows 0-31 (H1) are free: every wavefront has them in registers
+    // ---- layer 1 on half 0  ||  epilogue of (Ybar1, half 1); loads: H0 rows 32-63 -> GT rows 0-31
     zero16(acc0);
     eb.begin(&GT[(32 + l31) * 128 + fb]);
+    stage_half(H0, r0, GT, 1);
     mma_half(Ab, w1, acc0, l31, lh, [&](int ks) {
+      if (ks == 6) PP_WAIT_VMEM_N(4);            // all but the four loads above: G0 and the next tile's staging have landed
       eb.step(ks, acc1, pow2(-(e2 + ew2)), pow2(e11), ok1, crow + LS + 32 * 128, Ab + (32 + l31) * LDH2 + fb);
     });
     slot_max(&Mx[par][3], eb.vmax(pow2(-e11)), lane);
-    __syncthreads();                             // GT (H1) is free
-    stage_tile(H0, r0, GT);
-    // ---- layer 1 on half 1 (the H0 gates land meanwhile)
+    __syncthreads();
+    // ---- layer 1 on half 1 (H0 rows 32-63 land meanwhile)
     zero16(acc1);
     mma_half(Ab + 32 * LDH2, w1, acc1, l31, lh);
     PP_WAIT_VMEM();
     __syncthreads();
     // ---- epilogues of Ybar0 (image into tile Aa: the operand of the feature-gradient product)
     const int e00 = scale_exp(slot_get(&Mx[par][2]) * l1_1), e01 = scale_exp(slot_get(&Mx[par][3]) * l1_1);
-    eb.begin(&GT[l31 * 128 + fb]);
+    eb.begin(&G0[l31 * 128 + fb]);
     eb.all(acc0, pow2(-(e10 + ew1)), pow2(e00), ok0, crow + 2 * LS, Aa + l31 * LDH2 + fb);
-    eb.begin(&GT[(32 + l31) * 128 + fb]);
+    eb.begin(&GT[l31 * 128 + fb]);               // (H0 rows 32-63 live in GT rows 0-31)
     eb.all(acc1, pow2(-(e11 + ew1)), pow2(e01), ok1, crow + 2 * LS + 32 * 128, Aa + (32 + l31) * LDH2 + fb);
     if (more) logit_grads(tnext, par ^ 1);
-    __syncthreads();
+    __syncthreads();                             // GT is free
+    if (more) stage_tile(H1, tnext * TILE_ROWS, GT);      // the next tile's H1 gates: waited for after its first stage
     // ---- layer 0: feat_grad = Ybar0 . W0   (32 rows x 32 features per wavefront)
     {
       f32x16 fa;
@@ -1389,7 +1408,7 @@ __global__ __launch_bounds__(256) void k_rgb_fused_bwd_s(const float* __restrict
       w3_accumulate();
       out_layer_bwd(tnext, par ^ 1, Ab);
     }
-    __syncthreads();
+    __syncthreads();                             // (the next tile's H1 gates stay in flight across it)
   }
 
   // ---- flush W3bar, b3bar (thread = feature / output): atomics, or this work-group's row of `part` (ordered flush, pp_ordered.h)
