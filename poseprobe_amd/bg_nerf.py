@@ -18,6 +18,7 @@ Supported architecture = the reference default (lib/bg_nerf/train_settings/defau
 PoseProbe configuration uses; anything else raises NotImplementedError rather than silently taking another path.
 """
 import math
+import weakref
 
 import torch
 
@@ -68,16 +69,24 @@ def sparf_dtu_options(barf_c2f=(0.4, 0.7), sample_intvs=128, white_bg=False, max
     return opt
 
 
+def stratified_depths(opt, rand, depth_range):
+    """Stratified depths from uniform draws (renderer.py:665-700): rand [..., S, 1] (the reference's sample layout; a trailing
+    axis of 1 is read as that) or [..., S], fresh or replayed, on the device the depths are wanted on.  Sample i of a ray lies
+    in the i-th of S equal bins of depth_range, then goes through the opt.nerf.depth.param map."""
+    column = rand.dim() > 1 and rand.shape[-1] == 1
+    S = rand.shape[-2] if column else rand.shape[-1]
+    steps = torch.arange(S, device=rand.device).float()
+    depth = (rand + (steps[:, None] if column else steps)) / S * (depth_range[1] - depth_range[0]) + depth_range[0]
+    return {'metric': depth, 'inverse': 1 / (depth + 1e-8)}[opt.nerf.depth.param]
+
+
 def sample_depth(opt, batch_size, num_rays, n_samples, depth_range, mode=None, device='cuda', generator=None):
     """Stratified depth samples [B, num_rays, n_samples, 1] (renderer.py:665-700)."""
-    depth_min, depth_max = depth_range
     if opt.nerf.sample_stratified and mode not in ('val', 'eval', 'test'):
         rand = torch.rand(batch_size, num_rays, n_samples, 1, device=device, generator=generator)
     else:
         rand = 0.5 * torch.ones(batch_size, num_rays, n_samples, 1, device=device)
-    rand = rand + torch.arange(n_samples, device=device)[None, None, :, None].float()
-    depth = rand / n_samples * (depth_max - depth_min) + depth_min
-    return {'metric': depth, 'inverse': 1 / (depth + 1e-8)}[opt.nerf.depth.param]
+    return stratified_depths(opt, rand, depth_range)
 
 
 def sample_depth_from_pdf(weights, n_samples_coarse, n_samples_fine, depth_range, det, generator=None, grid=None):
@@ -124,12 +133,11 @@ class _Workspace:
 
     def __init__(self, R, S, dev):
         M = R * S
-        self.acts_floats, s = ops.nerf_workspace(M, R)
-        f = dict(dtype=torch.float32, device=dev)
+        self.acts_floats, self.scratch_floats = ops.nerf_workspace(M, R)
         self.R, self.S, self.dev = R, S, dev
-        self._acts = None
-        self.scratch = torch.zeros(s, **f)
+        self._acts = self._scratch = None
         self.count = torch.tensor([M], dtype=torch.int32, device=dev)
+        self.scene_pass = None                # the ScenePass of this shape, made by NeRF.scene_pass and evicted with this
 
     @property
     def acts(self):
@@ -137,29 +145,77 @@ class _Workspace:
             self._acts = torch.empty(self.acts_floats, dtype=torch.float32, device=self.dev)
         return self._acts
 
+    @property
+    def scratch(self):                        # (a forward-only user never asks for it)
+        if self._scratch is None:
+            self._scratch = torch.zeros(self.scratch_floats, dtype=torch.float32, device=self.dev)
+        return self._scratch
+
     def new_acts(self):
         return torch.empty(self.acts_floats, dtype=torch.float32, device=self.dev)
 
 
-class _InferWorkspace:
-    """Buffers of one forward-only pass shape (R rays x S samples): pp_nerf_infer's workspace - 224 floats per sample against the
-    2337 + 256 mask bytes of a pass that a backward may follow -, the sample outputs and the compositing outputs.  Nothing in
-    here is read by any backward pass."""
+class ScenePass:
+    """One forward / backward pair of one network at one (R rays x S samples) shape, without autograd: the sample outputs
+    (rgb_s, dens), the compositing outputs (rgb, d, op, w, cum, rv, dv) and - from the first backward on - the sample and ray
+    gradients (g_rgb_s, g_dens, g_ray_c, g_center, g_ray) and zero_r, as attributes.  One per network and shape
+    (NeRF.scene_pass), shared by everything that runs such pairs on the network - SceneEngine, pose_refine.PoseRefiner, the
+    forward-only SceneRenderer.render_view / render_rays - and overwritten by every call: a pair is forward, then backward,
+    with nothing of the same network and shape in between.  The loss gradients g_rgb / g_depth belong to the caller."""
 
-    def __init__(self, R, S, dev):
-        M = R * S
-        f = dict(dtype=torch.float32, device=dev)
-        self.R, self.S, self._work = R, S, None
-        self.count = torch.tensor([M], dtype=torch.int32, device=dev)
-        self.rgb_s, self.dens = torch.empty(M, 3, **f), torch.empty(M, **f)
+    def __init__(self, net, ws):
+        self.net, self.ws = weakref.proxy(net), weakref.proxy(ws)          # both outlive the pass they hold: no cycle
+        R, S = ws.R, ws.S
+        f = dict(dtype=torch.float32, device=ws.dev)
+        self.R, self.S, self._f = R, S, f
+        self.rgb_s, self.dens = torch.empty(R * S, 3, **f), torch.empty(R * S, **f)
         self.rgb, self.w = torch.empty(R, 3, **f), torch.empty(R, S, **f)
         self.d, self.op, self.cum, self.rv, self.dv = (torch.empty(R, **f) for _ in range(5))
+        self.g_rgb_s = self._work = None
 
-    @property
-    def work(self):                       # (a network on another route never asks for it)
-        if self._work is None:
-            self._work = torch.empty(ops.nerf_infer_workspace(self.R * self.S, self.R), dtype=torch.float32, device=self.rgb.device)
-        return self._work
+    def forward(self, center, ray, depth, keep_acts=True):
+        """center, ray [R,3], depth [R,S], contiguous fp32: pp_nerf_fwd into the shape's shared activation block and
+        pp_nerf_composite_fwd.  keep_acts=False (no backward follows): pp_nerf_infer on its own workspace - 224 floats per
+        sample against the 2337 + 256 mask bytes of the activation block - where the network's context selects the route it
+        has.  -> self"""
+        net, ws, R, S = self.net, self.ws, self.R, self.S
+        if not keep_acts and net.infer_route():
+            if self._work is None:
+                self._work = torch.empty(ops.nerf_infer_workspace(R * S, R), **self._f)
+            ops.nerf_infer(net.flat, center, ray, depth, net.band_weights(), ws.count, R, S, self._work, self.rgb_s, self.dens,
+                           net.ctx)
+        else:
+            ops.nerf_fwd(net.flat, center, ray, depth, net.band_weights(), ws.count, R, S, ws.acts, self.rgb_s, self.dens, net.ctx)
+        ops.nerf_composite_fwd(self.rgb_s, self.dens, depth, ray, R, S, net.white_bg, self.rgb, self.d, self.op, self.w, self.cum,
+                               self.rv, self.dv)
+        return self
+
+    def _composite_bwd(self, ray, depth, g_rgb, g_depth):
+        if self.g_rgb_s is None:
+            R, S, f = self.R, self.S, self._f
+            self.g_rgb_s, self.g_dens = torch.empty(R * S, 3, **f), torch.empty(R * S, **f)
+            self.g_ray_c, self.g_center, self.g_ray = (torch.empty(R, 3, **f) for _ in range(3))
+            self.zero_r = torch.zeros(R, **f)
+        ops.nerf_composite_bwd(self.rgb_s, self.dens, depth, ray, self.w, self.R, self.S, self.net.white_bg, g_rgb,
+                               self.zero_r if g_depth is None else g_depth, self.zero_r, None, self.g_rgb_s, self.g_dens,
+                               self.g_ray_c)
+
+    def backward(self, ray, depth, g_rgb, g_depth, grad_block):
+        """Backward of the last forward(): g_rgb [R,3], g_depth [R] (None: zero) = d loss / d (rgb, d) -> g_center, g_ray [R,3];
+        the parameter gradients are accumulated into grad_block."""
+        net, ws = self.net, self.ws
+        self._composite_bwd(ray, depth, g_rgb, g_depth)
+        ops.nerf_bwd(net.flat, ray, depth, ws.count, self.R, self.S, ws.acts, self.rgb_s, self.g_rgb_s, self.g_dens, ws.scratch,
+                     grad_block, self.g_center, self.g_ray, net.ctx)
+        return self.g_center, self.g_ray + self.g_ray_c
+
+    def backward_input(self, ray, depth, g_rgb, g_depth=None):
+        """backward() that forms no parameter gradient (pp_nerf_bwd_input): the network stays frozen."""
+        net, ws = self.net, self.ws
+        self._composite_bwd(ray, depth, g_rgb, g_depth)
+        ops.nerf_bwd_input(net.flat, ray, depth, ws.count, self.R, self.S, ws.acts, self.rgb_s, self.g_rgb_s, self.g_dens,
+                           ws.scratch, self.g_center, self.g_ray, net.ctx)
+        return self.g_center, self.g_ray + self.g_ray_c
 
 
 def plan_chunks(n_rays, chunk_rays):
@@ -370,30 +426,24 @@ class NeRF(torch.nn.Module):
         c = self.ctx if self.ctx is not None else _lib.default_context()
         return c.get('nerf_split') == 1 and (c.get('nerf_chain') & 1) == 1 and c.get('nerf_chain_head') == 1
 
-    def _infer_workspace(self, R, S):
-        cache = self.__dict__.setdefault('_iws', {})
-        ws = cache.get((R, S))
-        if ws is None:
-            if len(cache) >= 4:
-                cache.clear()
-            ws = cache[(R, S)] = _InferWorkspace(R, S, self.flat.device)
-        return ws
+    @property
+    def white_bg(self):
+        """Composite onto a white background (frequency_nerf.py:337)."""
+        return bool(self.opt.nerf.setbg_opaque or self.opt.mask_img)
+
+    def scene_pass(self, R, S):
+        """The ScenePass of this network at R rays x S samples, cached on (and evicted with) the shape's workspace."""
+        ws = self._workspace(R, S)
+        if ws.scene_pass is None:
+            ws.scene_pass = ScenePass(self, ws)
+        return ws.scene_pass
 
     @torch.no_grad()
     def infer_composite(self, opt, center, ray, depth):
-        """center, ray [R,3], depth [R,S], contiguous fp32 -> the _InferWorkspace of the shape, holding rgb_s, dens and the
-        compositing outputs of this call (overwritten by the next call of the same shape).  Forward only: pp_nerf_infer (or, on
+        """center, ray [R,3], depth [R,S], contiguous fp32 -> the ScenePass of the shape, holding rgb_s, dens and the
+        compositing outputs of this call (overwritten by the next pass of the same shape).  Forward only: pp_nerf_infer (or, on
         another route, pp_nerf_fwd into the shared activation block) and pp_nerf_composite_fwd."""
-        R, S = depth.shape
-        b = self._infer_workspace(R, S)
-        if self.infer_route():
-            ops.nerf_infer(self.flat, center, ray, depth, self.band_weights(), b.count, R, S, b.work, b.rgb_s, b.dens, self.ctx)
-        else:
-            ops.nerf_fwd(self.flat, center, ray, depth, self.band_weights(), b.count, R, S, self._workspace(R, S).acts, b.rgb_s,
-                         b.dens, self.ctx)
-        white = bool(opt.nerf.setbg_opaque or opt.mask_img)
-        ops.nerf_composite_fwd(b.rgb_s, b.dens, depth, ray, R, S, white, b.rgb, b.d, b.op, b.w, b.cum, b.rv, b.dv)
-        return b
+        return self.scene_pass(*depth.shape).forward(center, ray, depth, keep_acts=False)
 
     def _params(self):
         return [p for lin in list(self.mlp_feat) + list(self.mlp_rgb) for p in (lin.weight, lin.bias)]
@@ -419,10 +469,9 @@ class NeRF(torch.nn.Module):
         """Quadrature compositing (frequency_nerf.py:290-343); adds rgb, rgb_var, depth, depth_var, opacity, weights,
         all_cumulated to pred_dict.  depth_samples are treated as constants, as produced by the stratified sampler."""
         B, N, S = depth_samples.shape[:3]
-        white = bool(opt.nerf.setbg_opaque or opt.mask_img)
         rgb, d, op, w, cum, rv, dv = _Composite.apply(pred_dict['rgb_samples'].reshape(B * N * S, 3),
                                                      pred_dict['density_samples'].reshape(B * N * S),
-                                                     depth_samples.reshape(B * N, S), ray.reshape(B * N, 3), white)
+                                                     depth_samples.reshape(B * N, S), ray.reshape(B * N, 3), self.white_bg)
         pred_dict.update(rgb=rgb.view(B, N, 3), rgb_var=rv.view(B, N, 1), depth=d.view(B, N, 1), depth_var=dv.view(B, N, 1),
                          opacity=op.view(B, N, 1), weights=w.view(B, N, S, 1), all_cumulated=cum.view(B, N))
         return pred_dict
@@ -485,17 +534,13 @@ class SceneRenderer:
         N, S = ray.shape[1], opt.nerf.sample_intvs
         pred = Options(origins=center, viewdirs=ray)
         if rand is not None:
-            jitter = rand[0].to(self.device) + torch.arange(S, device=self.device)[None, None, :, None].float()
-            depth = jitter / S * (depth_range[1] - depth_range[0]) + depth_range[0]
-            depth = {'metric': depth, 'inverse': 1 / (depth + 1e-8)}[opt.nerf.depth.param]
+            depth = stratified_depths(opt, rand[0].to(self.device), depth_range)
         else:
             depth = sample_depth(opt, B, N, S, depth_range, mode=mode, device=self.device)
         coarse = self.nerf.forward_samples(opt, center, ray, depth, mode=mode)
         coarse['t'] = depth
         pred.update(self.nerf.composite(opt, ray, coarse, depth))
-        start = getattr(opt.nerf, 'ratio_start_fine_sampling_at_x', None)
-        skip_fine = start is not None and iter is not None and iter < opt.max_iter * start
-        if opt.nerf.fine_sampling and not skip_fine:
+        if self._fine_active(opt, iter):
             with torch.no_grad():
                 det = mode not in ('train', 'test-optim') or not opt.nerf.sample_stratified
                 grid = rand[1].to(self.device) if (rand is not None and not det) else None
@@ -521,9 +566,7 @@ class SceneRenderer:
         coarse = self.nerf.forward_samples(opt, center, ray, depth, mode=mode)
         coarse['t'] = depth
         pred.update(self.nerf.composite(opt, ray, coarse, depth))
-        start = getattr(opt.nerf, 'ratio_start_fine_sampling_at_x', None)
-        skip_fine = start is not None and iter is not None and iter < opt.max_iter * start
-        if opt.nerf.fine_sampling and not skip_fine:
+        if self._fine_active(opt, iter):
             fine = self.nerf_fine.forward_samples(opt, center, ray, depth, mode=mode)
             fine['t'] = depth
             fine = self.nerf_fine.composite(opt, ray, fine, depth)
@@ -545,12 +588,15 @@ class SceneRenderer:
         return Options({k: torch.cat(v, dim=1) for k, v in parts.items()})
 
 
-    # ---- forward-only whole views ------------------------------------------------------------------------------------------
-    def _fine_active(self, opt, iter):
+    @staticmethod
+    def _fine_active(opt, iter):
+        """The fine pass runs when fine_sampling is set and `iter`, if both it and ratio_start_fine_sampling_at_x are given, has
+        reached that share of max_iter (renderer.py:599-602)."""
         start = getattr(opt.nerf, 'ratio_start_fine_sampling_at_x', None)
         skip_fine = start is not None and iter is not None and iter < opt.max_iter * start
         return bool(opt.nerf.fine_sampling and not skip_fine)
 
+    # ---- forward-only whole views ------------------------------------------------------------------------------------------
     def _render_chunk(self, opt, center, ray, depth_range, mode, fine, out, c):
         """One chunk - center, ray [B, n, 3], the rays c .. c + n - 1 of every pose - through render's sequence of functions on
         render's shapes (the B * n rays of a chunk are one pass, as in render), written into out[key][:, c:c + n]."""
@@ -653,6 +699,43 @@ class _NetState:
         self.has_grad = False
 
 
+class _LossRing:
+    """256 slots for 0-dim losses that nobody reads back inside the step: a slot is rewritten 256 calls later."""
+
+    def __init__(self, dev):
+        self.slots, self.i = torch.zeros(256, dtype=torch.float32, device=dev), -1
+
+    def next(self):
+        self.i = (self.i + 1) % 256
+        return self.slots[self.i]
+
+
+class _LossGrads:
+    """d loss / d (rgb, depth) of one of SceneEngine's passes at R rows, and the ring of its photometric losses.  A call with Rp
+    photometric rows needs g_rgb [R,3] zero on the matched tail [Rp:] and g_depth [R] zero on the prefix [:Rp].  The loss
+    kernels overwrite the other rows - huber all of g_rgb[:Rp], pp_nerf_corres_loss all of g_depth[Rp:] - and nothing else
+    writes either buffer, so after a call both hold exactly that and `Rp` records the split; a call with another split zeroes
+    its two ranges before the kernels run.  g_rgb is made for the first call's split (zeros if that call has a tail).  g_depth
+    exists from the first call with matched rows on (all zero then: right for every split); a call without them gets None = the
+    pass's own zeros."""
+
+    def __init__(self, R, Rp, dev):
+        self.R, self.Rp = R, Rp
+        self.g_rgb, self.g_depth = (torch.empty if Rp == R else torch.zeros)(R, 3, dtype=torch.float32, device=dev), None
+        self.losses = _LossRing(dev)
+
+    def split(self, Rp, matched):
+        """-> g_rgb, g_depth (None unless `matched`) ready for a call with Rp photometric rows."""
+        if Rp != self.Rp:
+            self.g_rgb[Rp:].zero_()
+            if self.g_depth is not None:
+                self.g_depth[:Rp].zero_()
+            self.Rp = Rp
+        if matched and self.g_depth is None:
+            self.g_depth = torch.zeros(self.R, dtype=torch.float32, device=self.g_rgb.device)
+        return self.g_rgb, self.g_depth if matched else None
+
+
 class SceneEngine:
     """One optimisation step of the scene branch without autograd bookkeeping: forward, photometric loss, backward and one
     fused Adam update per packed parameter block (renderer.py:420-423 train_iteration + the optimiser step of
@@ -698,152 +781,85 @@ class SceneEngine:
         self.grad, self.m, self.v = self.states[0].grad, self.states[0].m, self.states[0].v
         self.step_count = 0
         self.seg_lr = torch.tensor([lr], dtype=torch.float32, device=net.flat.device)
-
-    @staticmethod
-    def _fwd(state, center, ray, depth):
-        """One network's forward and compositing into the per-shape step buffers -> (workspace, buffers)."""
-        net = state.net
-        R, S = depth.shape
-        ws = net._workspace(R, S)
-        f = dict(dtype=torch.float32, device=depth.device)
-        if getattr(ws, 'step_bufs', None) is None:
-            ws.step_bufs = dict(rgb_s=torch.empty(R * S, 3, **f), dens=torch.empty(R * S, **f), rgb=torch.empty(R, 3, **f),
-                                d=torch.empty(R, **f), op=torch.empty(R, **f), w=torch.empty(R, S, **f), cum=torch.empty(R, **f),
-                                rv=torch.empty(R, **f), dv=torch.empty(R, **f), g_rgb_s=torch.empty(R * S, 3, **f),
-                                g_dens=torch.empty(R * S, **f), g_ray_c=torch.empty(R, 3, **f), g_center=torch.empty(R, 3, **f),
-                                g_ray=torch.empty(R, 3, **f), zero_r=torch.zeros(R, **f), g_rgb=torch.empty(R, 3, **f),
-                                loss=torch.zeros(256, **f), loss_i=-1)
-        b = ws.step_bufs
-        white = bool(net.opt.nerf.setbg_opaque or net.opt.mask_img)
-        ops.nerf_fwd(net.flat, center, ray, depth, net.band_weights(), ws.count, R, S, ws.acts, b['rgb_s'], b['dens'], net.ctx)
-        ops.nerf_composite_fwd(b['rgb_s'], b['dens'], depth, ray, R, S, white, b['rgb'], b['d'], b['op'], b['w'], b['cum'],
-                               b['rv'], b['dv'])
-        return ws, b
-
-    @staticmethod
-    def _photometric(b, rgb, image, g_rgb, weight=2.0):
-        """2 * huber(delta = 0.5, mean) and its gradient on the [R,3] colours in one launch; the loss lands in a ring slot (the
-        returned 0-dim tensor is rewritten 256 passes later: read it - .item() / copy - before that)"""
-        b['loss_i'] = (b['loss_i'] + 1) % 256
-        loss = b['loss'][b['loss_i']]
-        ops.nerf_huber_loss(rgb, image.contiguous(), 0.5, weight, loss, g_rgb)
-        return loss
-
-    @staticmethod
-    def _bwd(state, ws, b, ray, depth, g_rgb, g_depth):
-        """Compositing and network backward of a pass run by _fwd -> (g_center, g_ray)."""
-        net = state.net
-        R, S = depth.shape
-        white = bool(net.opt.nerf.setbg_opaque or net.opt.mask_img)
-        ops.nerf_composite_bwd(b['rgb_s'], b['dens'], depth, ray, b['w'], R, S, white, g_rgb, g_depth,
-                               b['zero_r'], None, b['g_rgb_s'], b['g_dens'], b['g_ray_c'])
-        ops.nerf_bwd(net.flat, ray, depth, ws.count, R, S, ws.acts, b['rgb_s'], b['g_rgb_s'], b['g_dens'], ws.scratch,
-                     state.grad, b['g_center'], b['g_ray'], net.ctx)
-        state.has_grad = True
-        return b['g_center'], b['g_ray'] + b['g_ray_c']
-
-    @classmethod
-    def _pass(cls, state, center, ray, depth, image):
-        """One network: forward, compositing, 2 * huber(delta = 0.5, mean), backward.  -> loss, g_center, g_ray, weights."""
-        ws, b = cls._fwd(state, center, ray, depth)
-        loss = cls._photometric(b, b['rgb'], image, b['g_rgb'])
-        g_center, g_ray = cls._bwd(state, ws, b, ray, depth, b['g_rgb'], b['zero_r'])
-        return loss, g_center, g_ray, b['w']
+        self._loss_grads = {}                 # (pass, rows) -> _LossGrads
+        self._corres = None                   # (loss ring, g_w2c [2,3,4]) of the correspondence term, from its first use on
 
     def forward_backward(self, center, ray, depth, image, fine=False, depth_range=None, fine_grid=None, corres=None):
-        """center, ray [R,3]; depth [R,S]; image [R,3] -> (loss, g_center, g_ray); parameter gradients are accumulated into the
+        """center, ray [R,3]; depth [R,S]; image [Rp,3] -> (loss, g_center, g_ray); parameter gradients are accumulated into the
         networks' gradient blocks, which optimizer_step() consumes and re-zeroes.  fine=True adds the second pass
         (`depth_range` required; `fine_grid` [Nf + 1] replays the sampler's uniform draw).
-        corres (CorresRows): the union pass - center / ray / depth hold R = R_photo + 2M rows, image the R_photo photometric
-        rows, and the last 2M rows are the matched pixels of one view pair [self M | other M]; see _forward_backward_corres."""
-        if corres is not None:
-            return self._forward_backward_corres(center, ray, depth, image, fine, depth_range, fine_grid, corres)
-        loss, g_center, g_ray, w = self._pass(self.states[0], center, ray, depth, image)
-        if fine:
-            if self.net_fine is None or depth_range is None:
-                raise ValueError('SceneEngine: fine=True needs net_fine and depth_range')
-            opt = self.net.opt
-            S = depth.shape[1]
-            det = not opt.nerf.sample_stratified
-            if self.deterministic:
-                depth_f = self._fine_depths_ordered(w, depth, opt.nerf.sample_intvs_fine, depth_range, det, fine_grid)
-            else:
-                fine_t = sample_depth_from_pdf(w[None], S, opt.nerf.sample_intvs_fine, depth_range, det=det, grid=fine_grid)
-                depth_f = torch.cat([depth, fine_t[0, :, :, 0]], dim=1).sort(dim=1).values.contiguous()
-            loss_f, gc_f, gr_f, _ = self._pass(self.states[1], center, ray, depth_f, image)
-            loss, g_center, g_ray = loss + loss_f, g_center + gc_f, g_ray + gr_f
-        return loss, g_center, g_ray
-
-    @staticmethod
-    def _fine_depths_ordered(w, depth, n_fine, depth_range, det, grid):
-        """The fine pass's sorted [R, S + Nf] depths by ops.nerf_sample_pdf: the same draws as sample_depth_from_pdf (a replayed
-        `grid` [Nf + 1] or [R, Nf + 1], the regular grid when `det`, else a fresh host-side draw shared by the rays)."""
-        dev = depth.device
-        if grid is not None:
-            grid = grid.to(dev)
-        elif det:
-            grid = torch.linspace(0, 1, n_fine + 1, device=dev)
-        else:
-            grid = torch.rand(n_fine + 1).to(dev)
-        out = torch.empty(depth.shape[0], depth.shape[1] + n_fine, dtype=torch.float32, device=dev)
-        ops.nerf_sample_pdf(w, depth, grid.float().contiguous(), n_fine, depth_range, out)
-        return out
-
-    def _forward_backward_corres(self, center, ray, depth, image, fine, depth_range, fine_grid, corres):
-        """Photometric rows and matched-pixel rows in the same launches (the reference renders them in two calls, renderer.py
-        :420-423 and corres_loss.py:178-183): forward of every pass first, then the losses - huber on the photometric prefix,
-        pp_nerf_corres_loss on the tail, which needs the rendered depths of all passes - then the backward of every pass with
-        g_rgb zero on the tail and g_depth zero on the prefix.  The tail's fine samples come from its own coarse weights and
-        its own uniform grid (corres.fine_grid), as in a separate render call.  Also sets last_terms (photometric,
-        correspondence loss) and last_g_w2c [2,3,4] (the correspondence loss's direct pose gradient, overwritten next call)."""
-        Rp, R, M = image.shape[0], depth.shape[0], corres.pix_self.shape[0]
+        corres (CorresRows): the union pass - center / ray / depth hold R = Rp + 2M rows, image the Rp photometric rows, and the
+        last 2M rows are the matched pixels of one view pair [self M | other M], in the same launches as the photometric rows
+        (the reference renders them in two calls, renderer.py:420-423 and corres_loss.py:178-183).  Without it Rp = R.
+        One order for every step: the forward of every pass (coarse, then fine on depths drawn from the coarse weights), then
+        the losses - 2 * huber(delta = 0.5, mean) on the photometric prefix of every pass, pp_nerf_corres_loss on the tail,
+        which needs the rendered depths of all passes - then the backward of every pass with g_rgb zero on the tail and g_depth
+        zero on the prefix (_LossGrads).  Every loss lands in a ring slot (the returned 0-dim tensors are rewritten 256 calls
+        later: read them - .item() / copy - before that).  With corres also sets last_terms (photometric, correspondence
+        loss) and last_g_w2c [2,3,4] (the correspondence loss's direct pose gradient, overwritten next call)."""
+        R, Rp = depth.shape[0], image.shape[0]
+        M = 0 if corres is None else corres.pix_self.shape[0]
         if R != Rp + 2 * M:
             raise ValueError(f'SceneEngine: union pass of {R} rows, expected {Rp} photometric + 2 x {M} matched rows')
         if fine and (self.net_fine is None or depth_range is None):
             raise ValueError('SceneEngine: fine=True needs net_fine and depth_range')
-        dev = depth.device
-        f = dict(dtype=torch.float32, device=dev)
-        passes = [(self.states[0], depth) + self._fwd(self.states[0], center, ray, depth)]
+        passes = [(self.states[0], self.net.scene_pass(*depth.shape).forward(center, ray, depth), depth)]
         if fine:
-            opt = self.net.opt
-            S, Nf = depth.shape[1], opt.nerf.sample_intvs_fine
-            det = not opt.nerf.sample_stratified
+            depth_f = self._fine_depths(passes[0][1].w, depth, depth_range, fine_grid, Rp, corres)
+            passes.append((self.states[1], self.net_fine.scene_pass(*depth_f.shape).forward(center, ray, depth_f), depth_f))
+        image = image.contiguous()
+        grads, loss = [], None
+        for k, (st, p, dep) in enumerate(passes):
+            lg = self._loss_grads.get((k, R))
+            if lg is None:
+                if len(self._loss_grads) >= 8:
+                    self._loss_grads.clear()
+                lg = self._loss_grads[(k, R)] = _LossGrads(R, Rp, depth.device)
+            grads.append(lg.split(Rp, corres is not None))
+            l = lg.losses.next()
+            ops.nerf_huber_loss(p.rgb[:Rp], image, 0.5, 2.0 if corres is None else 2.0 * corres.photo_weight, l, lg.g_rgb[:Rp])
+            loss = l if loss is None else loss + l
+        if corres is not None:
+            if self._corres is None:
+                self._corres = _LossRing(depth.device), torch.zeros(2, 3, 4, dtype=torch.float32, device=depth.device)
+            loss_corr, g_w2c = self._corres[0].next(), self._corres[1]
+            ops.nerf_corres_loss(passes[0][1].d[Rp:], passes[1][1].d[Rp:] if fine else None, corres.pix_self, corres.pix_other,
+                                 corres.conf, corres.K_self, corres.K_other, corres.w2c_self, corres.w2c_other, corres.pixel_check,
+                                 corres.pixel_thresh, corres.depth_check, corres.depth_thresh, corres.weight, loss_corr,
+                                 grads[0][1][Rp:], grads[1][1][Rp:] if fine else None, g_w2c)
+            self.last_terms, self.last_g_w2c = dict(photometric=loss, corres=loss_corr), g_w2c
+            loss = loss + loss_corr
+        g_center = g_ray = None
+        for (st, p, dep), (g_rgb, g_depth) in zip(passes, grads):
+            gc, gr = p.backward(ray, dep, g_rgb, g_depth, st.grad)
+            st.has_grad = True
+            g_center, g_ray = (gc, gr) if g_center is None else (g_center + gc, g_ray + gr)
+        return loss, g_center, g_ray
+
+    def _fine_depths(self, w, depth, depth_range, fine_grid, Rp, corres):
+        """The fine pass's sorted [R, S + Nf] depths: the coarse depths merged with Nf inverse-transform samples of the coarse
+        weights w [R, S] on a uniform grid - replayed (`fine_grid` [Nf + 1]), the regular one when sample_stratified is off, else
+        a fresh host-side draw shared by the rays.  In the union pass the tail's samples come from its own grid
+        (corres.fine_grid), as in a separate render call: the grid is then per ray, [R, Nf + 1].  deterministic:
+        ops.nerf_sample_pdf on the same grid instead of sample_depth_from_pdf + cat + sort."""
+        opt, dev = self.net.opt, depth.device
+        S, Nf = depth.shape[1], opt.nerf.sample_intvs_fine
+        det = not opt.nerf.sample_stratified
+        grid = fine_grid
+        if corres is not None:
             grid = None
             if not det:
                 gp = fine_grid if fine_grid is not None else torch.rand(Nf + 1)
                 gc = corres.fine_grid if corres.fine_grid is not None else torch.rand(Nf + 1)
-                grid = torch.cat([gp.to(dev).expand(Rp, Nf + 1), gc.to(dev).expand(2 * M, Nf + 1)])
-            if self.deterministic:
-                depth_f = self._fine_depths_ordered(passes[0][3]['w'], depth, Nf, depth_range, det, grid)
-            else:
-                fine_t = sample_depth_from_pdf(passes[0][3]['w'][None], S, Nf, depth_range, det=det, grid=grid)
-                depth_f = torch.cat([depth, fine_t[0, :, :, 0]], dim=1).sort(dim=1).values.contiguous()
-            passes.append((self.states[1], depth_f) + self._fwd(self.states[1], center, ray, depth_f))
-        grads, loss_photo = [], None
-        for st, dep, ws, b in passes:
-            cb = getattr(ws, 'corres_bufs', None)
-            if cb is None or cb['Rp'] != Rp:          # g_rgb stays zero on the tail, g_depth on the prefix
-                cb = ws.corres_bufs = dict(Rp=Rp, g_rgb=torch.zeros(R, 3, **f), g_d=torch.zeros(R, **f))
-            l = self._photometric(b, b['rgb'][:Rp], image, cb['g_rgb'][:Rp], 2.0 * corres.photo_weight)
-            loss_photo = l if loss_photo is None else loss_photo + l
-            grads.append(cb)
-        if getattr(self, '_corres', None) is None:
-            self._corres = dict(loss=torch.zeros(256, **f), i=-1, g_w2c=torch.zeros(2, 3, 4, **f))
-        c = self._corres
-        c['i'] = (c['i'] + 1) % 256
-        loss_corr = c['loss'][c['i']]
-        fine_b = passes[1][3] if fine else None
-        ops.nerf_corres_loss(passes[0][3]['d'][Rp:], fine_b['d'][Rp:] if fine else None, corres.pix_self, corres.pix_other,
-                             corres.conf, corres.K_self, corres.K_other, corres.w2c_self, corres.w2c_other, corres.pixel_check,
-                             corres.pixel_thresh, corres.depth_check, corres.depth_thresh, corres.weight, loss_corr,
-                             grads[0]['g_d'][Rp:], grads[1]['g_d'][Rp:] if fine else None, c['g_w2c'])
-        g_center = g_ray = None
-        for (st, dep, ws, b), cb in zip(passes, grads):
-            gc, gr = self._bwd(st, ws, b, ray, dep, cb['g_rgb'], cb['g_d'])
-            g_center, g_ray = (gc, gr) if g_center is None else (g_center + gc, g_ray + gr)
-        self.last_terms = dict(photometric=loss_photo, corres=loss_corr)
-        self.last_g_w2c = c['g_w2c']
-        return loss_photo + loss_corr, g_center, g_ray
+                grid = torch.cat([gp.to(dev).expand(Rp, Nf + 1), gc.to(dev).expand(depth.shape[0] - Rp, Nf + 1)])
+        if not self.deterministic:
+            fine_t = sample_depth_from_pdf(w[None], S, Nf, depth_range, det=det, grid=grid)
+            return torch.cat([depth, fine_t[0, :, :, 0]], dim=1).sort(dim=1).values.contiguous()
+        if grid is None:
+            grid = torch.linspace(0, 1, Nf + 1, device=dev) if det else torch.rand(Nf + 1)
+        out = torch.empty(depth.shape[0], S + Nf, dtype=torch.float32, device=dev)
+        ops.nerf_sample_pdf(w, depth, grid.to(dev).float().contiguous(), Nf, depth_range, out)
+        return out
 
     def optimizer_step(self, grad_scale=1.0):
         """torch.optim.Adam semantics (lib/utils.py:294-299); also re-zeroes the gradient blocks for the next step.  Like

@@ -110,36 +110,29 @@ class DualBranchEngine:
         opt = sc.net.opt
         V, N, S = (e.V if n_views is None else n_views), pixels.shape[0], opt.nerf.sample_intvs
         center, ray, dir_cam = self.scene_rays(pixels, V)
-        if depth_rand is None:
-            depth = bg_nerf.sample_depth(opt, V, N, S, self.depth_range, mode='train', device=pixels.device)
-        else:
-            jit = depth_rand + torch.arange(S, device=pixels.device)[None, None, :, None].float()
-            depth = jit / S * (self.depth_range[1] - self.depth_range[0]) + self.depth_range[0]
-        if corres is None:
-            loss_bg, g_center, g_ray = sc.forward_backward(center.reshape(V * N, 3).contiguous(),
-                                                           ray.reshape(V * N, 3).contiguous(), depth.reshape(V * N, S).contiguous(),
-                                                           image.reshape(V * N, 3), fine=fine, depth_range=self.depth_range,
-                                                           fine_grid=fine_grid)
-        else:
+
+        def depths(rand, n_views, n_rays):                  # [n_views, n_rays, S, 1]: a fresh draw, or a replayed one
+            if rand is None:
+                return bg_nerf.sample_depth(opt, n_views, n_rays, S, self.depth_range, mode='train', device=pixels.device)
+            return bg_nerf.stratified_depths(opt, rand, self.depth_range)
+
+        center, ray, depth = center.reshape(V * N, 3), ray.reshape(V * N, 3), depths(depth_rand, V, N).reshape(V * N, S)
+        rows = None
+        if corres is not None:
             i, j = int(corres['i']), int(corres['j'])
             if not (0 <= i < V and 0 <= j < V and i != j):
                 raise ValueError(f'DualBranchEngine: correspondence pair ({i}, {j}) is not a pair of the {V} views in play')
             M = corres['pix_self'].shape[0]
             c_center, c_ray, c_dir = self.pair_rays(i, j, corres['pix_self'], corres['pix_other'])
-            if corres_rand is None:
-                c_depth = bg_nerf.sample_depth(opt, 2, M, S, self.depth_range, mode='train', device=pixels.device)
-            else:
-                jit = corres_rand + torch.arange(S, device=pixels.device)[None, None, :, None].float()
-                c_depth = jit / S * (self.depth_range[1] - self.depth_range[0]) + self.depth_range[0]
             K = self.intrinsics()
             rows = bg_nerf.CorresRows(corres['pix_self'], corres['pix_other'], corres['conf'], K[i], K[j], e.w2c[i], e.w2c[j],
                                       corres['weight'], opt=corres.get('opt', opt), fine_grid=corres_fine_grid,
                                       photo_weight=corres.get('photo_weight', 1.0))
-            loss_bg, g_center, g_ray = sc.forward_backward(
-                torch.cat([center.reshape(V * N, 3), c_center.reshape(2 * M, 3)]),
-                torch.cat([ray.reshape(V * N, 3), c_ray.reshape(2 * M, 3)]),
-                torch.cat([depth.reshape(V * N, S), c_depth.reshape(2 * M, S)]), image.reshape(V * N, 3), fine=fine,
-                depth_range=self.depth_range, fine_grid=fine_grid, corres=rows)
+            center, ray = torch.cat([center, c_center.reshape(2 * M, 3)]), torch.cat([ray, c_ray.reshape(2 * M, 3)])
+            depth = torch.cat([depth, depths(corres_rand, 2, M).reshape(2 * M, S)])
+        loss_bg, g_center, g_ray = sc.forward_backward(center.contiguous(), ray.contiguous(), depth.contiguous(),
+                                                       image.reshape(V * N, 3), fine=fine, depth_range=self.depth_range,
+                                                       fine_grid=fine_grid, corres=rows)
         # fold the ray gradients into d L_bg / d c2w and through the object engine's pose Jacobian
         g_ray_p, g_center_p = g_ray[:V * N].view(V, N, 3), g_center[:V * N].view(V, N, 3)
         if self.deterministic:                          # fixed summation order; views that are not in play receive zeros

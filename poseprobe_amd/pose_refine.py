@@ -38,14 +38,6 @@ def check_intrinsics(K):
     return Kh.contiguous()
 
 
-def depths_from_rand(opt, rand, depth_range):
-    """Stratified depths from uniform draws rand [..., S] in the op order of bg_nerf.sample_depth / SceneRenderer.render."""
-    S = rand.shape[-1]
-    jitter = rand + torch.arange(S, device=rand.device).float()
-    depth = jitter / S * (depth_range[1] - depth_range[0]) + depth_range[0]
-    return {'metric': depth, 'inverse': 1 / (depth + 1e-8)}[opt.nerf.depth.param]
-
-
 class PoseRefiner:
     def __init__(self, net, opt, H, W, K, depth_range, rand_rays=None, lr=5e-4, betas=(0.9, 0.999), eps=1e-8):
         """net: the coarse bg_nerf.NeRF (frozen here); K [3,3] upper-triangular with K[2,2] = 1, checked once (ValueError);
@@ -71,19 +63,16 @@ class PoseRefiner:
 
     def _buffers(self):
         if self._b is None:
-            dev, N, S = self.net.flat.device, self.N, self.S
+            dev, N = self.net.flat.device, self.N
             f = dict(dtype=torch.float32, device=dev)
             r3 = lambda: torch.empty(N, 3, **f)
             self._b = dict(
-                ws=self.net._workspace(N, S), K=self.K_host.to(dev), base=torch.empty(1, 3, 4, **f), se3=torch.zeros(1, 6, **f),
+                K=self.K_host.to(dev), base=torch.empty(1, 3, 4, **f), se3=torch.zeros(1, 6, **f),
                 m=torch.zeros(6, **f), v=torch.zeros(6, **f), se3_grad=torch.zeros(1, 6, **f),
                 mask=torch.ones(1, dtype=torch.int32, device=dev), w2c=torch.empty(1, 3, 4, **f), c2w=torch.empty(1, 3, 4, **f),
                 jac=torch.empty(1, 12, 6, **f), seg_end=torch.tensor([6], dtype=torch.int32, device=dev),
-                seg_lr=torch.tensor([self.lr], **f), center=r3(), ray=r3(), dir_cam=r3(), target=r3(), rgb=r3(), g_rgb=r3(),
-                g_ray_c=r3(), g_center=r3(), g_ray=r3(), g_ray_sum=r3(), rgb_s=torch.empty(N * S, 3, **f), dens=torch.empty(N * S, **f),
-                g_rgb_s=torch.empty(N * S, 3, **f), g_dens=torch.empty(N * S, **f), d=torch.empty(N, **f), op=torch.empty(N, **f),
-                w=torch.empty(N, S, **f), cum=torch.empty(N, **f), rv=torch.empty(N, **f), dv=torch.empty(N, **f),
-                zero_r=torch.zeros(N, **f), g_c2w=torch.empty(1, 3, 4, **f))
+                seg_lr=torch.tensor([self.lr], **f), center=r3(), ray=r3(), dir_cam=r3(), target=r3(), g_rgb=r3(),
+                g_c2w=torch.empty(1, 3, 4, **f))
         return self._b
 
     def _check(self, base_w2c, image, iters, replay):
@@ -104,11 +93,11 @@ class PoseRefiner:
             if int(idx.min()) < 0 or int(idx.max()) >= self.H * self.W:
                 raise ValueError(f'replay: ray_idx outside [0, {self.H * self.W})')
 
-    def _backward(self, b, depth):
-        """Compositing and network backward w.r.t. the rays (tools/time_pose_refine.py swaps the full backward in here)."""
-        net, N, S = self.net, self.N, self.S
-        ops.nerf_bwd_input(net.flat, b['ray'], depth, b['ws'].count, N, S, b['ws'].acts, b['rgb_s'], b['g_rgb_s'], b['g_dens'],
-                           b['ws'].scratch, b['g_center'], b['g_ray'], net.ctx)
+    def _backward(self, p, b, depth):
+        """Compositing and network backward of the pass p w.r.t. the rays -> g_center, g_ray (tools/time_pose_refine.py swaps the
+        full backward in here).  The loss gradient is all of the refiner's own g_rgb and no depth gradient: the pass may be the
+        one a SceneEngine on the same network and shape uses, and nothing that user wrote is read."""
+        return p.backward_input(b['ray'], depth, b['g_rgb'])
 
     @torch.no_grad()
     def refine(self, base_w2c, image, iters=500, generator=None, replay=None):
@@ -124,7 +113,7 @@ class PoseRefiner:
         net, opt, N, S, H, W = self.net, self.opt, self.N, self.S, self.H, self.W
         b = self._buffers()
         dev = net.flat.device
-        ws = b['ws']
+        p = net.scene_pass(N, S)
         image = image.detach().to(dev).float().contiguous()
         b['base'][0].copy_(base_w2c.detach().to(dev).float())
         for k in ('se3', 'm', 'v', 'se3_grad'):
@@ -134,28 +123,21 @@ class PoseRefiner:
             rand_all = replay['depth_rand'].to(dev).float()
         losses = torch.zeros(iters, dtype=torch.float32, device=dev)
         first = torch.zeros(6, dtype=torch.float32, device=dev)
-        white = bool(opt.nerf.setbg_opaque or opt.mask_img)
         se3_flat, grad_flat = b['se3'].view(-1), b['se3_grad'].view(-1)
         for it in range(iters):
             ops.pose_fwd(b['se3'], b['base'], b['mask'], b['w2c'], b['c2w'], b['jac'])
             if replay is not None:
                 ray_idx = idx_all[it]
-                depth = depths_from_rand(opt, rand_all[it], self.depth_range).contiguous()
+                depth = bg_nerf.stratified_depths(opt, rand_all[it], self.depth_range).contiguous()
             else:
                 ray_idx = torch.randperm(H * W, device=dev, generator=generator)[:N].to(torch.int32)
                 depth = bg_nerf.sample_depth(opt, 1, N, S, self.depth_range, mode='train', device=dev,
                                              generator=generator).view(N, S)
             ops.nerf_rays_select(b['c2w'][0], b['K'], ray_idx, H, W, image, b['center'], b['ray'], b['dir_cam'], b['target'])
-            ops.nerf_fwd(net.flat, b['center'], b['ray'], depth, net.band_weights(), ws.count, N, S, ws.acts, b['rgb_s'], b['dens'],
-                         net.ctx)
-            ops.nerf_composite_fwd(b['rgb_s'], b['dens'], depth, b['ray'], N, S, white, b['rgb'], b['d'], b['op'], b['w'], b['cum'],
-                                   b['rv'], b['dv'])
-            ops.nerf_mse_loss(b['rgb'], b['target'], 1.0, losses[it:it + 1], b['g_rgb'])
-            ops.nerf_composite_bwd(b['rgb_s'], b['dens'], depth, b['ray'], b['w'], N, S, white, b['g_rgb'], b['zero_r'], b['zero_r'],
-                                   None, b['g_rgb_s'], b['g_dens'], b['g_ray_c'])
-            self._backward(b, depth)
-            torch.add(b['g_ray'], b['g_ray_c'], out=b['g_ray_sum'])
-            ops.nerf_c2w_fold(b['g_ray_sum'][None], b['g_center'][None], b['dir_cam'][None], b['g_c2w'])
+            p.forward(b['center'], b['ray'], depth)
+            ops.nerf_mse_loss(p.rgb, b['target'], 1.0, losses[it:it + 1], b['g_rgb'])
+            g_center, g_ray = self._backward(p, b, depth)
+            ops.nerf_c2w_fold(g_ray[None], g_center[None], b['dir_cam'][None], b['g_c2w'])
             ops.pose_bwd(b['jac'], b['g_c2w'], b['se3_grad'])
             if it == 0:
                 first.copy_(grad_flat)

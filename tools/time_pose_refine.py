@@ -26,19 +26,17 @@ import torch
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
 sys.path.insert(0, ROOT)
-from poseprobe_amd import bg_nerf, camera, evaluation, ops, pose_refine      # noqa: E402
+from poseprobe_amd import bg_nerf, camera, evaluation, pose_refine           # noqa: E402
 from poseprobe_amd import synthetic as syn                                    # noqa: E402
 
 
 class FullBackwardRefiner(pose_refine.PoseRefiner):
     """Variant (b): the loop of PoseRefiner with the full backward, its parameter gradients thrown away."""
 
-    def _backward(self, b, depth):
-        net = self.net
+    def _backward(self, p, b, depth):
         if getattr(self, '_discard', None) is None:
-            self._discard = torch.zeros_like(net.flat)
-        ops.nerf_bwd(net.flat, b['ray'], depth, b['ws'].count, self.N, self.S, b['ws'].acts, b['rgb_s'], b['g_rgb_s'], b['g_dens'],
-                     b['ws'].scratch, self._discard, b['g_center'], b['g_ray'], net.ctx)
+            self._discard = torch.zeros_like(self.net.flat)
+        return p.backward(b['ray'], depth, b['g_rgb'], None, self._discard)
 
 
 def timed(fn, runs):
