@@ -326,6 +326,9 @@ extern "C" int pp_feat_generic_bwd_k0(const pp_scene* sc, const float* pts, cons
                                       const float* k0_raw_grad, float* k0_grad_cl, void* stream) {
   PP_REQUIRE(sc && pts && count && feat_grad && k0_grad_cl, "null pointer");
   PP_REQUIRE(capacity > 0 && sc->k0_dim <= 16, "capacity<=0 or k0_dim>16");
+  // as the forward (its optional normal columns carry no k0 gradient): the k0 columns read below must lie inside a row
+  int width = sc->k0_dim - k0_skip + 3 + 6 * sc->pos_pe + 3 + 6 * sc->view_pe;
+  PP_REQUIRE(ld % 32 == 0 && width <= ld && k0_skip >= 0 && k0_skip <= sc->k0_dim, "feature width does not fit ld (multiple of 32)");
   hipLaunchKernelGGL(k_feat_generic_bwd_k0, dim3(pp_div_up(capacity * 16, 256)), dim3(256), 0, pp_stream(stream),
                      pp_scene_dev(sc), pts, sel, k0_skip, ld, count, capacity, feat_grad, k0_raw_grad, k0_grad_cl);
   PP_CHECK_LAUNCH();

@@ -88,7 +88,7 @@ class _DVGORender(torch.autograd.Function):
         ops.feat_generic_fwd(sc, channels_last_view(k0), pts, st['viewdirs'], ray_id, None, None, sel, skip, ld, count, cap,
                              feat, k0_raw)
         params = torch.cat([p.detach().reshape(-1) for p in st['packed'](mlp)])
-        acts = torch.empty(n_gemm, cap, 128, **f)
+        acts = torch.empty(ops.mlp_workspace(ld, n_gemm, cap)[0], **f)
         rgb = torch.empty(cap, 3, **f)
         ops.mlp_fwd(params, feat, ld, n_gemm, count, cap, k0_raw, model.k0_dim, acts, rgb)
         rgb_eff = torch.where(sel.bool()[:, None], rgb, torch.full_like(rgb, 0.5))   # rgb_logit stays 0 where unmasked
@@ -121,7 +121,7 @@ class _DVGORender(torch.autograd.Function):
         g_alpha = g_alpha + g_alpha_up
         g_rgb = (g_rgb + g_rgb_up) * sel.bool()[:, None]
         n_gemm = model.rgbnet_kwargs['rgbnet_depth'] - 1
-        scratch = torch.empty(3 * cap * 128 + 16384, **f)
+        scratch = torch.empty(ops.mlp_workspace(ld, n_gemm, cap)[1], **f)
         pgrad = torch.zeros_like(params)
         g_feat = torch.empty(cap, ld, **f)
         g_k0raw = None if k0_raw is None else torch.zeros(cap, model.k0_dim, **f)

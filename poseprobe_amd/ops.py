@@ -532,6 +532,13 @@ def feat_generic_bwd_k0(sc, pts, sel, k0_skip, ld, count, capacity, feat_grad, k
               capacity, _f(feat_grad), _f(k0_raw_grad), _f(k0_grad_cl), _stream())
 
 
+def mlp_workspace(in_ld, n_gemm, capacity):
+    """-> (acts, scratch) in floats for mlp_fwd / mlp_bwd of this shape, from the library's workspace query."""
+    a, s = ctypes.c_int64(), ctypes.c_int64()
+    _lib.call('pp_mlp_workspace', int(in_ld), int(n_gemm), int(capacity), ctypes.byref(a), ctypes.byref(s))
+    return a.value, s.value
+
+
 def mlp_fwd(params, feat, in_ld, n_gemm, count, capacity, logit_add, logit_add_ld, acts, out, ctx=None):
     _lib.call('pp_mlp_fwd', _f(params), _f(feat), int(in_ld), int(n_gemm), _i(count), capacity, _f(logit_add),
               int(logit_add_ld), _f(acts), _f(out), _h(ctx), _stream())

@@ -168,23 +168,44 @@ def test_surface_point_queries_match_reference():
     assert torch.isfinite(ro_g.grad).all() and float(ro_g.grad.abs().sum()) > 0
 
 
-def test_directvoxgo_twin_matches_reference():
-    """DirectVoxGO.forward (lib/dvgo_ori.py:289-379) + gradients of density / k0 / rgbnet vs the reference's golden."""
+# fixtures of oracle/make_golden.py::DVGO_CONFIGS: name -> (rgbnet_dim, rgbnet_direct, rgbnet_depth).  dvgo_nodirect: layer-by-layer
+# MLP (ld 96) with the diffuse logits; dvgo_fused_*: widths 64 / 61 round to ld 64 with three hidden layers, which takes the
+# layer-fused kernels (with the diffuse logits for _nodirect); dvgo_deep: five hidden layers.
+DVGO_FIXTURES = {'dvgo_g16': (12, True, 3), 'dvgo_nodirect': (12, False, 3), 'dvgo_fused_direct': (4, True, 4),
+                 'dvgo_fused_nodirect': (4, False, 4), 'dvgo_deep': (16, True, 6)}
+
+
+def dvgo_twin(name):
+    """The twin loaded with a fixture's state -> (fixture, model on the GPU, its Linear layers in order)."""
     from poseprobe_amd import synthetic as syn
     from poseprobe_amd.dvgo_ori import DirectVoxGO
-    d = load('dvgo_g16.npz')
+    dim, direct, depth = DVGO_FIXTURES[name]
+    d = load(name + '.npz')
     G = int(d['G'])
-    m = DirectVoxGO(syn.XYZ_MIN, syn.XYZ_MAX, num_voxels=G ** 3, num_voxels_base=G ** 3, alpha_init=1e-2, rgbnet_dim=12,
-                    rgbnet_direct=True, rgbnet_depth=3, rgbnet_width=128, posbase_pe=5, viewbase_pe=4,
+    m = DirectVoxGO(syn.XYZ_MIN, syn.XYZ_MAX, num_voxels=G ** 3, num_voxels_base=G ** 3, alpha_init=1e-2, rgbnet_dim=dim,
+                    rgbnet_direct=direct, rgbnet_depth=depth, rgbnet_width=128, posbase_pe=5, viewbase_pe=4,
                     fast_color_thres=1e-4)
     sd = m.state_dict()
-    assert {'xyz_min', 'xyz_max', 'density', 'k0', 'posfreq', 'viewfreq', 'rgbnet.0.weight', 'rgbnet.0.bias',
-            'rgbnet.2.0.weight', 'rgbnet.2.0.bias', 'rgbnet.3.weight', 'rgbnet.3.bias'} == set(sd.keys())
+    keys = ['rgbnet.0'] + [f'rgbnet.{i}.0' for i in range(2, depth)] + [f'rgbnet.{depth}']
+    assert ({'xyz_min', 'xyz_max', 'density', 'k0', 'posfreq', 'viewfreq'} | {k + s for k in keys for s in ('.weight', '.bias')}
+            == set(sd.keys()))
     sd['density'], sd['k0'] = torch.tensor(d['density']), torch.tensor(d['k0'])
-    for li, key in enumerate(['rgbnet.0', 'rgbnet.2.0', 'rgbnet.3']):
+    for li, key in enumerate(keys):
         sd[key + '.weight'], sd[key + '.bias'] = torch.tensor(d[f'rgbnet.{li}.weight']), torch.tensor(d[f'rgbnet.{li}.bias'])
     m.load_state_dict(sd)
     m = m.cuda()
+    lins = [l for l in m.rgbnet.modules() if isinstance(l, torch.nn.Linear)]
+    assert len(lins) == depth and [k + '.weight' for k in keys] == [n for n, _ in m.named_parameters() if n.endswith('.weight')]
+    return d, m, lins
+
+
+@pytest.mark.parametrize('fixture', list(DVGO_FIXTURES))
+def test_directvoxgo_twin_matches_reference(fixture):
+    """DirectVoxGO.forward (lib/dvgo_ori.py:289-379) + gradients of density / k0 / rgbnet vs the reference's golden."""
+    d, m, lins = dvgo_twin(fixture)
+    if fixture == 'dvgo_g16':
+        assert {'xyz_min', 'xyz_max', 'density', 'k0', 'posfreq', 'viewfreq', 'rgbnet.0.weight', 'rgbnet.0.bias',
+                'rgbnet.2.0.weight', 'rgbnet.2.0.bias', 'rgbnet.3.weight', 'rgbnet.3.bias'} == set(m.state_dict().keys())
     ro, rd, vd = (torch.tensor(d[k]).cuda() for k in ('rays_o', 'rays_d', 'viewdirs'))
     out = m(ro, rd, vd, global_step=5, near=0.24, far=4.8, bg=1, stepsize=0.5, inverse_y=True, flip_x=False, flip_y=False,
             jitter=torch.tensor(d['jitter']))
@@ -201,7 +222,7 @@ def test_directvoxgo_twin_matches_reference():
     tol = dict(rtol=1e-3, scaled=2e-5)
     assert_close(c(m.density.grad), d['grad_density'], atol=1e-9, name='g.density', **tol)
     assert_close(c(m.k0.grad), d['grad_k0'], atol=1e-9, name='g.k0', **tol)
-    for li, lin in enumerate([m.rgbnet[0], m.rgbnet[2][0], m.rgbnet[3]]):
+    for li, lin in enumerate(lins):
         assert_close(c(lin.weight.grad), d[f'grad.rgbnet.{li}.weight'], atol=1e-9, name=f'g.rgbnet{li}.W', **tol)
         assert_close(c(lin.bias.grad), d[f'grad.rgbnet.{li}.bias'], atol=1e-9, name=f'g.rgbnet{li}.b', **tol)
 
@@ -260,21 +281,11 @@ def test_reference_style_training_loop_with_hip_adam(tmp_path):
         assert torch.equal(a.cpu(), b.cpu()), k
 
 
-def test_directvoxgo_twin_backward_is_complete():
+@pytest.mark.parametrize('fixture', list(DVGO_FIXTURES))
+def test_directvoxgo_twin_backward_is_complete(fixture):
     """Random linear functional over the twin's differentiable outputs (pixels, alphainv_cum, weights, raw_alpha, depth):
     value and the gradients of density, k0 and rgbnet against the reference."""
-    from poseprobe_amd import synthetic as syn
-    from poseprobe_amd.dvgo_ori import DirectVoxGO
-    d = load('dvgo_g16.npz')
-    G = int(d['G'])
-    m = DirectVoxGO(syn.XYZ_MIN, syn.XYZ_MAX, num_voxels=G ** 3, num_voxels_base=G ** 3, alpha_init=1e-2, rgbnet_dim=12,
-                    rgbnet_direct=True, rgbnet_depth=3, rgbnet_width=128, posbase_pe=5, viewbase_pe=4, fast_color_thres=1e-4)
-    sd = m.state_dict()
-    sd['density'], sd['k0'] = torch.tensor(d['density']), torch.tensor(d['k0'])
-    for li, key in enumerate(['rgbnet.0', 'rgbnet.2.0', 'rgbnet.3']):
-        sd[key + '.weight'], sd[key + '.bias'] = torch.tensor(d[f'rgbnet.{li}.weight']), torch.tensor(d[f'rgbnet.{li}.bias'])
-    m.load_state_dict(sd)
-    m = m.cuda()
+    d, m, lins = dvgo_twin(fixture)
     ro, rd, vd = (torch.tensor(d[k]).cuda() for k in ('rays_o', 'rays_d', 'viewdirs'))
     out = m(ro, rd, vd, global_step=5, near=0.24, far=4.8, bg=1, stepsize=0.5, inverse_y=True, flip_x=False, flip_y=False,
             jitter=torch.tensor(d['jitter']))
@@ -287,7 +298,7 @@ def test_directvoxgo_twin_backward_is_complete():
     tol = dict(rtol=2e-3, atol=1e-6, scaled=1e-3)
     assert_close(c(m.density.grad), d['lf_g_density'], name='g.density', **tol)
     assert_close(c(m.k0.grad), d['lf_g_k0'], name='g.k0', **tol)
-    for li, lin in enumerate([m.rgbnet[0], m.rgbnet[2][0], m.rgbnet[3]]):
+    for li, lin in enumerate(lins):
         assert_close(c(lin.weight.grad), d[f'lf_g.rgbnet.{li}.weight'], name=f'g.rgbnet{li}.W', **tol)
         assert_close(c(lin.bias.grad), d[f'lf_g.rgbnet.{li}.bias'], name=f'g.rgbnet{li}.b', **tol)
 
