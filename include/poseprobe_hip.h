@@ -228,9 +228,9 @@ int pp_color_feat_bwd(const pp_scene* sc, const float* k0_cl, const float* pts, 
  * coexist in one process and on concurrent threads (a context itself must not be modified while a call uses it).
  * Names (meaning and ranges: csrc/pp_common.h, csrc/pp_error.hip):
  *   arithmetic   mlp_split (bit mask: object-branch MLP kernels as 3 fp16 products per fp32 product; 0 = fp32 MFMA instructions),
- *                nerf_split (scene branch likewise), mlp_fused, nerf_chain
- *   scheduling   mlp_wgs, grid_chunks, nerf_chain_head, mlp_pack (see pp_mlp_pack),
- *                warp_lean (see pp_warp_lean_begin)
+ *                nerf_split (scene branch likewise), mlp_fused,
+ *                nerf_chain (scene branch: 3 = the fused forward and backward chains, 0 = one GEMM per layer; nothing in between)
+ *   scheduling   mlp_wgs, grid_chunks, mlp_pack (see pp_mlp_pack), warp_lean (see pp_warp_lean_begin)
  * pp_nerf_fwd and pp_nerf_bwd of one pass (and the two stages of a two-stage backward) must see the same option values.
  * Unknown names / out-of-range values are refused; pp_context_get_option(NULL, ...) reads the defaults. */
 int pp_context_create(void** ctx);
@@ -607,7 +607,7 @@ int pp_nerf_bwd(const float* params, const float* ray, const float* depth, const
                 const float* g_rgb_samples, const float* g_density_samples, float* scratch, float* params_grad,
                 float* g_center, float* g_ray, void* ctx, void* stream);
 /* Backward of pp_nerf_fwd with respect to the rays only (frozen parameters: test-time pose refinement): the launches of
- * pp_nerf_bwd without its nine weight-gradient products, in both routes of option nerf_chain and both arithmetics.  g_center and
+ * pp_nerf_bwd without its nine weight-gradient products, on the fused route and on the layer-by-layer route of either arithmetic.  g_center and
  * g_ray are bit-identical to pp_nerf_bwd's on the same inputs; no parameter gradient exists (the two thin heads' sums, whose
  * kernels also record operand maxima the later kernels read, are added into a part of `scratch` that nothing reads before
  * the data-gradient kernels of either route overwrite it).  Same workspaces as pp_nerf_bwd (pp_nerf_workspace is unchanged).  A workspace attached with
@@ -620,8 +620,8 @@ int pp_nerf_bwd_input(const float* params, const float* ray, const float* depth,
  * pp_nerf_fwd's on the same inputs and context (same operand scales, same accumulation, same summation order).  No layer
  * output and no ReLU mask is written to memory: work = 224 floats per sample (encoded points 64, view encoding 32, the colour
  * head's hidden layer 128) + the operand-maximum slots and the packed weight stream (573 504 floats, independent of the sample
- * count), against pp_nerf_workspace's 2337 floats + 256 mask bytes per sample.  Only the default route has this form: a context
- * with nerf_split != 1, the forward bit of nerf_chain clear or nerf_chain_head != 1 is refused with PP_ERR_INVALID_ARG (use
+ * count), against pp_nerf_workspace's 2337 floats + 256 mask bytes per sample.  Only the fused route (the default) has this form: a context
+ * with nerf_split != 1 or nerf_chain != 3 is refused with PP_ERR_INVALID_ARG (use
  * pp_nerf_fwd there).  pp_nerf_bwd cannot follow this call. */
 int pp_nerf_infer_workspace(int64_t n_samples, int64_t n_rays, int64_t* work_floats);
 int pp_nerf_infer(const float* params, const float* center, const float* ray, const float* depth, const float* bands,

@@ -92,8 +92,7 @@ def header_abi_version(path=HEADER):
 # (include/poseprobe_hip.h).  The Python host keeps ONE default context per process for callers that do not bring their own;
 # PP_<NAME>=<int> in the host's environment seeds it once.  set_option / get_option below act on that host-side default
 # context (A/B scripts, tests); engines built with `options=...` own a private context and are unaffected by it.
-OPTION_NAMES = ('mlp_fused', 'grid_chunks', 'nerf_split', 'mlp_split', 'mlp_wgs', 'nerf_chain', 'nerf_chain_head',
-                'mlp_pack', 'warp_lean')
+OPTION_NAMES = ('mlp_fused', 'grid_chunks', 'nerf_split', 'mlp_split', 'mlp_wgs', 'nerf_chain', 'mlp_pack', 'warp_lean')
 
 
 class Context:

@@ -420,11 +420,11 @@ class NeRF(torch.nn.Module):
         return ws
 
     def infer_route(self):
-        """True when this network's context selects the route pp_nerf_infer has (nerf_split = 1, the forward bit of nerf_chain,
-        nerf_chain_head = 1: the defaults); otherwise forward-only passes go through pp_nerf_fwd and the shared block."""
+        """True when this network's context selects the route pp_nerf_infer has (the fused one: nerf_split = 1, nerf_chain = 3,
+        the defaults); otherwise forward-only passes go through pp_nerf_fwd and the shared block."""
         from . import _lib
         c = self.ctx if self.ctx is not None else _lib.default_context()
-        return c.get('nerf_split') == 1 and (c.get('nerf_chain') & 1) == 1 and c.get('nerf_chain_head') == 1
+        return c.get('nerf_split') == 1 and c.get('nerf_chain') == 3
 
     @property
     def white_bg(self):

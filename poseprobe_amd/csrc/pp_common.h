@@ -22,9 +22,9 @@ enum PPOption {
   PP_OPT_NERF_SPLIT,           // scene branch: every matrix product as three fp16 products (1) or on the fp32 instructions (0)
   PP_OPT_MLP_SPLIT,            // bit mask: layer-fused object-branch MLP kernels with three fp16 products per fp32 product (pp_mlp_split.hip); 1 warp fwd, 2 warp bwd, 4 rgb fwd, 8 rgb bwd, 16 weight-gradient chains
   PP_OPT_MLP_WGS,              // work-groups of the persistent object-branch MLP kernels (0 = one per CU); fewer leave CUs to a concurrent HBM-bound kernel
-  PP_OPT_NERF_CHAIN,           // scene branch: bit 1 = the eight feature layers + density head of the forward pass as one kernel with the tile resident in LDS
-                               // (pp_nerf_trunk.h), 3 = the data-gradient chain of the backward pass too (0 = one GEMM per layer)
-  PP_OPT_NERF_CHAIN_HEAD,      // scene branch: 1 = the colour head's hidden layer as a ninth stage of the fused forward chain
+  PP_OPT_NERF_CHAIN,           // scene branch: 3 = the fused route: the eight feature layers, the density head and the colour head's hidden layer of the forward pass as one
+                               // kernel with the tile resident in LDS (pp_nerf_trunk.h), the data-gradient chain of the backward pass as one more; 0 = one GEMM per layer
+                               // (the tests' reference).  1 and 2, a retired hybrid of the two, are refused
   PP_OPT_MLP_PACK,             // 1: the split-precision object-branch MLP kernels read a weight pack recorded in the context by pp_mlp_pack
                                // for the params pointer they are given, 0: they always derive it in their prologues
   PP_OPT_WARP_LEAN,            // 1: pp_warp_lean_begin records a lean scope (the warp net's kernels then leave out what the weight-gradient

@@ -20,7 +20,7 @@ struct PPOptionDef { const char* name; int dflt, lo, hi; };
 static const PPOptionDef g_opt_def[PP_OPT_COUNT] = {
     {"mlp_fused", 1, 0, 1},          {"grid_chunks", 0, 0, 4096},  {"nerf_split", 1, 0, 1},
     {"mlp_split", 31, 0, 31},        {"mlp_wgs", 0, 0, 4096},      {"nerf_chain", 3, 0, 3},
-    {"nerf_chain_head", 1, 0, 1},    {"mlp_pack", 1, 0, 1},        {"warp_lean", 1, 0, 1},
+    {"mlp_pack", 1, 0, 1},           {"warp_lean", 1, 0, 1},
 };
 // compiled-in defaults: constants, never written after static initialisation
 static const struct PPDefaults {
@@ -73,6 +73,11 @@ extern "C" int pp_context_set_option(void* ctx, const char* name, int32_t value)
   if (i < 0) { pp_set_error("pp_context_set_option: unknown option '%s'", name ? name : "(null)"); return PP_ERR_INVALID_ARG; }
   if (value < g_opt_def[i].lo || value > g_opt_def[i].hi) {
     pp_set_error("pp_context_set_option: %s = %d outside [%d, %d]", name, value, g_opt_def[i].lo, g_opt_def[i].hi);
+    return PP_ERR_INVALID_ARG;
+  }
+  if (i == PP_OPT_NERF_CHAIN && value != 0 && value != 3) {
+    pp_set_error("pp_context_set_option: nerf_chain = %d selected a hybrid of the fused and the layer-by-layer route, which is retired: "
+                 "3 (fused) or 0 (layer by layer)", value);
     return PP_ERR_INVALID_ARG;
   }
   static_cast<PPContext*>(ctx)->opt[i] = value;

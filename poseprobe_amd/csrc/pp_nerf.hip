@@ -85,7 +85,7 @@ static int64_t nerf_acts_floats(int64_t M) {
 }
 static const int64_t NERF_PART_FLOATS = 512 * 392;       // NERF_PART_WGS x NERF_PART_LD: partial rows of the thin heads' backward kernels
 
-// scratch of the backward pass; M = samples, R = rays.  Both routes (NerfRoute::chain_bwd) use d7, dH, dEnc0 .. dView, part, DY and
+// scratch of the backward pass; M = samples, R = rays.  Both routes (NerfRoute::chain) use d7, dH, dEnc0 .. dView, part, DY and
 // of the transposed weights WT[0], WT[4] (encoding gradients) and R0T (view gradient); both fill all of WT.  The rest of WT and the
 // three image groups as such feed the layer-by-layer data-gradient GEMMs only: the fused chain reads its weights through
 // k_pack_trunk's stream, which starts at r0t_img and runs over the three groups (TR_STEPS x TR_WSTEP bytes, less than their sum).
@@ -697,32 +697,28 @@ static const int NERF_BM = 128;
 static constexpr int NERF_GEMM_WGS = 256;   // persistent work-groups per column block of the NT GEMMs (measured 256 = 512 > 384 > 128)
 static constexpr int NERF_TN_WGS = 128;     // row splits of a weight-gradient block: 128 x 4 blocks = 2 work-groups per CU, one round
 // The scene-branch options (pp_context_set_option; defaults = the measured best on MI355X) of one call, resolved once by pp_nerf_fwd /
-// pp_nerf_bwd from the context they are handed.  The fused chains work on the operand maxima that only the split-precision path
-// records, so chain_fwd, chain_bwd and head are false without `split`, whatever their options say.
+// pp_nerf_bwd from the context they are handed.  Three routes: the fused one (the default) and one layer-by-layer route per
+// arithmetic.  The fused chains work on the operand maxima that only the split-precision path records, so `chain` is false
+// without `split`, whatever its option says.
 struct NerfRoute {
   // nerf_split: every matrix product (forward, data and weight gradients) as three fp16 products with fp32 accumulation
   // (pp_gemm_split.h: error against fp64 equal to the fp32 matrix instructions', a third of their matrix-pipe time); the 256-wide
   // layers on pp_gemm_planes.h (weights pre-split into LDS images once per pass, 128 x 256 tile on eight wavefronts).  false puts
   // all of them on the fp32 matrix instructions (A/B runs, bisecting)
   bool split;
-  // nerf_chain bit 1: forward pass with the eight feature layers and the density head as ONE kernel that keeps a 128-sample tile
-  // in LDS across the layers (pp_nerf_trunk.h); false = one GEMM per layer
-  bool chain_fwd;
-  // nerf_chain = 3: the data-gradient chain of the backward pass likewise; the ReLU masks then travel in the fused kernels' own
-  // layout, so both passes of a step must see the same value
-  bool chain_bwd;
-  // nerf_chain_head: the colour head's 288 -> 128 layer rides as a ninth stage of the fused forward chain
-  bool head;
-  explicit NerfRoute(const int* o)
-      : split(o[PP_OPT_NERF_SPLIT] == 1), chain_fwd(split && (o[PP_OPT_NERF_CHAIN] & 1)), chain_bwd(split && o[PP_OPT_NERF_CHAIN] == 3),
-        head(chain_fwd && o[PP_OPT_NERF_CHAIN_HEAD] == 1) {}
+  // nerf_chain = 3: the forward pass runs the eight feature layers, the density head and the colour head's 288 -> 128 layer (the
+  // ninth stage) as ONE kernel that keeps a 64-sample tile in LDS across the layers (pp_nerf_trunk.h), the backward pass its
+  // data-gradient chain likewise; the ReLU masks travel in the fused kernels' own layout, so both passes of a step must see the
+  // same value.  false (nerf_chain = 0) = one GEMM per layer in both passes
+  bool chain;
+  explicit NerfRoute(const int* o) : split(o[PP_OPT_NERF_SPLIT] == 1), chain(split && o[PP_OPT_NERF_CHAIN] == 3) {}
 };
 
 // a fused chain (pp_nerf_trunk.h): 64-row tiles on four wavefronts, two work-groups per CU
-template <bool BWD, bool MROW, bool KEEP = true>
+template <bool BWD, bool KEEP = true>
 static void launch_trunk(const TrunkArgs& T, const int32_t* count, int M, hipStream_t st) {
   const int tiles = pp_div_up(M, 64), cus = pp_num_cus();
-  hipLaunchKernelGGL((k_nerf_trunk<BWD, MROW, KEEP>), dim3(tiles < 2 * cus ? tiles : 2 * cus), dim3(256), 0, st, T, count, M);
+  hipLaunchKernelGGL((k_nerf_trunk<BWD, KEEP>), dim3(tiles < 2 * cus ? tiles : 2 * cus), dim3(256), 0, st, T, count, M);
 }
 
 template <int EPI>
@@ -783,6 +779,49 @@ static void nerf_gemm_tn(hipStream_t st, bool split, const float* Y, int ldy, in
     hipLaunchKernelGGL((k_gemm_tn<1, 64>), g, b, 0, st, Y, ldy, X, ldx, Kx, Wbar, ldx, bbar, count, 1, rows);
 }
 
+// What a split-precision forward pass needs before its first matrix product: the operand maxima of the nine weight matrices and
+// the bound of the encoded points in the slots `mx`, then the weights in the form its route reads - the fused chain's stream of
+// nine stages at `wstream`, or (wstream == nullptr) the eight feature layers' plane images at wimg[0 .. 7].
+static void nerf_fwd_prepare(hipStream_t st, const float* params, const NerfLayout& L, const float* center, const float* ray,
+                             const float* depth, int n_rays, int n_samples, float* mx, unsigned char* wstream, _Float16* const* wimg) {
+  hipMemsetAsync(mx, 0, MX_SLOTS * sizeof(float), st);
+  NerfWmaxJobs J;
+  for (int l = 0; l < 7; ++l) { J.src[l] = params + L.w[l]; J.n[l] = 256 * NERF_IN_LD[l]; }
+  J.src[7] = params + L.wd; J.n[7] = 257 * 256;
+  J.src[8] = params + L.r0; J.n[8] = 128 * 288;
+  hipLaunchKernelGGL(k_nerf_wmax, dim3(16, 9), dim3(256), 0, st, J, mx);
+  hipLaunchKernelGGL(k_nerf_enc_bound, dim3(n_rays < 256 ? pp_div_up(n_rays, 4) : 64), dim3(256), 0, st, center, ray, depth, n_rays, n_samples, mx);
+  if (wstream) {
+    TrunkPackJobs P;
+    for (int l = 0; l < 8; ++l) { P.src[l] = params + L.w[l]; P.ld[l] = NERF_IN_LD[l]; P.mx_w[l] = MX_W0 + l; }
+    P.src[8] = params + L.r0; P.ld[8] = 288; P.mx_w[8] = MX_R0;        // the colour head's hidden layer rides as a ninth stage
+    P.nsteps = TR_STEPS + 10;
+    hipLaunchKernelGGL(k_pack_trunk<false>, dim3(P.nsteps * 4), dim3(256), 0, st, P, mx, wstream);
+  } else {
+    PlanePackJobs P;
+    P.n = 8;
+    for (int l = 0; l < 8; ++l) {
+      P.src[l] = params + L.w[l]; P.dst[l] = wimg[l]; P.ld[l] = NERF_IN_LD[l]; P.K[l] = NERF_IN_LD[l]; P.mx_slot[l] = MX_W0 + l;
+    }
+    hipLaunchKernelGGL(k_pack_planes, dim3(16, 8), dim3(256), 0, st, P, mx);
+  }
+}
+
+// Arguments of the fused forward chain, as far as they do not depend on where its activations go: the caller adds out[8],
+// in2 / in2_ld and, for a pass that a backward pass follows, what that one reads (out[0 .. 7] with ld, bitsr, raw).
+static TrunkArgs nerf_fwd_trunk_args(const float* params, const NerfLayout& L, const float* enc, const unsigned char* wstream,
+                                     float* density, float* mx) {
+  TrunkArgs T;
+  memset(&T, 0, sizeof(T));
+  T.in = enc; T.in_ld = 64;
+  for (int l = 0; l < 8; ++l) { T.bias[l] = params + L.b[l]; T.mx_w[l] = MX_W0 + l; T.mx_out[l] = MX_A0 + l; }
+  T.wstream = wstream;
+  T.wd = params + L.wd; T.bd = params + L.bd; T.density = density;
+  T.mx = mx; T.mx_in = MX_ENC;
+  T.head = 1; T.ld[8] = 128; T.bias[8] = params + L.br0; T.mx_w[8] = MX_R0;
+  return T;
+}
+
 extern "C" int pp_nerf_fwd(const float* params, const float* center, const float* ray, const float* depth,
                            const float* bands, const int32_t* count, int32_t n_rays, int32_t n_samples, float* acts,
                            float* rgb_samples, float* density_samples, void* ctx, void* stream) {
@@ -794,45 +833,16 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
   const NerfLayout L = nerf_layout();
   NerfActs A = nerf_acts(acts, M);
   float* mx = rt.split ? A.mx : nullptr;
-  if (mx) {
-    hipMemsetAsync(mx, 0, MX_SLOTS * sizeof(float), st);
-    NerfWmaxJobs J;
-    for (int l = 0; l < 7; ++l) { J.src[l] = params + L.w[l]; J.n[l] = 256 * NERF_IN_LD[l]; }
-    J.src[7] = params + L.wd; J.n[7] = 257 * 256;
-    J.src[8] = params + L.r0; J.n[8] = 128 * 288;
-    hipLaunchKernelGGL(k_nerf_wmax, dim3(16, 9), dim3(256), 0, st, J, mx);
-    hipLaunchKernelGGL(k_nerf_enc_bound, dim3(n_rays < 256 ? pp_div_up(n_rays, 4) : 64), dim3(256), 0, st, center, ray, depth, n_rays, n_samples, mx);
-    if (rt.chain_fwd) {
-      TrunkPackJobs P;
-      for (int l = 0; l < 8; ++l) { P.src[l] = params + L.w[l]; P.ld[l] = NERF_IN_LD[l]; P.mx_w[l] = MX_W0 + l; }
-      P.src[8] = params + L.r0; P.ld[8] = 288; P.mx_w[8] = MX_R0;        // the colour head's hidden layer rides as a ninth stage
-      P.nsteps = rt.head ? TR_STEPS + 10 : TR_STEPS;
-      hipLaunchKernelGGL(k_pack_trunk<false>, dim3(P.nsteps * 4), dim3(256), 0, st, P, mx, reinterpret_cast<unsigned char*>(A.wimg[0]));
-    } else {
-      PlanePackJobs P;
-      P.n = 8;
-      for (int l = 0; l < 8; ++l) {
-        P.src[l] = params + L.w[l]; P.dst[l] = A.wimg[l]; P.ld[l] = NERF_IN_LD[l]; P.K[l] = NERF_IN_LD[l]; P.mx_slot[l] = MX_W0 + l;
-      }
-      hipLaunchKernelGGL(k_pack_planes, dim3(16, 8), dim3(256), 0, st, P, mx);
-    }
-  }
+  unsigned char* const wstream = reinterpret_cast<unsigned char*>(A.wimg[0]);      // the fused chain's weights take the plane images' place
+  if (mx) nerf_fwd_prepare(st, params, L, center, ray, depth, n_rays, n_samples, mx, rt.chain ? wstream : nullptr, A.wimg);
   hipLaunchKernelGGL(k_nerf_encode<true>, dim3(pp_div_up(M, 16)), dim3(256), 0, st, center, ray, depth, bands, M,
                      n_samples, A.enc, A.a[3], A.a[7]);
-  if (rt.chain_fwd) {
-    TrunkArgs T;
-    memset(&T, 0, sizeof(T));
-    T.in = A.enc; T.in_ld = 64;
-    for (int l = 0; l < 8; ++l) {
-      T.out[l] = A.a[l]; T.ld[l] = NERF_OUT_LD[l]; T.bias[l] = params + L.b[l]; T.bits[l] = reinterpret_cast<uint32_t*>(A.bits[l]);
-      T.bitsr[l] = A.bits[l]; T.mx_w[l] = MX_W0 + l; T.mx_out[l] = MX_A0 + l;
-    }
-    T.wstream = reinterpret_cast<const unsigned char*>(A.wimg[0]);
-    T.wd = params + L.wd; T.bd = params + L.bd; T.raw = A.raw; T.density = density_samples;
-    T.mx = mx; T.mx_in = MX_ENC;
-    T.head = rt.head; T.out[8] = A.h; T.ld[8] = 128; T.bias[8] = params + L.br0; T.mx_w[8] = MX_R0; T.in2 = A.a[7] + 256; T.in2_ld = 288;
-    if (rt.chain_bwd) launch_trunk<false, true>(T, count, M, st);       // masks in the layout the fused backward chain reads
-    else launch_trunk<false, false>(T, count, M, st);
+  if (rt.chain) {
+    TrunkArgs T = nerf_fwd_trunk_args(params, L, A.enc, wstream, density_samples, mx);
+    for (int l = 0; l < 8; ++l) { T.out[l] = A.a[l]; T.ld[l] = NERF_OUT_LD[l]; T.bitsr[l] = A.bits[l]; }
+    T.raw = A.raw;
+    T.out[8] = A.h; T.in2 = A.a[7] + 256; T.in2_ld = 288;
+    launch_trunk<false>(T, count, M, st);
   } else {
     const float* in = A.enc;
     for (int l = 0; l < 8; ++l) {
@@ -843,10 +853,10 @@ extern "C" int pp_nerf_fwd(const float* params, const float* center, const float
     }
     hipLaunchKernelGGL(k_nerf_density_fwd, dim3(pp_div_up(M, 4)), dim3(256), 0, st, A.a[6], params + L.wd, params + L.bd, M,
                        A.raw, density_samples);
-  }
-  if (!rt.head)         // (else the fused chain has produced the head's hidden layer as its ninth stage)
+    // the colour head's hidden layer (the fused chain's ninth stage)
     nerf_gemm<EPI_RELU>(st, rt.split, A.a[7], 288, params + L.r0, 288, 288, 128, params + L.br0, nullptr, 0, A.h, 128, count, M,
                         mx ? mx + MX_A0 + 7 : nullptr, mx ? mx + MX_R0 : nullptr, nullptr);
+  }
   hipLaunchKernelGGL(k_nerf_rgb_fwd, dim3(pp_div_up(M * 16, 256)), dim3(256), 0, st, params + L.r1, params + L.br1, A.h, M,
                      rgb_samples);
   PP_CHECK_LAUNCH();
@@ -884,37 +894,17 @@ extern "C" int pp_nerf_infer(const float* params, const float* center, const flo
   const NerfRoute rt(pp_options(ctx));
   PP_REQUIRE(params && center && ray && depth && bands && count && work && rgb_samples && density_samples, "null pointer");
   PP_REQUIRE(n_rays > 0 && n_samples > 0 && (int64_t)n_rays * n_samples < (1LL << 30), "bad sizes");
-  PP_REQUIRE(rt.split && rt.chain_fwd && rt.head,
-             "only the default route (nerf_split = 1, the forward bit of nerf_chain, nerf_chain_head = 1) has a forward-only "
-             "form: use pp_nerf_fwd");
+  PP_REQUIRE(rt.chain, "only the fused route (nerf_split = 1, nerf_chain = 3: the defaults) has a forward-only form: use pp_nerf_fwd");
   hipStream_t st = pp_stream(stream);
   const int M = n_rays * n_samples;
   const NerfLayout L = nerf_layout();
   const NerfInferWork X = nerf_infer_work(work, M);
-  float* mx = X.mx;
-  hipMemsetAsync(mx, 0, MX_SLOTS * sizeof(float), st);
-  NerfWmaxJobs J;
-  for (int l = 0; l < 7; ++l) { J.src[l] = params + L.w[l]; J.n[l] = 256 * NERF_IN_LD[l]; }
-  J.src[7] = params + L.wd; J.n[7] = 257 * 256;
-  J.src[8] = params + L.r0; J.n[8] = 128 * 288;
-  hipLaunchKernelGGL(k_nerf_wmax, dim3(16, 9), dim3(256), 0, st, J, mx);
-  hipLaunchKernelGGL(k_nerf_enc_bound, dim3(n_rays < 256 ? pp_div_up(n_rays, 4) : 64), dim3(256), 0, st, center, ray, depth, n_rays, n_samples, mx);
-  TrunkPackJobs P;
-  for (int l = 0; l < 8; ++l) { P.src[l] = params + L.w[l]; P.ld[l] = NERF_IN_LD[l]; P.mx_w[l] = MX_W0 + l; }
-  P.src[8] = params + L.r0; P.ld[8] = 288; P.mx_w[8] = MX_R0;
-  P.nsteps = TR_STEPS + 10;
-  hipLaunchKernelGGL(k_pack_trunk<false>, dim3(P.nsteps * 4), dim3(256), 0, st, P, mx, X.wstream);
+  nerf_fwd_prepare(st, params, L, center, ray, depth, n_rays, n_samples, X.mx, X.wstream, nullptr);
   hipLaunchKernelGGL(k_nerf_encode<false>, dim3(pp_div_up(M, 16)), dim3(256), 0, st, center, ray, depth, bands, M, n_samples,
                      X.enc, static_cast<float*>(nullptr), X.view);
-  TrunkArgs T;
-  memset(&T, 0, sizeof(T));
-  T.in = X.enc; T.in_ld = 64;
-  for (int l = 0; l < 8; ++l) { T.bias[l] = params + L.b[l]; T.mx_w[l] = MX_W0 + l; T.mx_out[l] = MX_A0 + l; }
-  T.wstream = X.wstream;
-  T.wd = params + L.wd; T.bd = params + L.bd; T.density = density_samples;
-  T.mx = mx; T.mx_in = MX_ENC;
-  T.head = 1; T.out[8] = X.h; T.ld[8] = 128; T.bias[8] = params + L.br0; T.mx_w[8] = MX_R0; T.in2 = X.view; T.in2_ld = 32;
-  launch_trunk<false, true, false>(T, count, M, st);
+  TrunkArgs T = nerf_fwd_trunk_args(params, L, X.enc, X.wstream, density_samples, X.mx);
+  T.out[8] = X.h; T.in2 = X.view; T.in2_ld = 32;
+  launch_trunk<false, false>(T, count, M, st);
   hipLaunchKernelGGL(k_nerf_rgb_fwd, dim3(pp_div_up(M * 16, 256)), dim3(256), 0, st, params + L.r1, params + L.br1, X.h, M,
                      rgb_samples);
   PP_CHECK_LAUNCH();
@@ -966,7 +956,7 @@ static void nerf_bwd_body(const float* params, const float* ray, const float* de
   // split-precision path: operand maxima of the gradient tensors are recorded by their producers (slots MX_DH .. MX_DHSUM)
   float* mx = rt.split ? A.mx : nullptr;
   if (mx) hipMemsetAsync(mx + MX_DH, 0, (MX_DHSUM - MX_DH + 1) * sizeof(float), st);
-  const bool chain = rt.chain_bwd;
+  const bool chain = rt.chain;
   // where k_nerf_part_finish adds the heads' parameter sums: R1 | br1 | wd | bd
   float* discard = DY[0];                          // input_only: the head of the DY block (see above)
   float* g_r1 = input_only ? discard : params_grad + L.r1;
@@ -1026,7 +1016,7 @@ static void nerf_bwd_body(const float* params, const float* ray, const float* de
     T.wstream = reinterpret_cast<const unsigned char*>(Sc.r0t_img);
     T.wd = params + L.wd; T.draw = d7 + 256; T.draw_ld = 288;
     T.mx = mx; T.mx_in = MX_DH;
-    launch_trunk<true, true>(T, count, M, st);
+    launch_trunk<true>(T, count, M, st);
   } else {                                           // one GEMM per layer, masked by the ReLU bits of its output's layer
     nerf_gemm<EPI_MASK>(st, rt.split, dH, 128, Sc.R0T, 128, 128, 256, nullptr, A.a[7], 288, d7, 288, count, M, slot(MX_DH), slot(MX_R0),
                         slot(MX_P), A.bits[7], Sc.r0t_img);

@@ -23,11 +23,10 @@
 // Scales.  The layer-by-layer path scales a GEMM's input by the power of two derived from the maximum of the WHOLE tensor,
 // which a fused kernel cannot know before it has finished; it uses the maximum of the TILE (>= as many significant bits),
 // reduced through LDS between the two barriers of the epilogue, and still records the tensor maxima for the kernels downstream.
-// ReLU masks: one bit per activation, 32 bytes per sample and layer either way.  MROW = false writes the layout the
-// layer-by-layer data-gradient kernels read (pp_gemm.h gemm_epilogue: 16 rows of a column per 16-bit word; a lane holds 16
-// columns of one row here, so the 32 x 32 bit block of a wavefront is transposed with v_cmp - the 64-lane mask of one
-// accumulator register = two columns x 32 rows -, v_writelane and a nibble shuffle); MROW = true writes the lane's own 16
-// columns as one word, [row][column block][lane half], which is what the fused backward chain reads back in the same lane.
+// ReLU masks: one bit per activation, 32 bytes per sample and layer, as 16-bit words [row][column block][lane half]: a lane
+// holds 16 consecutive columns of one row per 32 x 32 block, the forward chain writes them as one word, and the backward chain
+// reads that word back in the same lane.  (The layer-by-layer kernels keep a layout of their own - pp_gemm.h gemm_epilogue: 16
+// rows of a column per word -, so a step's forward and backward pass run on the same route.)
 // The density head (row 0 of the reference's last feature layer applied to layer 6's output) is folded into layer 6's
 // epilogue: per-wavefront partial dot products through LDS, summed in a fixed order; its gradient enters the backward chain
 // as the rank-1 term d raw[row] * wd[k] in the epilogue of the stage that produces d(layer 6).
@@ -44,8 +43,7 @@ struct TrunkArgs {
   float* out[9];                        // stage outputs, fp32 [M][ld] (forward stage 8 = the colour head's hidden layer, [M][128])
   int ld[9];
   const float* bias[9];                 // forward
-  uint32_t* bits[8];                    // forward, MROW = false: ReLU masks in the layer-by-layer layout (pairs of its 16-bit words)
-  uint16_t* bitsr[8];                   // MROW: [row][8 column blocks][2 lane halves] words; forward writes stage s's, backward reads the mask of stage s's OUTPUT
+  uint16_t* bitsr[8];                   // ReLU masks, [row][8 column blocks][2 lane halves] words; forward writes stage s's, backward reads the mask of stage s's OUTPUT
   const unsigned char* wstream;         // k_pack_trunk's image
   const float* wd;                      // density head weights (forward: NULL = not folded; backward: the rank-1 term)
   const float* bd;
@@ -138,10 +136,6 @@ __device__ __forceinline__ void tr_step(const unsigned char* img, const pp_half8
   }
 }
 
-// lane `lane_` (a literal) of v_ <- the scalar s_
-// (s_nop: the scalar comes straight from a vector compare; the compiler's hazard recogniser does not look into inline assembly,
-// and without the wait states the lane receives the PREVIOUS compare's mask - found by the gradient parity test)
-#define TR_WRITELANE(v_, s_, lane_) asm("s_nop 4\n\tv_writelane_b32 %0, %1, %2" : "+v"(v_) : "s"(s_), "n"(lane_))
 #define TR_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")   // LDS-only: the loads in flight stay in flight
 
 // BWD = false: stages = layers 0 .. 7 (bias, ReLU, masks out, density head at layer 6), streamed chunks: 2 in front of layers 0 and 4
@@ -157,7 +151,7 @@ __device__ __forceinline__ void tr_step(const unsigned char* img, const pp_half8
 // KEEP = false (forward only, pp_nerf_infer): nothing a backward pass would read leaves the work-group - no stage output is sent
 // to HBM from the image (TR_DRAIN), no mask word is formed, raw is not stored; what remains are the last stage's rows (the colour
 // head's hidden layer) and the densities.  The arithmetic of every stage is the one of KEEP = true, so these are the same bits.
-template <bool BWD, bool MROW, bool KEEP = true>
+template <bool BWD, bool KEEP = true>
 __global__ __launch_bounds__(256, 2) void k_nerf_trunk(TrunkArgs T, const int32_t* __restrict__ count, int rcap) {
   constexpr int NW = 4;                 // wavefronts of a work-group
   constexpr int TM = NW / 2;            // 32-row blocks of a tile
@@ -396,45 +390,19 @@ __global__ __launch_bounds__(256, 2) void k_nerf_trunk(TrunkArgs T, const int32_
         }
       }
       if (KEEP && !BWD && !hstage) {
-        if (MROW) {
-          uint16_t* __restrict__ br = T.bitsr[l];
+        uint16_t* __restrict__ br = T.bitsr[l];
 #pragma unroll
-          for (int t = 0; t < TM; ++t)
+        for (int t = 0; t < TM; ++t)
 #pragma unroll
-            for (int u = 0; u < TU; ++u) {
-              // bit j <-> accumulator register j of the lane.  The values are ReLU outputs (+0 or positive): bits + 0x7FFFFFFF
-              // carries into bit 31 exactly for the positive ones, and v_alignbit shifts that bit into the word - 2 instructions per value
-              unsigned m = 0u;
+          for (int u = 0; u < TU; ++u) {
+            // bit j <-> accumulator register j of the lane.  The values are ReLU outputs (+0 or positive): bits + 0x7FFFFFFF
+            // carries into bit 31 exactly for the positive ones, and v_alignbit shifts that bit into the word - 2 instructions per value
+            unsigned m = 0u;
 #pragma unroll
-              for (int j = 15; j >= 0; --j) m = __builtin_amdgcn_alignbit(m, __float_as_uint(acc[t][u][j]) + 0x7FFFFFFFu, 31);
-              const int row = r0 + t * 32 + l31;
-              if (row < R) br[((size_t)row * 8 + TU * w + u) * 2 + lh] = (uint16_t)m;
-            }
-        } else {
-          uint32_t* __restrict__ bits = T.bits[l];
-#pragma unroll
-          for (int t = 0; t < TM; ++t)
-#pragma unroll
-            for (int u = 0; u < TU; ++u) {
-              // lane c of rm <- the 32 row bits of column c: the 64-lane compare mask of accumulator register j is rows 0..31 of
-              // column (j & 3) + 8 (j >> 2) in its low word and of that column + 4 in its high word
-              unsigned rm = 0u;
-#pragma unroll
-              for (int j = 0; j < 16; ++j) {
-                const unsigned long long bal = __ballot(acc[t][u][j] > 0.f);
-                const unsigned blo = (unsigned)bal, bhi = (unsigned)(bal >> 32);
-                TR_WRITELANE(rm, blo, (j & 3) + 8 * (j >> 2));
-                TR_WRITELANE(rm, bhi, (j & 3) + 8 * (j >> 2) + 4);
-              }
-              // word of row half h' of a column = nibbles h', h' + 2, h' + 4, h' + 6 of its row bits; all 32 columns at once
-              unsigned e = rm & 0x0F0F0F0Fu, o = (rm >> 4) & 0x0F0F0F0Fu;
-              e = (e | (e >> 4)) & 0x00FF00FFu;
-              o = (o | (o >> 4)) & 0x00FF00FFu;
-              e = (e | (e >> 8)) & 0x0000FFFFu;
-              o = (o | (o >> 8)) & 0x0000FFFFu;
-              if (lane < 32) bits[((size_t)(r0 >> 5) + t) * 256 + 32 * (TU * w + u) + lane] = e | (o << 16);
-            }
-        }
+            for (int j = 15; j >= 0; --j) m = __builtin_amdgcn_alignbit(m, __float_as_uint(acc[t][u][j]) + 0x7FFFFFFFu, 31);
+            const int row = r0 + t * 32 + l31;
+            if (row < R) br[((size_t)row * 8 + TU * w + u) * 2 + lh] = (uint16_t)m;
+          }
       }
       // maximum of each row of 16 lanes by four DPP moves (no LDS round trips, unlike __shfl_xor), then four lanes per
       // wavefront into the LDS slot (all 64 lanes on one address measured far slower: +120 k ticks per work-group)

@@ -68,6 +68,15 @@ def test_options_live_in_caller_owned_contexts():
     with pytest.raises(_lib.PoseProbeError):
         a.set('nerf_chain_nw', 4)           # retired option
     with pytest.raises(_lib.PoseProbeError):
+        a.set('nerf_chain_head', 0)         # retired option
+    for hybrid in (1, 2):                   # retired values: fused forward chain with the layer-by-layer backward
+        with pytest.raises(_lib.PoseProbeError, match='retired'):
+            a.set('nerf_chain', hybrid)
+    a.set('nerf_chain', 0)
+    assert a.get('nerf_chain') == 0
+    a.set('nerf_chain', 3)
+    assert a.get('nerf_chain') == 3 == _lib.library_default('nerf_chain')
+    with pytest.raises(_lib.PoseProbeError):
         a.set('mlp_split', 64)
     assert set(a.options()) == set(_lib.OPTION_NAMES)
 

@@ -751,23 +751,22 @@ def repack_masks_for_the_layer_by_layer_backward(acts, M):
     return out
 
 
-@pytest.mark.parametrize('R,S,chain,head', [(1023, 128, 3, 1), (1023, 128, 1, 0), (37, 50, 3, 0), (37, 50, 1, 1), (1, 2, 3, 1)])
-def test_scene_trunk_kernel_equals_layer_by_layer_path(R, S, chain, head):
-    """Option nerf_chain (csrc/pp_nerf_trunk.h: the eight feature layers + density head as one kernel, tile resident in LDS)
-    against the layer-by-layer GEMMs on the same inputs: every stored activation, the raw density and the sample outputs
-    agree to fp32 rounding of a 256..320-term sum (the two paths scale their fp16 operand pairs by different powers of two -
-    tile maximum vs tensor maximum - so they are not bit-identical), the one-bit ReLU masks the data-gradient kernels read
-    agree wherever the activations of both paths have the same state (and ARE that state), and the tensor maxima recorded
-    for the backward pass agree.  Sizes: four tiles per work-group, a ragged last tile, less than one tile.  chain = 1: fused
-    forward writing the masks in the layer-by-layer layout; chain = 3: in the fused chains' own layout ([row][wavefront][lane
-    half], bit j <-> column 32 w + 4 half + (j & 3) + 8 (j >> 2)), followed by a backward pass of both paths on the same
-    upstream gradients (parameter, centre and ray gradients).  head: the colour head's hidden layer as the forward chain's
-    ninth stage (compared through the sample colours)."""
+@pytest.mark.parametrize('R,S', [(1023, 128), (37, 50), (1, 2)])
+def test_scene_trunk_kernel_equals_layer_by_layer_path(R, S):
+    """The fused route (nerf_chain = 3, csrc/pp_nerf_trunk.h: the eight feature layers + density head + the colour head's hidden
+    layer as one kernel, tile resident in LDS) against the layer-by-layer GEMMs (nerf_chain = 0) on the same inputs: every stored
+    activation, the raw density and the sample outputs agree to fp32 rounding of a 256..320-term sum (the two paths scale their
+    fp16 operand pairs by different powers of two - tile maximum vs tensor maximum - so they are not bit-identical), the one-bit
+    ReLU masks the data-gradient kernels read agree wherever the activations of both paths have the same state (and ARE that
+    state), and the tensor maxima recorded for the backward pass agree.  Sizes: four tiles per work-group, a ragged last tile,
+    less than one tile.  The fused chain writes its masks in its own layout ([row][wavefront][lane half], bit j <-> column
+    32 w + 4 half + (j & 3) + 8 (j >> 2)); at every size a backward pass of both paths follows on the same upstream gradients
+    (parameter, centre and ray gradients).  The ninth stage is compared through the sample colours."""
     from poseprobe_amd import bg_nerf, ops
     dev = 'cuda'
     opt = bg_nerf.default_options(sample_intvs=S)
     torch.manual_seed(5)
-    nets = [bg_nerf.NeRF(opt, device=dev, options={'nerf_chain': c, 'nerf_chain_head': head}) for c in (chain, 0)]
+    nets = [bg_nerf.NeRF(opt, device=dev, options={'nerf_chain': c}) for c in (3, 0)]
     g = torch.Generator().manual_seed(R + S)
     with torch.no_grad():
         for lin in list(nets[0].mlp_feat) + list(nets[0].mlp_rgb):
@@ -818,15 +817,13 @@ def test_scene_trunk_kernel_equals_layer_by_layer_path(R, S, chain, head):
             out = torch.zeros(Mp // 32, 32, 256, dtype=torch.bool, device=dev)
             out[:, rows.reshape(-1), :] = bits.permute(0, 2, 3, 1).reshape(Mp // 32, 32, 256)
             return out.view(Mp, 256)[:M]
-        s1, s0 = (mask_states_rows(b1, M) if chain == 3 else states(b1)), states(b0)
+        s1, s0 = mask_states_rows(b1, M), states(b0)
         x1, x0 = acts_l[l]
         assert torch.equal(s1, x1 > 0), f'layer {l}: mask bits of the fused kernel are not the states of its own activations'
         assert torch.equal(s0, x0 > 0)
         assert int((s1 != s0).sum()) <= max(2, 2e-6 * s1.numel()), f'layer {l}: {int((s1 != s0).sum())} states differ'
     assert_close(d1, d0, rtol=2e-5, scaled=2e-6, name='density')
     assert_close(rgb1, rgb0, rtol=0, atol=2e-6, name='rgb samples')
-    if chain != 3:
-        return
     # backward of both paths on the SAME forward state: the fused forward's activation block, with its mask planes re-packed
     # into the layer-by-layer layout for the layer-by-layer backward - identical ReLU states, so the gradients must agree
     # to rounding (no allowance for flipped states)

@@ -113,7 +113,7 @@ def test_infer_workspace_is_at_most_225_floats_per_sample():
 
 
 # ------------------------------------------------------------------------------------------------ 3. other routes
-@pytest.mark.parametrize('options', [{'nerf_split': 0}, {'nerf_chain': 0}, {'nerf_chain_head': 0}], ids=lambda o: next(iter(o)))
+@pytest.mark.parametrize('options', [{'nerf_split': 0}, {'nerf_chain': 0}], ids=lambda o: next(iter(o)))
 def test_other_routes_are_refused_by_the_kernel_entry_and_served_by_the_fallback(options):
     from poseprobe_amd import _lib, bg_nerf, ops, synthetic as syn
     net, opt = _net(1.0, seed=2, options=options, sample_intvs=24)

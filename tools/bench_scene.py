@@ -7,7 +7,7 @@ R = int(sys.argv[1]) if len(sys.argv) > 1 else 3072
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 128
 steps = int(sys.argv[3]) if len(sys.argv) > 3 else 20
 opt = bg_nerf.default_options()
-chain = int(sys.argv[4]) if len(sys.argv) > 4 else 3
+chain = int(sys.argv[4]) if len(sys.argv) > 4 else 3          # 3 = the fused route, 0 = one GEMM per layer
 extra = {k: int(v) for k, v in (a.split('=') for a in sys.argv[5:])}
 net = bg_nerf.NeRF(opt, device='cuda', options={'nerf_chain': chain, **extra}); net.progress.data.fill_(0.6)
 eng = bg_nerf.SceneEngine(net, lr=1e-3)
