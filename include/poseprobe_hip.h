@@ -45,7 +45,7 @@ const char* pp_last_error(void);
  * ownership from stage 1 to stage 2 explicitly -, pp_nerf_fwd / pp_nerf_bwd, pp_grid_tv_adam_step{,_sparse});
  * pp_scene gained `sdf_index_exact`; new: pp_sdf_crossing_dense_bwd, pp_context_set_option / pp_context_get_option.  4 (this header): the
  * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
- * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_mc_* group, the pp_pnp_* group,
+ * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_featproj_* group, the pp_mc_* group, the pp_pnp_* group,
  * the pp_dtu_* group, the pp_ssim_* group, pp_step_begin, pp_march_loss_bwd / pp_march_loss_workspace, pp_geometry_plain_fwd /
  * pp_geometry_plain_bwd, pp_keep_compact / pp_keep_scatter_bwd.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
@@ -718,6 +718,38 @@ int pp_reproj_pose_fold(const pp_scene* sc, const int32_t* own, const float* pix
                         const float* c2w, const float* w2c, int32_t n_views, const float* rays_o, const float* rays_d,
                         const float* g_o, const float* g_d, const float* g_viewdirs, const float* g_t_min, const float* g_w2c,
                         float* g_c2w, void* stream);
+
+/* ---------------------------------------------------------------- object branch: surface-projection feature loss
+ * lib/recon_scene.py:371-439 (get_project_feature_loss) for ONE view pair (view_i, view_j), inverse_y without flips.  Query A
+ * (rays_o, rays_d, t_min, acc; the caller's differentiable render of R rays) gives p = o + d (t_min + acc), hit = acc > 0.
+ * Every per-row array holds `capacity` rows; rows at or beyond n_rows are never read and get zeros.
+ * pp_featproj_reproject: q = w2c[view_j] p; q_z < nl: q := (nl, nl, nl); pix_ref [capacity,2] = K_j q / q_z
+ * (lib/common.py:450-465), own_ref [capacity] int32 = view_j - the inputs of pp_reproj_rays for query B.  Rows from n_rows on get
+ * own_ref = -1 (no view: pp_reproj_rays gives them a ray that misses the box) and pixel (0, 0).  nl must be positive. */
+int pp_featproj_reproject(int32_t n_rows, int32_t capacity, int32_t view_j, const float* rays_o, const float* rays_d,
+                          const float* t_min, const float* acc, const float* intr, const float* w2c, int32_t n_views, float nl,
+                          int32_t* own_ref, float* pix_ref, void* stream);
+/* The loss and every gradient up to the renderer.  ref_*: query B (forward only), p_ref and hit_ref as above.
+ *   q_v = w2c[v] p for v = view_i, view_j with the near-plane replacement (which stops that view's gradient of the row);
+ *   (x, y)_v = (2 u / (W - 1) - 1, 2 v / (H - 1) - 1), (u, v) = K_v q / q_z                            (lib/common.py:468-492)
+ *   valid = |p - p_ref| < 2 voxel_size && hit && hit_ref && max(|x|, |y|) <= 1 in both views
+ *   per layer l: a, b = bilinear samples (grid_sample, align_corners, zero padding) of feat_l[view_i], feat_l[view_j] at the
+ *   two positions; cos = (a / max(|a|, 1e-8)) . (b / max(|b|, 1e-8)) with torch.nn.functional.cosine_similarity's derivative
+ *   L = sum_l (1 - sum_valid cos / n_valid); without a valid row L and every gradient are exactly 0 (the reference: NaN).
+ * feat0..feat3: n_layers <= 4 maps, channels-last [n_views,h,w,C] fp32 (unused ones NULL); layer_dims: HOST array
+ * [n_layers,3] int32 of (C, h, w), 1 <= C <= 512, h, w >= 2.
+ * Outputs, all overwritten: terms [6] = (L, n_valid, sum_valid cos of layers 0..3); valid [capacity] uint8; cosv
+ * [n_layers,capacity] (0 where not valid); g_q [capacity,6] = the gradient of scale weight L on (q_i, q_j); g_depth [capacity],
+ * g_o / g_d [capacity,3] = its gradient on query A's depth and on the ray's explicit share of p (g_o = g_p, g_d = depth g_p);
+ * g_w2c [n_views,3,4] = the direct gradient on w2c (zero but for view_i and view_j).  Three launches: one work-group for the
+ * flags and n_valid, one wavefront per row with lanes across channels, one work-group for the sums over rows.  Fixed summation
+ * order, no atomics: identical inputs give identical bits. */
+int pp_featproj_loss(int32_t n_rows, int32_t capacity, int32_t view_i, int32_t view_j, const float* rays_o, const float* rays_d,
+                     const float* t_min, const float* acc, const float* ref_rays_o, const float* ref_rays_d,
+                     const float* ref_t_min, const float* ref_acc, const float* intr, const float* w2c, int32_t n_views, float nl,
+                     float voxel_size, int32_t H, int32_t W, int32_t n_layers, const float* feat0, const float* feat1,
+                     const float* feat2, const float* feat3, const int32_t* layer_dims, float weight, float scale, float* terms,
+                     uint8_t* valid, float* cosv, float* g_q, float* g_depth, float* g_o, float* g_d, float* g_w2c, void* stream);
 
 /* ---------------------------------------------------------------- scene branch: ordered weight-gradient flush
  * The nine weight-gradient products of pp_nerf_bwd end in float atomics: up to 512 work-groups (row splits x 128 x 128 output

@@ -455,7 +455,7 @@ class TrainEngine:
     def __init__(self, cfg: SceneConfig, n_views, H, W, n_rand, device='cuda', lr_pose=1e-3, lr_pose_end=1e-4,
                  pose_iters=1, lrate_decay=10, loss_scale=0.1, weight_main=1.0, weight_tv_k0=0.01, weight_mask=0.1,
                  fix_first=True, capacity=None, x_slab=None, dist_ctx=None, deterministic_scatter=False, options=None,
-                 deterministic=False, reproj_rows=0, fuse_head=True, fuse_rays=True, fuse_wgrad=True):
+                 deterministic=False, reproj_rows=0, fuse_head=True, fuse_rays=True, fuse_wgrad=True, featproj_rows=0):
         """fuse_head / fuse_rays (default path only, see `side_by_side`): the step starts with ONE launch (ops.step_begin: pose forward,
         step scalars, zero block, weight pack) / composites, evaluates the ray losses and differentiates the composite in ONE launch
         (ops.march_loss_bwd) - DESIGN 17.  False: the separate launches (A/B runs, tests); also plain attributes of the engine.
@@ -463,6 +463,11 @@ class TrainEngine:
         net's (pass_scope(join_wgrad=True)).  False: the two launches.
         reproj_rows: row capacity of the engine-native reprojection pass (`reprojection_grads`); each row is one ray of a second
         Workspace(reproj_rows, reproj_rows * n_samples).  0 (default): no second workspace, nothing changes.
+        featproj_rows: row capacity of the surface-projection feature pass (`surface_projection_grads`); each row is one ray of a
+        Workspace(featproj_rows, featproj_rows * n_samples) for the differentiable query (about 18 KB per sample) and one ray of a
+        forward-only workspace for the reference query (no activations, no gradient buffers: about 0.4 KB per sample), i.e.
+        18.4 KB * n_samples per row (160^3 voxels, 186 samples: 3.4 MB per row, the reference's 256 rows: 0.9 GB).  0 (default):
+        nothing is allocated, no launch differs.
         deterministic: bit-reproducible train step.  Implies deterministic_scatter and additionally replaces every other
         floating-point sum of the object-branch step that feeds a parameter update and depends on the order in which work-groups
         or lanes finish - the weight and bias gradients of both MLPs, their thin layers, the alpha / beta gradient of the geometry
@@ -576,6 +581,12 @@ class TrainEngine:
         self.last_reproj_terms = None
         if self.reproj_rows > 0:
             self._alloc_reproj()
+        self.featproj_rows = int(featproj_rows)
+        self.ws_featproj = self.ws_featproj_ref = None
+        self.feature_maps = None
+        self.last_featproj_terms = None
+        if self.featproj_rows > 0:
+            self._alloc_featproj()
 
     def _alloc_reproj(self):
         """Buffers of reprojection_grads: a workspace of its own (the main pass's activations stay untouched) and the per-row
@@ -597,7 +608,38 @@ class TrainEngine:
             # the (sic) formula has a negative radicand for such a box: torch.clamp then propagates NaN, the kernel's fmaxf would not
             raise ValueError('reproj_rows > 0: Voxurf.diagonal_length is not finite for this box (sum(xyz_max - xyz_min ** 2) < 0)')
 
+    def _alloc_featproj(self):
+        """Buffers of surface_projection_grads: a full workspace for query A (depth-only loss: its ray-level colour gradients are
+        zero for good), a forward-only one for query B, and the per-row buffers of the pp_featproj_* kernels."""
+        R, S = self.featproj_rows, self.cfg.n_samples
+        f = dict(dtype=torch.float32, device=self.dev)
+        ws = self.ws_featproj = Workspace(R, R * S, self.dev, ctx=self.ctx)
+        for t in (ws.g_rgbm, ws.g_last, ws.g_cw):
+            t.zero_()
+        self.ws_featproj_ref = Workspace(R, R * S, self.dev, backward=False, keep_activations=False, ctx=self.ctx)
+        z = lambda *shape: torch.zeros(*shape, **f)
+        self._fp = dict(own_ref=torch.zeros(R, dtype=torch.int32, device=self.dev), pix_ref=z(R, 2), terms=z(2 + ops.FEATPROJ_MAX_LAYERS),
+                        valid=torch.zeros(R, dtype=torch.uint8, device=self.dev), cos=z(ops.FEATPROJ_MAX_LAYERS, R), g_q=z(R, 6),
+                        g_depth=z(R), g_o=z(R, 3), g_d=z(R, 3), go=z(R, 3), gd=z(R, 3), gv=z(R, 3), g_w2c=z(self.V, 3, 4),
+                        g_c2w=z(self.V, 3, 4), se3=z(self.V, 6))
+
     # ---- data / parameter loading ---------------------------------------------------------------------------
+    def set_feature_maps(self, features):
+        """features: 1 to 4 per-view feature maps [V, C, h, w] (the reference's data_dict['vgg_features']; any tensors of that
+        shape, numpy or torch), 1 <= C <= 512, h, w >= 2.  Converted ONCE to the layout the gather reads - channels-last [V, h, w, C]
+        fp32 on the device - and kept."""
+        maps = []
+        for t in features:
+            t = torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t)
+            if t.dim() != 4 or t.shape[0] != self.V:
+                raise ValueError(f'a feature map must be [n_views = {self.V}, C, h, w], got {tuple(t.shape)}')
+            if not (1 <= t.shape[1] <= ops.FEATPROJ_MAX_CHANNELS and t.shape[2] >= 2 and t.shape[3] >= 2):
+                raise ValueError(f'a feature map needs 1 <= C <= {ops.FEATPROJ_MAX_CHANNELS} and h, w >= 2, got {tuple(t.shape)}')
+            maps.append(t.detach().to(self.dev, torch.float32).permute(0, 2, 3, 1).contiguous())
+        if not 1 <= len(maps) <= ops.FEATPROJ_MAX_LAYERS:
+            raise ValueError(f'{len(maps)} feature maps: need 1 to {ops.FEATPROJ_MAX_LAYERS}')
+        self.feature_maps = maps
+
     def set_views(self, images, masks, Ks, w2c_init):
         """images [V,H,W,3], masks [V,H,W,1|none], Ks [V,3,3], w2c_init [V,3,4] (numpy or torch)."""
         t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32).to(self.dev).contiguous()
@@ -823,6 +865,76 @@ class TrainEngine:
         t = rp['terms']
         self.last_reproj_terms = dict(err=t[0], near=t[1], n_valid=t[2])
         return self.last_reproj_terms
+
+    def surface_projection_grads(self, rows, global_step, weight, nl, jitter=None, jitter_ref=None, scale=None):
+        """Surface-projection feature loss of one view pair (recon_utils.get_project_feature_loss; lib/recon_scene.py:371-439,
+        :610-619) inside the engine's own launches: the rows are a second ray batch through the object branch's kernels on a
+        workspace of its own (query A), their surface points are projected into view `other`, a forward-only third batch (query B)
+        renders there and decides which rows see the same surface, and the cosine distance of the feature maps (set_feature_maps)
+        at the two projections is differentiated by the pp_featproj_* kernels.  The gradient of scale * weight * L is ACCUMULATED
+        into flat.grad (warp network, sdf_alpha / sdf_beta) and se3_grad (views own, other and the rows' source views).  k0_grad /
+        k0_touched are left exactly as they are.  No autograd, no host synchronisation, no parameter copy.
+        Must run after render_and_grads and before optimizer_step: it uses that step's w2c / c2w / jac and BARF weights.
+        rows: dict(src [R] int32 source view of each ray, pix [R,2] pixel (x, y) it goes through - pixel centres are x + 0.5,
+        y + 0.5 -, own = i, other = j the view pair; optional n_rows <= R: the rows in play), R <= featproj_rows.
+        jitter / jitter_ref [R]: the training-mode per-ray jitter of query A / B; None: drawn on the device.  nl > 0: near plane.
+        scale: None = the engine's loss_scale.  Leaves last_featproj_terms = dict(loss, n_valid, cos [n_layers]: the per-layer
+        sums of cos over the valid rows) as device tensors.  Without a valid row the term and its gradients are exactly 0 (the
+        reference: NaN)."""
+        if self.ws_featproj is None:
+            raise ValueError('surface_projection_grads needs an engine built with featproj_rows > 0')
+        if self.deterministic:
+            raise ValueError('the surface-projection pass is out of the scope of deterministic=True: its render backward uses the '
+                             'separate geometry backward, which keeps float atomics')
+        if self.dist is not None:
+            raise NotImplementedError('the surface-projection pass is not sharded across ranks')
+        if not self.cfg.inverse_y:
+            raise NotImplementedError('the surface-projection pass implements inverse_y=True without flips (the DTU setting)')
+        if self.feature_maps is None:
+            raise ValueError('surface_projection_grads needs feature maps (set_feature_maps)')
+        cfg, ws, wb, sc, fp, P = self.cfg, self.ws_featproj, self.ws_featproj_ref, self.cfg.pp, self._fp, self.flat
+        R = rows['src'].shape[0]
+        n = int(rows.get('n_rows', R))
+        cap = self.featproj_rows
+        if not 0 < n <= R <= cap:
+            raise ValueError(f'{n} of {R} rows with featproj_rows = {cap}')
+        i, j = int(rows['own']), int(rows['other'])
+        if not (0 <= i < self.V and 0 <= j < self.V):
+            raise ValueError(f'view pair ({i}, {j}) with {self.V} views')
+
+        def per_row(t):                                             # rows past R are rays that miss the box: any jitter will do
+            if t is None:
+                return torch.rand(cap, device=self.dev)
+            return t if t.shape[0] >= cap else torch.cat([t, t.new_zeros(cap - t.shape[0])])
+        jitter, jitter_ref = per_row(jitter), per_row(jitter_ref)
+        scale = self.loss_scale if scale is None else scale
+        L = len(self.feature_maps)
+        par = (self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), cfg.inv_s(global_step), self.pe_w)
+        ops.reproj_rays(sc, rows['src'], rows['pix'], n, self.intr, self.c2w, ws.rays_o, ws.rays_d, ws.viewdirs)
+        self.core.sample(ws, jitter)
+        with self.core.pass_scope(P, self.mlp_pack, ws):
+            self.core.forward(ws, *par)
+            # query B: rays of view j through the projections; its forward stores nothing a backward would need
+            ops.featproj_reproject(n, j, ws.rays_o, ws.rays_d, ws.t_min, ws.depth_acc, self.intr, self.w2c, nl, fp['own_ref'],
+                                   fp['pix_ref'])
+            ops.reproj_rays(sc, fp['own_ref'], fp['pix_ref'], n, self.intr, self.c2w, wb.rays_o, wb.rays_d, wb.viewdirs)
+            self.core.sample(wb, jitter_ref)
+            self.core.forward(wb, *par)
+            ops.featproj_loss(n, i, j, ws.rays_o, ws.rays_d, ws.t_min, ws.depth_acc, wb.rays_o, wb.rays_d, wb.t_min, wb.depth_acc,
+                              self.intr, self.w2c, nl, cfg.voxel_size, self.H, self.W, self.feature_maps, weight, scale, fp['terms'],
+                              fp['valid'], fp['cos'], fp['g_q'], fp['g_depth'], fp['g_o'], fp['g_d'], fp['g_w2c'])
+            # depth-only loss: ws.g_rgbm / g_last / g_cw stay zero; no colour-grid gradient is requested (k0_grad = None, no scatter)
+            self.core.backward(ws, *par, None, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
+                               g_depth=fp['g_depth'])
+            ops.raygen_select_bwd(sc, None, None, None, 0, 0, True, ws.rays_o, ws.rays_d, ws.t_min, ws.ray_start, ws.g_pts, ws.step,
+                                  ws.g_view_s, fp['g_o'], fp['g_d'], None, fp['g_depth'], fp['go'], fp['gd'], fp['gv'], None)
+        ops.reproj_pose_fold(sc, rows['src'], rows['pix'], n, self.intr, self.c2w, self.w2c, ws.rays_o, ws.rays_d, fp['go'], fp['gd'],
+                             fp['gv'], None, fp['g_w2c'], fp['g_c2w'])
+        ops.pose_bwd(self.jac, fp['g_c2w'], fp['se3'])
+        self.se3_grad += fp['se3']
+        t = fp['terms']
+        self.last_featproj_terms = dict(loss=t[0], n_valid=t[1], cos=t[2:2 + L])
+        return self.last_featproj_terms
 
     def _upload_step_scalars(self, progress):
         """BARF weights for this step and the learning rates the optimiser will use at the END of this step (the

@@ -79,7 +79,7 @@ class DualBranchEngine:
         return c2w[:, None, :, 3].expand_as(ray), ray, dir_cam
 
     def forward_backward(self, ray_idx, jitter, global_step, pixels, image, depth_rand=None, fine=False, fine_grid=None,
-                         n_views=None, corres=None, corres_rand=None, corres_fine_grid=None, reproj=None):
+                         n_views=None, corres=None, corres_rand=None, corres_fine_grid=None, reproj=None, featproj=None):
         """ray_idx / jitter: the object branch's batch (engine.TrainEngine.train_step); pixels [N, 2] + image [V, N, 3]: the
         scene branch's batch; depth_rand [V, N, S, 1] / fine_grid [Nf + 1] optionally replay the samplers' draws.  On return every gradient
         buffer (object engine's k0 / MLPs / se3 - the pose gradient of BOTH branches - and the scene engine's block) is
@@ -92,7 +92,12 @@ class DualBranchEngine:
         reprojection + near-surface terms (lib/recon_scene.py:621-637) through engine.TrainEngine.reprojection_grads (the object
         engine needs reproj_rows > 0): loss_scale * (weight_near_surface * near + weight_projection * err) joins the object
         branch's gradients - the pose, and in mode 'render' the warp network and sdf_alpha / sdf_beta; the object engine's
-        last_reproj_terms holds the scalars as device tensors."""
+        last_reproj_terms holds the scalars as device tensors.
+        featproj: dict(rows, weight, nl, jitter=None, jitter_ref=None) adds the object loss's surface-projection feature term
+        (lib/recon_scene.py:610-619) through engine.TrainEngine.surface_projection_grads (the object engine needs featproj_rows > 0
+        and feature maps): loss_scale * weight * L joins the object branch's gradients - the pose, the warp network and sdf_alpha /
+        sdf_beta; the object engine's last_featproj_terms holds the scalars as device tensors.  Runs beside `reproj`, with the same
+        refusals."""
         e, sc = self.obj, self.scene
         if corres is not None and e.dist is not None:
             raise NotImplementedError('DualBranchEngine: the correspondence term is not sharded across ranks')
@@ -102,11 +107,20 @@ class DualBranchEngine:
                                  'atomics)')
             if e.dist is not None:
                 raise NotImplementedError('DualBranchEngine: the reprojection term is not sharded across ranks')
+        if featproj is not None:
+            if self.deterministic or getattr(e, 'deterministic', False):
+                raise ValueError('DualBranchEngine: featproj is out of the scope of deterministic=True (its render backward keeps float '
+                                 'atomics)')
+            if e.dist is not None:
+                raise NotImplementedError('DualBranchEngine: the surface-projection term is not sharded across ranks')
         out = e.render_and_grads(ray_idx, jitter, global_step)            # also refreshes e.c2w / e.jac for this step
         if reproj is not None:
             e.reprojection_grads(reproj['rows'], reproj['mode'], global_step, jitter=reproj.get('jitter'),
                                  weight_projection=reproj['weight_projection'], weight_near_surface=reproj['weight_near_surface'],
                                  nl=reproj['nl'], pixel_thre=reproj.get('pixel_thre'))
+        if featproj is not None:
+            e.surface_projection_grads(featproj['rows'], global_step, featproj['weight'], featproj['nl'], jitter=featproj.get('jitter'),
+                                       jitter_ref=featproj.get('jitter_ref'))
         opt = sc.net.opt
         V, N, S = (e.V if n_views is None else n_views), pixels.shape[0], opt.nerf.sample_intvs
         center, ray, dir_cam = self.scene_rays(pixels, V)
@@ -155,11 +169,11 @@ class DualBranchEngine:
         return out, loss_bg
 
     def train_step(self, ray_idx, jitter, global_step, pixels, image, depth_rand=None, optimize_pose=True, fine=False,
-                   fine_grid=None, n_views=None, before_step=None, corres=None, reproj=None):
+                   fine_grid=None, n_views=None, before_step=None, corres=None, reproj=None, featproj=None):
         """fine=True: the scene branch also runs its fine network (after ratio_start_fine_sampling_at_x of the schedule).
         before_step: callable run after both branches' backward and before the optimiser step (the trainer mixes its extra
-        pose-only loss terms into se3_grad there).  corres, reproj: see forward_backward."""
-        extra = {k: v for k, v in (('corres', corres), ('reproj', reproj)) if v is not None}
+        pose-only loss terms into se3_grad there).  corres, reproj, featproj: see forward_backward."""
+        extra = {k: v for k, v in (('corres', corres), ('reproj', reproj), ('featproj', featproj)) if v is not None}
         out = self.forward_backward(ray_idx, jitter, global_step, pixels, image, depth_rand, fine, fine_grid, n_views, **extra)
         if before_step is not None:
             before_step()

@@ -732,6 +732,44 @@ def reproj_pose_fold(sc, own, pix, n_rows, intr, c2w, w2c, rays_o, rays_d, g_o, 
               _f(rays_o), _f(rays_d), _f(g_o), _f(g_d), _f(g_viewdirs), _f(g_t_min), _f(g_w2c), _f(g_c2w), _stream())
 
 
+# ------------------------------------------------------------------------------------------- object branch: surface-projection feature loss
+FEATPROJ_MAX_LAYERS = 4
+FEATPROJ_MAX_CHANNELS = 512
+
+
+def featproj_reproject(n_rows, view_j, rays_o, rays_d, t_min, acc, intr, w2c, nl, own_ref, pix_ref):
+    """Surface points of query A -> pix_ref [capacity,2], own_ref [capacity] int32: the rows of query B (pp_featproj_reproject)."""
+    cap, V = pix_ref.shape[0], w2c.shape[0]
+    _rows_at_least(n_rows, (rays_o, 3, 'rays_o'), (rays_d, 3, 'rays_d'), (t_min, 1, 't_min'), (acc, 1, 'acc'))
+    _rows_at_least(cap, (own_ref, 1, 'own_ref'), (pix_ref, 2, 'pix_ref'))
+    _rows_at_least(V, (intr, 4, 'intr'))
+    _lib.call('pp_featproj_reproject', int(n_rows), int(cap), int(view_j), _f(rays_o), _f(rays_d), _f(t_min), _f(acc), _f(intr),
+              _f(w2c), int(V), float(nl), _i(own_ref), _f(pix_ref), _stream())
+
+
+def featproj_loss(n_rows, view_i, view_j, rays_o, rays_d, t_min, acc, ref_rays_o, ref_rays_d, ref_t_min, ref_acc, intr, w2c, nl,
+                  voxel_size, H, W, layers, weight, scale, terms, valid, cosv, g_q, g_depth, g_o, g_d, g_w2c):
+    """See pp_featproj_loss (include/poseprobe_hip.h).  layers: up to four channels-last [V,h,w,C] fp32 maps.  The per-row outputs
+    define the capacity (g_o [capacity,3])."""
+    cap, V, L = g_o.shape[0], w2c.shape[0], len(layers)
+    if not 1 <= L <= FEATPROJ_MAX_LAYERS:
+        raise ValueError(f'{L} feature layers: need 1 to {FEATPROJ_MAX_LAYERS}')
+    for t in layers:
+        if t.dim() != 4 or t.shape[0] != V:
+            raise RuntimeError(f'a feature layer must be [n_views = {V}, h, w, C], got {tuple(t.shape)}')
+    _rows_at_least(n_rows, (rays_o, 3, 'rays_o'), (rays_d, 3, 'rays_d'), (t_min, 1, 't_min'), (acc, 1, 'acc'),
+                   (ref_rays_o, 3, 'ref_rays_o'), (ref_rays_d, 3, 'ref_rays_d'), (ref_t_min, 1, 'ref_t_min'), (ref_acc, 1, 'ref_acc'))
+    _rows_at_least(cap, (valid, 1, 'valid'), (cosv, L, 'cosv'), (g_q, 6, 'g_q'), (g_depth, 1, 'g_depth'), (g_d, 3, 'g_d'))
+    _rows_at_least(V, (intr, 4, 'intr'), (g_w2c, 12, 'g_w2c'))
+    _rows_at_least(2 + FEATPROJ_MAX_LAYERS, (terms, 1, 'terms'))
+    dims = (ctypes.c_int32 * (3 * L))(*[int(x) for t in layers for x in (t.shape[3], t.shape[1], t.shape[2])])
+    feats = [_f(t, 'feature layer') for t in layers] + [None] * (FEATPROJ_MAX_LAYERS - L)
+    _lib.call('pp_featproj_loss', int(n_rows), int(cap), int(view_i), int(view_j), _f(rays_o), _f(rays_d), _f(t_min), _f(acc),
+              _f(ref_rays_o), _f(ref_rays_d), _f(ref_t_min), _f(ref_acc), _f(intr), _f(w2c), int(V), float(nl), float(voxel_size),
+              int(H), int(W), L, *feats, ctypes.cast(dims, ctypes.c_void_p), float(weight), float(scale), _f(terms), _u8(valid),
+              _f(cosv), _f(g_q), _f(g_depth), _f(g_o), _f(g_d), _f(g_w2c), _stream())
+
+
 # ------------------------------------------------------------------------------------------- scene branch: ordered step
 def nerf_ordered_workspace():
     """Bytes of the workspace of the scene branch's ordered weight-gradient flush (pp_nerf_ordered_workspace): 512 slots of

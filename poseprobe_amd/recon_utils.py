@@ -4,8 +4,8 @@ optimised.  Pure torch on device tensors; the surface points themselves come fro
 (`Voxurf.query_sdf_point_wocuda_render` / `_wodeform`).
 
 Reference behaviour mirrored (not its code): lib/recon_scene.py:93-113 (get_ray_dir), :313-319 (point_to_ray_distance),
-:321-369 (get_project_error); lib/camera.py:251-253 (world2cam); lib/common.py:450-465 (project_to_cam_real);
-lib/losses.py:77-103 (compute_diff_loss).
+:321-369 (get_project_error), :371-439 (get_project_feature_loss); lib/camera.py:251-253 (world2cam); lib/common.py:76-109
+(get_tensor_values), :450-465 (project_to_cam_real), :468-492 (project_to_cam); lib/losses.py:77-103 (compute_diff_loss).
 """
 import numpy as np
 import torch
@@ -118,3 +118,58 @@ def get_project_error(model, Ks, HW, nl, global_step, current_pose, coord0, coor
         valid = valid & (dist.detach() <= pixel_thre)
     get_project_error.last_valid = valid            # diagnostics for callers / tests (how many matches took part)
     return compute_diff_loss('huber', dist, weights=conf, mask=valid, delta=1.), near_surface
+
+
+def project_to_cam(points, camera_mat, HW):
+    """Pinhole projection into normalised image coordinates (lib/common.py:468-492): x = 2 u / (W - 1) - 1, y = 2 v / (H - 1) - 1
+    with HW[0] = (H, W); also whether max(|x|, |y|) <= 1  -> [B,N,2], [B,N] bool."""
+    uv = project_to_cam_real(points, camera_mat)
+    H, W = float(np.asarray(HW)[0][0]), float(np.asarray(HW)[0][1])
+    xy = torch.stack([2 * uv[..., 0] / (W - 1) - 1, 2 * uv[..., 1] / (H - 1) - 1], -1)
+    return xy, xy.abs().max(dim=-1)[0] <= 1
+
+
+def get_project_feature_loss(model, Ks, HW, nl, global_step, current_pose, features, src, pix, i, j, inverse_y=True, flip_x=False,
+                             flip_y=False, use_deform=True, jitter=None, jitter_ref=None, **render_kwargs):
+    """Surface-based feature loss of one view pair (i, j) (lib/recon_scene.py:371-439 with len(i_list) == 1; lib/common.py:76-109,
+    :450-492), inverse_y without flips.
+
+    src [R] (long) and pix [R,2]: the rays of query A - view and pixel (x, y) each goes through (a pixel centre is x + 0.5,
+    y + 0.5).  The reference takes them from the first training view, whichever pair was drawn.  features: per layer a map
+    [V,C,h,w].  Every ray is lifted to its surface point p (expected depth of the full render), p is projected into view j and
+    rendered again from there (query B, no gradient); rows whose two surface points lie within two voxels of each other, which
+    both queries hit and which project into both images are valid.  Per layer the feature maps of views i and j are sampled
+    bilinearly at the two projections; the loss is sum_l (1 - mean over valid rows of their cosine similarity).
+    DEVIATION: without a valid row the reference takes the mean of an empty tensor (NaN); here the loss is 0 * sum(p) - zero,
+    with zero gradients.  jitter / jitter_ref [R]: the training-mode jitter of the two queries (None: drawn)."""
+    if not inverse_y or flip_x or flip_y:
+        raise NotImplementedError('get_project_feature_loss implements inverse_y=True without flips (the DTU setting)')
+    src = torch.as_tensor(src, device=current_pose.device).long()
+    rk = dict(render_kwargs, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y)
+    c2w = camera.pose.invert(current_pose)
+    o, d = get_ray_dir(pix[:, None], Ks[src], c2w[src], inverse_y, flip_x, flip_y, mode='no_center')
+    kw = {} if jitter is None else dict(jitter=jitter)
+    p, hit, _ = model.query_sdf_point_wocuda_render(o[:, 0], d[:, 0], global_step=global_step, use_deform=use_deform, keep_dim=True,
+                                                    **rk, **kw)
+
+    def cam(v):                                             # [1,R,3] camera-frame points with the near-plane replacement
+        q = world2cam(p[None], current_pose[v:v + 1])
+        return torch.where((q[..., 2:] < nl).expand_as(q), torch.full_like(q, float(nl)), q)
+    with torch.no_grad():
+        pix_ref = project_to_cam_real(cam(j), Ks[j:j + 1])
+        o_r, d_r = get_ray_dir(pix_ref, Ks[j:j + 1], c2w[j:j + 1], inverse_y, flip_x, flip_y, mode='no_center')
+        kw = {} if jitter_ref is None else dict(jitter=jitter_ref)
+        p_ref, hit_ref, _ = model.query_sdf_point_wocuda_render(o_r[0], d_r[0], global_step=global_step, use_deform=use_deform,
+                                                                keep_dim=True, **rk, **kw)
+        close = torch.linalg.norm(p - p_ref, dim=-1) < model.voxel_size * 2
+    views = [i, j]
+    xy, inside = project_to_cam(torch.cat([cam(i), cam(j)], 0), Ks[views], HW)
+    valid = inside[0] & inside[1] & close & hit_ref.bool() & hit.bool()
+    get_project_feature_loss.last_valid = valid
+    if not bool(valid.any()):
+        return p.sum() * 0.0
+    loss = 0.
+    for feat in features:
+        val = F.grid_sample(feat[views], xy[:, None], mode='bilinear', align_corners=True)[:, :, 0].permute(0, 2, 1)   # [2,R,C]
+        loss = loss + (1 - torch.cosine_similarity(val[0][valid], val[1][valid], dim=-1).mean())
+    return loss

@@ -142,6 +142,26 @@ def reproj_sample_size(n_matches, reproj_rows):
     return min(int(n_matches), int(reproj_rows) // 2)
 
 
+def surface_projection_active(global_step, max_iter, ratio_end_pose, n_iters_object, start_object=0):
+    """The surface-projection feature term joins the object loss while the object branch is optimised AND poses are
+    (`weight_surface_projection > 0 and IsOptimizePose` inside `if optimize_object_nerf`, lib/recon_scene.py:594, :610)."""
+    return object_phase(global_step, n_iters_object, start_object) and pose_phase(global_step, max_iter, ratio_end_pose)
+
+
+def surface_projection_pair(rng, pairs, n_active):
+    """One (i, j) of `pairs` whose views are both among the first n_active, drawn from the numpy RandomState `rng`
+    (lib/recon_scene.py:611-612 draws an index into the pair table); None - and no draw - while no pair is live."""
+    live = [(int(i), int(j)) for i, j in pairs if i < n_active and j < n_active]
+    if not live:
+        return None
+    return live[rng.randint(len(live))]
+
+
+def surface_projection_sample_size(n_rays, H, W):
+    """Rays of a step of the term: min(256, H W) in the reference (lib/recon_scene.py:372)."""
+    return min(int(n_rays), int(H) * int(W))
+
+
 class ReprojectionTerm:
     """The reprojection + near-surface pose terms of the live loop (lib/recon_scene.py:624-637) as a `pose_terms` entry of
     DualBranchTrainer: one matched view pair is drawn per step among the ACTIVE views, every matched pixel is lifted to the
@@ -192,7 +212,7 @@ class ReprojectionTerm:
 class DualBranchTrainer:
     def __init__(self, obj_engine, opt, max_iter=60000, lr=1e-3, lr_end=1e-4, ratio_start_fine=0.3, ratio_end_pose=0.3,
                  depth_range=(0.5, 3.0), seed=0, incremental_step=0, pose_initialiser=None, pose_terms=(), scene_matches=None,
-                 deterministic=False, reprojection=None):
+                 deterministic=False, reprojection=None, surface_projection=None):
         """incremental_step > 0: the incremental view schedule (`active_views`); a view that joins gets its initial pose from
         `pose_initialiser(view, w2c_of_previous_view [3,4]) -> w2c [3,4]` - the reference's PnP hand-off (cv2.solvePnPRansac on
         matcher output, lib/recon_scene.py:202-214, :276-310) plugs in here: `pnp.PnPInitialiser` is its counterpart on the HIP
@@ -216,7 +236,16 @@ class DualBranchTrainer:
         capacity: matches beyond reproj_rows // 2 are subsampled on the device, a fresh subset every step - a DEVIATION from
         the reference, which uses every match.  The capacity costs one second render workspace: about 18 KB per sample, i.e.
         18 KB * n_samples per row (160^3 voxels, 186 samples: 3.4 MB per row, 1024 rows = 512 matches: 3.5 GB).  The same term
-        may not also be given as a ReprojectionTerm in pose_terms (ValueError: it would be counted twice)."""
+        may not also be given as a ReprojectionTerm in pose_terms (ValueError: it would be counted twice).
+        surface_projection: dict(features, pairs, weight, nl, n_rays=256, seed=0) - the surface-based feature term of the object
+        loss (lib/recon_scene.py:371-439, :610-619; configs/dtu_e2e: weight_surface_projection = 1e-3) inside the engine's own
+        launches (TrainEngine.surface_projection_grads).  features: the per-view feature maps, a list of [V,C,h,w] (the reference's
+        VGG features - an input here, as the matcher's output is); pairs: the (i, j) view pairs.  Per step one pair among the active
+        views is drawn from RandomState(seed) and min(n_rays, H W) pixels of view 0 - the reference always shoots from the first
+        training view - on the device; active only while `surface_projection_active` holds (optional keys n_iters_object -
+        default: the engine's cfg.N_iters - and start_object = 0).  obj_engine must have been built with featproj_rows >=
+        min(n_rays, H W); the capacity costs 18.4 KB * n_samples per row (TrainEngine).  last_featproj records the pair and the row
+        count of the step, or None."""
         self.opt, self.max_iter = opt, max_iter
         self.terms = loss_terms(getattr(opt, 'loss_type', None))
         self.photo_weight = loss_weight(opt, 'photometric') if 'loss_type' in opt else 1.0
@@ -250,6 +279,21 @@ class DualBranchTrainer:
             r['rng'] = np.random.RandomState(r['seed'])
             self.reprojection = r
         self.last_reproj = None
+        self.surface_projection = None
+        if surface_projection is not None:
+            if deterministic or getattr(obj_engine, 'deterministic', False):
+                raise ValueError('surface_projection= is out of the scope of deterministic=True (its render backward keeps float atomics)')
+            r = dict(n_rays=256, seed=0, n_iters_object=obj_engine.cfg.N_iters, start_object=0)
+            r.update(surface_projection)
+            r['n'] = surface_projection_sample_size(r['n_rays'], obj_engine.H, obj_engine.W)
+            if getattr(obj_engine, 'featproj_rows', 0) < r['n']:
+                raise ValueError(f"surface_projection= needs an object engine built with featproj_rows >= {r['n']}")
+            obj_engine.set_feature_maps(r.pop('features'))
+            r['pairs'] = [(int(i), int(j)) for i, j in r['pairs']]
+            r['rng'] = np.random.RandomState(r['seed'])
+            r['gen'] = torch.Generator(device=obj_engine.dev).manual_seed(r['seed'])
+            self.surface_projection = r
+        self.last_featproj = None
         self.lr, self.lr_end = lr, lr_end
         self.ratio_start_fine, self.ratio_end_pose = ratio_start_fine, ratio_end_pose
         dev = obj_engine.dev
@@ -343,6 +387,23 @@ class DualBranchTrainer:
         return dict(rows=rows, mode=self.last_reproj['mode'], weight_projection=r['weight_projection'],
                     weight_near_surface=r['weight_near_surface'], nl=r['nl'], pixel_thre=r['pixel_thre'])
 
+    def _featproj_batch(self, global_step, k):
+        """The surface-projection rows of this step, or None: one live pair drawn on the host, the pixels of view 0 on the device
+        (through their centres).  Shapes depend on host values only."""
+        r = self.surface_projection
+        if r is None or not surface_projection_active(global_step, self.max_iter, self.ratio_end_pose, r['n_iters_object'],
+                                                      r['start_object']):
+            return None
+        pair = surface_projection_pair(r['rng'], r['pairs'], k)
+        if pair is None:
+            return None
+        e, n = self.joint.obj, r['n']
+        flat = torch.randperm(e.H * e.W, device=self.dev, generator=r['gen'])[:n]
+        pix = torch.stack([(flat % e.W).float() + 0.5, (flat // e.W).float() + 0.5], dim=-1).contiguous()
+        rows = dict(src=torch.zeros(n, dtype=torch.int32, device=self.dev), pix=pix, own=pair[0], other=pair[1])
+        self.last_featproj = dict(pair=pair, n_rows=n)
+        return dict(rows=rows, weight=r['weight'], nl=r['nl'])
+
     def _mix_pose_terms(self, k):
         """loss += w_i * L_i(poses) for the extra pose-only terms: their se3 gradient joins the object branch's (which the
         engine scales by loss_scale = 0.1, lib/recon_scene.py:648)."""
@@ -373,6 +434,10 @@ class DualBranchTrainer:
         self.last_reproj = None
         reproj = self._reproj_batch(global_step, k)
         extra = {} if reproj is None else {'reproj': reproj}
+        self.last_featproj = None
+        featproj = self._featproj_batch(global_step, k)
+        if featproj is not None:
+            extra['featproj'] = featproj
         out = self.joint.train_step(ray_idx, jitter, global_step, pixels, image, fine=fine,
                                     optimize_pose=pose_phase(global_step, self.max_iter, self.ratio_end_pose), n_views=k,
                                     before_step=(lambda: self.last_pose_terms.update(self._mix_pose_terms(k))) if self.pose_terms else None,
