@@ -82,6 +82,8 @@ def se3_to_SE3(wu):
 
 
 def pose_from(R, t):
+    if R.dtype == t.dtype == torch.float64:      # the float64 yardstick of the pose kernels (tests/ray_reference.py) stays float64
+        return torch.cat([R, t[..., None]], dim=-1)
     return torch.cat([R.float(), t.float()[..., None]], dim=-1)
 
 

@@ -71,6 +71,30 @@ def assert_close(a, b, rtol=1e-5, atol=1e-6, name='', scaled=0.0):
                            f'max |ref| {np.abs(b).max():.3e}')
 
 
+EPS = float(np.finfo(np.float32).eps)
+
+
+def cu(x, dtype=torch.float32):
+    return torch.as_tensor(np.asarray(x)).to('cuda', dtype).contiguous()
+
+
+def npf(x):
+    return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
+
+
+def check(name, hip, r64, r32, scale, ulps=8):
+    """|hip - ref64| <= 2 |ref32 - ref64| + ulps * eps32 * scale (scale broadcast against the values)."""
+    hip, r64, r32 = npf(hip), npf(r64), npf(r32)
+    assert hip.shape == r64.shape == r32.shape, f'{name}: shapes {hip.shape} {r64.shape} {r32.shape}'
+    err = np.abs(hip - r64)
+    bound = 2 * np.abs(r32 - r64) + ulps * EPS * np.broadcast_to(npf(scale), r64.shape)
+    bad = ~(err <= bound)
+    if bad.any():
+        i = np.unravel_index(np.argmax(np.where(bad, err / np.maximum(bound, 1e-300), 0)), err.shape)
+        raise AssertionError(f'{name}: {bad.sum()}/{err.size} beyond the bound; worst at {i}: hip {hip[i]:.9g} ref64 '
+                             f'{r64[i]:.9g} ref32 {r32[i]:.9g} bound {bound[i]:.3g}')
+
+
 def assert_mostly_close(a, b, rtol, scaled, name='', outlier_frac=0.03, outlier_scaled=3e-2):
     """For gradients of ReLU networks compared across two fp32 implementations: a pre-activation that lies within rounding
     distance of zero flips its mask in one of them and changes that sample's contribution discretely (a handful of the ~1e7

@@ -1,5 +1,6 @@
 """GPU parity tests, kernel level: every test calls the HIP path through the C ABI (poseprobe_amd.ops) and checks
-it against the oracle (CPU restatement) or the golden vectors produced by the reference."""
+it against the oracle (CPU restatement) or the golden vectors produced by the reference.
+Seeded edge cases of the pose, ray, sampler and loss kernels beyond these fixtures: tests/test_hip_ray_kernels.py."""
 import numpy as np
 import pytest
 import torch

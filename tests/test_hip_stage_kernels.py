@@ -13,34 +13,13 @@ import pytest
 import torch
 
 from tests import stage_reference as SR
+from tests.helpers import EPS, check, cu, npf  # noqa: F401  (EPS: imported from here by other test modules)
 
 pytestmark = pytest.mark.gpu
 
-EPS = float(np.finfo(np.float32).eps)
 SENT = 1234.5
 XYZ_MIN = np.array([-0.6, -0.55, -0.7], np.float32)
 XYZ_MAX = np.array([0.6, 0.5, 0.45], np.float32)
-
-
-def cu(x, dtype=torch.float32):
-    return torch.as_tensor(np.asarray(x)).to('cuda', dtype).contiguous()
-
-
-def npf(x):
-    return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
-
-
-def check(name, hip, r64, r32, scale, ulps=8):
-    """|hip - ref64| <= 2 |ref32 - ref64| + ulps * eps32 * scale (scale broadcast against the values)."""
-    hip, r64, r32 = npf(hip), npf(r64), npf(r32)
-    assert hip.shape == r64.shape == r32.shape, f'{name}: shapes {hip.shape} {r64.shape} {r32.shape}'
-    err = np.abs(hip - r64)
-    bound = 2 * np.abs(r32 - r64) + ulps * EPS * np.broadcast_to(npf(scale), r64.shape)
-    bad = ~(err <= bound)
-    if bad.any():
-        i = np.unravel_index(np.argmax(np.where(bad, err / np.maximum(bound, 1e-300), 0)), err.shape)
-        raise AssertionError(f'{name}: {bad.sum()}/{err.size} beyond the bound; worst at {i}: hip {hip[i]:.9g} ref64 '
-                             f'{r64[i]:.9g} ref32 {r32[i]:.9g} bound {bound[i]:.3g}')
 
 
 def rowmax(*xs):
