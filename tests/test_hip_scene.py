@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from tests.helpers import assert_close, assert_mostly_close, load
+from tests.scene_mlp_reference import mask_pack_cols, mask_states_cols, mask_states_rows  # noqa: F401  (the two mask-plane layouts)
 
 pytestmark = pytest.mark.gpu
 
@@ -711,33 +712,6 @@ def test_scene_kernels_stay_inside_their_buffers(nerf_split):
         torch.cuda.empty_cache()
 
 
-def mask_states_rows(b, M):
-    """One mask plane of the fused chains' layout (int32 view: [row][column block][lane half] 16-bit words, bit j <-> column
-    32 block + 4 half + (j & 3) + 8 (j >> 2)) -> [M, 256] bool."""
-    Mp, dev = (M + 127) // 128 * 128, b.device
-    wds = torch.stack([b & 0xFFFF, (b >> 16) & 0xFFFF], -1).view(Mp, 8, 2)                   # [row][w][half]
-    j = torch.arange(16, device=dev)
-    bits = ((wds[..., None] >> j) & 1).bool()                                                  # [row, w, half, j]
-    col = (32 * torch.arange(8, device=dev)[:, None, None] + 4 * torch.arange(2, device=dev)[None, :, None]
-           + ((j & 3) + 8 * (j >> 2))[None, None, :]).reshape(-1)
-    out = torch.zeros(Mp, 256, dtype=torch.bool, device=dev)
-    out[:, col] = bits.reshape(Mp, 256)
-    return out[:M]
-
-
-def mask_pack_cols(st):
-    """[M, 256] bool -> one mask plane of the layer-by-layer layout, as int64 values of its 32-bit words [row group of 32][column]."""
-    M, dev = st.shape[0], st.device
-    Mp = (M + 127) // 128 * 128
-    full = torch.zeros(Mp, 256, dtype=torch.bool, device=dev)
-    full[:M] = st
-    j = torch.arange(16, device=dev)
-    rows = ((j & 3) + 8 * (j >> 2))[None, :] + 4 * torch.arange(2, device=dev)[:, None]          # [half, j]
-    x = full.view(Mp // 32, 32, 256)[:, rows.reshape(-1), :].view(Mp // 32, 2, 16, 256)          # [g, half, j, col]
-    wds = (x.to(torch.int64) << j[None, None, :, None]).sum(2)                                    # [g, half, col]
-    return (wds[:, 0] | (wds[:, 1] << 16)).to(torch.int64).view(-1)                              # [g * 256 + col]
-
-
 def repack_masks_for_the_layer_by_layer_backward(acts, M):
     """Copy of a fused forward's activation block (nerf_chain = 3) with its eight mask planes re-packed into the layout the
     layer-by-layer data-gradient kernels read: the same ReLU states, so both backward routes can run on one forward state."""
@@ -808,16 +782,7 @@ def test_scene_trunk_kernel_equals_layer_by_layer_path(R, S):
         b1 = a1[off:off + Mp * 8].view(torch.int32)
         b0 = a0[off:off + Mp * 8].view(torch.int32)
         off += Mp * 8
-        # unpack: word [row group of 32][column][half] (16 bits), bit j <-> row 32 g + (j & 3) + 8 (j >> 2) + 4 half
-        def states(b):
-            wds = torch.stack([b & 0xFFFF, (b >> 16) & 0xFFFF], -1).view(Mp // 32, 256, 2)
-            j = torch.arange(16, device=dev)
-            bits = ((wds[..., None] >> j) & 1).bool()                 # [g, col, half, j]
-            rows = ((j & 3) + 8 * (j >> 2))[None, :] + 4 * torch.arange(2, device=dev)[:, None]      # [half, j]
-            out = torch.zeros(Mp // 32, 32, 256, dtype=torch.bool, device=dev)
-            out[:, rows.reshape(-1), :] = bits.permute(0, 2, 3, 1).reshape(Mp // 32, 32, 256)
-            return out.view(Mp, 256)[:M]
-        s1, s0 = mask_states_rows(b1, M), states(b0)
+        s1, s0 = mask_states_rows(b1, M), mask_states_cols(b0, M)
         x1, x0 = acts_l[l]
         assert torch.equal(s1, x1 > 0), f'layer {l}: mask bits of the fused kernel are not the states of its own activations'
         assert torch.equal(s0, x0 > 0)
