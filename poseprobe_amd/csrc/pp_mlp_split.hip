@@ -183,8 +183,8 @@ typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 
 // Epilogue of one 32-row half, lane = row, registers = features fb + 8 q + c, as EIGHT batched steps so that it can be issued
 // between the MFMAs of another half (step i after operand group i).  y = acc * inv + bias; COLS == 4: `bias` is zero in the
-// tangent lanes and the sign of the primal lane's pre-activation gates the whole quad (y == +0 counts as open: rows that are
-// exactly zero have zero tangents as well); fp32 copy to HBM for the backward pass (rows with `ok`), next tile to LDS as a split
+// tangent lanes and the primal lane's pre-activation gates the whole quad by the sign of 0 - y, which is set for y > 0 alone: +0 and
+// -0 close the gate as in every other kernel (stored activation > 0); fp32 copy to HBM for the backward pass (rows with `ok`), next tile to LDS as a split
 // image scaled by snext (SPLIT) or as the fp32 view.
 // Every step is a batch over all 16 elements with no instruction depending on its predecessor: a lone wavefront per SIMD has
 // nothing else to issue while a VALU result matures (DPP needs two wait states after the write of its source, v_cndmask one
@@ -217,14 +217,14 @@ struct HalfEpilogue {
       if (COLS == 4) {
 #pragma unroll
         for (int e = 0; e < 16; ++e)
-          asm("v_mov_b32_dpp %0, %1 quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(p[e]) : "v"(y[e]));
+          asm("v_subrev_f32_dpp %0, %1, %2 quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(p[e]) : "v"(y[e]), "v"(0.f));
 #pragma unroll
-        for (int e = 0; e < 16; ++e) asm("v_ashrrev_i32 %0, 31, %1" : "=v"(p[e]) : "v"(p[e]));      // all ones where the primal row is negative
+        for (int e = 0; e < 16; ++e) asm("v_ashrrev_i32 %0, 31, %1" : "=v"(p[e]) : "v"(p[e]));      // all ones where the primal row is > 0
       }
     } else if (i == 2) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        if (COLS == 4) asm("v_bfi_b32 %0, %1, 0, %2" : "=v"(y[e]) : "v"(p[e]), "v"(y[e]));          // y & ~mask
+        if (COLS == 4) asm("v_and_b32 %0, %1, %2" : "=v"(y[e]) : "v"(p[e]), "v"(y[e]));             // y & mask
         else y[e] = fmaxf(y[e], 0.f);
       }
     } else if (SPLIT && i == 3) {
@@ -406,8 +406,26 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
     layer0(1, acc1);
     const float inv0 = pow2(-(ein + ew0)), ninv0 = pow2(-e0);
     HalfEpilogue<4, true> ea;          // epilogue state of the half that is being written out
+    // full form: the stored tangent rows of X0 are the weights themselves, gate0 ? W0[n][i] : 0 - what the lean rebuild and the
+    // other routes use - not the (hi + lo) / s that the product returns (up to 1 ulp off); the LDS image stays as it is.  Behind
+    // the epilogue's own store of the same lane to the same addresses.
+    auto exact_tangents = [&](bool ok, float* __restrict__ row) {
+      if (LEAN) return;
+      float v[16];
+      const int ti = primal ? 0 : (l31 & 3) - 1;          // tangent direction of this lane's row
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const bool open = __shfl(ea.y[e], lane & ~3, 64) > 0.f;
+        v[e] = open ? params[WPF_W0 + (fb + 8 * (e >> 2) + (e & 3)) * 3 + ti] : 0.f;
+      }
+      if (ok && !primal) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(row + 8 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+      }
+    };
     ea.begin(brow(3));
     ea.all(acc0, inv0, sc0, ok0 && (!LEAN || primal), crow, arow0);
+    exact_tangents(ok0, crow);
     slot_max(&Mx[par][0], ea.vmax(ninv0), lane);
     __syncthreads();
     if (tid < 8) Mx[par ^ 1][tid] = 0u;                   // the next tile's slots (last read a tile ago)
@@ -415,6 +433,7 @@ __global__ __launch_bounds__(256) void k_warp_fused_fwd_s(const float* __restric
     zero16(acc0);
     ea.begin(brow(3));
     mma_half(&At[0][0], w1, acc0, l31, lh, [&](int ks) { ea.step(ks, acc1, inv0, sc0, ok1 && (!LEAN || primal), crow + 32 * 128, arow0 + 32 * LDH2); });
+    exact_tangents(ok1, crow + 32 * 128);
     slot_max(&Mx[par][1], ea.vmax(ninv0), lane);
     park(par ^ 1, pnext);                                  // next tile's positions (read after >= 3 barriers)
     __syncthreads();

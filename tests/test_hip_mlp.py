@@ -4,6 +4,7 @@ of / exactly / one past a 16-sample (warp) and 64-row (rgbnet) tile, a capacity 
 enough tiles for several persistent iterations per work-group.
 
 Tolerances (fp32, different summation order than torch): values rtol 1e-4 / atol 1e-5; gradients 1e-3 of the tensor's max.
+Every stage of both chains against float64 on its own stored inputs, with no row excused: tests/test_hip_object_mlp_kernels.py.
 """
 import numpy as np
 import pytest
