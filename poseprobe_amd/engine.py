@@ -588,18 +588,23 @@ class TrainEngine:
         if self.featproj_rows > 0:
             self._alloc_featproj()
 
-    def _alloc_reproj(self):
-        """Buffers of reprojection_grads: a workspace of its own (the main pass's activations stay untouched) and the per-row
-        gradients.  The ray-level colour gradients of that workspace are zero for good: the pass has a depth-only loss."""
-        R, S, cfg = self.reproj_rows, self.cfg.n_samples, self.cfg
-        f = dict(dtype=torch.float32, device=self.dev)
-        ws = self.ws_reproj = Workspace(R, R * S, self.dev, ctx=self.ctx)
+    def _alloc_aux(self, R):
+        """What each auxiliary pass (reprojection_grads, surface_projection_grads) owns: a workspace of its own for R rays (the main
+        pass's activations stay untouched) whose ray-level colour gradients are zero for good - the passes have depth-only losses -,
+        and the per-row and per-view gradient buffers of their common backward (_depth_loss_pass, _pose_fold)."""
+        ws = Workspace(R, R * self.cfg.n_samples, self.dev, ctx=self.ctx)
         for t in (ws.g_rgbm, ws.g_last, ws.g_cw):
             t.zero_()
-        z = lambda *shape: torch.zeros(*shape, **f)
-        self._rp = dict(g_p=z(R, 3), g_depth=z(R), g_o=z(R, 3), g_d=z(R, 3), go=z(R, 3), gd=z(R, 3), gv=z(R, 3), g_t=z(R),
-                        p=z(R, 3), hit=torch.zeros(R, dtype=torch.uint8, device=self.dev), terms=z(3),
-                        g_w2c=z(self.V, 3, 4), g_c2w=z(self.V, 3, 4), se3=z(self.V, 6))
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=self.dev)
+        return ws, dict(g_depth=z(R), g_o=z(R, 3), g_d=z(R, 3), go=z(R, 3), gd=z(R, 3), gv=z(R, 3), g_w2c=z(self.V, 3, 4),
+                        g_c2w=z(self.V, 3, 4), se3=z(self.V, 6))
+
+    def _alloc_reproj(self):
+        """Buffers of reprojection_grads: _alloc_aux and what pp_reproj_loss and the crossing query write per row."""
+        R, cfg = self.reproj_rows, self.cfg
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=self.dev)
+        self.ws_reproj, self._rp = self._alloc_aux(R)
+        self._rp.update(g_p=z(R, 3), g_t=z(R), p=z(R, 3), hit=torch.zeros(R, dtype=torch.uint8, device=self.dev), terms=z(3))
         # the reference's "centre" and diagonal (lib/recon_scene.py:344, lib/voxurf_coarse.py:102; both sic), in its fp32 arithmetic
         lo, hi = (torch.tensor(np.asarray(a, dtype=np.float32)) for a in (cfg.xyz_min, cfg.xyz_max))
         self._rp_centre = [float(x) for x in (lo + hi)]
@@ -609,19 +614,14 @@ class TrainEngine:
             raise ValueError('reproj_rows > 0: Voxurf.diagonal_length is not finite for this box (sum(xyz_max - xyz_min ** 2) < 0)')
 
     def _alloc_featproj(self):
-        """Buffers of surface_projection_grads: a full workspace for query A (depth-only loss: its ray-level colour gradients are
-        zero for good), a forward-only one for query B, and the per-row buffers of the pp_featproj_* kernels."""
-        R, S = self.featproj_rows, self.cfg.n_samples
-        f = dict(dtype=torch.float32, device=self.dev)
-        ws = self.ws_featproj = Workspace(R, R * S, self.dev, ctx=self.ctx)
-        for t in (ws.g_rgbm, ws.g_last, ws.g_cw):
-            t.zero_()
-        self.ws_featproj_ref = Workspace(R, R * S, self.dev, backward=False, keep_activations=False, ctx=self.ctx)
-        z = lambda *shape: torch.zeros(*shape, **f)
-        self._fp = dict(own_ref=torch.zeros(R, dtype=torch.int32, device=self.dev), pix_ref=z(R, 2), terms=z(2 + ops.FEATPROJ_MAX_LAYERS),
-                        valid=torch.zeros(R, dtype=torch.uint8, device=self.dev), cos=z(ops.FEATPROJ_MAX_LAYERS, R), g_q=z(R, 6),
-                        g_depth=z(R), g_o=z(R, 3), g_d=z(R, 3), go=z(R, 3), gd=z(R, 3), gv=z(R, 3), g_w2c=z(self.V, 3, 4),
-                        g_c2w=z(self.V, 3, 4), se3=z(self.V, 6))
+        """Buffers of surface_projection_grads: _alloc_aux for query A, a forward-only workspace for query B, and the per-row buffers
+        of the pp_featproj_* kernels."""
+        R = self.featproj_rows
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=self.dev)
+        self.ws_featproj, self._fp = self._alloc_aux(R)
+        self.ws_featproj_ref = Workspace(R, R * self.cfg.n_samples, self.dev, backward=False, keep_activations=False, ctx=self.ctx)
+        self._fp.update(own_ref=torch.zeros(R, dtype=torch.int32, device=self.dev), pix_ref=z(R, 2), terms=z(2 + ops.FEATPROJ_MAX_LAYERS),
+                        valid=torch.zeros(R, dtype=torch.uint8, device=self.dev), cos=z(ops.FEATPROJ_MAX_LAYERS, R), g_q=z(R, 6))
 
     # ---- data / parameter loading ---------------------------------------------------------------------------
     def set_feature_maps(self, features):
@@ -789,6 +789,50 @@ class TrainEngine:
                 ops.pose_bwd(self.jac, self.c2w_grad, self.se3_grad)
         return s_val, w_dyn
 
+    # ---- the auxiliary passes: a second ray batch through the object branch's kernels, on buffers of its own (_alloc_aux) ----------
+    def _refuse_aux(self, name, ws, method, capacity):
+        """What neither auxiliary pass does.  name: the pass in the messages' words; ws: its workspace, None without `capacity`."""
+        if ws is None:
+            raise ValueError(f'{method} needs an engine built with {capacity} > 0')
+        if self.deterministic:
+            raise ValueError(f'the {name} pass is out of the scope of deterministic=True: its render backward uses the separate '
+                             'geometry backward, which keeps float atomics')
+        if self.dist is not None:
+            raise NotImplementedError(f'the {name} pass is not sharded across ranks')
+        if not self.cfg.inverse_y:
+            raise NotImplementedError(f'the {name} pass implements inverse_y=True without flips (the DTU setting)')
+
+    def _row_jitter(self, jitter, cap):
+        """Training-mode per-ray jitter over a pass's whole capacity.  None: drawn on the device; shorter: zero-padded (the rows past
+        the caller's are rays that miss the box: any jitter will do)."""
+        if jitter is None:
+            return torch.rand(cap, device=self.dev)
+        return jitter if jitter.shape[0] >= cap else torch.cat([jitter, jitter.new_zeros(cap - jitter.shape[0])])
+
+    def _depth_loss_pass(self, ws, b, view, pix, n, global_step, loss):
+        """The sampled rays of `ws` rendered and differentiated for a loss on their depth, then folded into the pose: a weight pack and
+        a lean scope of the pass's own, on its own buffers (render_and_grads closed its ones); forward; loss(par) - it leaves the
+        loss's gradients in b['g_depth'] (depth), b['g_o'] / b['g_d'] (ray, direct) and b['g_w2c'] -; backward; ray backward; _pose_fold."""
+        P = self.flat
+        par = (self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), self.cfg.inv_s(global_step), self.pe_w)
+        with self.core.pass_scope(P, self.mlp_pack, ws):
+            self.core.forward(ws, *par)
+            loss(par)
+            # depth-only loss: ws.g_rgbm / g_last / g_cw stay zero; no colour-grid gradient is requested (k0_grad = None, no scatter)
+            self.core.backward(ws, *par, None, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
+                               g_depth=b['g_depth'])
+            ops.raygen_select_bwd(self.cfg.pp, None, None, None, 0, 0, True, ws.rays_o, ws.rays_d, ws.t_min, ws.ray_start, ws.g_pts,
+                                  ws.step, ws.g_view_s, b['g_o'], b['g_d'], None, b['g_depth'], b['go'], b['gd'], b['gv'], None)
+        self._pose_fold(ws, b, view, pix, n, b['gv'], None)
+
+    def _pose_fold(self, ws, b, view, pix, n, g_v, g_t):
+        """Ray gradients b['go'] / b['gd'] (+ g_v on viewdirs, g_t on t_min; None: none) of the rows' views and the loss's direct
+        b['g_w2c'] -> c2w -> through the step's Jacobian, ADDED to se3_grad."""
+        ops.reproj_pose_fold(self.cfg.pp, view, pix, n, self.intr, self.c2w, self.w2c, ws.rays_o, ws.rays_d, b['go'], b['gd'], g_v, g_t,
+                             b['g_w2c'], b['g_c2w'])
+        ops.pose_bwd(self.jac, b['g_c2w'], b['se3'])
+        self.se3_grad += b['se3']
+
     def reprojection_grads(self, rows, mode, global_step, jitter=None, weight_projection=1.0, weight_near_surface=1.0, nl=0.0,
                            pixel_thre=None, scale=None):
         """Reprojection + near-surface terms of matched pixels (recon_utils.get_project_error; lib/recon_scene.py:321-369, :621-637)
@@ -803,47 +847,23 @@ class TrainEngine:
         while at most two views are active) - or 'render' - expected ray depth of the full render
         (query_sdf_point_wocuda_render).  jitter [R] (training-mode per-ray jitter); None: drawn on the device.
         scale: None = the engine's loss_scale.  Leaves last_reproj_terms = dict(err, near, n_valid) as device tensors."""
-        if self.ws_reproj is None:
-            raise ValueError('reprojection_grads needs an engine built with reproj_rows > 0')
-        if self.deterministic:
-            raise ValueError('the reprojection pass is out of the scope of deterministic=True: its render backward uses the separate '
-                             'geometry backward, which keeps float atomics')
-        if self.dist is not None:
-            raise NotImplementedError('the reprojection pass is not sharded across ranks')
-        if not self.cfg.inverse_y:
-            raise NotImplementedError('the reprojection pass implements inverse_y=True without flips (the DTU setting)')
+        self._refuse_aux('reprojection', self.ws_reproj, 'reprojection_grads', 'reproj_rows')
         if mode not in ('crossing', 'render'):
             raise ValueError(f"mode must be 'crossing' or 'render', got {mode!r}")
-        cfg, ws, sc, rp, P = self.cfg, self.ws_reproj, self.cfg.pp, self._rp, self.flat
+        cfg, ws, sc, rp, cap = self.cfg, self.ws_reproj, self.cfg.pp, self._rp, self.reproj_rows
         R = rows['own'].shape[0]
         n = int(rows.get('n_rows', R))
-        if not 0 < n <= R <= self.reproj_rows:
-            raise ValueError(f'{n} of {R} rows with reproj_rows = {self.reproj_rows}')
-        cap = self.reproj_rows
-        if jitter is None:
-            jitter = torch.rand(cap, device=self.dev)
-        elif jitter.shape[0] < cap:                               # rows past R are rays that miss the box: any jitter will do
-            jitter = torch.cat([jitter, jitter.new_zeros(cap - jitter.shape[0])])
-        render = mode == 'render'
+        if not 0 < n <= R <= cap:
+            raise ValueError(f'{n} of {R} rows with reproj_rows = {cap}')
+        jitter = self._row_jitter(jitter, cap)
         scale = self.loss_scale if scale is None else scale
         ops.reproj_rays(sc, rows['own'], rows['pix'], n, self.intr, self.c2w, ws.rays_o, ws.rays_d, ws.viewdirs)
         self.core.sample(ws, jitter)
         loss_args = (self.intr, self.w2c, self._rp_centre, self._rp_half_diag, nl, pixel_thre, weight_near_surface,
                      weight_projection, scale, rp['terms'], rp['g_p'], rp['g_depth'], rp['g_o'], rp['g_d'], rp['g_w2c'])
-        if render:
-            par = (self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), cfg.inv_s(global_step), self.pe_w)
-            # a weight pack and a lean scope of this pass's own, on its own buffers (render_and_grads closed its ones)
-            with self.core.pass_scope(P, self.mlp_pack, ws):
-                self.core.forward(ws, *par)
-                ops.reproj_loss(True, n, rows['other'], rows['match'], rows['conf'], ws.rays_o, ws.rays_d, None, None, ws.t_min,
-                                ws.depth_acc, *loss_args)
-                # depth-only loss: ws.g_rgbm / g_last / g_cw stay zero; no colour-grid gradient is requested (k0_grad = None, no scatter)
-                self.core.backward(ws, *par, None, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
-                                   g_depth=rp['g_depth'])
-                ops.raygen_select_bwd(sc, None, None, None, 0, 0, True, ws.rays_o, ws.rays_d, ws.t_min, ws.ray_start, ws.g_pts,
-                                      ws.step, ws.g_view_s, rp['g_o'], rp['g_d'], None, rp['g_depth'], rp['go'], rp['gd'], rp['gv'],
-                                      None)
-            g_o, g_d, g_v, g_t = rp['go'], rp['gd'], rp['gv'], None
+        if mode == 'render':
+            self._depth_loss_pass(ws, rp, rows['own'], rows['pix'], n, global_step, lambda par: ops.reproj_loss(
+                True, n, rows['other'], rows['match'], rows['conf'], ws.rays_o, ws.rays_d, None, None, ws.t_min, ws.depth_acc, *loss_args))
         else:
             S = cfg.n_samples
             dist = cfg.step_dist
@@ -857,11 +877,7 @@ class TrainEngine:
                                        rp['go'], rp['gd'], rp['g_t'])
             rp['go'].add_(rp['g_o'])
             rp['gd'].add_(rp['g_d'])
-            g_o, g_d, g_v, g_t = rp['go'], rp['gd'], None, rp['g_t']
-        ops.reproj_pose_fold(sc, rows['own'], rows['pix'], n, self.intr, self.c2w, self.w2c, ws.rays_o, ws.rays_d, g_o, g_d, g_v,
-                             g_t, rp['g_w2c'], rp['g_c2w'])
-        ops.pose_bwd(self.jac, rp['g_c2w'], rp['se3'])
-        self.se3_grad += rp['se3']
+            self._pose_fold(ws, rp, rows['own'], rows['pix'], n, None, rp['g_t'])
         t = rp['terms']
         self.last_reproj_terms = dict(err=t[0], near=t[1], n_valid=t[2])
         return self.last_reproj_terms
@@ -881,39 +897,23 @@ class TrainEngine:
         scale: None = the engine's loss_scale.  Leaves last_featproj_terms = dict(loss, n_valid, cos [n_layers]: the per-layer
         sums of cos over the valid rows) as device tensors.  Without a valid row the term and its gradients are exactly 0 (the
         reference: NaN)."""
-        if self.ws_featproj is None:
-            raise ValueError('surface_projection_grads needs an engine built with featproj_rows > 0')
-        if self.deterministic:
-            raise ValueError('the surface-projection pass is out of the scope of deterministic=True: its render backward uses the '
-                             'separate geometry backward, which keeps float atomics')
-        if self.dist is not None:
-            raise NotImplementedError('the surface-projection pass is not sharded across ranks')
-        if not self.cfg.inverse_y:
-            raise NotImplementedError('the surface-projection pass implements inverse_y=True without flips (the DTU setting)')
+        self._refuse_aux('surface-projection', self.ws_featproj, 'surface_projection_grads', 'featproj_rows')
         if self.feature_maps is None:
             raise ValueError('surface_projection_grads needs feature maps (set_feature_maps)')
-        cfg, ws, wb, sc, fp, P = self.cfg, self.ws_featproj, self.ws_featproj_ref, self.cfg.pp, self._fp, self.flat
+        cfg, ws, wb, sc, fp, cap = self.cfg, self.ws_featproj, self.ws_featproj_ref, self.cfg.pp, self._fp, self.featproj_rows
         R = rows['src'].shape[0]
         n = int(rows.get('n_rows', R))
-        cap = self.featproj_rows
         if not 0 < n <= R <= cap:
             raise ValueError(f'{n} of {R} rows with featproj_rows = {cap}')
         i, j = int(rows['own']), int(rows['other'])
         if not (0 <= i < self.V and 0 <= j < self.V):
             raise ValueError(f'view pair ({i}, {j}) with {self.V} views')
-
-        def per_row(t):                                             # rows past R are rays that miss the box: any jitter will do
-            if t is None:
-                return torch.rand(cap, device=self.dev)
-            return t if t.shape[0] >= cap else torch.cat([t, t.new_zeros(cap - t.shape[0])])
-        jitter, jitter_ref = per_row(jitter), per_row(jitter_ref)
+        jitter, jitter_ref = self._row_jitter(jitter, cap), self._row_jitter(jitter_ref, cap)
         scale = self.loss_scale if scale is None else scale
-        L = len(self.feature_maps)
-        par = (self.k0_cl, self.sdf, P.view('sdf_ab'), P.view('rgbnet'), P.view('warp'), cfg.inv_s(global_step), self.pe_w)
         ops.reproj_rays(sc, rows['src'], rows['pix'], n, self.intr, self.c2w, ws.rays_o, ws.rays_d, ws.viewdirs)
         self.core.sample(ws, jitter)
-        with self.core.pass_scope(P, self.mlp_pack, ws):
-            self.core.forward(ws, *par)
+
+        def loss(par):
             # query B: rays of view j through the projections; its forward stores nothing a backward would need
             ops.featproj_reproject(n, j, ws.rays_o, ws.rays_d, ws.t_min, ws.depth_acc, self.intr, self.w2c, nl, fp['own_ref'],
                                    fp['pix_ref'])
@@ -923,17 +923,9 @@ class TrainEngine:
             ops.featproj_loss(n, i, j, ws.rays_o, ws.rays_d, ws.t_min, ws.depth_acc, wb.rays_o, wb.rays_d, wb.t_min, wb.depth_acc,
                               self.intr, self.w2c, nl, cfg.voxel_size, self.H, self.W, self.feature_maps, weight, scale, fp['terms'],
                               fp['valid'], fp['cos'], fp['g_q'], fp['g_depth'], fp['g_o'], fp['g_d'], fp['g_w2c'])
-            # depth-only loss: ws.g_rgbm / g_last / g_cw stay zero; no colour-grid gradient is requested (k0_grad = None, no scatter)
-            self.core.backward(ws, *par, None, P.view('sdf_ab', 'grad'), P.view('rgbnet', 'grad'), P.view('warp', 'grad'),
-                               g_depth=fp['g_depth'])
-            ops.raygen_select_bwd(sc, None, None, None, 0, 0, True, ws.rays_o, ws.rays_d, ws.t_min, ws.ray_start, ws.g_pts, ws.step,
-                                  ws.g_view_s, fp['g_o'], fp['g_d'], None, fp['g_depth'], fp['go'], fp['gd'], fp['gv'], None)
-        ops.reproj_pose_fold(sc, rows['src'], rows['pix'], n, self.intr, self.c2w, self.w2c, ws.rays_o, ws.rays_d, fp['go'], fp['gd'],
-                             fp['gv'], None, fp['g_w2c'], fp['g_c2w'])
-        ops.pose_bwd(self.jac, fp['g_c2w'], fp['se3'])
-        self.se3_grad += fp['se3']
+        self._depth_loss_pass(ws, fp, rows['src'], rows['pix'], n, global_step, loss)
         t = fp['terms']
-        self.last_featproj_terms = dict(loss=t[0], n_valid=t[1], cos=t[2:2 + L])
+        self.last_featproj_terms = dict(loss=t[0], n_valid=t[1], cos=t[2:2 + len(self.feature_maps)])
         return self.last_featproj_terms
 
     def _upload_step_scalars(self, progress):

@@ -21,10 +21,9 @@ class DualBranchEngine:
         sum.  GUARANTEE (the conditions of TrainEngine's): identical state, ray_idx, jitter, global_step, pixels, image, replayed
         depth_rand / fine_grid / corres_rand / corres_fine_grid and the same corres rows give, after every train_step, bit-identical
         k0, k0_m, k0_v, flat.data, flat.m, flat.v, se3, se3_m, se3_v of the object engine and flat, m, v of the coarse and the
-        fine scene network - coarse phase, hierarchical phase, and both with the correspondence term.  Not covered: extra pose
-        terms a caller mixes into se3_grad through torch autograd (trainer.ReprojectionTerm), the engine-native reprojection pass
-        (forward_backward(reproj=...): refused with ValueError), multi-rank runs, and
-        bg_nerf.SceneRenderer's autograd route.  Off (default): nothing changes."""
+        fine scene network - coarse phase, hierarchical phase, and both with the correspondence term.  Not covered: the
+        engine-native reprojection and surface-projection passes (forward_backward(reproj=... / featproj=...): refused with
+        ValueError), multi-rank runs, and bg_nerf.SceneRenderer's autograd route.  Off (default): nothing changes."""
         self.deterministic = bool(deterministic)
         if self.deterministic:
             if not getattr(obj_engine, 'deterministic', False):
@@ -101,18 +100,14 @@ class DualBranchEngine:
         e, sc = self.obj, self.scene
         if corres is not None and e.dist is not None:
             raise NotImplementedError('DualBranchEngine: the correspondence term is not sharded across ranks')
-        if reproj is not None:
+        for key, name, term in (('reproj', 'reprojection', reproj), ('featproj', 'surface-projection', featproj)):
+            if term is None:
+                continue
             if self.deterministic or getattr(e, 'deterministic', False):
-                raise ValueError('DualBranchEngine: reproj is out of the scope of deterministic=True (its render backward keeps float '
+                raise ValueError(f'DualBranchEngine: {key} is out of the scope of deterministic=True (its render backward keeps float '
                                  'atomics)')
             if e.dist is not None:
-                raise NotImplementedError('DualBranchEngine: the reprojection term is not sharded across ranks')
-        if featproj is not None:
-            if self.deterministic or getattr(e, 'deterministic', False):
-                raise ValueError('DualBranchEngine: featproj is out of the scope of deterministic=True (its render backward keeps float '
-                                 'atomics)')
-            if e.dist is not None:
-                raise NotImplementedError('DualBranchEngine: the surface-projection term is not sharded across ranks')
+                raise NotImplementedError(f'DualBranchEngine: the {name} term is not sharded across ranks')
         out = e.render_and_grads(ray_idx, jitter, global_step)            # also refreshes e.c2w / e.jac for this step
         if reproj is not None:
             e.reprojection_grads(reproj['rows'], reproj['mode'], global_step, jitter=reproj.get('jitter'),
@@ -169,14 +164,11 @@ class DualBranchEngine:
         return out, loss_bg
 
     def train_step(self, ray_idx, jitter, global_step, pixels, image, depth_rand=None, optimize_pose=True, fine=False,
-                   fine_grid=None, n_views=None, before_step=None, corres=None, reproj=None, featproj=None):
+                   fine_grid=None, n_views=None, corres=None, reproj=None, featproj=None):
         """fine=True: the scene branch also runs its fine network (after ratio_start_fine_sampling_at_x of the schedule).
-        before_step: callable run after both branches' backward and before the optimiser step (the trainer mixes its extra
-        pose-only loss terms into se3_grad there).  corres, reproj, featproj: see forward_backward."""
+        corres, reproj, featproj: see forward_backward."""
         extra = {k: v for k, v in (('corres', corres), ('reproj', reproj), ('featproj', featproj)) if v is not None}
         out = self.forward_backward(ray_idx, jitter, global_step, pixels, image, depth_rand, fine, fine_grid, n_views, **extra)
-        if before_step is not None:
-            before_step()
         e = self.obj
         e.grad_scale = 1.0
         if e.dist is not None:

@@ -19,7 +19,7 @@ import random
 import numpy as np
 import torch
 
-from . import bg_nerf
+from . import bg_nerf, ops
 from .joint import DualBranchEngine
 
 
@@ -162,81 +162,42 @@ def surface_projection_sample_size(n_rays, H, W):
     return min(int(n_rays), int(H) * int(W))
 
 
-class ReprojectionTerm:
-    """The reprojection + near-surface pose terms of the live loop (lib/recon_scene.py:624-637) as a `pose_terms` entry of
-    DualBranchTrainer: one matched view pair is drawn per step among the ACTIVE views, every matched pixel is lifted to the
-    current surface, moved into the other view and compared with its match (recon_utils.get_project_error).  The surface
-    point comes from the zero-crossing query of the raw template while at most two views are active
-    (`pose_use_deform = optimize_object_nerf and len(selected_i_train) > 2`, :584 - i.e. at the start of EVERY run) and from
-    the rendered depth afterwards; both are differentiated by the HIP backward (pp_sdf_crossing_dense_bwd / the render
-    chain), so the pose receives the reference's gradient in either phase.
-
-    pairs: list of (i, j, coord_i [P,2], coord_j [P,2], conf [P]) - matcher output, an input here as in bg_losses.
-    weight_projection / weight_near_surface: cfg_train.projection_dis_error / cfg_train.weight_near_surface
-    (configs/dtu_e2e/scan1.py:60-61: 1e-3 / 1e-1)."""
-    __name__ = 'reprojection'
-
-    def __init__(self, obj_engine, pairs, nl, weight_projection, weight_near_surface, pixel_thre=200, inverse_y=True,
-                 flip_x=False, flip_y=False, seed=0):
-        self.e, self.pairs = obj_engine, list(pairs)
-        self.nl, self.w_proj, self.w_near, self.pixel_thre = float(nl), float(weight_projection), float(weight_near_surface), pixel_thre
-        self.flags = dict(inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y)
-        self.rng = np.random.RandomState(seed)
-        self.model = obj_engine.voxurf_view()
-        self.global_step = 0
-        self.last = {}
-
-    def __call__(self, se3, w2c_init, n_active):
-        from . import camera, recon_utils
-        e = self.e
-        live = [p for p in self.pairs if p[0] < n_active and p[1] < n_active]
-        if not live:
-            return 0.0, se3.sum() * 0.0
-        i, j, ci, cj, conf = live[self.rng.randint(len(live))]
-        use_deform = n_active > 2                                   # recon_scene.py:584
-        if use_deform:
-            e.voxurf_view(self.model)                               # the rendered-depth query reads the current parameters
-        w2c, _ = camera.current_pose_c2w(se3, w2c_init, fix_first=bool(e.refine_mask[0] == 0))
-        cfg = e.cfg
-        Ks = torch.zeros(e.V, 3, 3, device=e.dev)
-        Ks[:, 0, 0], Ks[:, 1, 1], Ks[:, 0, 2], Ks[:, 1, 2], Ks[:, 2, 2] = e.intr[:, 0], e.intr[:, 1], e.intr[:, 2], e.intr[:, 3], 1.
-        err, near = recon_utils.get_project_error(
-            self.model, Ks, np.array([[e.H, e.W]] * e.V), self.nl, self.global_step, w2c, cj[None].to(e.dev), ci[None].to(e.dev),
-            np.array([j]), np.array([i]), conf[None].to(e.dev), use_deform=use_deform, pixel_thre=self.pixel_thre,
-            near=cfg.near, far=cfg.far, bg=cfg.bg, stepsize=cfg.stepsize, **self.flags)
-        self.last = dict(projection_dis_error=float(err.detach()), loss_near_surface=float(near.detach()), use_deform=use_deform,
-                         pair=(i, j), hits=int(recon_utils.get_project_error.last_valid.sum()))
-        return 1.0, self.w_near * near + self.w_proj * err
+def _term_options(name, given, obj_engine, deterministic, **defaults):
+    """The option dict `name`= of DualBranchTrainer (an auxiliary term of the object loss on the engine's own launches) with the
+    defaults filled in and 'rng', the RandomState(seed) its view pair is drawn from; refused beside deterministic=True."""
+    if deterministic or getattr(obj_engine, 'deterministic', False):
+        raise ValueError(f'{name}= is out of the scope of deterministic=True (its render backward keeps float atomics)')
+    r = dict(defaults, seed=0, n_iters_object=obj_engine.cfg.N_iters, start_object=0)
+    r.update(given)
+    r['rng'] = np.random.RandomState(r['seed'])
+    return r
 
 
 class DualBranchTrainer:
     def __init__(self, obj_engine, opt, max_iter=60000, lr=1e-3, lr_end=1e-4, ratio_start_fine=0.3, ratio_end_pose=0.3,
-                 depth_range=(0.5, 3.0), seed=0, incremental_step=0, pose_initialiser=None, pose_terms=(), scene_matches=None,
+                 depth_range=(0.5, 3.0), seed=0, incremental_step=0, pose_initialiser=None, scene_matches=None,
                  deterministic=False, reprojection=None, surface_projection=None):
         """incremental_step > 0: the incremental view schedule (`active_views`); a view that joins gets its initial pose from
         `pose_initialiser(view, w2c_of_previous_view [3,4]) -> w2c [3,4]` - the reference's PnP hand-off (cv2.solvePnPRansac on
         matcher output, lib/recon_scene.py:202-214, :276-310) plugs in here: `pnp.PnPInitialiser` is its counterpart on the HIP
         path (PnP-RANSAC kernels, the previous pose as the fallback); the default is its `use_identical` variant (the
-        previous view's current pose).  pose_terms: extra pose-only loss terms mixed into the object loss as the reference
-        mixes its reprojection / near-surface terms (:616-637): callables `f(se3 [V,6] requiring grad, w2c_init, n_active)
-        -> (weight, scalar loss)`, differentiated by torch autograd through camera.current_pose_c2w.
+        previous view's current pose).
         scene_matches: per view i, (pix_self [P,2], pix_other [P,2], conf [P][, partner]) - the reference's coord1_scene[i],
         coord0_scene[i], mconf_scene[i] (recon_scene.py:247-257), paired with view pair_partner(i) unless a partner is given;
         read when opt.loss_type contains 'corres'.
         deterministic: passed to DualBranchEngine (needs a deterministic, single-GPU obj_engine): the joint step's own sums run
-        in fixed orders.  Out of its scope: `pose_terms` (differentiated by torch autograd) and multi-rank runs.
+        in fixed orders.  Out of its scope: `reprojection`, `surface_projection` and multi-rank runs.
         reprojection: dict(pairs, nl, weight_projection, weight_near_surface, pixel_thre=200, seed=0) - the reprojection +
         near-surface terms of the object loss (lib/recon_scene.py:621-637; configs/dtu_e2e/scan1.py:60-61: 1e-3 / 1e-1) inside
         the engine's own launches (TrainEngine.reprojection_grads): complete gradients (pose, and from the third active view on
-        the warp network and sdf_alpha / sdf_beta), no autograd, no host synchronisation.  pairs as ReprojectionTerm's: (i, j,
-        coord_i [P,2], coord_j [P,2], conf [P]); one pair among the active views is drawn per step from RandomState(seed), both
+        the warp network and sdf_alpha / sdf_beta), no autograd, no host synchronisation.  pairs: (i, j, coord_i [P,2],
+        coord_j [P,2], conf [P]), matcher output; one pair among the active views is drawn per step from RandomState(seed), both
         directions of its matches are the step's rows; mode 'render' iff more than two views are active (:584); active in the
         object phase only (`object_phase(global_step, n_iters_object, start_object)`; optional keys n_iters_object - default: the
         engine's cfg.N_iters - and start_object = 0).  obj_engine must have been built with reproj_rows > 0, the row
         capacity: matches beyond reproj_rows // 2 are subsampled on the device, a fresh subset every step - a DEVIATION from
         the reference, which uses every match.  The capacity costs one second render workspace: about 18 KB per sample, i.e.
-        18 KB * n_samples per row (160^3 voxels, 186 samples: 3.4 MB per row, 1024 rows = 512 matches: 3.5 GB).  The same term
-        may not also be given as a ReprojectionTerm in pose_terms (ValueError: it would be counted twice).
+        18 KB * n_samples per row (160^3 voxels, 186 samples: 3.4 MB per row, 1024 rows = 512 matches: 3.5 GB).
         surface_projection: dict(features, pairs, weight, nl, n_rays=256, seed=0) - the surface-based feature term of the object
         loss (lib/recon_scene.py:371-439, :610-619; configs/dtu_e2e: weight_surface_projection = 1e-3) inside the engine's own
         launches (TrainEngine.surface_projection_grads).  features: the per-view feature maps, a list of [V,C,h,w] (the reference's
@@ -261,36 +222,25 @@ class DualBranchTrainer:
             for p in pair_table(scene_matches)]
         self.pair_rng = random.Random(seed)
         self.last_scene_terms = None
-        self.incremental_step, self.pose_initialiser, self.pose_terms = incremental_step, pose_initialiser, tuple(pose_terms)
+        self.incremental_step, self.pose_initialiser = incremental_step, pose_initialiser
         self.n_active = None
         self.reprojection = None
         if reprojection is not None:
-            if any(isinstance(t, ReprojectionTerm) for t in self.pose_terms):
-                raise ValueError('reprojection= together with a ReprojectionTerm in pose_terms: the term would be counted twice')
             if getattr(obj_engine, 'reproj_rows', 0) < 2:
                 raise ValueError('reprojection= needs an object engine built with reproj_rows >= 2')
-            if deterministic or getattr(obj_engine, 'deterministic', False):
-                raise ValueError('reprojection= is out of the scope of deterministic=True (its render backward keeps float atomics)')
-            r = dict(pixel_thre=200, seed=0, n_iters_object=obj_engine.cfg.N_iters, start_object=0)
-            r.update(reprojection)
-            dev_ = obj_engine.dev
-            fl = lambda t: torch.as_tensor(t, dtype=torch.float32).to(dev_)
+            r = _term_options('reprojection', reprojection, obj_engine, deterministic, pixel_thre=200)
+            fl = lambda t: torch.as_tensor(t, dtype=torch.float32).to(obj_engine.dev)
             r['pairs'] = [(int(i), int(j), fl(ci), fl(cj), fl(cf)) for i, j, ci, cj, cf in r['pairs']]
-            r['rng'] = np.random.RandomState(r['seed'])
             self.reprojection = r
         self.last_reproj = None
         self.surface_projection = None
         if surface_projection is not None:
-            if deterministic or getattr(obj_engine, 'deterministic', False):
-                raise ValueError('surface_projection= is out of the scope of deterministic=True (its render backward keeps float atomics)')
-            r = dict(n_rays=256, seed=0, n_iters_object=obj_engine.cfg.N_iters, start_object=0)
-            r.update(surface_projection)
+            r = _term_options('surface_projection', surface_projection, obj_engine, deterministic, n_rays=256)
             r['n'] = surface_projection_sample_size(r['n_rays'], obj_engine.H, obj_engine.W)
             if getattr(obj_engine, 'featproj_rows', 0) < r['n']:
                 raise ValueError(f"surface_projection= needs an object engine built with featproj_rows >= {r['n']}")
             obj_engine.set_feature_maps(r.pop('features'))
             r['pairs'] = [(int(i), int(j)) for i, j in r['pairs']]
-            r['rng'] = np.random.RandomState(r['seed'])
             r['gen'] = torch.Generator(device=obj_engine.dev).manual_seed(r['seed'])
             self.surface_projection = r
         self.last_featproj = None
@@ -329,7 +279,6 @@ class DualBranchTrainer:
             self.n_active = k if self.incremental_step <= 0 else min(k, 2)
         while self.n_active < k:
             v = self.n_active
-            from . import ops
             ops.pose_fwd(e.se3, e.w2c_init, e.refine_mask, e.w2c, e.c2w, e.jac)          # current pose of the previous view
             prev = e.w2c[v - 1].detach().clone()
             init = prev if self.pose_initialiser is None else torch.as_tensor(self.pose_initialiser(v, prev.cpu()),
@@ -361,9 +310,9 @@ class DualBranchTrainer:
                     weight=self.corres_weight / corres_gamma(global_step, self.opt, self.max_iter))
 
     def _reproj_batch(self, global_step, k):
-        """The reprojection rows of this step, or None: one live pair drawn on the host (as ReprojectionTerm draws it), both
-        directions of its matches as rows - own view j first, as ReprojectionTerm orders them -, subsampled on the device to
-        reproj_rows // 2 matches.  Shapes depend on host values only."""
+        """The reprojection rows of this step, or None: one live pair drawn on the host, both directions of its matches as rows -
+        own view j first, get_project_error's order -, subsampled on the device to reproj_rows // 2 matches.  Shapes depend on host
+        values only."""
         r = self.reprojection
         if r is None:
             return None
@@ -372,7 +321,7 @@ class DualBranchTrainer:
         live = [p for p in r['pairs'] if p[0] < k and p[1] < k]
         if not live:
             return None
-        i, j, ci, cj, conf = live[r['rng'].randint(len(live))]           # the draw sequence of ReprojectionTerm, empty pairs included
+        i, j, ci, cj, conf = live[r['rng'].randint(len(live))]           # the draw is over ALL live pairs, empty ones included
         if ci.shape[0] == 0:                                               # a drawn pair without matches: no term this step
             return None
         n = reproj_sample_size(ci.shape[0], self.joint.obj.reproj_rows)
@@ -404,32 +353,12 @@ class DualBranchTrainer:
         self.last_featproj = dict(pair=pair, n_rows=n)
         return dict(rows=rows, weight=r['weight'], nl=r['nl'])
 
-    def _mix_pose_terms(self, k):
-        """loss += w_i * L_i(poses) for the extra pose-only terms: their se3 gradient joins the object branch's (which the
-        engine scales by loss_scale = 0.1, lib/recon_scene.py:648)."""
-        if not self.pose_terms:
-            return {}
-        e = self.joint.obj
-        se3 = e.se3.detach().clone().requires_grad_(True)
-        values, total = {}, 0.
-        for i, term in enumerate(self.pose_terms):
-            if hasattr(term, 'global_step'):
-                term.global_step = self.global_step
-            w, val = term(se3, e.w2c_init, k)
-            values[getattr(term, '__name__', f'term{i}')] = float(val.detach())
-            total = total + w * val
-        (total * e.loss_scale).backward()
-        e.se3_grad += se3.grad * e.refine_mask[:, None].to(se3.grad.dtype)
-        return values
-
     def train_step(self, global_step):
         """One iteration of the joint loop; returns (object-branch summary, scene loss)."""
         self.iteration += 1
-        self.global_step = global_step
         k = self._admit_views(global_step)
         fine = fine_phase(global_step, self.max_iter, self.ratio_start_fine, self.nerf_fine is not None)
         ray_idx, jitter, pixels, image = self.sample_batch(k)
-        self.last_pose_terms = {}
         corres = self._corres_batch(global_step, k)
         self.last_reproj = None
         reproj = self._reproj_batch(global_step, k)
@@ -440,7 +369,6 @@ class DualBranchTrainer:
             extra['featproj'] = featproj
         out = self.joint.train_step(ray_idx, jitter, global_step, pixels, image, fine=fine,
                                     optimize_pose=pose_phase(global_step, self.max_iter, self.ratio_end_pose), n_views=k,
-                                    before_step=(lambda: self.last_pose_terms.update(self._mix_pose_terms(k))) if self.pose_terms else None,
                                     corres=corres, **extra)
         self.last_scene_terms = self.joint.last_scene_terms
         self.joint.scene.set_lr(scene_lr(self.iteration, self.lr, self.lr_end, self.max_iter))
@@ -450,16 +378,21 @@ class DualBranchTrainer:
             self.nerf_fine.progress.data.fill_(p)
         return out
 
+    def _active_poses(self):
+        """-> k, w2c [k,3,4]: the active views' current poses, the engine's w2c refreshed from the pose parameters as the head of
+        the next step refreshes it."""
+        e = self.joint.obj
+        k = e.V if self.n_active is None else self.n_active
+        ops.pose_fwd(e.se3, e.w2c_init, e.refine_mask, e.w2c, e.c2w, e.jac)
+        return k, e.w2c[:k].detach()
+
     def pose_error(self, pose_GT_w2c):
         """Rotation (degrees) / translation (x 100) error of the active views' current poses against pose_GT_w2c [>= k,3,4] after
         aligning them to it (evaluation.evaluate_poses; the number lib/recon_scene.py:664-668 logs): -> (error, aligned, sim3).
         Not part of train_step; it refreshes the engine's w2c from the pose parameters, as the head of the next step does."""
-        from . import evaluation, ops
-        e = self.joint.obj
-        k = e.V if self.n_active is None else self.n_active
-        ops.pose_fwd(e.se3, e.w2c_init, e.refine_mask, e.w2c, e.c2w, e.jac)
-        GT = torch.as_tensor(pose_GT_w2c)
-        return evaluation.evaluate_poses(e.w2c[:k].detach(), GT[:k, :3])
+        from . import evaluation
+        k, w2c = self._active_poses()
+        return evaluation.evaluate_poses(w2c, torch.as_tensor(pose_GT_w2c)[:k, :3])
 
     def evaluate_test_views(self, pose_GT_w2c_train, pose_GT_w2c_test, images_test, Ks_test, **kw):
         """Held-out views by the reference's protocol (eval.py:1353-1416; evaluation.evaluate_test_views with this trainer's
@@ -467,24 +400,19 @@ class DualBranchTrainer:
         refinement against the frozen scene networks (refine=False skips it), full-view renders, PSNR / SSIM.  The networks and
         the optimiser state are left as they are.  render='view' (optionally chunk_rays=) renders through the forward-only
         SceneRenderer.render_view."""
-        from . import evaluation, ops
-        e = self.joint.obj
-        k = e.V if self.n_active is None else self.n_active
-        ops.pose_fwd(e.se3, e.w2c_init, e.refine_mask, e.w2c, e.c2w, e.jac)
-        GT = torch.as_tensor(pose_GT_w2c_train)
-        return evaluation.evaluate_test_views(self.nerf, self.nerf_fine, self.opt, e.w2c[:k].detach(), GT[:k, :3], pose_GT_w2c_test,
-                                              images_test, Ks_test, self.joint.depth_range, **kw)
+        from . import evaluation
+        k, w2c = self._active_poses()
+        return evaluation.evaluate_test_views(self.nerf, self.nerf_fine, self.opt, w2c, torch.as_tensor(pose_GT_w2c_train)[:k, :3],
+                                              pose_GT_w2c_test, images_test, Ks_test, self.joint.depth_range, **kw)
 
     def novel_views(self, intr, H, W, dataset='dtu', n_frames=60, chunk_rays=8192):
         """The novel-view sequence of the reference's generate_videos_synthesis (renderer.py:1213-1310) around the active views'
         current poses, rendered by this trainer's networks at its depth range (gen_videos.render_novel_views):
         -> dict(poses_w2c [F,3,4], rgb [F,H,W,3], depth [F,H,W]) on the device.  Networks and optimiser state are not written."""
-        from . import gen_videos, ops
-        e = self.joint.obj
-        k = e.V if self.n_active is None else self.n_active
-        ops.pose_fwd(e.se3, e.w2c_init, e.refine_mask, e.w2c, e.c2w, e.jac)
+        from . import gen_videos
+        _, w2c = self._active_poses()
         renderer = bg_nerf.SceneRenderer(self.opt, nerf=self.nerf, nerf_fine=self.nerf_fine)
-        return gen_videos.render_novel_views(renderer, self.opt, e.w2c[:k].detach(), intr, H, W, self.joint.depth_range,
+        return gen_videos.render_novel_views(renderer, self.opt, w2c, intr, H, W, self.joint.depth_range,
                                              dataset=dataset, n_frames=n_frames, chunk_rays=chunk_rays)
 
     # ---- `model_last.pth.tar` (renderer.py:1028-1051 save_snapshot, recon_scene.py:827-838 load) ----------------------------

@@ -496,3 +496,48 @@ def test_trainer_steps_with_the_term_and_leaves_the_scalars_on_the_device():
         else:
             assert tr.last_featproj is None
         assert bool(torch.isfinite(eng.se3).all()) and bool(torch.isfinite(eng.flat.data).all())
+
+
+RENDER_CALLS = ['pp_reproj_rays', 'pp_sample_dense', 'pp_mlp_pack', 'pp_warp_lean_begin', 'pp_warp_fwd', 'pp_geometry_fwd',
+                'pp_color_feat_fwd', 'pp_rgbnet_fwd', 'pp_march_fwd', 'pp_reproj_loss', 'pp_march_bwd', 'pp_rgbnet_bwd',
+                'pp_color_feat_bwd', 'pp_geometry_bwd', 'pp_warp_bwd', 'pp_raygen_select_bwd', 'pp_mlp_pack_invalidate',
+                'pp_warp_lean_end', 'pp_reproj_pose_fold', 'pp_pose_bwd']
+CROSSING_CALLS = ['pp_reproj_rays', 'pp_sample_dense', 'pp_reproj_dense_pts', 'pp_grid_sample_fwd', 'pp_sdf_first_crossing',
+                  'pp_reproj_loss', 'pp_sdf_crossing_dense_bwd', 'pp_reproj_pose_fold', 'pp_pose_bwd']
+FEATPROJ_CALLS = ['pp_reproj_rays', 'pp_sample_dense', 'pp_mlp_pack', 'pp_warp_lean_begin', 'pp_warp_fwd', 'pp_geometry_fwd',
+                  'pp_color_feat_fwd', 'pp_rgbnet_fwd', 'pp_march_fwd', 'pp_featproj_reproject', 'pp_reproj_rays', 'pp_sample_dense',
+                  'pp_warp_fwd', 'pp_geometry_fwd', 'pp_color_feat_fwd', 'pp_rgbnet_fwd', 'pp_march_fwd', 'pp_featproj_loss',
+                  'pp_march_bwd', 'pp_rgbnet_bwd', 'pp_color_feat_bwd', 'pp_geometry_bwd', 'pp_warp_bwd', 'pp_raygen_select_bwd',
+                  'pp_mlp_pack_invalidate', 'pp_warp_lean_end', 'pp_reproj_pose_fold', 'pp_pose_bwd']
+
+
+def test_the_auxiliary_passes_make_their_library_calls_in_a_fixed_order(monkeypatch):
+    """Entry points recorded around _lib.call (as tests/test_hip_step_launches.py records them) over reprojection_grads in both modes
+    and surface_projection_grads, on the two 24^3 fixtures: each pass makes exactly the calls of its list, in that order - the
+    weight pack and the lean scope of its own opened before the forward chain and closed behind the ray backward, ahead of the pose
+    fold.  The passes share their skeleton on the host (TrainEngine._depth_loss_pass, _pose_fold); the literal lists are what a change
+    to that host code may not move."""
+    from poseprobe_amd import _lib
+    from tests import test_hip_reproj as RP
+    d = load('reproj_g24.npz')
+    rp, fp = RP._engine(d), _engine()
+    RP._main_pass(rp)
+    _main_pass(fp)
+    rows, kw = RP._rows(d), dict(jitter=torch.tensor(d['jitter']).cuda(), nl=float(d['nl']), pixel_thre=200, scale=1.0)
+    names = []
+    real = _lib.call
+    monkeypatch.setattr(_lib, 'call', lambda name, *a: (names.append(name), real(name, *a))[1])
+    seen = {}
+    for mode in ('render', 'crossing'):
+        names.clear()
+        rp.reprojection_grads(rows, mode, GS, **kw)
+        seen[mode] = list(names)
+    names.clear()
+    fp.surface_projection_grads(_rows(), GS, **_pass_kw())
+    seen['featproj'] = list(names)
+    torch.cuda.synchronize()
+    for k, v in seen.items():
+        print(k, v)
+    assert seen['render'] == RENDER_CALLS
+    assert seen['crossing'] == CROSSING_CALLS
+    assert seen['featproj'] == FEATPROJ_CALLS

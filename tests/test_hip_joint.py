@@ -170,8 +170,7 @@ def test_joint_step_through_rccl_on_one_rank_matches_plain():
 def test_trainer_incremental_views_pose_hand_off_and_loss_mixing():
     """The trainer counterpart's control decisions (lib/recon_scene.py:552-649): views join one by one at multiples of
     `incremental_step`, a joining view starts from a handed-over pose (default = the previous view's current pose, the
-    reference's `use_identical`; a callback stands where cv2.solvePnPRansac does), batches only touch active views, and
-    extra pose-only terms are mixed into the object loss (scaled by 0.1 with it) before the optimiser step."""
+    reference's `use_identical`; a callback stands where cv2.solvePnPRansac does) and batches only touch active views."""
     from poseprobe_amd import bg_nerf
     from poseprobe_amd.trainer import DualBranchTrainer, active_views
     assert [active_views(s, 6, 100) for s in (0, 99, 100, 250, 400, 10 ** 6)] == [2, 2, 3, 4, 6, 6]
@@ -188,14 +187,11 @@ def test_trainer_incremental_views_pose_hand_off_and_loss_mixing():
         out[:, 3] += torch.tensor([0.01, -0.02, 0.03])
         return out
 
-    def pull_to_zero(se3, w2c_init, k):
-        return 0.5, (se3[:k] ** 2).sum()
-
     for initialiser in (None, from_pnp):
         eng, _ = build_engine(d)
         eng.zero_grads()
         torch.manual_seed(3)
-        tr = DualBranchTrainer(eng, opt, max_iter=20, incremental_step=2, pose_initialiser=initialiser, pose_terms=(pull_to_zero,))
+        tr = DualBranchTrainer(eng, opt, max_iter=20, incremental_step=2, pose_initialiser=initialiser)
         init_before, se3_before = eng.w2c_init.clone(), eng.se3.clone()
         ray_idx, _, pixels, image = tr.sample_batch(2)
         assert int(ray_idx.max()) < 2 * H * W and image.shape[0] == 2 and pixels.shape[0] == 96 // 2
@@ -203,7 +199,6 @@ def test_trainer_incremental_views_pose_hand_off_and_loss_mixing():
             tr.train_step(step)
         assert tr.n_active == 2 and torch.equal(eng.w2c_init[2], init_before[2]) and torch.equal(eng.se3[2], se3_before[2])
         assert not torch.equal(eng.se3[1], se3_before[1])         # an active, refined view moves
-        assert 'pull_to_zero' in tr.last_pose_terms
         from poseprobe_amd import ops
         ops.pose_fwd(eng.se3, eng.w2c_init, eng.refine_mask, eng.w2c, eng.c2w, eng.jac)
         pose1 = eng.w2c[1].clone()
@@ -216,21 +211,13 @@ def test_trainer_incremental_views_pose_hand_off_and_loss_mixing():
             assert_close(calls[-1][1], pose1.cpu(), rtol=0, atol=1e-6, name='previous pose handed to the initialiser')
             assert_close(eng.w2c_init[2][:, 3], (pose1[:, 3].cpu() + torch.tensor([0.01, -0.02, 0.03])), rtol=0, atol=1e-6, name='initialised pose')
         assert float(eng.se3[2].abs().max()) > 0.0               # ... and is refined from its first step on
-        # the mixing itself: d(0.1 * 0.5 * |se3|^2) / d se3 on the refined views
-        eng.se3_grad.zero_()
-        tr._mix_pose_terms(3)
-        expect = 0.1 * 0.5 * 2.0 * eng.se3 * eng.refine_mask[:, None]
-        assert_close(eng.se3_grad, expect.cpu(), rtol=1e-6, atol=1e-9, name='mixed pose term')
-        eng.se3_grad.zero_()
 
 
-def test_reprojection_term_differentiates_the_zero_crossing_query_while_two_views_are_active():
-    """trainer.ReprojectionTerm (lib/recon_scene.py:584, :624-637): with <= 2 active views the surface point is the zero
-    crossing of the raw template and its pose gradient flows through pp_sdf_crossing_dense_bwd (BOTH views of the pair
-    receive a gradient: the 'own' view through the query's rays, the other through world2cam); with 3 views it is the
-    rendered depth.  The mixed gradient equals the term's autograd gradient times loss_scale on the refined views."""
-    from poseprobe_amd import bg_nerf, camera, recon_utils
-    from poseprobe_amd.trainer import DualBranchTrainer, ReprojectionTerm
+def test_zero_crossing_query_contributes_to_the_pose_gradient_of_both_views():
+    """recon_utils.get_project_error on engine.voxurf_view() (lib/recon_scene.py:584, :624-637): with <= 2 active views the surface
+    point is the zero crossing of the raw template and its pose gradient flows through pp_sdf_crossing_dense_bwd - BOTH views of
+    the pair receive a gradient: the 'own' view through the query's rays, the other through world2cam."""
+    from poseprobe_amd import camera, recon_utils
     d = load('forward_g24_s10.npz')
     eng, _ = build_engine(d)
     eng.zero_grads()
@@ -238,57 +225,35 @@ def test_reprojection_term_differentiates_the_zero_crossing_query_while_two_view
     g = torch.Generator().manual_seed(11)
     P = 40
     mk = lambda: (torch.rand(P, 2, generator=g) * torch.tensor([W - 1., H - 1.]) * 0.5 + torch.tensor([W, H]) * 0.25)
-    pairs = [(0, 1, mk(), mk(), torch.rand(P, generator=g)), (1, 2, mk(), mk(), torch.rand(P, generator=g)),
-             (0, 2, mk(), mk(), torch.rand(P, generator=g))]
-    term = ReprojectionTerm(eng, pairs, nl=0.1, weight_projection=1.0, weight_near_surface=0.1, seed=0)
-    with torch.no_grad():
-        eng.refine_mask[0] = 1                  # let view 0 move too, so that BOTH views of the (0, 1) pair show their share
-    se3 = eng.se3.detach().clone().requires_grad_(True)
-    torch.manual_seed(7)                        # the query draws its per-ray jitter from the global generator (as the reference does)
-    w, val = term(se3, eng.w2c_init, 2)
-    assert term.last['use_deform'] is False and term.last['pair'] == (0, 1) and w == 1.0
-    val.backward()
-    g2 = se3.grad.clone()
-    assert float(g2[0].abs().max()) > 0 and float(g2[1].abs().max()) > 0 and float(g2[2].abs().max()) == 0
-    # the same loss with the surface points detached: only the world2cam half of the gradient is left (what round 2 had)
-    i, j, ci, cj, conf = pairs[0]
-
-    class Detached:
-        xyz_min, xyz_max, diagonal_length = term.model.xyz_min, term.model.xyz_max, term.model.diagonal_length
-
-        def query_sdf_point_wocuda_wodeform(self, o, dd, **kw):
-            p, m, s = term.model.query_sdf_point_wocuda_wodeform(o.detach(), dd.detach(), **kw)
-            return p.detach(), m, s
-
-    se3b = eng.se3.detach().clone().requires_grad_(True)
-    w2c, _ = camera.current_pose_c2w(se3b, eng.w2c_init, fix_first=False)
+    i, j, ci, cj, conf = 0, 1, mk(), mk(), torch.rand(P, generator=g)
+    model = eng.voxurf_view()
     Ks = torch.zeros(3, 3, 3, device='cuda')
     Ks[:, 0, 0], Ks[:, 1, 1], Ks[:, 0, 2], Ks[:, 1, 2], Ks[:, 2, 2] = eng.intr[:, 0], eng.intr[:, 1], eng.intr[:, 2], eng.intr[:, 3], 1.
-    torch.manual_seed(7)
-    err, near = recon_utils.get_project_error(Detached(), Ks, np.array([[H, W]] * 3), 0.1, 0, w2c, cj[None].cuda(), ci[None].cuda(),
-                                              np.array([j]), np.array([i]), conf[None].cuda(), use_deform=False, pixel_thre=200,
-                                              near=eng.cfg.near, far=eng.cfg.far, bg=0, stepsize=eng.cfg.stepsize)
-    assert_close(np.float32((0.1 * near + 1.0 * err).item()), np.float32(val.item()), rtol=1e-5, atol=1e-7, name='term value')
-    (0.1 * near + 1.0 * err).backward()
-    assert int(term.last['hits']) >= 10, term.last
-    assert float((g2 - se3b.grad).abs().max()) > 0.02 * float(g2.abs().max()), 'the query must contribute to the pose gradient'
-    # three active views: rendered-depth query over the engine's live parameters
-    se3c = eng.se3.detach().clone().requires_grad_(True)
-    term.rng = np.random.RandomState(1)
-    w, val3 = term(se3c, eng.w2c_init, 3)
-    assert term.last['use_deform'] is True
-    val3.backward()
-    assert torch.isfinite(se3c.grad).all() and float(se3c.grad.abs().max()) > 0
-    # mixing into the engine's pose gradient through the trainer
-    opt = bg_nerf.default_options(sample_intvs=16)
-    opt.nerf.rand_rays = 96
-    term.rng = np.random.RandomState(0)
-    tr = DualBranchTrainer(eng, opt, max_iter=20, incremental_step=4, pose_terms=(term,))
-    tr.global_step = 0
-    eng.se3_grad.zero_()
-    torch.manual_seed(7)
-    vals = tr._mix_pose_terms(2)
-    assert 'reprojection' in vals
-    assert_close(eng.se3_grad, (eng.loss_scale * g2 * eng.refine_mask[:, None]).cpu(), rtol=1e-4, atol=1e-7, name='mixed reprojection gradient')
-    tr.train_step(0)                                            # and a whole joint step runs with it
-    assert term.last['use_deform'] is False
+
+    def term(model):
+        """0.1 * near + err of the pair (0, 1) and its gradient on se3, every view refined so that BOTH views show their share."""
+        se3 = eng.se3.detach().clone().requires_grad_(True)
+        w2c, _ = camera.current_pose_c2w(se3, eng.w2c_init, fix_first=False)
+        torch.manual_seed(7)                    # the query draws its per-ray jitter from the global generator (as the reference does)
+        err, near = recon_utils.get_project_error(model, Ks, np.array([[H, W]] * 3), 0.1, 0, w2c, cj[None].cuda(), ci[None].cuda(),
+                                                  np.array([j]), np.array([i]), conf[None].cuda(), use_deform=False, pixel_thre=200,
+                                                  near=eng.cfg.near, far=eng.cfg.far, bg=0, stepsize=eng.cfg.stepsize)
+        val = 0.1 * near + 1.0 * err
+        val.backward()
+        return val.detach(), se3.grad.clone(), int(recon_utils.get_project_error.last_valid.sum())
+
+    val, g2, hits = term(model)
+    assert float(g2[0].abs().max()) > 0 and float(g2[1].abs().max()) > 0 and float(g2[2].abs().max()) == 0
+
+    # the same loss with the surface points detached: only the world2cam half of the gradient is left
+    class Detached:
+        xyz_min, xyz_max, diagonal_length = model.xyz_min, model.xyz_max, model.diagonal_length
+
+        def query_sdf_point_wocuda_wodeform(self, o, dd, **kw):
+            p, m, s = model.query_sdf_point_wocuda_wodeform(o.detach(), dd.detach(), **kw)
+            return p.detach(), m, s
+
+    val_b, g2b, _ = term(Detached())
+    assert_close(np.float32(val_b.item()), np.float32(val.item()), rtol=1e-5, atol=1e-7, name='term value')
+    assert hits >= 10, hits
+    assert float((g2 - g2b).abs().max()) > 0.02 * float(g2.abs().max()), 'the query must contribute to the pose gradient'

@@ -61,8 +61,11 @@ def _forward_twice(eng, ws, jitter):
         torch.cuda.synchronize()
         got.append((ws.warp_out.clone(), ws.warp_acts.clone()))
     assert int(ws.count.item()) > N                                 # more than one 64-row tile of samples
-    assert torch.equal(got[0][0], got[1][0]), 'warp_out: the forward after the failed pass read a pack of the old weights'
-    assert torch.equal(got[0][1], got[1][1]), 'warp_acts: the forward after the failed pass ran inside a stale lean scope'
+    # bit patterns, not values: warp_out's rows past the samples are never written, and whatever the allocator left there (NaN
+    # included, which no value comparison calls equal to itself) is the same in both runs
+    same = lambda a, b: torch.equal(a.view(torch.int32), b.view(torch.int32))
+    assert same(got[0][0], got[1][0]), 'warp_out: the forward after the failed pass read a pack of the old weights'
+    assert same(got[0][1], got[1][1]), 'warp_acts: the forward after the failed pass ran inside a stale lean scope'
 
 
 def _boom(*a, **k):

@@ -99,7 +99,7 @@ def test_term_is_active_in_the_object_phase_only():
     assert DualBranchTrainer(_stub_engine(), bg_nerf.default_options(), max_iter=10)._reproj_batch(0, 3) is None
 
 
-def test_an_empty_pair_takes_part_in_the_draw_as_it_does_in_reprojection_term():
+def test_an_empty_pair_takes_part_in_the_draw():
     pairs = _pairs()
     empty = (0, 2, torch.zeros(0, 2), torch.zeros(0, 2), torch.zeros(0))
     tr = _trainer(reprojection=dict(pairs=pairs[:2] + [empty], seed=5))
@@ -125,10 +125,6 @@ def test_a_box_without_a_finite_diagonal_is_refused():
 
 
 def test_trainer_refusals():
-    from poseprobe_amd.trainer import ReprojectionTerm
-    term = ReprojectionTerm.__new__(ReprojectionTerm)               # the constructor needs a device; its type is what counts
-    with pytest.raises(ValueError, match='counted twice'):
-        _trainer(pose_terms=(term,))
     with pytest.raises(ValueError, match='reproj_rows'):
         _trainer(_stub_engine(reproj_rows=0))
     with pytest.raises(ValueError, match='deterministic=True'):
@@ -168,3 +164,16 @@ def test_engine_refusals_come_before_any_launch():
     eng.dist = object()
     with pytest.raises(NotImplementedError, match='not sharded'):
         eng.reprojection_grads(rows, 'render', 0)
+
+
+def test_the_autograd_pose_term_route_is_gone():
+    """trainer.ReprojectionTerm, DualBranchTrainer(pose_terms=) and DualBranchEngine.train_step(before_step=) were the autograd route
+    of the pose terms; reprojection= / surface_projection= on the engine's own launches are the only one."""
+    from poseprobe_amd import bg_nerf, trainer
+    from poseprobe_amd.joint import DualBranchEngine
+    assert not hasattr(trainer, 'ReprojectionTerm')
+    with pytest.raises(TypeError, match='pose_terms'):
+        trainer.DualBranchTrainer(_stub_engine(), bg_nerf.default_options(), max_iter=10, pose_terms=())
+    joint = DualBranchEngine(_stub_engine(), bg_nerf.NeRF(bg_nerf.default_options(), device='cpu'))
+    with pytest.raises(TypeError, match='before_step'):
+        joint.train_step(None, None, 0, None, None, before_step=lambda: None)

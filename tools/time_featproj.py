@@ -4,9 +4,6 @@ and one feature layer of 256 channels at H / 4 x W / 4 (a smooth random field pl
 
     none       joint.DualBranchEngine.train_step without the term (engine built without featproj_rows)
     native     train_step(featproj=...): TrainEngine.surface_projection_grads
-    autograd   train_step with recon_utils.get_project_feature_loss on the drop-in module (engine.voxurf_view()) differentiated by
-               torch autograd in before_step, its pose gradient added to se3_grad (the route trainer.ReprojectionTerm takes for its
-               term: the parameter gradients of the module are dropped)
     pass       surface_projection_grads alone, on the state a step left
     kernels    the new launches alone (pp_featproj_reproject + the three of pp_featproj_loss) on the buffers a pass left
 
@@ -45,8 +42,7 @@ def main():
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
-    from poseprobe_amd import bg_nerf, camera, ops
-    from poseprobe_amd import recon_utils as RU
+    from poseprobe_amd import bg_nerf, ops
     from poseprobe_amd.joint import DualBranchEngine
     dev = 'cuda'
     opt = bg_nerf.default_options(sample_intvs=S_SCENE)
@@ -62,13 +58,11 @@ def main():
     one_engine = torch.cuda.memory_allocated() - before
     native = build(featproj_rows=ROWS)
     workspaces = torch.cuda.memory_allocated() - before - 2 * one_engine
-    auto = build()
     g = torch.Generator().manual_seed(1)
     feat = F.interpolate(torch.randn(V, C_FEAT, 8, 8, generator=g), size=(H // 4, W // 4), mode='bilinear', align_corners=True)
     feat = (feat + 0.05 * torch.randn(feat.shape, generator=g)).to(dev)
     native.set_feature_maps([feat])
-    model = auto.voxurf_view()
-    joints = {'plain': joint_of(plain), 'native': joint_of(native), 'auto': joint_of(auto)}
+    joints = {'plain': joint_of(plain), 'native': joint_of(native)}
     rays = draws(a.steps)
     n_pix = opt.nerf.rand_rays // V
     px = [(torch.rand(n_pix, 2, generator=g) * torch.tensor([W - 1., H - 1.])).to(dev) for _ in range(a.steps)]
@@ -76,26 +70,12 @@ def main():
     gs = 10
     rng = np.random.RandomState(0)
     gen = torch.Generator(device=dev).manual_seed(2)
-    Ks = torch.zeros(V, 3, 3, device=dev)
-    Ks[:, 0, 0], Ks[:, 1, 1], Ks[:, 0, 2], Ks[:, 1, 2], Ks[:, 2, 2] = (*auto.intr.T, 1.)
-    HW = np.array([[H, W]] * V)
-    rk = dict(near=auto.cfg.near, far=auto.cfg.far, bg=auto.cfg.bg, stepsize=auto.cfg.stepsize)
 
     def rows():
         flat = torch.randperm(H * W, device=dev, generator=gen)[:ROWS]
         i, j = PAIRS[rng.randint(len(PAIRS))]
         pix = torch.stack([(flat % W).float() + 0.5, (flat // W).float() + 0.5], -1).contiguous()
         return dict(src=torch.zeros(ROWS, dtype=torch.int32, device=dev), pix=pix, own=i, other=j)
-
-    def autograd_term():
-        e, r = auto, rows()
-        e.voxurf_view(model)
-        se3 = e.se3.detach().clone().requires_grad_(True)
-        w2c, _ = camera.current_pose_c2w(se3, e.w2c_init, fix_first=True)
-        loss = RU.get_project_feature_loss(model, Ks, HW, NL, gs, w2c, [feat], r['src'].long(), r['pix'], r['own'], r['other'], **rk)
-        (loss * WEIGHT * e.loss_scale).backward()
-        e.se3_grad += se3.grad * e.refine_mask[:, None].to(se3.grad.dtype)
-        model.zero_grad(set_to_none=True)
 
     def kernels():
         e, ws, wb, fp = native, native.ws_featproj, native.ws_featproj_ref, native._fp
@@ -110,7 +90,6 @@ def main():
 
     legs = {'none': lambda s: step('plain', s),
             'native': lambda s: step('native', s, featproj=dict(rows=rows(), weight=WEIGHT, nl=NL)),
-            'autograd': lambda s: step('auto', s, before_step=autograd_term),
             'pass': lambda s: native.surface_projection_grads(rows(), gs, WEIGHT, NL),
             'kernels': lambda s: kernels()}
     for leg, f in legs.items():
@@ -136,7 +115,7 @@ def main():
     res = {'workload': f'160^3 grid, {V} x {H} x {W} views, {N} object rays, scene branch {V} x {n_pix} rays x {S_SCENE} samples '
                        f'(coarse phase), {ROWS} rows, one layer of {C_FEAT} channels at {H // 4} x {W // 4}',
            'steps_per_block': a.steps, 'rounds': a.rounds, 'ms_median': med, 'ms_min_max': {k: [min(v), max(v)] for k, v in ms.items()},
-           'term_cost_ms': {k: med[k] - med['none'] for k in ('native', 'autograd')},
+           'term_cost_ms': {'native': med['native'] - med['none']},
            'kernels_share_of_the_pass': med['kernels'] / med['pass'], 'n_valid_at_the_kernels_leg': n_valid,
            'must_move_bytes': must_move, 'achieved_GB_per_s': must_move / (med['kernels'] * 1e-3) / 1e9,
            'workspaces_MB': workspaces / 2 ** 20, 'object_samples_per_ray': native.cfg.n_samples,

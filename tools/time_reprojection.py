@@ -4,8 +4,6 @@ synthetic matches per view pair - surface voxels of the SDF template projected i
 joint.DualBranchEngine.train_step:
 
     none               no reprojection term (the default step; engine built without reproj_rows)
-    autograd_crossing  trainer.ReprojectionTerm mixed in through DualBranchTrainer._mix_pose_terms, two active views
-    autograd_render    the same with three active views (rendered-depth query through the drop-in autograd node)
     native_crossing    train_step(reproj=dict(mode='crossing', ...)): TrainEngine.reprojection_grads
     native_render      train_step(reproj=dict(mode='render', ...))
 
@@ -78,7 +76,6 @@ def main():
     assert torch.cuda.is_available(), 'needs a GPU'
     from poseprobe_amd import bg_nerf
     from poseprobe_amd.joint import DualBranchEngine
-    from poseprobe_amd.trainer import DualBranchTrainer, ReprojectionTerm
     dev = 'cuda'
     opt = bg_nerf.default_options(sample_intvs=S_SCENE)
 
@@ -93,12 +90,8 @@ def main():
     one_engine = torch.cuda.memory_allocated() - before
     native = build(reproj_rows=2 * MATCHES)
     second_ws = torch.cuda.memory_allocated() - before - 2 * one_engine
-    auto = build()
     pairs = surface_matches(plain)
-    term = ReprojectionTerm(auto, pairs, nl=NL, weight_projection=W_PROJ, weight_near_surface=W_NEAR, pixel_thre=THRE, seed=0)
-    tr = DualBranchTrainer(auto, opt, max_iter=60000, pose_terms=(term,))          # its joint engine is the autograd legs'
-    tr.global_step = 10                                  # _mix_pose_terms hands it to the term: every leg runs at step 10
-    joints = {'plain': joint_of(plain), 'native': joint_of(native), 'auto': tr.joint}
+    joints = {'plain': joint_of(plain), 'native': joint_of(native)}
     rows = {(p[0], p[1]): rows_of(p, dev) for p in pairs}
     rng = np.random.RandomState(0)
     rays = draws(a.steps)
@@ -115,8 +108,6 @@ def main():
                                 pixel_thre=THRE))
 
     legs = {'none': ('plain', lambda: {}),
-            'autograd_crossing': ('auto', lambda: dict(before_step=lambda: tr._mix_pose_terms(2))),
-            'autograd_render': ('auto', lambda: dict(before_step=lambda: tr._mix_pose_terms(3))),
             'native_crossing': ('native', lambda: native_kw('crossing')),
             'native_render': ('native', lambda: native_kw('render'))}
 
@@ -146,7 +137,7 @@ def main():
            'ms_per_step_min_max': {k: [min(v), max(v)] for k, v in ms.items()},
            'term_cost_ms': {k: med[k] - med['none'] for k in med if k != 'none'},
            'second_workspace_MB': second_ws / 2 ** 20, 'object_samples_per_ray': native.cfg.n_samples,
-           'last_native_terms': terms, 'last_autograd_terms': {k: v for k, v in term.last.items() if k != 'pair'}}
+           'last_native_terms': terms}
     line = json.dumps(res)
     print(line)
     if a.out:
