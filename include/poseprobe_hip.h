@@ -47,7 +47,7 @@ const char* pp_last_error(void);
  * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
  * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_featproj_* group, the pp_mc_* group, the pp_pnp_* group,
  * the pp_dtu_* group, the pp_ssim_* group, pp_step_begin, pp_march_loss_bwd / pp_march_loss_workspace, pp_geometry_plain_fwd /
- * pp_geometry_plain_bwd, pp_keep_compact / pp_keep_scatter_bwd.
+ * pp_geometry_plain_bwd, pp_keep_compact / pp_keep_scatter_bwd, pp_vertex_feat.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
  * (poseprobe_amd/_lib.py does): the signatures changed, so a stale caller would pass a stream where a pointer is read. */
 #define PP_ABI_VERSION 4
@@ -814,6 +814,16 @@ int pp_mc_count(const float* u, int32_t X, int32_t Y, int32_t Z, float threshold
                 int32_t* counts, void* stream);
 int pp_mc_emit(const float* u, int32_t X, int32_t Y, int32_t Z, float threshold, void* work, int64_t work_bytes,
                float* vertices, int32_t n_vertices, int32_t* triangles, int32_t n_triangles, void* stream);
+
+/* Vertex attributes of an extracted mesh (csrc/pp_mesh_color.hip): the render path's colour stage with every
+ * vertex seen head-on.  pts [n,3] in model coordinates; warp_out [n,4,4] = pp_warp_fwd's rows for these points, or NULL for the
+ * plain template (use_deform=False).  g = d sdf / d p is pp_geometry_fwd's `gradient` (pp_geometry_plain_fwd's without
+ * warp_out); normal [n,3] = g / (|g| + 1e-5); feat [n,64] = the row pp_rgbnet_fwd reads, as pp_color_feat_fwd lays it out, with
+ * the view embedding formed from viewdir = -normal: [k0 (12) | xyz PE (33) | view PE (9) | normal (3) | 0 (7)].  pe_w [6] as
+ * for pp_color_feat_fwd.  One forward-only launch: no atomics, no workspace, rows from n on are not written; n = 0 launches
+ * nothing.  Only k0_dim = 12, pos_pe = 5, view_pe = 1 (PP_ERR_UNSUPPORTED otherwise). */
+int pp_vertex_feat(const pp_scene* sc, const float* sdf_grid, const float* sdf_ab, const float* k0_cl, const float* pts,
+                   const float* warp_out, const float* pe_w, int32_t n, float* normal, float* feat, void* stream);
 
 /* ---------------------------------------------------------------- pose initialisation: PnP-RANSAC
  * lib/recon_scene.py:276-310 hands surface points and matched pixels to cv2.solvePnPRansac on the host; here they stay on the

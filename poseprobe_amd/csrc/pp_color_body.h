@@ -9,13 +9,18 @@ __device__ __forceinline__ float pp_norm3c(float x, float y, float z) { return s
 // sample m of the feature builder.  NORMAL = false: columns [0, C + 6 + 6 Lp + 6 Lv) only (54 for the <12, 5, 1> layout) - the normal
 // columns and the zero padding are written by the geometry role of the same launch (pp_geometry.hip, k_geometry_color_fwd);
 // `gradient` is not read then.
-template <int TC, int TLP, int TLV, bool NORMAL>
+// HEADON = true (the mesh colour kernel, pp_mesh_color.hip: a vertex seen head-on, no ray): `gradient` is this sample's own g[3], not
+// a table indexed by m; the view direction is minus the normal g / (|g| + 1e-5) formed here in registers, viewdirs / ray_id / count
+// are not read (every m < capacity is live) and the normal is handed back in normal_out[3].  HEADON = false compiles to the code it
+// compiled to before the parameter existed.
+template <int TC, int TLP, int TLV, bool NORMAL, bool HEADON = false>
 __device__ __forceinline__ void color_feat_fwd_body(int m, const SceneDev& sc, const float* __restrict__ k0,
                                                     const float* __restrict__ pts, const float* __restrict__ viewdirs,
                                                     const int32_t* __restrict__ ray_id, const float* __restrict__ gradient,
                                                     const float* __restrict__ pe_w, const int32_t* __restrict__ count,
-                                                    int capacity, float* __restrict__ feat) {
-  int M = min(count[0], capacity);
+                                                    int capacity, float* __restrict__ feat, float* normal_out = nullptr) {
+  static_assert(!HEADON || NORMAL, "a head-on row carries its normal");
+  int M = HEADON ? capacity : min(count[0], capacity);
   if (m >= M) return;
   float f[PP_FEAT_LD];
 #pragma unroll
@@ -54,10 +59,15 @@ __device__ __forceinline__ void color_feat_fwd_body(int m, const SceneDev& sc, c
     }
   }
   o += 3 + 6 * Lp;
-  int r = ray_id[m];
+  float nrm[3];
+  if (HEADON) {
+    float gn = pp_norm3c(gradient[0], gradient[1], gradient[2]) + 1e-5f;
+    for (int a = 0; a < 3; ++a) normal_out[a] = nrm[a] = gradient[a] / gn;
+  }
+  int r = HEADON ? 0 : ray_id[m];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    float va = viewdirs[r * 3 + a];
+    float va = HEADON ? -nrm[a] : viewdirs[r * 3 + a];
     f[o + a] = va;
     float fr = 1.f;
 #pragma unroll
@@ -71,7 +81,11 @@ __device__ __forceinline__ void color_feat_fwd_body(int m, const SceneDev& sc, c
   }
   o += 3 + 6 * Lv;
   float4* dst = reinterpret_cast<float4*>(feat + (size_t)m * PP_FEAT_LD);
-  if (NORMAL) {
+  if (HEADON) {
+    for (int a = 0; a < 3; ++a) f[o + a] = nrm[a];
+#pragma unroll
+    for (int q = 0; q < PP_FEAT_LD / 4; ++q) dst[q] = make_float4(f[q * 4], f[q * 4 + 1], f[q * 4 + 2], f[q * 4 + 3]);
+  } else if (NORMAL) {
     float g[3] = {gradient[m * 3], gradient[m * 3 + 1], gradient[m * 3 + 2]};
     float gn = pp_norm3c(g[0], g[1], g[2]) + 1e-5f;
     for (int a = 0; a < 3; ++a) f[o + a] = g[a] / gn;

@@ -242,3 +242,29 @@ def validate_mesh(model, cfg, resolution=128, threshold=0.0, prefix='', world_sp
     if gt_eval:
         return eval(mesh_path, scene=scene, eval_dir=mesh_dir, dataset_dir='data/DTU', suffix=prefix + 'eval', runtime=runtime)[2]
     return 0.
+
+
+def validate_deform_mesh(model, cfg, resolution=128, threshold=0.0, prefix='', world_space=False, scale_mats_np=None, gt_eval=False,
+                         extract_color=False, scene=122, runtime=True, **kw):
+    """lib/recon_scene.py:846-875, the export the training loop ends its object phase with (:748-751): extract the DEFORMED mesh
+    of `model` on its box (mesh.voxurf_extract_deform_geometry), with extract_color shade every vertex through the colour net
+    (mesh.voxurf_vertex_colors on the UNSCALED vertices, the normal direction as the view direction), apply the world_space
+    transform and write {cfg.basedir}/{cfg.expname}/meshes/deform{prefix}.ply.  With gt_eval the file is scored as
+    validate_mesh scores its own (-> over_all); 0.0 otherwise.  Of the extra keyword arguments, use_deform / global_step / chunk
+    go to the colour pass; the rest (smooth, ...) is ignored."""
+    vertices0, triangles = mesh.voxurf_extract_deform_geometry(model, model.xyz_min.detach().float(), model.xyz_max.detach().float(),
+                                                               resolution=resolution, threshold=threshold)
+    colors = None
+    if extract_color:
+        color_kw = {k: kw[k] for k in ('use_deform', 'global_step', 'chunk') if k in kw}
+        colors = mesh.voxurf_vertex_colors(model, vertices0, **color_kw)
+    vertices = vertices0
+    if world_space and scale_mats_np is not None:
+        vertices = vertices0 * scale_mats_np[0, 0] + scale_mats_np[:3, 3][None]
+    mesh_dir = os.path.join(cfg.basedir, cfg.expname, 'meshes')
+    os.makedirs(mesh_dir, exist_ok=True)
+    mesh_path = os.path.join(mesh_dir, 'deform' + prefix + '.ply')
+    mesh.write_ply(mesh_path, vertices, triangles, vertex_colors=colors)
+    if gt_eval:
+        return eval(mesh_path, scene=scene, eval_dir=mesh_dir, dataset_dir='data/DTU', suffix=prefix + 'eval', runtime=runtime)[2]
+    return 0.

@@ -4,6 +4,8 @@
     from poseprobe_amd import mesh
     vertices, triangles = mesh.voxurf_extract_deform_geometry(model, bound_min, bound_max, resolution=512)
     mesh.write_ply('mesh.ply', vertices, triangles)
+    attr = mesh.vertex_attributes(model, vertices)          # unit normals and colours on the device (csrc/pp_mesh_color.hip)
+    mesh.write_ply('mesh.ply', vertices, triangles, vertex_colors=attr['colors'], vertex_normals=attr['normals'])
 
 The field is sampled into a DEVICE lattice (no host copy per block), triangulated there, and only the finished mesh is
 copied to the host.  Semantics of the triangulation (include/poseprobe_hip.h, DESIGN.md "Mesh extraction"): a corner is below
@@ -171,15 +173,115 @@ def dvgo_extract_geometry(model, bound_min, bound_max, resolution=128, threshold
     return extract_geometry(bound_min, bound_max, _resolution(model, resolution), threshold, query, device=model.density.device)
 
 
-def write_ply(path, vertices, triangles, vertex_colors=None):
+SHIPPED_COLOR_STAGE = dict(k0_dim=12, posbase_pe=5, viewbase_pe=1, rgbnet_width=128)
+
+
+def _color_stage_config(model):
+    """The SceneConfig of the model's box and colour stage (its pp_scene, its BARF weights); refuses what pp_vertex_feat does not cover."""
+    from .engine import SceneConfig
+    kw = getattr(model, 'rgbnet_kwargs', {})
+    got = dict(k0_dim=int(getattr(model, 'k0_dim', -1)), posbase_pe=kw.get('posbase_pe'), viewbase_pe=kw.get('viewbase_pe'),
+               rgbnet_width=kw.get('rgbnet_width'))
+    if got != SHIPPED_COLOR_STAGE:
+        raise NotImplementedError(f'vertex colours cover the shipped colour stage {SHIPPED_COLOR_STAGE} only, the model has {got}')
+    cfg = SceneConfig(model.xyz_min.cpu().numpy(), model.xyz_max.cpu().numpy(), int(model.num_voxels), N_iters=model.N_iters,
+                      barf_c2f=None if model.barf_c2f is None else tuple(model.barf_c2f), posbase_pe=got['posbase_pe'],
+                      viewbase_pe=got['viewbase_pe'], k0_dim=got['k0_dim'], out_range=model.warp_network.output_range)
+    if list(cfg.world_size) != [int(s) for s in model.sdf.grid.shape[2:]]:
+        raise RuntimeError(f'the sdf template is {tuple(model.sdf.grid.shape[2:])}, num_voxels gives {cfg.world_size}')
+    return cfg
+
+
+def _device_vertices(vertices, dev):
+    if isinstance(vertices, np.ndarray):
+        vertices = torch.from_numpy(np.array(vertices, dtype=np.float32)).to(dev)       # (a copy: the array may be read-only)
+    if not isinstance(vertices, torch.Tensor):
+        raise TypeError('vertices must be a torch.Tensor or a numpy array')
+    if not vertices.is_cuda:
+        raise RuntimeError('vertices must be a CUDA tensor')
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError('vertices must be [Nv, 3]')
+    return vertices.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+@torch.no_grad()
+def vertex_attributes(model, vertices, use_deform=True, global_step=None, chunk=262144):
+    """Normals and colours of mesh vertices on the device: the colour stage of the render path with every vertex seen head-on
+    (the reference's drivers call a `mesh_color_forward` that its Voxurf does not define).  vertices [Nv,3] in MODEL
+    coordinates (before any world_space scaling): a numpy array is uploaded, a CPU tensor is refused.
+        g = d sdf / d p        the render path's `gradient`: through the warp net (use_deform=True) or the plain template's
+                               interpolated central differences (use_deform=False)
+        normal = g / (|g| + 1e-5), viewdir = -normal
+        rgb = sigmoid(rgbnet([k0(p) | PE(p) | PE(viewdir) | normal]))
+    The BARF weights follow the model's stored `progress` (global_step=None) or global_step / N_iters; nothing of the model is
+    written.  Three launches per chunk of `chunk` vertices (pp_warp_fwd, pp_vertex_feat, pp_rgbnet_fwd, no activations kept);
+    buffers are allocated once, for min(chunk, Nv) rows; every row is computed on its own, so the result does not depend on `chunk`.
+    -> dict(normals [Nv,3], colors [Nv,3] in [0,1]), float32 on the device."""
+    dev = model.sdf.grid.device
+    v = _device_vertices(vertices, dev)
+    cfg = _color_stage_config(model)
+    if not use_deform:
+        model._check_template_mode(False)
+    chunk = int(chunk)
+    if chunk <= 0:
+        raise ValueError('chunk must be positive')
+    Nv = v.shape[0]
+    f = dict(dtype=torch.float32, device=dev)
+    normals, colors = torch.empty(Nv, 3, **f), torch.empty(Nv, 3, **f)
+    if Nv == 0:
+        return dict(normals=normals, colors=colors)
+    progress = float(model.progress.detach()) if global_step is None else global_step / model.N_iters
+    with torch.cuda.device(dev):
+        pe_w = torch.from_numpy(cfg.pe_weights(progress)).to(dev)
+        model.k0.ensure_layout()
+        k0_cl = channels_last_view(model.k0.grid.detach())
+        sdf = model.sdf.grid.detach()[0, 0].contiguous()
+        flat = model._flat_params(dev)
+        ctx = getattr(model, 'pp_ctx', None)
+        from . import _lib
+        octx = _lib.default_context() if ctx is None else ctx
+        split = octx.get('mlp_split') if octx.get('mlp_fused') else 0       # forward-only MLP calls: the split-precision kernels (the default)
+        cap = min(chunk, Nv)
+        pts = torch.zeros(cap, 3, **f)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        warp_out = torch.empty(cap, 16, **f) if use_deform else None
+        warp_acts = None if (split & 1 or not use_deform) else torch.empty(4, cap * 4, 128, **f)
+        rgb_acts = None if split & 4 else torch.empty(3, cap, 128, **f)
+        feat, rgb = torch.empty(cap, ops.FEAT_LD, **f), torch.empty(cap, 3, **f)
+        for at in range(0, Nv, cap):
+            n = min(cap, Nv - at)
+            pts[:n] = v[at:at + n]
+            count.fill_(n)
+            if use_deform:
+                ops.warp_fwd(flat.view('warp'), pts, count, cap, cfg.out_range, warp_acts, warp_out, ctx)
+            ops.vertex_feat(cfg.pp, sdf, flat.view('sdf_ab'), k0_cl, pts, warp_out, pe_w, n, normals[at:at + n], feat)
+            ops.rgbnet_fwd(flat.view('rgbnet'), feat, count, cap, rgb_acts, rgb, ctx)
+            colors[at:at + n] = rgb[:n]
+    return dict(normals=normals, colors=colors)
+
+
+def voxurf_vertex_colors(model, vertices, **kw):
+    """The loop the reference's export drivers run over `model.mesh_color_forward` (lib/recon_scene.py:859-866): colours [Nv,3] in
+    [0,1] of the vertices, on the device; keyword arguments as vertex_attributes."""
+    return vertex_attributes(model, vertices, **kw)['colors']
+
+
+def write_ply(path, vertices, triangles, vertex_colors=None, vertex_normals=None):
     """Binary little-endian PLY: vertices [Nv,3] (stored as float32), triangles [Nt,3] (int32 lists of 3), optional
-    vertex_colors [Nv,3] uint8 (or floats in [0,1]).  trimesh is not a dependency."""
+    vertex_normals [Nv,3] (stored as float32 nx ny nz) and vertex_colors [Nv,3] uint8 (or floats in [0,1]).  trimesh is not a
+    dependency."""
     to_np = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
     v = to_np(vertices).astype('<f4').reshape(-1, 3)
     t = to_np(triangles).astype('<i4').reshape(-1, 3)
     fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
     header = ['ply', 'format binary_little_endian 1.0', f'element vertex {len(v)}', 'property float x', 'property float y',
               'property float z']
+    if vertex_normals is not None:
+        nrm = to_np(vertex_normals).astype('<f4').reshape(-1, 3)
+        if len(nrm) != len(v):
+            raise ValueError('vertex_normals: one row per vertex')
+        fields += [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
+        header += ['property float nx', 'property float ny', 'property float nz']
     if vertex_colors is not None:
         c = to_np(vertex_colors).reshape(-1, 3)
         if c.dtype != np.uint8:
@@ -191,6 +293,8 @@ def write_ply(path, vertices, triangles, vertex_colors=None):
     header += [f'element face {len(t)}', 'property list uchar int vertex_indices', 'end_header']
     vert = np.empty(len(v), dtype=fields)
     vert['x'], vert['y'], vert['z'] = v[:, 0], v[:, 1], v[:, 2]
+    if vertex_normals is not None:
+        vert['nx'], vert['ny'], vert['nz'] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     if vertex_colors is not None:
         vert['red'], vert['green'], vert['blue'] = c[:, 0], c[:, 1], c[:, 2]
     face = np.empty(len(t), dtype=[('n', 'u1'), ('v', '<i4', (3,))])
@@ -205,10 +309,8 @@ _PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short':
               'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
 
 
-def read_ply(path):
-    """A minimal PLY reader: ascii and binary little-endian, scalar properties of the usual types, faces as lists of 3 vertex
-    indices -> (vertices [Nv,3] in the stored float type, triangles [Nt,3] int32 - empty for a point cloud).  Other vertex
-    properties (normals, colours) and other scalar-only elements are skipped.  It reads what `write_ply` writes."""
+def _read_ply(path):
+    """-> (columns of the vertex element by property name, triangles [Nt,3] int32 - empty for a point cloud)."""
     with open(path, 'rb') as f:
         data = f.read()
     end = data.find(b'end_header')
@@ -231,7 +333,7 @@ def read_ply(path):
                 elements[-1][2].append((w[2], _PLY_TYPES[w[1]]))
     if fmt not in ('ascii', 'binary_little_endian'):
         raise ValueError(f'{path}: format {fmt} is not supported (ascii and binary_little_endian are)')
-    vertices, triangles = None, np.empty((0, 3), np.int32)
+    vertex, triangles = None, np.empty((0, 3), np.int32)
     tokens = data[body:].split() if fmt == 'ascii' else None
     pos = 0 if fmt == 'ascii' else body
     for name, count, props in elements:
@@ -263,7 +365,25 @@ def read_ply(path):
             pos += count * dt.itemsize
             col = rows
         if name == 'vertex':
-            vertices = np.stack([col['x'], col['y'], col['z']], -1)
-    if vertices is None:
+            vertex = {p: col[p] for p, _ in props}
+    if vertex is None:
         raise ValueError(f'{path}: no vertex element')
-    return vertices, triangles
+    return vertex, triangles
+
+
+def read_ply(path):
+    """A minimal PLY reader: ascii and binary little-endian, scalar properties of the usual types, faces as lists of 3 vertex
+    indices -> (vertices [Nv,3] in the stored float type, triangles [Nt,3] int32 - empty for a point cloud).  Other vertex
+    properties (normals, colours: read_ply_attributes returns them) and other scalar-only elements are skipped.  It reads what
+    `write_ply` writes."""
+    col, triangles = _read_ply(path)
+    return np.stack([col['x'], col['y'], col['z']], -1), triangles
+
+
+def read_ply_attributes(path):
+    """read_ply with the vertex attributes: -> dict(vertices [Nv,3], triangles [Nt,3] int32, normals [Nv,3] (nx ny nz) or None,
+    colors [Nv,3] (red green blue, in the stored type: uint8 as write_ply writes them) or None)."""
+    col, triangles = _read_ply(path)
+    group = lambda names: np.stack([col[n] for n in names], -1) if all(n in col for n in names) else None
+    return dict(vertices=group(('x', 'y', 'z')), triangles=triangles, normals=group(('nx', 'ny', 'nz')),
+                colors=group(('red', 'green', 'blue')))

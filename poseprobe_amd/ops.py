@@ -851,6 +851,18 @@ def mc_emit(u, threshold, work, vertices, n_vertices, triangles, n_triangles):
               int(n_triangles), _stream())
 
 
+def vertex_feat(sc, sdf_grid, sdf_ab, k0_cl, pts, warp_out, pe_w, n, normal, feat):
+    """Rows [0, n) of normal [.,3] and of feat [.,64] (the rgbnet's input, view direction = -normal) for the vertices pts [.,3]
+    (pp_vertex_feat); warp_out [.,16] = warp_fwd's rows of these points, None = the plain template.  n = 0 launches nothing."""
+    n = int(n)
+    voxels = int(sc.size[0]) * int(sc.size[1]) * int(sc.size[2])
+    _rows_at_least(n, (pts, 3, 'pts'), (warp_out, 16, 'warp_out'), (normal, 3, 'normal'), (feat, FEAT_LD, 'feat'))
+    _rows_at_least(voxels, (sdf_grid, 1, 'sdf_grid'), (k0_cl, int(sc.k0_dim), 'k0_cl'))
+    _rows_at_least(1, (sdf_ab, 2, 'sdf_ab'), (pe_w, int(sc.pos_pe) + int(sc.view_pe), 'pe_w'))
+    _lib.call('pp_vertex_feat', ctypes.byref(sc), _f(sdf_grid, 'sdf_grid'), _f(sdf_ab, 'sdf_ab'), _f(k0_cl, 'k0_cl'), _f(pts, 'pts'),
+              _f(warp_out, 'warp_out'), _f(pe_w, 'pe_w'), n, _f(normal, 'normal'), _f(feat, 'feat'), _stream())
+
+
 # ------------------------------------------------------------------------------------------- pose initialisation (PnP-RANSAC)
 def pnp_workspace(P, H):
     """Bytes of device workspace pp_pnp_ransac needs for P rows and H hypotheses (a pure host call)."""

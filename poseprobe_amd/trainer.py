@@ -415,6 +415,18 @@ class DualBranchTrainer:
         return gen_videos.render_novel_views(renderer, self.opt, w2c, intr, H, W, self.joint.depth_range,
                                              dataset=dataset, n_frames=n_frames, chunk_rays=chunk_rays)
 
+    def export_mesh(self, cfg, **kw):
+        """The mesh export the reference's training loop ends its object phase with (lib/recon_scene.py:748-751):
+        dtu_eval.validate_deform_mesh on the object engine's CURRENT parameters, read through its drop-in view
+        (TrainEngine.voxurf_view: built once, re-pointed at the live buffers on every call) -> the driver's return value.
+        global_step (the BARF weights of the colour pass with extract_color=True) defaults to the object engine's step count;
+        the other keyword arguments are validate_deform_mesh's.  The engine and the optimiser state are left as they are."""
+        from . import dtu_eval
+        e = self.joint.obj
+        self._mesh_view = e.voxurf_view(getattr(self, '_mesh_view', None))
+        kw.setdefault('global_step', e.n_step)
+        return dtu_eval.validate_deform_mesh(self._mesh_view, cfg, **kw)
+
     # ---- `model_last.pth.tar` (renderer.py:1028-1051 save_snapshot, recon_scene.py:827-838 load) ----------------------------
     def _adam_state_dict(self):
         """torch.optim.Adam.state_dict() layout over [nerf.parameters(), nerf_fine.parameters()] (lib/utils.py:294-299)."""

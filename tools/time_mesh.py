@@ -1,12 +1,16 @@
 """Times of mesh extraction (poseprobe_amd.mesh) on a 160^3 Voxurf model with the synthetic scene's box and a perturbed warp net,
 at lattice resolutions 128, 256 and 512: the device field fill (plain and deform), marching cubes (pp_mc_count, pp_mc_emit) and
-the device-to-host copy of the mesh.  Everything runs in ONE process; each stage is warmed up, then timed `--runs` times with
+the device-to-host copy of the mesh, and the colour pass over the mesh's vertices (mesh.vertex_attributes: pp_warp_fwd,
+pp_vertex_feat, pp_rgbnet_fwd per chunk of 262144 vertices), whole and launch by launch on its first chunk.  Everything runs in ONE process; each stage is warmed up, then timed `--runs` times with
 device events (the copy with a host clock around a synchronising copy); medians are reported.
 
 Beside each marching-cubes time: the bytes the stage has to move, from the shapes alone -
   count: the field once (4 N) + one flag byte per point (N)
   emit:  flags twice (2 N) + one vertex base per point written (4 N) + the output (12 Nv + 12 Nt)
-(the field and the bases are read again near the surface only; that traffic is not counted) - and that figure over the time
+(the field and the bases are read again near the surface only; that traffic is not counted)
+  colour pass, per vertex: pp_warp_fwd 12 B in + 64 B out; pp_vertex_feat 12 + 64 B in, 256 + 12 B out (the k0 and template
+         gathers are served by the caches: vertices arrive in lattice order); pp_rgbnet_fwd 256 B in + 12 B out
+- and that figure over the time
 as a fraction of the achievable HBM rate of MI355X_MICROARCH.md (6.3 TB/s).  It is a whole-stage rate (launch gaps and the
 single-work-group tile scan included), not a kernel's share of peak.
 
@@ -66,6 +70,33 @@ def fmt(ms):
     return f'{statistics.median(ms):10.3f} ms  (min {min(ms):.3f}, max {max(ms):.3f}, {len(ms)} runs)'
 
 
+def color_launches(m, vw, runs, chunk=262144):
+    """The three launches of one chunk of mesh.vertex_attributes (use_deform=True, no activations kept), each timed on its own."""
+    from poseprobe_amd import mesh, ops
+    from poseprobe_amd.grid import channels_last_view
+    cfg = mesh._color_stage_config(m)
+    n = min(chunk, vw.shape[0])
+    f = dict(dtype=torch.float32, device='cuda')
+    pts = vw[:n].contiguous()
+    flat, ctx = m._flat_params(pts.device), getattr(m, 'pp_ctx', None)
+    m.k0.ensure_layout()
+    k0_cl, sdf = channels_last_view(m.k0.grid.detach()), m.sdf.grid.detach()[0, 0].contiguous()
+    pe_w = torch.from_numpy(cfg.pe_weights(1.0)).cuda()
+    count = torch.full((1,), n, dtype=torch.int32, device='cuda')
+    warp_out, normal, feat, rgb = torch.empty(n, 16, **f), torch.empty(n, 3, **f), torch.empty(n, ops.FEAT_LD, **f), torch.empty(n, 3, **f)
+    stages = (('pp_warp_fwd', 76, lambda: ops.warp_fwd(flat.view('warp'), pts, count, n, cfg.out_range, None, warp_out, ctx)),
+              ('pp_vertex_feat', 344, lambda: ops.vertex_feat(cfg.pp, sdf, flat.view('sdf_ab'), k0_cl, pts, warp_out, pe_w, n, normal, feat)),
+              ('pp_vertex_feat, plain', 280, lambda: ops.vertex_feat(cfg.pp, sdf, flat.view('sdf_ab'), k0_cl, pts, None, pe_w, n, normal, feat)),
+              ('pp_rgbnet_fwd', 268, lambda: ops.rgbnet_fwd(flat.view('rgbnet'), feat, count, n, None, rgb, ctx)))
+    out = [f'one chunk of {n} vertices, launch by launch:']
+    for name, per_vertex, fn in stages:
+        ms = device_ms(fn, runs)
+        rate = per_vertex * n / (statistics.median(ms) * 1e-3)
+        out.append(f'{name:28s}  {fmt(ms)}  {per_vertex * n / 2 ** 20:9.1f} MiB to move, {rate / 1e12:.3f} TB/s = '
+                   f'{rate / HBM_ACHIEVABLE:.1%} of achievable HBM')
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--resolutions', type=int, nargs='+', default=[128, 256, 512])
@@ -109,7 +140,15 @@ def main():
             vertices.cpu(), triangles.cpu()
             host.append((time.perf_counter() - t0) * 1e3)
         lines.append(f'device-to-host copy of the mesh ({12 * (nv + nt) / 2 ** 20:.1f} MiB, pageable)  {fmt(host[1:])}')
-        del u, work, vertices, triangles
+        # ---- colour pass over this mesh's vertices (model coordinates, on the device)
+        vw = (vertices / (res - 1.0) * (hi - lo)[None] + lo[None]).contiguous()
+        for name, deform, per_vertex in (('deform', True, 76 + 344 + 268), ('plain', False, 280 + 268)):
+            ms = device_ms(lambda: mesh.vertex_attributes(m, vw, use_deform=deform), a.runs)
+            rate = per_vertex * nv / (statistics.median(ms) * 1e-3)
+            lines.append(f'vertex_attributes, {name:6s}     {fmt(ms)}  {per_vertex * nv / 2 ** 20:9.1f} MiB to move, {rate / 1e12:.3f} TB/s = '
+                         f'{rate / HBM_ACHIEVABLE:.1%} of achievable HBM')
+        lines += color_launches(m, vw, a.runs)
+        del u, work, vertices, triangles, vw
         torch.cuda.empty_cache()
     text = '\n'.join(lines)
     print(text)
