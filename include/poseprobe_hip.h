@@ -47,7 +47,7 @@ const char* pp_last_error(void);
  * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
  * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_featproj_* group, the pp_mc_* group, the pp_pnp_* group,
  * the pp_dtu_* group, the pp_ssim_* group, pp_step_begin, pp_march_loss_bwd / pp_march_loss_workspace, pp_geometry_plain_fwd /
- * pp_geometry_plain_bwd, pp_keep_compact / pp_keep_scatter_bwd, pp_vertex_feat.
+ * pp_geometry_plain_bwd, pp_keep_compact / pp_keep_scatter_bwd, pp_vertex_feat, the pp_cc_* group.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
  * (poseprobe_amd/_lib.py does): the signatures changed, so a stale caller would pass a stream where a pointer is read. */
 #define PP_ABI_VERSION 4
@@ -824,6 +824,41 @@ int pp_mc_emit(const float* u, int32_t X, int32_t Y, int32_t Z, float threshold,
  * nothing.  Only k0_dim = 12, pos_pe = 5, view_pe = 1 (PP_ERR_UNSUPPORTED otherwise). */
 int pp_vertex_feat(const pp_scene* sc, const float* sdf_grid, const float* sdf_ab, const float* k0_cl, const float* pts,
                    const float* warp_out, const float* pe_w, int32_t n, float* normal, float* feat, void* stream);
+
+/* Connected components of an indexed mesh (csrc/pp_mesh_components.hip): triangles [n_triangles,3] int32 over
+ * n_vertices vertices; two vertices are connected when some triangle contains both (a shared vertex is enough).
+ *   labels [n_vertices] int32 = the smallest vertex index of the vertex's component; -1 for a vertex no triangle references.
+ * That is the unique fixpoint of "hook to the smaller label, then shortcut", reached in rounds of two launches (hook: one thread
+ * per triangle, atomicMin; jump: one thread per vertex, a bounded walk of its own chain).  A round reads only what the round
+ * before left and combines it with minima, so labels AND the number of rounds are pure functions of the mesh.  No launch waits
+ * for another work-group; the host decides when to stop.
+ * pp_cc_workspace (pure host function): bytes of `work` - two int32 arrays of n_vertices, each rounded up to 256 bytes.
+ * pp_cc_rounds runs rounds first_round .. first_round + n_rounds - 1 (first_round = 0 initialises labels and work first;
+ *   1 <= n_rounds <= 1024) and sets changed[k] (DEVICE int32 [n_rounds], cleared by the call, raised by plain stores) to 1 iff
+ *   the k-th of them changed a label.  A round that changes nothing is the fixpoint, and so is every round after it.  `labels`
+ *   and `work` carry the state from call to call.  n_triangles = 0 leaves every label at -1.
+ * pp_cc_count: vertex_counts / triangle_counts [n_vertices] int32 (cleared by the call), indexed BY ROOT: the referenced
+ *   vertices / the triangles of the component whose smallest index it is (a triangle belongs to its first vertex's component);
+ *   0 at every index that is no root.  Integer atomicAdd, one per wavefront where the wavefront shares a label.
+ * pp_cc_keep_masks: root_keep [n_vertices] uint8 marks the roots of the components to keep -> vertex_keep [n_vertices] and
+ *   triangle_keep [n_triangles] int32, 1 for a referenced vertex / a triangle of a marked component and 0 otherwise.
+ * pp_cc_compact: vertex_scan / triangle_scan = the INCLUSIVE prefix sums of the two masks (the caller's scan).  Kept vertex v
+ *   goes to row vertex_scan[v] - 1 of out_vertices [n_out_vertices,3] and out_index (= v); kept triangle i goes to row
+ *   triangle_scan[i] - 1 of out_triangles with its three ids renumbered through vertex_scan: the kept rows stay in their
+ *   relative order, the winding is untouched.  Rows from n_out_* on are not written.
+ * A triangle with an index outside [0, n_vertices) is skipped by every kernel (the Python host refuses such a mesh first).
+ * All refuse, before any GPU call: null pointers where rows exist, negative counts, more than 2^30 vertices or 2^29 triangles
+ * (PP_ERR_UNSUPPORTED), a workspace that is too small. */
+int pp_cc_workspace(int32_t n_vertices, int64_t* bytes);
+int pp_cc_rounds(const int32_t* triangles, int32_t n_triangles, int32_t n_vertices, int32_t first_round, int32_t n_rounds,
+                 int32_t* labels, void* work, int64_t work_bytes, int32_t* changed, void* stream);
+int pp_cc_count(const int32_t* labels, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles, int32_t* vertex_counts,
+                int32_t* triangle_counts, void* stream);
+int pp_cc_keep_masks(const int32_t* labels, int32_t n_vertices, const int32_t* triangles, int32_t n_triangles,
+                     const uint8_t* root_keep, int32_t* vertex_keep, int32_t* triangle_keep, void* stream);
+int pp_cc_compact(const float* vertices, const int32_t* triangles, const int32_t* vertex_scan, const int32_t* triangle_scan,
+                  int32_t n_vertices, int32_t n_triangles, float* out_vertices, int32_t* out_index, int32_t* out_triangles,
+                  int32_t n_out_vertices, int32_t n_out_triangles, void* stream);
 
 /* ---------------------------------------------------------------- pose initialisation: PnP-RANSAC
  * lib/recon_scene.py:276-310 hands surface points and matched pixels to cv2.solvePnPRansac on the host; here they stay on the

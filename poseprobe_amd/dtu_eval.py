@@ -226,13 +226,15 @@ def eval(in_file, scene, eval_dir, dataset_dir='data/DTU', suffix='', max_dist=2
 
 
 def validate_mesh(model, cfg, resolution=128, threshold=0.0, prefix='', world_space=False, scale_mats_np=None, gt_eval=False,
-                  runtime=True, scene=122, extract_color=False, **kw):
+                  runtime=True, scene=122, extract_color=False, keep=None, **kw):
     """run.py:94-131: extract the mesh of `model` on its box, write {cfg.basedir}/{cfg.expname}/meshes/{scene}_{prefix}.ply and,
-    with gt_eval, score it: -> over_all (0.0 without gt_eval).  Extra keyword arguments (smooth, ...) are ignored."""
+    with gt_eval, score it: -> over_all (0.0 without gt_eval).  keep (None: every component, else as mesh.keep_components:
+    'largest', a triangle count or a fraction of the largest) drops connected components on the device before the mesh is
+    written and scored.  Extra keyword arguments (smooth, ...) are ignored."""
     if extract_color:
         raise NotImplementedError('validate_mesh: extract_color=True (vertex colours from the colour net) is not implemented')
     vertices, triangles = mesh.voxurf_extract_geometry(model, model.xyz_min.detach().float(), model.xyz_max.detach().float(),
-                                                       resolution=resolution, threshold=threshold)
+                                                       resolution=resolution, threshold=threshold, keep=keep)
     if world_space and scale_mats_np is not None:
         vertices = vertices * scale_mats_np[0, 0] + scale_mats_np[:3, 3][None]
     mesh_dir = os.path.join(cfg.basedir, cfg.expname, 'meshes')
@@ -245,15 +247,16 @@ def validate_mesh(model, cfg, resolution=128, threshold=0.0, prefix='', world_sp
 
 
 def validate_deform_mesh(model, cfg, resolution=128, threshold=0.0, prefix='', world_space=False, scale_mats_np=None, gt_eval=False,
-                         extract_color=False, scene=122, runtime=True, **kw):
+                         extract_color=False, scene=122, runtime=True, keep=None, **kw):
     """lib/recon_scene.py:846-875, the export the training loop ends its object phase with (:748-751): extract the DEFORMED mesh
     of `model` on its box (mesh.voxurf_extract_deform_geometry), with extract_color shade every vertex through the colour net
     (mesh.voxurf_vertex_colors on the UNSCALED vertices, the normal direction as the view direction), apply the world_space
     transform and write {cfg.basedir}/{cfg.expname}/meshes/deform{prefix}.ply.  With gt_eval the file is scored as
-    validate_mesh scores its own (-> over_all); 0.0 otherwise.  Of the extra keyword arguments, use_deform / global_step / chunk
-    go to the colour pass; the rest (smooth, ...) is ignored."""
+    validate_mesh scores its own (-> over_all); 0.0 otherwise.  keep (None: every component, else as mesh.keep_components) drops
+    connected components on the device right after the extraction: only the kept vertices are shaded, written and scored.  Of the
+    extra keyword arguments, use_deform / global_step / chunk go to the colour pass; the rest (smooth, ...) is ignored."""
     vertices0, triangles = mesh.voxurf_extract_deform_geometry(model, model.xyz_min.detach().float(), model.xyz_max.detach().float(),
-                                                               resolution=resolution, threshold=threshold)
+                                                               resolution=resolution, threshold=threshold, keep=keep)
     colors = None
     if extract_color:
         color_kw = {k: kw[k] for k in ('use_deform', 'global_step', 'chunk') if k in kw}

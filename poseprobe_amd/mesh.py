@@ -6,6 +6,8 @@
     mesh.write_ply('mesh.ply', vertices, triangles)
     attr = mesh.vertex_attributes(model, vertices)          # unit normals and colours on the device (csrc/pp_mesh_color.hip)
     mesh.write_ply('mesh.ply', vertices, triangles, vertex_colors=attr['colors'], vertex_normals=attr['normals'])
+    kept = mesh.keep_components(vertices, triangles, keep='largest', attributes=attr)     # drop the floaters (csrc/pp_mesh_components.hip)
+    mesh.write_ply('clean.ply', kept['vertices'], kept['triangles'], vertex_colors=kept['colors'], vertex_normals=kept['normals'])
 
 The field is sampled into a DEVICE lattice (no host copy per block), triangulated there, and only the finished mesh is
 copied to the host.  Semantics of the triangulation (include/poseprobe_hip.h, DESIGN.md "Mesh extraction"): a corner is below
@@ -73,10 +75,14 @@ def _host(b):
     return (b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)).astype(np.float32)
 
 
-def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, N=64, device='cuda'):
-    """lib/dvgo_ori.py:695-703 -> (vertices [Nv,3] in world coordinates, triangles [Nt,3] int32), numpy."""
+def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, N=64, device='cuda', keep=None):
+    """lib/dvgo_ori.py:695-703 -> (vertices [Nv,3] in world coordinates, triangles [Nt,3] int32), numpy.  keep (None: everything,
+    else as keep_components) drops connected components on the device, before the mesh is copied to the host."""
     u = extract_fields_device(bound_min, bound_max, resolution, query_func, N, device)
     vertices, triangles = marching_cubes(u, threshold)
+    if keep is not None:
+        kept = keep_components(vertices, triangles, keep)
+        vertices, triangles = kept['vertices'], kept['triangles']
     b_min, b_max = _host(bound_min), _host(bound_max)
     vertices = vertices.cpu().numpy() / (int(resolution) - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
     return vertices, triangles.cpu().numpy()
@@ -139,18 +145,18 @@ def voxurf_deform_field(model):
     return query
 
 
-def voxurf_extract_geometry(model, bound_min, bound_max, resolution=128, threshold=0.0, **kwargs):
+def voxurf_extract_geometry(model, bound_min, bound_max, resolution=128, threshold=0.0, keep=None, **kwargs):
     """Voxurf.extract_geometry (lib/voxurf_coarse.py:1250-1263).  The reference's line reads `self.self.sdf.grid` and fails
-    without smoothing; the evident intent (the raw template) is implemented.  Extra keyword arguments are ignored as the
-    reference's **kwargs are."""
+    without smoothing; the evident intent (the raw template) is implemented.  keep as extract_geometry; the other extra keyword
+    arguments are ignored as the reference's **kwargs are."""
     return extract_geometry(bound_min, bound_max, _resolution(model, resolution), threshold, voxurf_field(model),
-                            device=model.sdf.grid.device)
+                            device=model.sdf.grid.device, keep=keep)
 
 
-def voxurf_extract_deform_geometry(model, bound_min, bound_max, resolution=128, threshold=0.0, **kwargs):
-    """Voxurf.extract_deform_geometry (lib/voxurf_coarse.py:1224-1248)."""
+def voxurf_extract_deform_geometry(model, bound_min, bound_max, resolution=128, threshold=0.0, keep=None, **kwargs):
+    """Voxurf.extract_deform_geometry (lib/voxurf_coarse.py:1224-1248); keep as extract_geometry."""
     return extract_geometry(bound_min, bound_max, _resolution(model, resolution), threshold, voxurf_deform_field(model),
-                            device=model.sdf.grid.device)
+                            device=model.sdf.grid.device, keep=keep)
 
 
 def dvgo_field(model, mode='density'):
@@ -264,6 +270,168 @@ def voxurf_vertex_colors(model, vertices, **kw):
     """The loop the reference's export drivers run over `model.mesh_color_forward` (lib/recon_scene.py:859-866): colours [Nv,3] in
     [0,1] of the vertices, on the device; keyword arguments as vertex_attributes."""
     return vertex_attributes(model, vertices, **kw)['colors']
+
+
+CC_BATCH = 4                 # rounds of the labelling per host read
+CC_MAX_BATCHES = 64          # batches before connected_components gives up (DESIGN.md §15.2 has the reasoning behind both)
+
+
+def _mesh_triangles(triangles, n_vertices, device=None):
+    """triangles [Nt,3] -> contiguous int32 on the device, every index inside [0, n_vertices).  A numpy array (any integer type)
+    is checked on the host and uploaded; a device tensor must be int32 and costs one reduction and one host read; a CPU tensor is
+    refused.  Type, dtype and shape are looked at before the device is."""
+    Nv = int(n_vertices)
+    if Nv < 0:
+        raise ValueError('n_vertices must not be negative')
+    if Nv > 2 ** 30:
+        raise ValueError('at most 2^30 vertices')
+    is_np = isinstance(triangles, np.ndarray)
+    if not (is_np or isinstance(triangles, torch.Tensor)):
+        raise TypeError('triangles must be a torch.Tensor or a numpy array')
+    if is_np and not np.issubdtype(triangles.dtype, np.integer):
+        raise TypeError(f'triangles must hold integers, got {triangles.dtype}')
+    if not is_np and triangles.dtype != torch.int32:
+        raise TypeError(f'triangles must be torch.int32, got {triangles.dtype}')
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError(f'triangles must be [Nt, 3], got {tuple(triangles.shape)}')
+    if triangles.shape[0] > 2 ** 29:
+        raise ValueError('at most 2^29 triangles')
+    if not is_np and not triangles.is_cuda:
+        raise RuntimeError('triangles must be a CUDA tensor')
+    if triangles.shape[0] > 0:
+        if is_np:
+            lo, hi = int(triangles.min()), int(triangles.max())
+        else:
+            lo, hi = torch.stack(torch.aminmax(triangles.detach())).tolist()
+        if lo < 0 or hi >= Nv:
+            raise ValueError(f'triangles index vertices {lo}..{hi}, there are {Nv}')
+    if is_np:
+        return torch.from_numpy(np.array(triangles, dtype=np.int32)).to('cuda' if device is None else device)   # (a copy: the array may be read-only)
+    return triangles.detach().contiguous()
+
+
+@torch.no_grad()
+def connected_components(triangles, n_vertices, info=None):
+    """Connected components of an indexed mesh on the device (csrc/pp_mesh_components.hip): two vertices are
+    connected when some triangle contains both.  triangles [Nt,3] int32 on the device (a numpy array is uploaded); an index outside
+    [0, n_vertices) is a ValueError before anything runs.
+    -> dict(labels [Nv] int32: the smallest vertex index of the vertex's component, -1 for a vertex no triangle references;
+            roots [C] int32 ascending: the components' labels; vertex_counts [C], triangle_counts [C] int32: their referenced
+            vertices and triangles; n_components: C, an int), tensors on the device.
+    The labelling runs in rounds (hook + jump), CC_BATCH rounds per host read; info (a dict) receives `rounds`, the rounds up to
+    and including the first one that changed nothing - a pure function of the mesh, like the labels.  RuntimeError after
+    CC_MAX_BATCHES batches without a fixpoint."""
+    return _connected_components(_mesh_triangles(triangles, n_vertices), int(n_vertices), info)
+
+
+def _connected_components(t, Nv, info):
+    """connected_components on triangles _mesh_triangles has checked (keep_components checks once and comes here)."""
+    Nt, dev = t.shape[0], t.device
+    if info is not None:
+        info['rounds'] = 0
+    i32 = dict(dtype=torch.int32, device=dev)
+    labels = torch.empty(Nv, **i32)
+    empty = torch.empty(0, **i32)
+    if Nv == 0:
+        return dict(labels=labels, roots=empty, vertex_counts=empty.clone(), triangle_counts=empty.clone(), n_components=0)
+    with torch.cuda.device(dev):
+        work = torch.empty(ops.cc_workspace(Nv), dtype=torch.uint8, device=dev)
+        changed = torch.empty(CC_BATCH, **i32)
+        rounds = 0
+        if Nt == 0:
+            ops.cc_rounds(t, Nv, 0, 1, labels, work, changed)          # initialises: every label -1, no round to run
+        else:
+            done = 0
+            while rounds == 0:
+                if done >= CC_BATCH * CC_MAX_BATCHES:
+                    raise RuntimeError(f'connected_components: labels still changing after {done} rounds '
+                                       f'({CC_MAX_BATCHES} batches of {CC_BATCH}); {Nv} vertices, {Nt} triangles')
+                ops.cc_rounds(t, Nv, done, CC_BATCH, labels, work, changed)
+                moved = changed.tolist()
+                if 0 in moved:
+                    rounds = done + moved.index(0) + 1
+                done += CC_BATCH
+        by_root_v, by_root_t = torch.empty(Nv, **i32), torch.empty(Nv, **i32)
+        ops.cc_count(labels, t, by_root_v, by_root_t)
+        roots = torch.nonzero(by_root_v > 0).reshape(-1)                # a root is referenced and counts itself
+        out = dict(labels=labels, roots=roots.to(torch.int32), vertex_counts=by_root_v[roots], triangle_counts=by_root_t[roots],
+                   n_components=int(roots.numel()))
+    if info is not None:
+        info['rounds'] = rounds
+    return out
+
+
+def _check_keep(keep):
+    if isinstance(keep, str):
+        if keep != 'largest':
+            raise ValueError(f"keep: unknown rule '{keep}' ('largest', an int or a float in (0, 1))")
+    elif isinstance(keep, bool) or not isinstance(keep, (int, float, np.integer, np.floating)):
+        raise TypeError(f"keep must be 'largest', an int or a float in (0, 1), got {type(keep).__name__}")
+    elif isinstance(keep, (int, np.integer)):
+        if keep < 0:
+            raise ValueError('keep: a minimum triangle count must not be negative')
+    elif not 0.0 < keep < 1.0:
+        raise ValueError(f'keep: a fraction must lie in (0, 1), got {keep}')
+
+
+@torch.no_grad()
+def keep_components(vertices, triangles, keep='largest', attributes=None, info=None):
+    """Drop connected components of a mesh on the device.  vertices [Nv,3], triangles [Nt,3] int32 (device tensors, or numpy arrays
+    that are uploaded).  keep:
+        'largest'           the component with the most triangles, ties to the lowest root
+        an int              every component with at least that many triangles
+        a float in (0, 1)   every component with at least that fraction of the largest component's triangle count
+                            (float64: count >= keep * largest)
+    -> dict(vertices [Nv',3] float32, triangles [Nt',3] int32, vertex_index [Nv'] int32: each kept vertex's old index,
+            n_components: before the filter, n_kept: after), plus `attributes` - a dict of [Nv, ...] tensors or arrays - subset
+    with vertex_index under the same keys.  Kept vertices and triangles stay in their relative order and the winding is untouched;
+    vertices no triangle references are dropped.  Host reads: the index check (device triangles only), one per batch of rounds, the
+    number of roots (torch.nonzero) and one for the kept counts.  info as connected_components'."""
+    _check_keep(keep)
+    dev = next((x.device for x in (vertices, triangles) if isinstance(x, torch.Tensor) and x.is_cuda), torch.device('cuda'))
+    if not isinstance(vertices, (torch.Tensor, np.ndarray)):
+        raise TypeError('vertices must be a torch.Tensor or a numpy array')
+    if not (vertices.is_floating_point() if isinstance(vertices, torch.Tensor) else np.issubdtype(vertices.dtype, np.floating)):
+        raise TypeError(f'vertices must hold floats, got {vertices.dtype}')
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError(f'vertices must be [Nv, 3], got {tuple(vertices.shape)}')
+    Nv = len(vertices)
+    attributes = {} if attributes is None else dict(attributes)
+    for k, a in attributes.items():
+        if k in ('vertices', 'triangles', 'vertex_index', 'n_components', 'n_kept'):
+            raise ValueError(f'attributes: the key {k!r} is one of the result\'s own')
+        if not isinstance(a, (torch.Tensor, np.ndarray)) or a.ndim < 1 or a.shape[0] != Nv:
+            raise ValueError(f'attributes[{k!r}] must be a tensor or an array with one row per vertex ({Nv})')
+    t = _mesh_triangles(triangles, Nv, dev)
+    v = _device_vertices(vertices, dev)
+    cc = _connected_components(t, Nv, info)
+    C, Nt = cc['n_components'], t.shape[0]
+    i32 = dict(dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        tcount = cc['triangle_counts']
+        if C == 0:
+            keep_c = torch.zeros(0, dtype=torch.bool, device=dev)
+        elif isinstance(keep, str):
+            keep_c = tcount == tcount.max()
+            keep_c &= torch.cumsum(keep_c, 0) == 1                      # ties: the lowest root
+        elif isinstance(keep, (int, np.integer)):
+            keep_c = tcount >= int(keep)
+        else:
+            keep_c = tcount.double() >= float(keep) * tcount.max().double()
+        root_keep = torch.zeros(Nv, dtype=torch.uint8, device=dev)
+        root_keep[cc['roots'][keep_c].long()] = 1
+        vkeep, tkeep = torch.empty(Nv, **i32), torch.empty(Nt, **i32)
+        ops.cc_keep_masks(cc['labels'], t, root_keep, vkeep, tkeep)
+        vscan, tscan = torch.cumsum(vkeep, 0, dtype=torch.int32), torch.cumsum(tkeep, 0, dtype=torch.int32)
+        zero = torch.zeros(1, **i32)
+        nv, nt, n_kept = torch.cat([vscan[-1:] if Nv else zero, tscan[-1:] if Nt else zero, keep_c.sum().to(torch.int32)[None]]).tolist()
+        out_v, out_i, out_t = torch.empty(nv, 3, dtype=torch.float32, device=dev), torch.empty(nv, **i32), torch.empty(nt, 3, **i32)
+        ops.cc_compact(v, t, vscan, tscan, out_v, out_i, out_t)
+        out = dict(vertices=out_v, triangles=out_t, vertex_index=out_i, n_components=C, n_kept=n_kept)
+        index = out_i.long()
+        for k, a in attributes.items():
+            out[k] = a[index.cpu().numpy()] if isinstance(a, np.ndarray) else a[index.to(a.device)]
+    return out
 
 
 def write_ply(path, vertices, triangles, vertex_colors=None, vertex_normals=None):

@@ -863,6 +863,69 @@ def vertex_feat(sc, sdf_grid, sdf_ab, k0_cl, pts, warp_out, pe_w, n, normal, fea
               _f(warp_out, 'warp_out'), _f(pe_w, 'pe_w'), n, _f(normal, 'normal'), _f(feat, 'feat'), _stream())
 
 
+# ------------------------------------------------------------------------------------------- mesh cleaning (connected components)
+def cc_workspace(n_vertices):
+    """Bytes of device workspace pp_cc_rounds needs for n_vertices vertices (a pure host call)."""
+    b = ctypes.c_int64()
+    _lib.call('pp_cc_workspace', int(n_vertices), ctypes.byref(b))
+    return b.value
+
+
+def _cc_mesh(triangles, n_vertices, *per_vertex):
+    if triangles is not None and (triangles.dim() != 2 or triangles.shape[1] != 3):
+        raise RuntimeError('triangles must be [.,3]')
+    Nv = int(n_vertices)
+    for t, name in per_vertex:
+        if t is not None and t.numel() != Nv:
+            raise RuntimeError(f'{name}: {t.numel()} elements, {Nv} expected')
+    return 0 if triangles is None else int(triangles.shape[0]), Nv
+
+
+def cc_rounds(triangles, n_vertices, first_round, n_rounds, labels, work, changed):
+    """Rounds first_round .. first_round + n_rounds - 1 of the component labelling of triangles [Nt,3] int32 (first_round = 0
+    initialises labels [Nv] int32 and work); changed [n_rounds] int32 <- 1 where that round changed a label."""
+    Nt, Nv = _cc_mesh(triangles, n_vertices, (labels, 'labels'))
+    if changed is not None and changed.numel() < int(n_rounds):
+        raise RuntimeError(f'changed: {changed.numel()} elements, {int(n_rounds)} expected')
+    _lib.call('pp_cc_rounds', _i(triangles, 'triangles'), Nt, Nv, int(first_round), int(n_rounds), _i(labels, 'labels'),
+              _u8(work, 'work'), 0 if work is None else int(work.numel()), _i(changed, 'changed'), _stream())
+
+
+def cc_count(labels, triangles, vertex_counts, triangle_counts):
+    """labels [Nv] of cc_rounds at its fixpoint -> vertex_counts, triangle_counts [Nv] int32 indexed by root (0 elsewhere)."""
+    Nt, Nv = _cc_mesh(triangles, 0 if labels is None else labels.numel(), (vertex_counts, 'vertex_counts'),
+                      (triangle_counts, 'triangle_counts'))
+    _lib.call('pp_cc_count', _i(labels, 'labels'), Nv, _i(triangles, 'triangles'), Nt, _i(vertex_counts, 'vertex_counts'),
+              _i(triangle_counts, 'triangle_counts'), _stream())
+
+
+def cc_keep_masks(labels, triangles, root_keep, vertex_keep, triangle_keep):
+    """root_keep [Nv] uint8 marks the roots to keep -> vertex_keep [Nv], triangle_keep [Nt] int32 (1 = kept)."""
+    Nt, Nv = _cc_mesh(triangles, 0 if labels is None else labels.numel(), (root_keep, 'root_keep'), (vertex_keep, 'vertex_keep'))
+    if triangle_keep is not None and triangle_keep.numel() != Nt:
+        raise RuntimeError(f'triangle_keep: {triangle_keep.numel()} elements, {Nt} expected')
+    _lib.call('pp_cc_keep_masks', _i(labels, 'labels'), Nv, _i(triangles, 'triangles'), Nt, _u8(root_keep, 'root_keep'),
+              _i(vertex_keep, 'vertex_keep'), _i(triangle_keep, 'triangle_keep'), _stream())
+
+
+def cc_compact(vertices, triangles, vertex_scan, triangle_scan, out_vertices, out_index, out_triangles):
+    """vertex_scan [Nv] / triangle_scan [Nt] int32 = inclusive scans of cc_keep_masks' masks -> the kept rows, in order, in
+    out_vertices [Nv',3], out_index [Nv'] int32 (old indices) and out_triangles [Nt',3] int32 (renumbered)."""
+    if vertices is not None and (vertices.dim() != 2 or vertices.shape[1] != 3):
+        raise RuntimeError('vertices must be [.,3]')
+    Nt, Nv = _cc_mesh(triangles, 0 if vertices is None else vertices.shape[0], (vertex_scan, 'vertex_scan'))
+    if triangle_scan is not None and triangle_scan.numel() != Nt:
+        raise RuntimeError(f'triangle_scan: {triangle_scan.numel()} elements, {Nt} expected')
+    for t, name in ((out_vertices, 'out_vertices'), (out_triangles, 'out_triangles')):
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise RuntimeError(f'{name} must be [.,3]')
+    if out_index.numel() != out_vertices.shape[0]:
+        raise RuntimeError(f'out_index: {out_index.numel()} elements, {out_vertices.shape[0]} expected')
+    _lib.call('pp_cc_compact', _f(vertices, 'vertices'), _i(triangles, 'triangles'), _i(vertex_scan, 'vertex_scan'),
+              _i(triangle_scan, 'triangle_scan'), Nv, Nt, _f(out_vertices, 'out_vertices'), _i(out_index, 'out_index'),
+              _i(out_triangles, 'out_triangles'), int(out_vertices.shape[0]), int(out_triangles.shape[0]), _stream())
+
+
 # ------------------------------------------------------------------------------------------- pose initialisation (PnP-RANSAC)
 def pnp_workspace(P, H):
     """Bytes of device workspace pp_pnp_ransac needs for P rows and H hypotheses (a pure host call)."""

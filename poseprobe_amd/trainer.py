@@ -420,7 +420,9 @@ class DualBranchTrainer:
         dtu_eval.validate_deform_mesh on the object engine's CURRENT parameters, read through its drop-in view
         (TrainEngine.voxurf_view: built once, re-pointed at the live buffers on every call) -> the driver's return value.
         global_step (the BARF weights of the colour pass with extract_color=True) defaults to the object engine's step count;
-        the other keyword arguments are validate_deform_mesh's.  The engine and the optimiser state are left as they are."""
+        the other keyword arguments are validate_deform_mesh's - among them keep= ('largest', a triangle count or a fraction of
+        the largest component), which drops the mesh's stray connected components on the device before it is shaded, written and
+        scored (mesh.keep_components).  The engine and the optimiser state are left as they are."""
         from . import dtu_eval
         e = self.joint.obj
         self._mesh_view = e.voxurf_view(getattr(self, '_mesh_view', None))

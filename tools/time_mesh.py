@@ -1,6 +1,7 @@
 """Times of mesh extraction (poseprobe_amd.mesh) on a 160^3 Voxurf model with the synthetic scene's box and a perturbed warp net,
 at lattice resolutions 128, 256 and 512: the device field fill (plain and deform), marching cubes (pp_mc_count, pp_mc_emit) and
-the device-to-host copy of the mesh, and the colour pass over the mesh's vertices (mesh.vertex_attributes: pp_warp_fwd,
+the device-to-host copy of the mesh, the connected components of the mesh and the 'largest' filter (pp_cc_*, beside the host round
+trip through scipy they replace), and the colour pass over the mesh's vertices (mesh.vertex_attributes: pp_warp_fwd,
 pp_vertex_feat, pp_rgbnet_fwd per chunk of 262144 vertices), whole and launch by launch on its first chunk.  Everything runs in ONE process; each stage is warmed up, then timed `--runs` times with
 device events (the copy with a host clock around a synchronising copy); medians are reported.
 
@@ -97,6 +98,85 @@ def color_launches(m, vw, runs, chunk=262144):
     return out
 
 
+def component_stage(vertices, triangles, runs):
+    """Connected components and the 'largest' filter on the extracted mesh (mesh.connected_components / keep_components,
+    csrc/pp_mesh_components.hip), stage by stage, and the host round trip through scipy.sparse.csgraph they replace."""
+    from poseprobe_amd import mesh, ops
+    nv, nt = vertices.shape[0], triangles.shape[0]
+    i32 = dict(dtype=torch.int32, device='cuda')
+    info = {}
+    cc = mesh.connected_components(triangles, nv, info)
+    rounds = info['rounds']
+    batches = -(-rounds // mesh.CC_BATCH)
+    labels, work = torch.empty(nv, **i32), torch.empty(ops.cc_workspace(nv), dtype=torch.uint8, device='cuda')
+    changed = torch.empty(mesh.CC_BATCH, **i32)
+    by_v, by_t = torch.empty(nv, **i32), torch.empty(nv, **i32)
+
+    def label():
+        for b in range(batches):
+            ops.cc_rounds(triangles, nv, b * mesh.CC_BATCH, mesh.CC_BATCH, labels, work, changed)
+
+    def one_round():                        # one more round at the fixpoint: a full pass over the mesh that changes nothing
+        ops.cc_rounds(triangles, nv, batches * mesh.CC_BATCH, 1, labels, work, changed)
+
+    tc = cc['triangle_counts']
+    keep_c = tc == tc.max()
+    keep_c &= torch.cumsum(keep_c, 0) == 1
+    root_keep = torch.zeros(nv, dtype=torch.uint8, device='cuda')
+    root_keep[cc['roots'][keep_c].long()] = 1
+    vkeep, tkeep = torch.empty(nv, **i32), torch.empty(nt, **i32)
+    ops.cc_keep_masks(cc['labels'], triangles, root_keep, vkeep, tkeep)
+    n_kept_v, n_kept_t = int(vkeep.sum()), int(tkeep.sum())
+    out_v, out_i, out_t = torch.empty(n_kept_v, 3, device='cuda'), torch.empty(n_kept_v, **i32), torch.empty(n_kept_t, 3, **i32)
+
+    def compact():
+        ops.cc_keep_masks(cc['labels'], triangles, root_keep, vkeep, tkeep)
+        ops.cc_compact(vertices, triangles, torch.cumsum(vkeep, 0, dtype=torch.int32), torch.cumsum(tkeep, 0, dtype=torch.int32),
+                       out_v, out_i, out_t)
+
+    out = [f'components: {cc["n_components"]}, largest {int(tc.max())} of {nt} triangles, kept {n_kept_v} vertices; {rounds} rounds '
+           f'({batches} batches of {mesh.CC_BATCH})']
+    ms_label = device_ms(label, runs)
+    out.append(f'labelling, {batches * mesh.CC_BATCH} rounds, no host read  {fmt(ms_label)}')
+    assert torch.equal(labels, cc['labels'])
+    per_round = [[] for _ in range(rounds)]                 # round by round (round 0 with the initialisation), one launch pair each
+    for _ in range(runs):
+        for r in range(rounds):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            ops.cc_rounds(triangles, nv, r, 1, labels, work, changed)
+            t1.record()
+            t1.synchronize()
+            per_round[r].append(t0.elapsed_time(t1))
+    out.append('round by round, medians (ms): ' + ' '.join(f'{statistics.median(x):.3f}' for x in per_round))
+    out.append(f'one round (hook + jump) at the fixpoint  {fmt(device_ms(one_round, runs))}')
+    out.append(f'pp_cc_count                          {fmt(device_ms(lambda: ops.cc_count(labels, triangles, by_v, by_t), runs))}')
+    out.append(f'masks + two torch.cumsum + pp_cc_compact  {fmt(device_ms(compact, runs))}')
+    out.append(f'mesh.connected_components (with its host reads)  {fmt(device_ms(lambda: mesh.connected_components(triangles, nv), runs))}')
+    out.append(f"mesh.keep_components(keep='largest') (all of the above)  "
+               f"{fmt(device_ms(lambda: mesh.keep_components(vertices, triangles, 'largest'), runs))}")
+    try:
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+    except ImportError:
+        return out + ['scipy is not installed: no host comparison']
+    host = []
+    for _ in range(runs + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        v, t = vertices.cpu().numpy(), triangles.cpu().numpy()
+        rows, cols = np.concatenate([t[:, 0], t[:, 0]]), np.concatenate([t[:, 1], t[:, 2]])
+        _, comp = connected_components(coo_matrix((np.ones(len(rows), np.int8), (rows, cols)), shape=(nv, nv)), directed=False)
+        big = np.argmax(np.bincount(comp[t[:, 0]]))
+        vk = comp == big
+        new = np.cumsum(vk, dtype=np.int32) - 1
+        kv, kt = torch.from_numpy(v[vk]).cuda(), torch.from_numpy(new[t[vk[t[:, 0]]]]).cuda()
+        torch.cuda.synchronize()
+        host.append((time.perf_counter() - t0) * 1e3)
+    assert torch.equal(kv, out_v) and torch.equal(kt, out_t)
+    return out + [f'host round trip: two copies + scipy.sparse.csgraph.connected_components + numpy compaction  {fmt(host[1:])}']
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--resolutions', type=int, nargs='+', default=[128, 256, 512])
@@ -140,6 +220,7 @@ def main():
             vertices.cpu(), triangles.cpu()
             host.append((time.perf_counter() - t0) * 1e3)
         lines.append(f'device-to-host copy of the mesh ({12 * (nv + nt) / 2 ** 20:.1f} MiB, pageable)  {fmt(host[1:])}')
+        lines += component_stage(vertices, triangles, a.runs)
         # ---- colour pass over this mesh's vertices (model coordinates, on the device)
         vw = (vertices / (res - 1.0) * (hi - lo)[None] + lo[None]).contiguous()
         for name, deform, per_vertex in (('deform', True, 76 + 344 + 268), ('plain', False, 280 + 268)):
