@@ -47,7 +47,7 @@ const char* pp_last_error(void);
  * auxiliary-stream placement of the weight-gradient kernels is gone with its join entry point and its two options.
  * Entry points added without a version change (no existing signature moved): the pp_reproj_* group, the pp_featproj_* group, the pp_mc_* group, the pp_pnp_* group,
  * the pp_dtu_* group, the pp_ssim_* group, pp_step_begin, pp_march_loss_bwd / pp_march_loss_workspace, pp_geometry_plain_fwd /
- * pp_geometry_plain_bwd, pp_keep_compact / pp_keep_scatter_bwd, pp_vertex_feat, the pp_cc_* group.
+ * pp_geometry_plain_bwd, pp_keep_compact / pp_keep_scatter_bwd, pp_vertex_feat, the pp_cc_* group, the pp_msdf_* group.
  * A binding MUST compare pp_abi_version() with the PP_ABI_VERSION it was built against before calling anything else
  * (poseprobe_amd/_lib.py does): the signatures changed, so a stale caller would pass a stream where a pointer is read. */
 #define PP_ABI_VERSION 4
@@ -859,6 +859,51 @@ int pp_cc_keep_masks(const int32_t* labels, int32_t n_vertices, const int32_t* t
 int pp_cc_compact(const float* vertices, const int32_t* triangles, const int32_t* vertex_scan, const int32_t* triangle_scan,
                   int32_t n_vertices, int32_t n_triangles, float* out_vertices, int32_t* out_index, int32_t* out_triangles,
                   int32_t n_out_vertices, int32_t n_out_triangles, void* stream);
+
+/* Signed distance of a triangle mesh at the nodes of a grid (csrc/pp_mesh_sdf.hip): the inverse of pp_mc_*.
+ * vertices [V,3] fp32, triangles [T,3] int32.  A triangle with an index outside [0, V) takes part in nothing (the Python host
+ * refuses such a mesh first).
+ * Cell grid as for pp_dtu_*: origin (ox, oy, oz), cubic cells of `edge`, nx x ny x nz cells, a coordinate's cell is
+ *   floor((p - o) / edge) in fp32 clamped into the grid, int64 keys (x ny + y) nz + z.  A triangle is registered in every cell
+ *   its bounding box, padded by edge / 64 on every side, overlaps.  pp_msdf_bin_count writes counts [T] int64 (DEVICE), the
+ *   caller scans them, pp_msdf_bin_emit writes the n_pairs (key, triangle) pairs triangle-major to keys / tris at offsets [T] =
+ *   the exclusive scan; n_pairs above 2^31 - 1 is PP_ERR_UNSUPPORTED, nothing is truncated.  The caller sorts the pairs by key.
+ * pp_msdf_nearest: the exact nearest point of the mesh for Q queries.  queries [Q,3], or NULL: the queries are the nodes
+ *   (xs[i], ys[j], zs[k]) of the grid xs [X], ys [Y], zs [Z] in the order (i Y + j) Z + k, and Q must be X Y Z.  Per pair the
+ *   closest point of the triangle is the best of the foot of the perpendicular (where it falls inside: barycentric weights from
+ *   n . (ap x ac), n . (ab x ap), n = ab x ac, used only when n . n > 0) and the closest points of the three sides taken as
+ *   segments (a side of no length is its end point), so a triangle without area takes part as a segment or a point.  fp32;
+ *   d2 = (dx dx + dy dy) + dz dz between the query and the rounded closest point.  The winner is the smallest d2, ties to the
+ *   lowest triangle index: a pure function of the inputs, whatever the cell grid.  Rings of cells at growing Chebyshev radius k
+ *   around the query's cell; before ring k >= 2 the search ends if d2 <= ((k - 1.02) edge)^2 or (k - 1.02) edge >= max_dist
+ *   (the margin covers the rounding of the cell coordinates, as for pp_dtu_nearest: at most 2^13 cells per axis).
+ *   dist [Q] = sqrt(d2), closest [Q,3], tri [Q] int32; (inf, NaN, -1) where no triangle has d2 < max_dist^2 (max_dist = inf:
+ *   no cap).  rings [Q] int32 (optional) receives the number of rings visited.
+ * pp_msdf_crossings: counts [X+1,Y,Z] int32 (cleared by the call; pp_msdf_crossing_slots, a pure host function, gives its
+ *   length).  For every column (j, k) the crossings of the line y = ys[j], z = zs[k] with the mesh are counted into the slot
+ *   s = the number of nodes with xs[i] < x*, x* the crossing's abscissa: node i is inside iff the sum of the slots 0 .. i is
+ *   odd (the caller's scan).  One wavefront per triangle walks the columns inside the triangle's (y, z) bounding box; integer
+ *   atomicAdd only.  Coverage is decided in fp64 on the (y, z) projection by edge functions with the fill rule of the
+ *   infinitesimal shift (+eps, +eps^2): a column on an edge belongs to the triangle iff the edge, walked with the interior on
+ *   its positive side, has dz < 0, or dz = 0 and dy > 0.  Every edge function is evaluated from the lexicographically
+ *   (y, z)-smaller end point and negated for the other direction, so the two triangles of an edge see the same number with
+ *   opposite sign.  A triangle whose projection has no area contributes nothing.
+ * xs, ys, zs must be strictly increasing (the caller's promise; X, Y, Z >= 1, X Y Z and (X + 1) Y Z at most 2^31 - 1).
+ * No float atomics, no allocation, no host read; results are bit-reproducible.  All refuse, before any GPU call: null pointers
+ * (except queries and rings), sizes below 1, a non-finite origin, a non-positive or non-finite edge, a max_dist that is NaN or
+ * not positive. */
+int pp_msdf_bin_count(const float* vertices, int32_t V, const int32_t* triangles, int32_t T, float ox, float oy, float oz, float edge,
+                      int32_t nx, int32_t ny, int32_t nz, int64_t* counts, void* stream);
+int pp_msdf_bin_emit(const float* vertices, int32_t V, const int32_t* triangles, int32_t T, float ox, float oy, float oz, float edge,
+                     int32_t nx, int32_t ny, int32_t nz, const int64_t* offsets, int64_t* keys, int32_t* tris, int64_t n_pairs,
+                     void* stream);
+int pp_msdf_nearest(const float* queries, int32_t Q, const float* xs, const float* ys, const float* zs, int32_t X, int32_t Y, int32_t Z,
+                    const float* vertices, int32_t V, const int32_t* triangles, int32_t T, const int64_t* keys, const int32_t* tris,
+                    int32_t n_pairs, float ox, float oy, float oz, float edge, int32_t nx, int32_t ny, int32_t nz, float max_dist,
+                    float* dist, float* closest, int32_t* tri, int32_t* rings, void* stream);
+int pp_msdf_crossing_slots(int32_t X, int32_t Y, int32_t Z, int64_t* slots);
+int pp_msdf_crossings(const float* vertices, int32_t V, const int32_t* triangles, int32_t T, const float* xs, const float* ys,
+                      const float* zs, int32_t X, int32_t Y, int32_t Z, int32_t* counts, void* stream);
 
 /* ---------------------------------------------------------------- pose initialisation: PnP-RANSAC
  * lib/recon_scene.py:276-310 hands surface points and matched pixels to cv2.solvePnPRansac on the host; here they stay on the

@@ -663,6 +663,17 @@ class TrainEngine:
             if se3 is not None:
                 self.se3.copy_(se3.to(self.dev))
 
+    def set_template(self, sdf):
+        """Install a frozen SDF template: sdf [X,Y,Z] or [1,1,X,Y,Z] (negative inside; tensor or numpy, any device), copied into the
+        engine's `sdf` as load_reference_params copies its own.  mesh.signed_distance_grid makes one from a mesh."""
+        sdf = torch.as_tensor(sdf)
+        if sdf.dim() == 5 and tuple(sdf.shape[:2]) == (1, 1):
+            sdf = sdf[0, 0]
+        if tuple(sdf.shape) != tuple(self.sdf.shape):
+            raise ValueError(f'set_template: the template is {tuple(sdf.shape)}, the engine\'s grid {tuple(self.sdf.shape)}')
+        with torch.no_grad():
+            self.sdf.copy_(sdf.detach().to(self.dev))
+
     def k0_reference_layout(self, t=None):
         t = self.k0_cl if t is None else t
         return t.permute(3, 0, 1, 2)[None]

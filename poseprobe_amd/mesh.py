@@ -555,3 +555,214 @@ def read_ply_attributes(path):
     group = lambda names: np.stack([col[n] for n in names], -1) if all(n in col for n in names) else None
     return dict(vertices=group(('x', 'y', 'z')), triangles=triangles, normals=group(('nx', 'ny', 'nz')),
                 colors=group(('red', 'green', 'blue')))
+
+
+# ------------------------------------------------------------------------------------------- mesh -> signed distance grid
+MSDF_MAX_CELLS = 1 << 13     # cells per axis of the triangle grid: keeps the rounding of a cell coordinate below 2^-8 of a cell
+MSDF_CELLS_ACROSS = 48       # the default cell edge is at least the mesh's longest extent over this
+
+
+def _check_points(x, name):
+    """x [N,3]: a float numpy array or a float device tensor; type, dtype and shape are looked at before the device is."""
+    if not isinstance(x, (torch.Tensor, np.ndarray)):
+        raise TypeError(f'{name} must be a torch.Tensor or a numpy array')
+    if not (x.is_floating_point() if isinstance(x, torch.Tensor) else np.issubdtype(x.dtype, np.floating)):
+        raise TypeError(f'{name} must hold floats, got {x.dtype}')
+    if x.ndim != 2 or x.shape[1] != 3:
+        raise ValueError(f'{name} must be [N, 3], got {tuple(x.shape)}')
+    if isinstance(x, torch.Tensor) and not x.is_cuda:
+        raise RuntimeError(f'{name} must be a CUDA tensor')
+
+
+def _mesh_on_device(vertices, triangles):
+    """(vertices float32 [Nv,3], triangles int32 [Nt,3]) on one device; an index out of range is a ValueError.  Everything that can
+    be refused without the device is refused before the first upload."""
+    _check_points(vertices, 'vertices')
+    dev = next((x.device for x in (vertices, triangles) if isinstance(x, torch.Tensor) and x.is_cuda), torch.device('cuda'))
+    t = _mesh_triangles(triangles, len(vertices), dev)
+    return _device_vertices(vertices, dev), t
+
+
+class _TriangleCells:
+    """The triangles of a mesh registered in a sparse grid of cubic cells over the mesh's bounding box (pp_msdf_bin_*): .keys
+    (ascending int64), .tris (int32), .grid = (origin, edge, cells).  Two host reads: the bounding box with the mean triangle
+    area, and the pair total."""
+
+    def __init__(self, v, t, cell_edge=None):
+        used = v[t.reshape(-1).long()].reshape(-1, 3, 3)
+        area = 0.5 * torch.linalg.cross(used[:, 1] - used[:, 0], used[:, 2] - used[:, 0]).norm(dim=-1).double().mean()
+        lo, hi = used.amin((0, 1)), used.amax((0, 1))
+        *box, area = torch.cat([lo.double(), hi.double(), area[None]]).tolist()
+        if not all(np.isfinite(box)):
+            raise ValueError('non-finite vertex coordinates')
+        lo, hi = box[:3], box[3:]
+        extent = max(h - l for l, h in zip(lo, hi))
+        if cell_edge is None:                       # about two triangles across a cell, and no more cells than a far query can walk
+            cell_edge = max(2.0 * np.sqrt(area) if np.isfinite(area) else 0.0, extent / MSDF_CELLS_ACROSS)
+        edge = float(np.float32(max(float(cell_edge), extent / (MSDF_MAX_CELLS - 2), 1e-30)))
+        cells = [min(int((h - l) / edge) + 1, MSDF_MAX_CELLS) for l, h in zip(lo, hi)]
+        self.grid = (lo, edge, cells)
+        counts = torch.empty(t.shape[0], dtype=torch.int64, device=v.device)
+        ops.msdf_bin_count(v, t, self.grid, counts)
+        ends = torch.cumsum(counts, 0)
+        self.n_pairs = int(ends[-1])
+        if self.n_pairs > 2 ** 31 - 1:
+            raise RuntimeError(f'{self.n_pairs} (cell, triangle) pairs: more than 2^31 - 1; use a larger cell_edge than {edge}')
+        keys = torch.empty(self.n_pairs, dtype=torch.int64, device=v.device)
+        tris = torch.empty(self.n_pairs, dtype=torch.int32, device=v.device)
+        ops.msdf_bin_emit(v, t, self.grid, (ends - counts).contiguous(), keys, tris, self.n_pairs)
+        self.keys, perm = torch.sort(keys, stable=True)
+        self.tris = tris[perm].contiguous()
+
+
+def _max_dist(max_dist):
+    if max_dist is None:
+        return float('inf')
+    max_dist = float(np.float32(max_dist))
+    if not max_dist > 0:
+        raise ValueError('max_dist must be positive')
+    return max_dist
+
+
+def _nearest_on_mesh(queries, axes, v, t, max_dist, cell_edge, info):
+    dev = v.device
+    Q = queries.shape[0] if queries is not None else int(np.prod([a.numel() for a in axes]))
+    dist = torch.full((Q,), float('inf'), dtype=torch.float32, device=dev)
+    closest = torch.full((Q, 3), float('nan'), dtype=torch.float32, device=dev)
+    tri = torch.full((Q,), -1, dtype=torch.int32, device=dev)
+    if info is not None:
+        info.update(cell_edge=None, cells=None, pairs=0, rings_mean=0.0, rings_max=0)
+    if Q == 0 or t.shape[0] == 0:
+        return dist, closest, tri
+    if Q > 2 ** 31 - 1:
+        raise ValueError('more than 2^31 - 1 queries')
+    with torch.cuda.device(dev):
+        cells = _TriangleCells(v, t, cell_edge)
+        rings = torch.empty(Q, dtype=torch.int32, device=dev) if info is not None else None
+        ops.msdf_nearest(queries, axes, v, t, cells.keys, cells.tris, cells.grid, max_dist, dist, closest, tri, rings)
+        if info is not None:
+            info.update(cell_edge=cells.grid[1], cells=list(cells.grid[2]), pairs=cells.n_pairs,
+                        rings_mean=float(rings.double().mean()), rings_max=int(rings.max()))
+    return dist, closest, tri
+
+
+@torch.no_grad()
+def unsigned_distance(points, vertices, triangles, max_dist=None, *, cell_edge=None, info=None):
+    """The exact distance from points [Q,3] to a triangle mesh on the device (csrc/pp_mesh_sdf.hip): vertices
+    [Nv,3], triangles [Nt,3]; every input a numpy array (uploaded) or a device tensor.
+    -> (dist [Q] float32, closest [Q,3] float32: the nearest point of the mesh, triangle [Q] int32: the triangle it lies on),
+    device tensors.  float32 arithmetic; among triangles at the same float32 squared distance the lowest index wins, so the result
+    is a pure function of the inputs - and does not depend on cell_edge, the edge of the internal search grid.  Triangles without
+    area take part as segments or points.  max_dist (optional) caps the search: (inf, NaN, -1) where nothing is nearer.  An
+    index outside the vertices is a ValueError.  info (a dict) receives cell_edge, cells, pairs (the (cell, triangle) pairs sorted),
+    rings_mean and rings_max (rings of cells a query visited)."""
+    _check_points(points, 'points')
+    v, t = _mesh_on_device(vertices, triangles)
+    return _nearest_on_mesh(_device_vertices(points, v.device), None, v, t, _max_dist(max_dist), cell_edge, info)
+
+
+def sdf_grid_axes(xyz_min, xyz_max, world_size):
+    """The node coordinates of a grid: node i of axis a sits at xyz_min[a] + i (xyz_max[a] - xyz_min[a]) / (world_size[a] - 1),
+    formed in float64 and rounded once -> three float32 numpy vectors.  (world_size 1: the single node sits at xyz_min.)"""
+    f64 = lambda b: np.asarray(b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b, dtype=np.float64).reshape(3)
+    lo, hi = f64(xyz_min), f64(xyz_max)             # (the values as given: a float32 box is taken exactly)
+    n = [int(s) for s in (world_size.tolist() if isinstance(world_size, (torch.Tensor, np.ndarray)) else world_size)]
+    if len(n) != 3 or min(n) < 1:
+        raise ValueError(f'world_size must be three positive counts, got {n}')
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+        raise ValueError('xyz_min and xyz_max must be finite with xyz_min < xyz_max')
+    axes = [(lo[a] + np.arange(n[a], dtype=np.float64) * ((hi[a] - lo[a]) / max(n[a] - 1, 1))).astype(np.float32) for a in range(3)]
+    if any(len(x) > 1 and not (np.diff(x) > 0).all() for x in axes):
+        raise ValueError('the float32 node coordinates are not strictly increasing: the grid is too fine for the box')
+    return axes
+
+
+def odd_edge_count(triangles):
+    """The number of undirected edges with an odd number of incident triangles (a triangle that repeats a vertex contributes its
+    sides as they are).  triangles [Nt,3] int on the device -> int (one host read).  0 is the condition under which the parity of
+    crossings is the same along every generic line, i.e. under which inside and outside are defined."""
+    t = triangles.long()
+    if t.shape[0] == 0:
+        return 0
+    e = torch.cat([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]])
+    e = e[e[:, 0] != e[:, 1]]                       # (a side from a vertex to itself is no edge)
+    if e.shape[0] == 0:
+        return 0
+    key = e.amin(1) * (int(t.max()) + 1) + e.amax(1)
+    _, counts = torch.unique(key, return_counts=True)
+    return int((counts % 2 == 1).sum())
+
+
+@torch.no_grad()
+def signed_distance_grid(vertices, triangles, xyz_min, xyz_max, world_size, check=True, info=None, *, cell_edge=None):
+    """The signed distance of a closed triangle mesh at the nodes of a grid, on the device (csrc/pp_mesh_sdf.hip):
+    the inverse of marching_cubes.  -> [X,Y,Z] float32, NEGATIVE inside, as the cuboid template and voxurf_field's -sdf have it.
+    Node (i,j,k) sits at xyz_min + (i,j,k) (xyz_max - xyz_min) / (world_size - 1) (sdf_grid_axes), where params_init.cube_sdf's
+    np.mgrid puts it.  The magnitude is unsigned_distance's; a node is inside iff the line through it along x crosses the mesh an
+    odd number of times before it - independent of the triangles' winding, so a reversed inner shell is a cavity.
+    Indices out of range are a ValueError.  check=True also refuses with ValueError non-finite vertices and a mesh in which some
+    undirected edge has an odd number of incident triangles (the message counts them) - the condition under which the parity is
+    defined: it admits the 4-triangle edges marching cubes can produce and rejects a surface cut open by the box.  check=False
+    computes whatever the counting gives.  info as unsigned_distance's."""
+    axes_np = sdf_grid_axes(xyz_min, xyz_max, world_size)
+    v, t = _mesh_on_device(vertices, triangles)
+    dev = v.device
+    if check:
+        if not bool(torch.isfinite(v).all()):
+            raise ValueError('signed_distance_grid: non-finite vertex coordinates')
+        odd = odd_edge_count(t)
+        if odd:
+            raise ValueError(f'signed_distance_grid: {odd} edges have an odd number of incident triangles: the mesh is not closed, '
+                             'so inside and outside are not defined (check=False computes the crossing parity anyway)')
+    X, Y, Z = (len(a) for a in axes_np)
+    if t.shape[0] == 0 or v.shape[0] == 0:
+        raise ValueError('signed_distance_grid: the mesh has no triangles')
+    with torch.cuda.device(dev):
+        axes = tuple(torch.from_numpy(a).to(dev) for a in axes_np)
+        dist, _, _ = _nearest_on_mesh(None, axes, v, t, float('inf'), cell_edge, info)
+        counts = torch.empty(ops.msdf_crossing_slots(X, Y, Z), dtype=torch.int32, device=dev)
+        ops.msdf_crossings(v, t, *axes, counts)
+        inside = (torch.cumsum(counts.view(X + 1, Y, Z)[:X], 0, dtype=torch.int32) & 1).bool()
+        dist = dist.view(X, Y, Z)
+        return torch.where(inside, -dist, dist)
+
+
+def save_sdf_grid(path, sdf, xyz_min, xyz_max):
+    """Write a template in the format the reference's MaskCache reads (lib/voxurf_coarse.py:1271-1282): a pickled dict with
+    sdf_grid_xyz [X,Y,Z] float32, xyz_min [3] and xyz_max [3] (numpy arrays)."""
+    import pickle
+    g = sdf.detach().cpu().numpy() if isinstance(sdf, torch.Tensor) else np.asarray(sdf)
+    g = np.ascontiguousarray(g.reshape(g.shape[-3:]), dtype=np.float32)
+    if g.ndim != 3:
+        raise ValueError('sdf must be [X,Y,Z] (or [1,1,X,Y,Z])')
+    with open(path, 'wb') as f:
+        pickle.dump({'sdf_grid_xyz': g, 'xyz_min': _host(xyz_min).reshape(3), 'xyz_max': _host(xyz_max).reshape(3)}, f)
+
+
+def load_sdf_grid(path):
+    """-> (sdf [X,Y,Z] float32, xyz_min [3], xyz_max [3]), numpy: what save_sdf_grid wrote.  The file is a pickle: load only files
+    you trust."""
+    import pickle
+    with open(path, 'rb') as f:
+        d = pickle.load(f)
+    if not isinstance(d, dict) or not all(k in d for k in ('sdf_grid_xyz', 'xyz_min', 'xyz_max')):
+        raise ValueError(f'{path}: not a template file (a dict with sdf_grid_xyz, xyz_min, xyz_max)')
+    g = np.asarray(d['sdf_grid_xyz'], dtype=np.float32)
+    if g.ndim != 3:
+        raise ValueError(f'{path}: sdf_grid_xyz must be [X,Y,Z], got {g.shape}')
+    return g, np.asarray(d['xyz_min'], np.float32).reshape(3), np.asarray(d['xyz_max'], np.float32).reshape(3)
+
+
+@torch.no_grad()
+def voxurf_template_from_mesh(model, vertices, triangles, reduce=1., smooth=False, ksize=3, sigma=1., check=True, info=None):
+    """Make a mesh (in MODEL coordinates) the frozen template of `model`: signed_distance_grid over the model's own box and
+    world_size, then model.init_sdf_from_sdf(sdf, smooth, reduce, ksize, sigma).
+        vertices, triangles = mesh.read_ply('probe.ply')
+        mesh.voxurf_template_from_mesh(model, vertices, triangles)
+    -> the [X,Y,Z] grid signed_distance_grid returned (with the defaults model.sdf.grid holds its bits)."""
+    dev = model.sdf.grid.device
+    v = torch.from_numpy(np.array(vertices, dtype=np.float32)).to(dev) if isinstance(vertices, np.ndarray) else vertices
+    sdf = signed_distance_grid(v, triangles, model.xyz_min, model.xyz_max, [int(s) for s in model.world_size.tolist()],
+                               check=check, info=info)
+    model.init_sdf_from_sdf(sdf[None, None], smooth=smooth, reduce=reduce, ksize=ksize, sigma=sigma)
+    return sdf

@@ -1052,6 +1052,84 @@ def dtu_nearest(queries, points, keys, order, grid, max_dist, d2, idx):
               *_dtu_grid(grid), ctypes.c_float(max_dist), _f(d2, 'd2'), _i(idx, 'idx'), _stream())
 
 
+# ------------------------------------------------------------------------------------------- mesh -> signed distance grid
+def _msdf_mesh(vertices, triangles):
+    for t, name in ((vertices, 'vertices'), (triangles, 'triangles')):
+        if t is not None and (t.dim() != 2 or t.shape[1] != 3):
+            raise RuntimeError(f'{name} must be [.,3]')
+    return (0 if vertices is None else int(vertices.shape[0])), (0 if triangles is None else int(triangles.shape[0]))
+
+
+def _msdf_axes(xs, ys, zs):
+    for t, name in ((xs, 'xs'), (ys, 'ys'), (zs, 'zs')):
+        if t is not None and t.dim() != 1:
+            raise RuntimeError(f'{name} must be a vector')
+    return tuple(0 if t is None else int(t.numel()) for t in (xs, ys, zs))
+
+
+def msdf_bin_count(vertices, triangles, grid, counts):
+    """vertices [V,3] fp32, triangles [T,3] int32 -> counts [T] int64: the cells of grid = (origin, edge, cells) every triangle's
+    padded bounding box overlaps."""
+    V, T = _msdf_mesh(vertices, triangles)
+    if counts is not None and counts.numel() != T:
+        raise RuntimeError(f'counts: {counts.numel()} elements, {T} expected')
+    _lib.call('pp_msdf_bin_count', _f(vertices, 'vertices'), V, _i(triangles, 'triangles'), T, *_dtu_grid(grid),
+              _ptr(counts, torch.int64, 'counts'), _stream())
+
+
+def msdf_bin_emit(vertices, triangles, grid, offsets, keys, tris, n_pairs):
+    """After msdf_bin_count: offsets [T] int64 = the exclusive scan of the counts -> the n_pairs (cell key, triangle) pairs in
+    keys [n_pairs] int64 and tris [n_pairs] int32, triangle-major."""
+    V, T = _msdf_mesh(vertices, triangles)
+    if offsets is not None and offsets.numel() != T:
+        raise RuntimeError(f'offsets: {offsets.numel()} elements, {T} expected')
+    for t, name in ((keys, 'keys'), (tris, 'tris')):
+        if t is not None and t.numel() < int(n_pairs):
+            raise RuntimeError(f'{name}: {t.numel()} elements, {int(n_pairs)} to be written')
+    _lib.call('pp_msdf_bin_emit', _f(vertices, 'vertices'), V, _i(triangles, 'triangles'), T, *_dtu_grid(grid),
+              _ptr(offsets, torch.int64, 'offsets'), _ptr(keys, torch.int64, 'keys'), _i(tris, 'tris'), ctypes.c_int64(int(n_pairs)),
+              _stream())
+
+
+def msdf_nearest(queries, axes, vertices, triangles, keys, tris, grid, max_dist, dist, closest, tri, rings=None):
+    """queries [Q,3] fp32, or None with axes = (xs [X], ys [Y], zs [Z]): the nodes of that grid, x-major; keys / tris: the pairs
+    of msdf_bin_emit sorted by key -> dist [Q], closest [Q,3] fp32 and tri [Q] int32 of the exact nearest point of the mesh,
+    ties to the lowest triangle; (inf, NaN, -1) beyond max_dist.  rings [Q] int32 (optional): rings of cells visited."""
+    V, T = _msdf_mesh(vertices, triangles)
+    xs, ys, zs = (None, None, None) if axes is None else axes
+    X, Y, Z = _msdf_axes(xs, ys, zs)
+    Q = _dtu_rows(queries, 'queries') if queries is not None else X * Y * Z
+    P = 0 if keys is None else int(keys.numel())
+    if tris is not None and tris.numel() != P:
+        raise RuntimeError(f'tris: {tris.numel()} elements, {P} expected')
+    if P > 2 ** 31 - 1:
+        raise RuntimeError('more than 2^31 - 1 (cell, triangle) pairs')
+    for t, n, name in ((dist, Q, 'dist'), (closest, 3 * Q, 'closest'), (tri, Q, 'tri'), (rings, Q, 'rings')):
+        if t is not None and t.numel() != n:
+            raise RuntimeError(f'{name}: {t.numel()} elements, {n} expected')
+    _lib.call('pp_msdf_nearest', _f(queries, 'queries'), Q, _f(xs, 'xs'), _f(ys, 'ys'), _f(zs, 'zs'), X, Y, Z, _f(vertices, 'vertices'), V,
+              _i(triangles, 'triangles'), T, _ptr(keys, torch.int64, 'keys'), _i(tris, 'tris'), P, *_dtu_grid(grid),
+              ctypes.c_float(max_dist), _f(dist, 'dist'), _f(closest, 'closest'), _i(tri, 'tri'), _i(rings, 'rings'), _stream())
+
+
+def msdf_crossing_slots(X, Y, Z):
+    """Elements of the int32 crossing counts [X+1,Y,Z] of msdf_crossings (a pure host call)."""
+    n = ctypes.c_int64()
+    _lib.call('pp_msdf_crossing_slots', int(X), int(Y), int(Z), ctypes.byref(n))
+    return n.value
+
+
+def msdf_crossings(vertices, triangles, xs, ys, zs, counts):
+    """counts [X+1,Y,Z] int32 (cleared first) <- per column (j, k) the crossings of the line y = ys[j], z = zs[k] with the mesh,
+    in the slot = the number of nodes with xs[i] below the crossing."""
+    V, T = _msdf_mesh(vertices, triangles)
+    X, Y, Z = _msdf_axes(xs, ys, zs)
+    if counts is not None and counts.numel() != (X + 1) * Y * Z:
+        raise RuntimeError(f'counts: {counts.numel()} elements, [{X + 1},{Y},{Z}] expected')
+    _lib.call('pp_msdf_crossings', _f(vertices, 'vertices'), V, _i(triangles, 'triangles'), T, _f(xs, 'xs'), _f(ys, 'ys'), _f(zs, 'zs'),
+              X, Y, Z, _i(counts, 'counts'), _stream())
+
+
 # ------------------------------------------------------------------------------------------- image score (SSIM)
 def ssim_tile():
     """Edge of the output tile one work-group of pp_ssim takes (a pure host call)."""

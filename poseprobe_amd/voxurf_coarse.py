@@ -402,6 +402,41 @@ class Voxurf(torch.nn.Module):
                 'i_train': self.i_train, 'N_iters': self.N_iters, 'camera_noise': self.camera_noise,
                 'range_shape': self.range_shape, 'rect_size': self.rect_size, **self.rgbnet_kwargs}
 
+    def _gaussian_3dconv(self, ksize=3, sigma=1):
+        """lib/voxurf_coarse.py:267-279: a frozen ksize^3 Gaussian with replicate padding, in the template's dtype and device."""
+        r = np.arange(-(ksize // 2), ksize // 2 + 1, 1)
+        xx, yy, zz = np.meshgrid(r, r, r)
+        kernel = torch.from_numpy(np.exp(-(xx ** 2 + yy ** 2 + zz ** 2) / (2 * sigma ** 2))).to(self.sdf.grid)
+        m = nn.Conv3d(1, 1, ksize, stride=1, padding=ksize // 2, padding_mode='replicate').to(self.sdf.grid)
+        m.weight.data = kernel[None, None, ...] / kernel.sum()
+        m.bias.data = torch.zeros(1).to(self.sdf.grid)
+        for p in m.parameters():
+            p.requires_grad = False
+        return m
+
+    @torch.no_grad()
+    def init_sdf_from_sdf(self, sdf0=None, smooth=False, reduce=1., ksize=3, sigma=1., zero2neg=True):
+        """lib/voxurf_coarse.py:287-299: install sdf0 [1,1,X,Y,Z] (negative inside) as the template.  A grid of another shape is
+        resized trilinearly with align_corners=True; smooth=True runs the reference's Gaussian (`_gaussian_3dconv`, replicate
+        padding) over sdf0 / reduce and divides the result by `reduce` AGAIN, as the reference's lines :293-294 do - with
+        smooth=False the division happens once.  zero2neg is accepted and unused, as there.  Resize and smoothing are torch
+        plumbing on the template's device.  The template stays frozen (the reference's smooth branch would rebind `sdf.grid` to a
+        plain tensor; here only its data changes), and smoothing at render time (smooth_ksize > 0) stays refused by the constructor.
+        mesh.signed_distance_grid makes such a grid from a mesh."""
+        if not isinstance(sdf0, torch.Tensor) or sdf0.dim() != 5 or sdf0.shape[:2] != (1, 1):
+            raise ValueError('sdf0 must be a [1,1,X,Y,Z] tensor')
+        g = self.sdf.grid
+        sdf0 = sdf0.detach().to(g)
+        if sdf0.shape != g.shape:
+            sdf0 = torch.nn.functional.interpolate(sdf0, size=tuple(int(s) for s in self.world_size), mode='trilinear',
+                                                   align_corners=True)
+        if smooth:
+            data = self._gaussian_3dconv(ksize, sigma)(sdf0 / reduce) / reduce
+        else:
+            data = sdf0 / reduce
+        self.sdf.grid.data = data.contiguous()
+        self.sdf.grid.requires_grad = False
+
     def get_MaskCache_kwargs(self):
         return {'xyz_min': self.xyz_min.cpu().numpy(), 'xyz_max': self.xyz_max.cpu().numpy(),
                 'act_shift': self.act_shift, 'voxel_size_ratio': self.voxel_size_ratio, 'nearest': self.nearest}
